@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's headline metric on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch that is already resident in HBM:
 ANS-encode 65 536 independent 4096-symbol streams (int32, stream-major) with one shared 12-bit
@@ -9,6 +9,13 @@ QuantizedGaussian(-50, 50, 3.2, 9.6) table into per-stream slabs, then ANS-decod
 (BASELINE.json configs[1], SURVEY.md 8d "C2").  With N > 1 every rank (one process per GPU) owns its own
 65 536 streams (weak scaling, no data-path collective).  `python bench.py --gpus N` starts its own ranks
 (re-executes itself under torch.distributed.run on 127.0.0.1) unless a launcher already did.
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the K timed steps, a check on the device
+that every rank's decoded symbols are its input, and the bench line (`value`, `ms_per_step`; no detail record).
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (dump_outputs below), so that two
+builds can be compared output for output on the same seeded inputs.  Everything described below -- per-kernel times, the
+roofline, the CPU-oracle comparison of every stream's words, the side legs, the `configs` block, the CPU baseline, the
+detail record -- is measured by `--full` runs only.
 
 Rank 0's LAST stdout line is the bench line: the contract's keys only, under 4 KB (contract_line below).  Everything
 else -- `configs`, `after_cache_flush`, `end_to_end`, `rate` -- is the detail record: bench_detail.json next to this script
@@ -1004,9 +1011,10 @@ ROOFLINE_KEYS = ("bound", "kernel", "achieved", "peak", "unit", "frac", "frac_co
 CPU_BASELINE_KEYS = ("value", "unit", "cores", "kind", "sample", "single_thread_value", "logical_cpus", "cgroup_cpu_quota")
 
 
-def contract_line(full):
+def contract_line(full, detail=True):
     """The LAST stdout line: the contract's keys only, prose cut short, <= LINE_LIMIT bytes whatever the run added to `full`.
-    The reports (`configs`, `after_cache_flush`, `end_to_end`, `rate`, notes) travel in the detail record instead."""
+    The reports (`configs`, `after_cache_flush`, `end_to_end`, `rate`, notes) travel in the detail record instead.
+    detail=False: a plain run, which writes no detail record to point to."""
     short = {k: full[k] for k in CONTRACT_KEYS if k in full}
     if "roofline" in short:
         short["roofline"] = {k: full["roofline"][k] for k in ROOFLINE_KEYS if k in full["roofline"]}
@@ -1019,7 +1027,8 @@ def contract_line(full):
         cfgs = full["configs"]
         short["configs_reported"] = len(cfgs)
         short["configs_bit_exact"] = all(c.get("bit_exact", True) for c in cfgs)
-    short["detail"] = "bench_detail.json (also the previous stdout line)"
+    if detail:
+        short["detail"] = "bench_detail.json (also the previous stdout line)"
     # whatever else grows: the line must stay parseable
     for victim in ("per_rank", "configs_error", "detail"):
         if len(json.dumps(short)) < LINE_LIMIT:
@@ -1040,6 +1049,31 @@ def emit(full, detail_path=None):
         print(json.dumps({"bench_detail_write_error": str(exc)[:200]}), flush=True)
     print(detail, flush=True)
     print(json.dumps(contract_line(full)), flush=True)
+
+
+DUMP_STREAMS = 1024        # streams whose words and decoded symbols --dump-outputs writes: ~23 MB at the default shape
+
+
+def dump_outputs(out_dir, enc, decoded, decode_status):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files two builds can be compared by.  Every stream's
+    `n_words`, `encode_status` and `decode_status` (float32: small integers); the words (float64: exact for u32) and decoded
+    symbols (float32) of DUMP_STREAMS streams drawn with a fixed seed, listed in `sample_streams`.  A stream's words are
+    zero past its n_words, so that neither the slab stride (tuned per run) nor what lies beyond a stream's end enters them."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    n_streams = decoded.shape[0]
+    pick = np.sort(np.random.default_rng(SEED).choice(n_streams, size=min(DUMP_STREAMS, n_streams), replace=False))
+    idx = torch.from_numpy(pick).to(decoded.device)
+    n_words = enc.n_words.cpu().numpy()
+    rows = enc.words.index_select(0, idx).cpu().numpy().view(np.uint32)
+    n_pick = np.minimum(n_words[pick], rows.shape[1])
+    width = int(n_pick.max(initial=0))
+    words = np.where(np.arange(width)[None, :] < n_pick[:, None], rows[:, :width], 0)
+    arrays = {"n_words": n_words.astype(np.float32), "encode_status": enc.status.cpu().numpy().astype(np.float32),
+              "decode_status": decode_status.cpu().numpy().astype(np.float32), "sample_streams": pick.astype(np.float64),
+              "words": words.astype(np.float64), "decoded": decoded.index_select(0, idx).cpu().numpy().astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
 
 
 def plumbing(args, rank, world, dist):
@@ -1091,13 +1125,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--streams", type=int, default=N_STREAMS, help="streams per GPU of the headline step (default: BASELINE config C2)")
     ap.add_argument("--c5-streams", type=int, default=C5_STREAMS, help="streams per GPU of the C5 shard entry")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: per-kernel times and the roofline, every "
+                         "stream's words against the CPU oracle, compaction, the end-to-end and cache-flush legs, the `configs` block, "
+                         "the CPU baseline, N > 1 per-rank figures; writes the detail record.  The --no-* switches below and "
+                         "--headline-only trim such a run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller as DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the host -> device -> host leg (pinned buffers, chunked over HIP streams)")
     ap.add_argument("--no-configs", action="store_true", help="headline only: skip the `configs` block")
     ap.add_argument("--headline-only", action="store_true",
-                    help="the timed step and nothing else on the GPU: no configs, no end-to-end leg, no cache-flush legs, no compaction, no CPU "
-                         "baseline -- the run whose rocprofv3 kernel trace holds ONLY the headline pair's hot launches (scripts/profile_round.sh)")
+                    help="with --full: the timed step and its per-kernel timing, nothing else on the GPU: no configs, no end-to-end leg, no "
+                         "cache-flush legs, no compaction, no CPU baseline -- the run whose rocprofv3 kernel trace holds ONLY the headline "
+                         "pair's hot launches (scripts/profile_round.sh)")
     ap.add_argument("--graph", action="store_true", help="replay the timed step as a HIP graph instead of launching eagerly")
     ap.add_argument("--slab-stride", default="tuned",
                     help="words between the headline batch's slabs: 'tuned' (batched.tuned_stride measures it before the warmup), "
@@ -1110,6 +1152,8 @@ def main():
                          "variable-length gather of per-stream words to rank 0, max-over-ranks timing) on host tensors -- "
                          "what tests/test_dist_cpu.py drives with --backend gloo in the CPU-only build container")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.headline_only:
         args.no_configs = args.no_end_to_end = args.no_cpu_baseline = True
 
@@ -1196,6 +1240,29 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, enc, decoded, eager_step.decode_status)
+
+    n_sym = n_streams * N_PER
+    headline = {
+        "metric": "Msymbols/s encode+decode, 64k x 4k-symbol streams, bit-exact vs CPU",
+        "value": round(world * n_sym * args.steps / elapsed / 1e6, 1),
+        "unit": "Msymbols/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u64", "data": "synthetic",
+        "config": {"workload": f"C2: {n_streams} streams/GPU x {N_PER} int32 symbols (stream-major), shared "
+                               f"12-bit QuantizedGaussian({LO},{HI},{MEAN},{STD}), AnsCoder (W,S,P)=({W},{S},{P}), "
+                               "encode into slabs + decode; u64 coder state, u32 words, i32 symbols", "streams_per_gpu": n_streams, "symbols_per_stream": N_PER,
+                   "parallelism": f"streams sharded over {world} GPU(s), no data-path collective"},
+    }
+    if not args.full:
+        # the figure's own check, on the device and after the timed steps: every rank decoded its input, no stream reported an error
+        ok = args.no_check or (bool(torch.equal(decoded, symbols)) and int(enc.status.abs().sum().item()) == 0)
+        if rank == 0:
+            print(json.dumps(contract_line(dict(headline, bit_exact=ok), detail=False)), flush=True)
+        return finish(dist, ok)
 
     # ---- per-kernel durations with HIP events on the launch stream (torch's current stream) ----
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
@@ -1210,7 +1277,6 @@ def main():
     dec_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
 
     total_words = enc.total_words()
-    n_sym = n_streams * N_PER
     # algorithmic bytes per launch: 4 B per int32 symbol + 4 B per compressed word, each way
     bytes_per_launch = 4 * n_sym + 4 * total_words
     # which kernels the dispatcher took for this shape on this box (the C2 shape: the producer / consumer encoder, cst_ans_pc.hip)
@@ -1269,17 +1335,7 @@ def main():
                 traffic = None
         dom_cold_ms = None if cold is None else (cold["encode_ms"] if dominant == enc_kernel else cold["decode_ms"])
         line = {
-            "metric": "Msymbols/s encode+decode, 64k x 4k-symbol streams, bit-exact vs CPU",
-            "value": round(world * n_sym * args.steps / elapsed / 1e6, 1),
-            "unit": "Msymbols/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u64", "data": "synthetic",
-            "config": {"workload": f"C2: {n_streams} streams/GPU x {N_PER} int32 symbols (stream-major), shared "
-                                   f"12-bit QuantizedGaussian({LO},{HI},{MEAN},{STD}), AnsCoder (W,S,P)=({W},{S},{P}), "
-                                   "encode into slabs + decode; u64 coder state, u32 words, i32 symbols", "streams_per_gpu": n_streams, "symbols_per_stream": N_PER,
-                       "parallelism": f"streams sharded over {world} GPU(s), no data-path collective"},
+            **headline,
             "bit_exact": ok, "bit_exact_scope": scope, "launch": launch_mode,
             "encode_ms": round(enc_ms, 4), "decode_ms": round(dec_ms, 4), "compact_ms": None if compact_ms is None else round(compact_ms, 4), "after_cache_flush": cold,
             "words_per_stream": round(total_words / n_streams, 2), "rate": rate_report(total_words, n_sym, W, model_entropy_bits(cdf, P)),
@@ -1305,6 +1361,10 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cdf, symbols.cpu().numpy())
         emit(line, args.detail_out)
+    finish(dist, ok)
+
+
+def finish(dist, ok):
     if dist is not None:
         try:
             dist.barrier()

@@ -9,7 +9,6 @@ from pathlib import Path
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 root = Path(__file__).resolve().parent.parent
 g, p = root / "gpurun_out", root / "profiles"
-shutil.copy(g / f"{tag}_bench.json", p / f"{tag}_bench.json")
 shutil.copy(g / f"{tag}_stats" / "bench.json", p / f"{tag}_bench_under_rocprof.json")
 (p / f"{tag}_api_variants.txt").write_text(
     f"# {tag}: scripts/bench_variants.py -- kernel times (HIP events, median of 5 launches each) of API variants around the headline shape,\n"

@@ -13,8 +13,8 @@ python scripts/bench_variants.py 2>&1 | grep -v amdgpu.ids > gpurun_out/${tag}_a
 python scripts/bench_per_symbol.py 2>&1 | grep -v amdgpu.ids > gpurun_out/${tag}_per_symbol.txt
 python scripts/bench_dropin_single_stream.py 2>&1 | grep -v amdgpu.ids > gpurun_out/${tag}_dropin_single_stream.txt
 scripts/microbench/bin/encstep > gpurun_out/${tag}_encstep.txt 2>&1
-python bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
-tail -c 400 gpurun_out/${tag}_bench.json
+python bench.py --full > profiles/${tag}_bench.json
+tail -c 400 profiles/${tag}_bench.json
 # the summaries are made HERE (gpurun merges at most 64 MiB back, the raw rocprofv3 outputs are more): profiles/<tag>_* of this
 # copy go home as gpurun_out/<tag>_profiles/, the raw directories stay behind
 python scripts/make_profile_summary.py $tag > gpurun_out/${tag}_summary.log 2>&1

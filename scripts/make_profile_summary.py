@@ -71,7 +71,7 @@ if trace.exists():
 
 fetch, write, l2 = pmc(f"{tag}_fetch"), pmc(f"{tag}_write"), pmc(f"{tag}_l2")
 traffic = {}
-lines = [f"# {tag}: rocprofv3 summary of `python bench.py --steps 20 --warmup 3 --no-cpu-baseline` (headline C2 + the `configs` block, 1 MI355X)", "",
+lines = [f"# {tag}: rocprofv3 summary of `python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline` (headline C2 + the `configs` block, 1 MI355X)", "",
          "Kernels by configuration: `ans_encode_pc_kernel` (coder + helper waves) and `ans_decode_kernel<32, 64, 0, true, ...8, true>` = C2 headline",
          "(`ans_encode_kernel<32, 64, 0, true, 8, ...>` = the one-wave encoder: batches the producer / consumer kernel does not take, here the tuner's odd strides); `ans_*_w16_kernel` = 16-bit words;",
          "`ans_encode_pc_kernel<true, false, true>` (the wide step) / `ans_decode_b16_kernel` = P = 24; `range_*_fast_kernel<...>` = C4 (`<1>`/`<false>`: P = 12, `<2>`/`<true>`: P = 24);",
@@ -118,7 +118,7 @@ if (hl / "bench_kernel_trace.csv").exists():
     for key, v in list(rows_h.items()):
         if len(v) > 2 * K + 1:
             rows_h[key] = v[-(2 * K + 1):-1]
-    lines += ["", f"## The timed loop alone: `python bench.py --steps 20 --warmup 3 --headline-only --no-check` under `rocprofv3 --kernel-trace`", "",
+    lines += ["", f"## The timed loop alone: `python bench.py --full --steps 20 --warmup 3 --headline-only --no-check` under `rocprofv3 --kernel-trace`", "",
               f"Only launches of the headline pair; the rows are the {2 * int(hb['steps'])} launches of the timed and the event-timed steps (the ramp and warmup launches in front of them run at rising clocks and are left out).  "
               f"The run's own line: encode {hb['encode_ms']} ms, decode {hb['decode_ms']} ms (HIP events), value {hb['value']} Msym/s; algorithmic bytes per launch {alg}.", "",
               "| kernel | grid | calls | avg us | median us | min | max | algorithmic / avg (GB/s) | of 8 TB/s | line's ms / avg |", "|---|---|---|---|---|---|---|---|---|---|"]

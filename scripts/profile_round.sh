@@ -7,7 +7,7 @@ set -u
 tag=${1:-r01}
 export TMPDIR=/tmp
 R=$PWD
-B="python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline"
+B="python $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline"
 # the slab strides bench.py measures at first use (batched.tuned_stride) are measured HERE, by an unprofiled run of the same
 # command, and remembered: the profiled runs below then hold the command's own launches only, not 63 measuring launches per
 # kernel at 21 other strides

@@ -19,7 +19,7 @@ def test_bench_with_two_ranks_on_one_gpu():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a GPU")
     env = dict(os.environ, CST_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--backend", "gloo", "--no-gather", "--steps", "3", "--warmup", "1",
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--no-gather", "--steps", "3", "--warmup", "1",
                           "--no-configs", "--no-cpu-baseline", "--no-end-to-end", "--slab-stride", "default"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
