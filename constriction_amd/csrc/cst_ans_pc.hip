@@ -9,6 +9,8 @@
 // cst_encode_loop_pc.inc -- and waves 4-7, their partners on the same SIMDs, do everything else (generated statements, too):
 //     loader (waves 4, 5; each for two coder waves), per tile:  next tile's symbols registers -> LDS tile buffer (requested two
 //                        tiles earlier), request a later one, s_barrier                          cst_encode_loop_pc_loader.inc
+//                        (round 7: it stages each symbol's TABLE ADDRESS, clamped into the table, and keeps the range check;
+//                        at the end, each row's largest raw table index -> the hand-off area)
 //     storer (waves 6, 7; each for two coder waves), per tile:  one complete 64-byte group below the write position the coder
 //                        last published ring -> slab (lane quads: whole 64-byte segments), s_barrier   cst_encode_loop_pc_storer.inc
 //     coder, per tile:   32 steps, candidate words into the lane's 64-slot LDS ring as before; once per tile: publish the
@@ -41,8 +43,8 @@ constexpr size_t kPcHandOff = kPcTileOff + kPcWaves * 2 * kPcTileBytes;
 constexpr size_t kPcLdsBytes = kPcHandOff + kPcWaves * kPcHandWaveBytes;
 static_assert(kPcLdsBytes <= 160 * 1024, "LDS budget");
 
-__device__ __forceinline__ void ans_encode_pc_coder_loop(uint32_t& lo, uint32_t& hi, int32_t& smin, int32_t& smax, const uint32_t (&tile_row_addr)[2],
-                                                         uint32_t ring_lane_addr, uint32_t publish_addr, uint32_t table_bias, uint32_t P, uint32_t n_tiles) {
+__device__ __forceinline__ void ans_encode_pc_coder_loop(uint32_t& lo, uint32_t& hi, const uint32_t (&tile_row_addr)[2], uint32_t ring_lane_addr,
+                                                         uint32_t publish_addr, uint32_t P, uint32_t n_tiles) {
 #include "cst_encode_loop_pc.inc"
 }
 
@@ -55,21 +57,21 @@ struct PcJumpArgs {
     uint32_t tiles, n_chunks;
 };
 
-__device__ __forceinline__ void ans_encode_pc_coder_loop_ck(uint32_t& lo, uint32_t& hi, int32_t& smin, int32_t& smax, const uint32_t (&tile_row_addr)[2],
-                                                            uint32_t ring_lane_addr, uint32_t publish_addr, uint32_t table_bias, uint32_t P, uint32_t n_tiles,
+__device__ __forceinline__ void ans_encode_pc_coder_loop_ck(uint32_t& lo, uint32_t& hi, const uint32_t (&tile_row_addr)[2], uint32_t ring_lane_addr,
+                                                            uint32_t publish_addr, uint32_t P, uint32_t n_tiles,
                                                             const uint32_t* ckpt_pos, const uint64_t* ckpt_state, uint32_t ckpt_tiles,
                                                             uint32_t ckpt_pos_off, uint32_t ckpt_state_off) {
 #include "cst_encode_loop_pc_ck.inc"
 }
 
 // ... at 12 < P <= 24 (round 5): unpacked entries {c, p, floor(2^64 / p)}, the step of cst_encode_loop_wide.inc
-__device__ __forceinline__ void ans_encode_pc_w_coder_loop(uint32_t& lo, uint32_t& hi, int32_t& smin, int32_t& smax, const uint32_t (&tile_row_addr)[2],
-                                                           uint32_t ring_lane_addr, uint32_t publish_addr, uint32_t table_bias, uint32_t P, uint32_t n_tiles) {
+__device__ __forceinline__ void ans_encode_pc_w_coder_loop(uint32_t& lo, uint32_t& hi, const uint32_t (&tile_row_addr)[2], uint32_t ring_lane_addr,
+                                                           uint32_t publish_addr, uint32_t P, uint32_t n_tiles) {
 #include "cst_encode_loop_pc_w.inc"
 }
 
-__device__ __forceinline__ void ans_encode_pc_w_coder_loop_ck(uint32_t& lo, uint32_t& hi, int32_t& smin, int32_t& smax, const uint32_t (&tile_row_addr)[2],
-                                                              uint32_t ring_lane_addr, uint32_t publish_addr, uint32_t table_bias, uint32_t P, uint32_t n_tiles,
+__device__ __forceinline__ void ans_encode_pc_w_coder_loop_ck(uint32_t& lo, uint32_t& hi, const uint32_t (&tile_row_addr)[2], uint32_t ring_lane_addr,
+                                                              uint32_t publish_addr, uint32_t P, uint32_t n_tiles,
                                                               const uint32_t* ckpt_pos, const uint64_t* ckpt_state, uint32_t ckpt_tiles,
                                                               uint32_t ckpt_pos_off, uint32_t ckpt_state_off) {
 #include "cst_encode_loop_pc_w_ck.inc"
@@ -77,12 +79,16 @@ __device__ __forceinline__ void ans_encode_pc_w_coder_loop_ck(uint32_t& lo, uint
 
 __device__ __forceinline__ void ans_encode_pc_helper_loop(uint32_t& flushed, const uint32_t (&tile_tr_addr)[2], uint32_t ring_lane_addr,
                                                           uint32_t publish_addr, uint32_t cap, uint32_t slab_off, const void* words_base,
-                                                          uint64_t symbols_base, uint32_t n_tiles, const uint32_t (&goff)[8]) {
+                                                          uint64_t symbols_base, uint32_t n_tiles, const uint32_t (&goff)[8], uint32_t table_bias,
+                                                          int32_t sym_lo, int32_t sym_hi, uint32_t bad_addr) {
 #include "cst_encode_loop_pc_helper.inc"
 }
 
+// (round 7) ... staging table addresses  table_bias + 16 clamp(symbol, sym_lo, sym_hi)  and the range check of every row it stages: at
+// the end, the row's largest raw table index to bad_addr + 4 row (+ kPcHandWaveBytes for the second coder wave)
 __device__ __forceinline__ void ans_encode_pc_loader_loop(const uint32_t (&tile_tr_addr)[2], uint64_t symbols_base, uint32_t row_block_bytes,
-                                                          uint32_t n_tiles, const uint32_t (&goff0)[8], const uint32_t (&goff1)[8]) {
+                                                          uint32_t n_tiles, const uint32_t (&goff0)[8], const uint32_t (&goff1)[8], uint32_t table_bias,
+                                                          int32_t sym_lo, int32_t sym_hi, uint32_t bad_addr) {
 #include "cst_encode_loop_pc_loader.inc"
 }
 
@@ -95,6 +101,12 @@ __device__ __forceinline__ void ans_encode_pc_storer_loop(uint32_t (&flushed)[2]
 __device__ __forceinline__ void ans_encode_pc_storer2_loop(uint32_t (&flushed)[2], const uint32_t (&ring_lane_addr)[2], const uint32_t (&publish_addr)[2],
                                                            const uint32_t (&cap)[2], const uint32_t (&slab_off)[2], const void* words_base, uint32_t n_tiles) {
 #include "cst_encode_loop_pc_storer2.inc"
+}
+
+// what the helper waves stage for a symbol: its table entry's LDS address, table + 16 (symbol - min_symbol) (the table at the
+// start of the workgroup's LDS)
+__device__ __forceinline__ uint32_t pc_table_bias(const AnsEncodeArgs& a, unsigned char* smem) {
+    return (uint32_t)__builtin_amdgcn_readfirstlane(lds_addr(smem) - 16u * (uint32_t)a.min_symbol);
 }
 
 // LDS hand-off between the two halves of a workgroup: this wave's LDS operations have completed, then the barrier.  (Not
@@ -171,7 +183,9 @@ __device__ __forceinline__ void pc_split_helper(const AnsEncodeArgs& a, unsigned
         const uint32_t tr_addr[2] = {t0, t0 + (uint32_t)kPcTileBytes};
         const uint32_t row_block = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)((first1 - first0) * N * 4));
         __builtin_amdgcn_s_waitcnt(0x0F70);             // vmcnt(0): the statement keeps its own book from here
-        ans_encode_pc_loader_loop(tr_addr, symbols_base, row_block, n_t, goff0, goff1);
+        const uint32_t bad_addr = lds_addr(smem + kPcHandOff + cw0 * kPcHandWaveBytes) + (uint32_t)((3 * kWave + (lane >> 3)) * 4);
+        ans_encode_pc_loader_loop(tr_addr, symbols_base, row_block, n_t, goff0, goff1, pc_table_bias(a, smem), a.min_symbol,
+                                  a.min_symbol + a.n_symbols - 1, bad_addr);
         pc_barrier();
         return;
     }
@@ -206,25 +220,20 @@ __global__ __launch_bounds__(kPcThreads) void ans_encode_pc_kernel(const AnsEnco
 
     if (!helper) {
         uint32_t lo = 0, hi = 0;
-        int32_t smin = a.min_symbol, smax = a.min_symbol;
         if (raw) { const uint64_t st = a.state[s]; lo = (uint32_t)st; hi = (uint32_t)(st >> 32); }
         const uint32_t row_addr[2] = {lds_addr(tile[0] + lane * kTileStride), lds_addr(tile[1] + lane * kTileStride)};
         pc_barrier();                                   // table and the first tile are in LDS
-        const uint32_t bias = lds_addr(table) - 16u * (uint32_t)a.min_symbol;
         const uint32_t jpos = (uint32_t)((s * jp.n_chunks + jp.n_chunks - 1) * 4), jstate = (uint32_t)((s * jp.n_chunks + jp.n_chunks - 1) * 8);
+        // (the tiles hold table addresses, and the helper waves that stage them report the range check: round 7)
         if constexpr (JUMP && WIDE)
-            ans_encode_pc_w_coder_loop_ck(lo, hi, smin, smax, row_addr, lds_addr(ring + lane), lds_addr(hand + lane), bias, (uint32_t)P, n_t, jp.pos, jp.state,
-                                          jp.tiles, jpos, jstate);
+            ans_encode_pc_w_coder_loop_ck(lo, hi, row_addr, lds_addr(ring + lane), lds_addr(hand + lane), (uint32_t)P, n_t, jp.pos, jp.state, jp.tiles, jpos, jstate);
         else if constexpr (JUMP)
-            ans_encode_pc_coder_loop_ck(lo, hi, smin, smax, row_addr, lds_addr(ring + lane), lds_addr(hand + lane), bias, (uint32_t)P, n_t, jp.pos, jp.state,
-                                        jp.tiles, jpos, jstate);
+            ans_encode_pc_coder_loop_ck(lo, hi, row_addr, lds_addr(ring + lane), lds_addr(hand + lane), (uint32_t)P, n_t, jp.pos, jp.state, jp.tiles, jpos, jstate);
         else if constexpr (WIDE)
-            ans_encode_pc_w_coder_loop(lo, hi, smin, smax, row_addr, lds_addr(ring + lane), lds_addr(hand + lane), bias, (uint32_t)P, n_t);
+            ans_encode_pc_w_coder_loop(lo, hi, row_addr, lds_addr(ring + lane), lds_addr(hand + lane), (uint32_t)P, n_t);
         else
-            ans_encode_pc_coder_loop(lo, hi, smin, smax, row_addr, lds_addr(ring + lane), lds_addr(hand + lane), bias, (uint32_t)P, n_t);
-        // largest raw table index seen: a symbol below min_symbol wraps to a huge one
+            ans_encode_pc_coder_loop(lo, hi, row_addr, lds_addr(ring + lane), lds_addr(hand + lane), (uint32_t)P, n_t);
         hand[kWave + lane] = lo; hand[2 * kWave + lane] = hi;
-        hand[3 * kWave + lane] = max((uint32_t)smax - (uint32_t)a.min_symbol, (uint32_t)smin - (uint32_t)a.min_symbol);
         pc_barrier();                                   // the last window and the final state are published
         return;
     }
@@ -247,7 +256,8 @@ __global__ __launch_bounds__(kPcThreads) void ans_encode_pc_kernel(const AnsEnco
     uint32_t flushed = 0;
     __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0): the statement keeps its own book from here
     ans_encode_pc_helper_loop(flushed, tr_addr, lds_addr(ring + lane), lds_addr(hand + lane), (uint32_t)a.stride_words,
-                              (uint32_t)(s * a.stride_words * 4), a.words, symbols_base, n_t, goff);
+                              (uint32_t)(s * a.stride_words * 4), a.words, symbols_base, n_t, goff, pc_table_bias(a, smem), a.min_symbol,
+                              a.min_symbol + a.n_symbols - 1, lds_addr(hand + 3 * kWave + (lane >> 3)));
     pc_barrier();                                       // the coder has published its last write position and the final state
     L.out.flushed = flushed;
     L.out.wr = hand[lane];

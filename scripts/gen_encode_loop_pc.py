@@ -9,8 +9,8 @@ each), reads complete word groups back from its ring, stores them and requests t
 the one wave, none of it memory time).  Here a second wave of the same workgroup -- the HELPER, compiler-scheduled C++ in
 cst_ans_pc.hip, on the same SIMD -- does all of that, and the wave generated below runs nothing but the coder steps:
 
-    quad g:  request the symbols of quad g-2 (one 16-B LDS read of the lane's tile row), fetch the four 16-B table
-             entries of quad g-1, fold quad g's symbols into smin / smax (the range check), run quad g's four steps.
+    quad g:  request the table addresses of quad g-2 (one 16-B LDS read of the lane's tile row: the loader stages addresses
+             and keeps the range check since round 7), fetch the four 16-B table entries of quad g-1, run quad g's four steps.
     words:   every step writes its candidate word to the lane's 64-slot LDS ring (layout [slot][lane]) and advances the
              write position if the word was really emitted (stack.rs:1035-1040), as in cst_encode_loop.inc.
     hand-off, once per tile at the top of quad 1 (every read of the current tile's row has returned by then):
@@ -143,22 +143,10 @@ def read_syms(a, g, buf, quad):
 
 
 def fetch_entries(a, g):
-    x, y, z, w = S[g % 4]
-    for i, sym in enumerate((w, z, y, x)):       # consumption order: .w first
-        ea = (EA0, EA1)[i & 1]
-        a.i(f"v_lshl_add_u32 {ea}, {sym}, 4, %[tbl]")
+    """the tile rows hold TABLE ADDRESSES, clamped into the table (round 7: the helper waves form them, stage_addrs below): one
+    LDS read per symbol and no VALU instruction.  The range check is the helpers', too: the coder's wave folds nothing."""
+    for i, ea in enumerate(reversed(S[g % 4])):       # consumption order: .w first
         a.ds(f"ds_read_b128 {E_T[g % 2][i]}, {ea}", f"E{g}")
-
-
-def fold_minmax(a, g):
-    """the range check: a symbol outside the model's support reads a garbage entry (harmless: LDS never faults) and flags its
-    stream at the end.  (Tried: one v_max3_u32 per two table ADDRESSES with the table at LDS address 0 -- half the
-    instructions, but (symbol - min) << 4 wraps for |symbol - min| >= 2^28 and such a symbol then passes as a valid one.)"""
-    x, y, z, w = S[g % 4]
-    a.i(f"v_max3_i32 %[smax], %[smax], {x}, {y}")
-    a.i(f"v_max3_i32 %[smax], %[smax], {z}, {w}")
-    a.i(f"v_min3_i32 %[smin], %[smin], {x}, {y}")
-    a.i(f"v_min3_i32 %[smin], %[smin], {z}, {w}")
 
 
 def hand_off(a):
@@ -230,7 +218,6 @@ def half(a, h, g0, site=0):
         fetch_entries(a, g + 1)
         if f"E{g}" in a.lds:
             a.wait_lds(f"E{g}", f"entries of quad {quad} are back", cap=True)
-        fold_minmax(a, g)
         for c, p, m0, m1 in E[g % 2]:
             coder_step(a, c, p, m0, m1)
     ck_hook(a, site)
@@ -285,8 +272,8 @@ def emit_coder(out):
     a, notes = gen()
     header = ["// GENERATED by scripts/gen_encode_loop_pc.py -- do not edit by hand (edit the generator and re-run it).",
               "// Coder half of the producer / consumer (32,64) ANS encoder: see ans_encode_pc_coder_loop in cst_ans_pc.hip."]
-    ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [smin] "+v"(smin), [smax] "+v"(smax)',
-           '    : [row0] "v"(tile_row_addr[0]), [row1] "v"(tile_row_addr[1]), [lanebase] "v"(ring_lane_addr), [pub] "v"(publish_addr), [tbl] "s"(table_bias),',
+    ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi)',
+           '    : [row0] "v"(tile_row_addr[0]), [row1] "v"(tile_row_addr[1]), [lanebase] "v"(ring_lane_addr), [pub] "v"(publish_addr),',
            '      [twoP] "v"(1u << P), [P] "s"(P), [c3f00] "s"(0x3f00u), [ntiles] "s"(n_tiles)' + (', [sh] "s"(32u - P)' if WIDE else '') + ck_operands(),
            "    : " + ", ".join(f'"{c}"' for c in CLOBBERS + ck_clobbers()) + ");"]
     out.write_text(a.render(header, ops))
@@ -307,6 +294,53 @@ def emit_coder(out):
 #       s_waitcnt lgkmcnt(0), s_barrier.
 # Past the last tile the statement keeps re-requesting and re-staging tile n - 1 (nobody reads those buffers any more).
 # ---------------------------------------------------------------------------------------------------------------------
+# ---------------------------------------------------------------------------------------------------------------------
+# Round 7: the helper that stages a tile stages TABLE ADDRESSES and keeps the range check -- the coder's wave spent one VALU
+# instruction per symbol on  symbol * 16 + table  and one on its min3 / max3 fold, and every instruction it issues costs it a
+# whole issue slot, while the helper's VALU work fills the SIMD's idle VALU cycles.  Per 4 staged symbols (one register of
+# the lane's row, rows (lane >> 3) + 8 k): min3 / max3 of the raw symbols into the lane's accumulators of row k (2 + 2),
+# v_med3_i32 into [min_symbol, max_symbol] (4: the address stays inside the table whatever the symbol) and
+# v_lshl_add_u32 (4).  At the end the 8 lanes of a row reduce their accumulators (DPP) and write the row's
+# "largest raw table index" -- what the coder's wave computed from its smin / smax until round 6 -- to the hand-off area.
+# ---------------------------------------------------------------------------------------------------------------------
+def stage_addrs(a, base, mn, mx):
+    """v[base .. base+3]: four symbols -> their table addresses, in place"""
+    r = [f"v{base + j}" for j in range(4)]
+    a.i(f"v_min3_i32 {mn}, {mn}, {r[0]}, {r[1]}", "the range check: raw symbols")
+    a.i(f"v_max3_i32 {mx}, {mx}, {r[0]}, {r[1]}")
+    a.i(f"v_min3_i32 {mn}, {mn}, {r[2]}, {r[3]}")
+    a.i(f"v_max3_i32 {mx}, {mx}, {r[2]}, {r[3]}")
+    for x in r:
+        a.i(f"v_med3_i32 {x}, {x}, %[symlo], %[symhi]")
+    for x in r:
+        a.i(f"v_lshl_add_u32 {x}, {x}, 4, %[tbl]", "table + 16 (symbol - min_symbol)")
+
+
+def range_init(a, accs):
+    for mn, mx in accs:
+        a.i(f"v_mov_b32 {mn}, %[symlo]")
+        a.i(f"v_mov_b32 {mx}, %[symlo]")
+
+
+def range_publish(a, accs, offsets):
+    """accs[j] = (min, max) of rows (lane >> 3) + 8 k: the row's min / max over its 8 lanes (xor 1, xor 2, the other quad of the
+    half row), then  max(smax - min_symbol, smin - min_symbol)  (unsigned: a symbol below min_symbol wraps to a huge index) to
+    the hand-off address + offsets[j] -- all 8 lanes of a row write the same word"""
+    a.i("s_nop 1", "(VALU write -> DPP read)")
+    for dpp in ("quad_perm:[1,0,3,2]", "quad_perm:[2,3,0,1]", "row_half_mirror"):
+        for mn, mx in accs:
+            a.i(f"v_min_i32_dpp {mn}, {mn}, {mn} {dpp} row_mask:0xf bank_mask:0xf")
+            a.i(f"v_max_i32_dpp {mx}, {mx}, {mx} {dpp} row_mask:0xf bank_mask:0xf")
+    for (mn, mx), off in zip(accs, offsets):
+        a.i(f"v_sub_u32 {mn}, {mn}, %[symlo]")
+        a.i(f"v_sub_u32 {mx}, {mx}, %[symlo]")
+        a.i(f"v_max_u32 {mx}, {mx}, {mn}")
+        a.ds(f"ds_write_b32 %[bad], {mx} offset:{off}", "bad", "largest raw table index of the row")
+
+
+HAND_WAVE_BYTES = 4 * 64 * 4                               # kPcHandWaveBytes
+
+
 OUT_HELPER = CSRC / "cst_encode_loop_pc_helper.inc"
 NSETS = int(os.environ.get("GEN_NSETS", "3"))           # register sets of prefetched tiles: a tile is requested NSETS windows before it is staged
 HBASE = 234 - 32 * NSETS
@@ -315,7 +349,7 @@ HR = {n: [tup(HBASE + 32 * i + 4 * k) for k in range(8)] for i, n in enumerate(S
 HFD = [(tup(234 + 4 * k, 2), tup(236 + 4 * k, 2), tup(234 + 4 * k)) for k in range(4)]
 HWR, HNCH, HLIM, HFADDR, HFOFF = (f"v{r}" for r in range(250, 255))
 HSAVE = "s[86:87]"
-H_CLOBBERS = [f"v{r}" for r in range(HBASE, 255)] + [f"s{r}" for r in range(80, 90)] + ["vcc", "scc", "memory"]
+H_CLOBBERS = [f"v{r}" for r in range(100, 116)] + [f"v{r}" for r in range(HBASE, 255)] + [f"s{r}" for r in range(80, 90)] + ["vcc", "scc", "memory"]
 HTR = ["%[tr0]", "%[tr1]"]
 
 
@@ -340,9 +374,14 @@ def h_load_set(a, name):
     h_advance_base(a)
 
 
+HACC = [(f"v{100 + 2 * k}", f"v{101 + 2 * k}") for k in range(8)]      # range check of rows (lane >> 3) + 8 k (below HBASE)
+assert HBASE >= 116
+
+
 def h_stage_set(a, name, buf):
     a.wait_vm(f"ld{name}", f"symbols in set {name} have arrived")
     for k in range(8):
+        stage_addrs(a, HBASE + 32 * SETS.index(name) + 4 * k, *HACC[k])
         a.ds(f"ds_write_b128 {HTR[buf]}, {HR[name][k]} offset:{1152 * k}", "tl")
 
 
@@ -407,6 +446,7 @@ def h_window(a, w):
 
 def gen_helper():
     a = Asm()
+    range_init(a, HACC)
     a.i("s_mov_b64 s[80:81], %[sbase]", "symbols of the LAST full tile of stream s0: tile 0")
     a.i("s_mov_b32 s82, %[ntiles]", "windows left")
     a.i("s_sub_u32 s83, %[ntiles], 1", "tiles left to request")
@@ -433,6 +473,7 @@ def gen_helper():
     assert HABL or (lds_end == a.lds and vm_end == a.vm), (vm_end, a.vm)
     a.i("2:")
     a.wait_vm_all("nothing may land in the scratch registers after the statement")
+    range_publish(a, HACC, [32 * k for k in range(8)])
     a.wait_lds_all()
     return a, notes
 
@@ -444,6 +485,7 @@ def main_helper():
     ops = ['    : [flushed] "+v"(flushed)',
            '    : [tr0] "v"(tile_tr_addr[0]), [tr1] "v"(tile_tr_addr[1]), [lanebase] "v"(ring_lane_addr), [pub] "v"(publish_addr),',
            '      [cap] "v"(cap), [slaboff] "v"(slab_off), [c3f00] "s"(0x3f00u), [wbase] "s"(words_base), [sbase] "s"(symbols_base), [ntiles] "s"(n_tiles),',
+           '      [tbl] "s"(table_bias), [symlo] "v"(sym_lo), [symhi] "v"(sym_hi), [bad] "v"(bad_addr),',
            '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in H_CLOBBERS) + ");"]
     OUT_HELPER.write_text(a.render(header, ops))
@@ -466,6 +508,8 @@ LSETS = int(os.environ.get("GEN_LSETS", "2"))           # register sets per code
 LSLEEP = int(os.environ.get("GEN_LSLEEP", "0"))         # experiment: spread a window's 16 requests over the window (64 LSLEEP cycles after each)
 LBASE = 228 - 64 * LSETS
 LR = {(c, i): [tup(LBASE + 32 * (LSETS * c + i) + 4 * k) for k in range(8)] for c in range(2) for i in range(LSETS)}
+LACC = {(c, k): (f"v{68 + 16 * c + 2 * k}", f"v{69 + 16 * c + 2 * k}") for c in range(2) for k in range(8)}   # range check (v68 .. v99)
+assert LBASE >= 100
 L_CLOBBERS = [f"v{r}" for r in range(LBASE, 228)] + [f"s{r}" for r in range(80, 90)] + ["vcc", "scc", "memory"]
 PAIR_TILE_OFF = 2 * 64 * 36 * 4                          # the partner coder's two tile buffers follow this one's
 
@@ -498,11 +542,13 @@ def l_stage(a, i, buf):
             if "stage32" in HABL:                 # a quarter of the register-file reads and LDS writes of the staging
                 a.ds(f"ds_write_b32 {HTR[buf]}, v{LBASE + 32 * (LSETS * c + i) + 4 * k} offset:{PAIR_TILE_OFF * c + 1152 * k}", "tl")
                 continue
+            stage_addrs(a, LBASE + 32 * (LSETS * c + i) + 4 * k, *LACC[(c, k)])
             a.ds(f"ds_write_b128 {HTR[buf]}, {LR[(c, i)][k]} offset:{PAIR_TILE_OFF * c + 1152 * k}", "tl")
 
 
 def gen_loader():
     a = Asm()
+    range_init(a, LACC.values())
     a.i("s_mov_b64 s[80:81], %[sbase]", "symbols of the LAST full tile of the pair's first stream: tile 0")
     a.i("s_add_u32 s84, s80, %[rowblock]", "... and of the second coder wave's first stream")
     a.i("s_addc_u32 s85, s81, 0")
@@ -535,6 +581,7 @@ def gen_loader():
     assert HABL or (lds_end == a.lds and vm_end == a.vm), (vm_end, a.vm)
     a.i("2:")
     a.wait_vm_all("nothing may land in the scratch registers after the statement")
+    range_publish(a, list(LACC.values()), [HAND_WAVE_BYTES * c + 32 * k for c, k in LACC])
     a.wait_lds_all()
     return a, notes
 
@@ -690,9 +737,10 @@ def main_split():
               "// Loader wave of the producer / consumer (32,64) ANS encoder: see ans_encode_pc_loader_loop in cst_ans_pc.hip."]
     ops = ['    :',
            '    : [tr0] "v"(tile_tr_addr[0]), [tr1] "v"(tile_tr_addr[1]), [sbase] "s"(symbols_base), [rowblock] "s"(row_block_bytes), [ntiles] "s"(n_tiles),',
+           '      [tbl] "s"(table_bias), [symlo] "v"(sym_lo), [symhi] "v"(sym_hi), [bad] "v"(bad_addr),',
            '      ' + ", ".join(f'[goff0_{k}] "v"(goff0[{k}])' for k in range(8)) + ",",
            '      ' + ", ".join(f'[goff1_{k}] "v"(goff1[{k}])' for k in range(8)),
-           "    : " + ", ".join(f'"{c}"' for c in L_CLOBBERS) + ");"]
+           "    : " + ", ".join(f'"{c}"' for c in [f"v{r}" for r in range(68, 100)] + L_CLOBBERS) + ");"]
     OUT_LOADER.write_text(a.render(header, ops))
     print(f"wrote {OUT_LOADER} ({a.n_instr()} instructions incl. prologue)")
     for n in notes:
