@@ -1386,6 +1386,89 @@ extern "C" {
     /// library's pool.
     pub fn cst_release_scratch() -> CstStatus;
 
+    /// HOST function: the reference's tree (huffman.rs:62-116, 200-230) for n probabilities: pop the two smallest
+    /// (probability, index) pairs -- ties on the smaller index; the first popped becomes bit 0 -- and push their sum as inner
+    /// node n, n+1, ... .  Writes h_nodes[2n - 1], the encoder representation: node i holds parent << 1 | bit, 0 marks the root.
+    /// f32_sums != 0: probabilities are f32 values and every sum is an f32 addition (the reference adds in the input's float
+    /// type, which changes trees).  CST_ERR_MODEL for n == 0 and for NaN, negative or infinite probabilities.
+    pub fn cst_huffman_tree(h_probs: *const f64, n: usize, f32_sums: i32, h_nodes: *mut u64) -> CstStatus;
+
+    /// Device codebook from h_nodes[2n - 1] (cst_huffman_tree), 1 <= n <= CST_HUFFMAN_MAX_SYMBOLS: codewords in both bit orders
+    /// (codewords of more than 32 bits -- up to ~3000 for f64 probabilities -- in a bit pool the encoder reads out of line), the
+    /// decode table of the first 12 bits and the inner nodes the decoder walks past it.  *out is an opaque handle (void *), for
+    /// the coder calls below and cst_huffman_codebook_destroy.  CST_ERR_MODEL if h_nodes is not such a tree; synchronises
+    /// `stream`.
+    pub fn cst_huffman_codebook_create(
+        h_nodes: *const u64,
+        n: usize,
+        stream: *mut c_void,
+        out: *mut *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_huffman_codebook_destroy(codebook: *mut c_void) -> CstStatus;
+
+    /// Slab stride (in words) that holds any stream of n_per_stream symbols: every codeword at the codebook's longest, the up to
+    /// 31 bits a continued call (d_cont) starts with and the seal, rounded up to whole 64-byte units.  0 for a bad argument.
+    pub fn cst_huffman_max_words(codebook: *const c_void, n_per_stream: usize, semantics: i32) -> usize;
+
+    /// Replaces, for every stream s:
+    ///     coder = StackCoder(); for x in reversed(symbols[s]): coder.encode_symbol(x, tree)     (semantics CST_HUFFMAN_STACK)
+    ///     coder = QueueEncoder(); for x in symbols[s]: coder.encode_symbol(x, tree)             (CST_HUFFMAN_QUEUE)
+    ///     d_words[s*stride_words ..], d_n_bits[s] = coder.get_compressed_and_bitrate()           (pybindings/symbol/mod.rs:207-221)
+    /// d_symbols    stream-major [n_streams][n_per_stream], int32 (symbol_bytes 4) or uint8 (1)
+    /// d_n_bits     out (may be NULL): the bitrate, the written bits without the seal (mod.rs:205-220)
+    /// d_cont       in/out (may be NULL): the container's partial word, partial | nbits << 32 with nbits < 32.  Given, the call
+    ///              continues from it and neither seals nor flushes the partial word: d_words gets the completed words only and
+    ///              d_cont the new partial word (what the single-coder drop-in keeps between calls).
+    /// d_status     a symbol < 0 or >= n: CST_STREAM_IMPOSSIBLE_SYMBOL (huffman.rs:134-137); a slab too small: CST_STREAM_CAPACITY.
+    ///              Either way n_words (and n_bits) are 0 and d_cont is left as it was.
+    /// cst_last_kernel_name: "huffman_encode_kernel", or "huffman_encode_long_kernel" for a codebook with codewords of more than
+    /// 32 bits.
+    pub fn cst_huffman_encode_batch(
+        codebook: *const c_void,
+        semantics: i32,
+        d_symbols: *const c_void,
+        symbol_bytes: i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_n_bits: *mut u64,
+        d_cont: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// Replaces, for every stream s, StackCoder(words[s]) resp. QueueDecoder(words[s]) and n_per_stream decode_symbol calls.  The
+    /// words of stream s are d_words[off(s) .. off(s) + d_n_words[s]) with off(s) = d_offsets ? d_offsets[s] : s * stride_words,
+    /// and words_capacity bounds them as for cst_ans_decode_batch.  symbol_bytes 1 needs n <= 256.
+    /// A stack stream is found by its seal, the HIGHEST set bit of its last word (the reference's from_compressed
+    /// looks at the lowest); no words or a zero last word: CST_STREAM_INVALID_DATA.  Running out of bits inside a codeword:
+    /// CST_STREAM_OUT_OF_DATA ("Ran out of bits in compressed data.", pybindings/symbol/mod.rs:386-395); the symbols from there on
+    /// read 0 and, as in the reference, every bit counts as read.
+    /// d_cont       in/out (may be NULL).  Queue: the read position in bits.  Stack: the partial word on top of the d_n_words[s]
+    ///              full words, partial | nbits << 32 (nbits < 32), instead of the seal search.  Out: the same after decoding.
+    /// d_n_words_out out (may be NULL).  Stack: the full words left below the partial word; queue: the words begun.
+    /// cst_last_kernel_name: "huffman_decode_kernel", or "huffman_decode_long_kernel" for codewords of more than 12 bits.
+    pub fn cst_huffman_decode_batch(
+        codebook: *const c_void,
+        semantics: i32,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_symbols: *mut c_void,
+        symbol_bytes: i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        d_cont: *mut u64,
+        d_n_words_out: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// bit-exact f64 special functions on device (test hooks for the model kernels)
     /// out[i] = erf(x[i]) resp. Gaussian cdf, evaluated by the same device code the table kernels use.
     pub fn cst_debug_erf(d_x: *const f64, d_out: *mut f64, n: usize, stream: *mut c_void) -> CstStatus;

@@ -2480,3 +2480,101 @@ impl Drop for Communicator {
         unsafe { ffi::cst_rccl_comm_destroy(self.raw) };
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Huffman symbol codes (constriction.symbol)
+// ---------------------------------------------------------------------------------------------------------------------
+
+/// `StackCoder` (last in, first out, sealed) or `QueueEncoder` / `QueueDecoder` (first in, first out): src/symbol/mod.rs.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum SymbolSemantics {
+    Stack = 0,
+    Queue = 1,
+}
+
+/// A device-resident Huffman codebook shared by every stream of a batch (`EncoderHuffmanTree` and `DecoderHuffmanTree` in one).
+pub struct HuffmanCodebook {
+    raw: *mut c_void,
+    n_symbols: usize,
+}
+
+/// The words, bitrates and statuses of a batched Huffman encode.
+pub struct HuffmanBatch {
+    pub words: DeviceBuffer<u32>,
+    pub n_words: DeviceBuffer<u32>,
+    pub n_bits: DeviceBuffer<u64>,
+    pub status: DeviceBuffer<i32>,
+    pub stride_words: usize,
+    pub n_streams: usize,
+    pub semantics: SymbolSemantics,
+}
+
+impl HuffmanCodebook {
+    /// The reference's tree construction (src/symbol/huffman.rs:62-116); `f32_sums`: the probabilities are f32 values and are
+    /// added in f32, as `EncoderHuffmanTree(np.float32 array)` does.
+    pub fn tree(probabilities: &[f64], f32_sums: bool) -> Result<Vec<u64>> {
+        let mut nodes = vec![0u64; (2 * probabilities.len()).saturating_sub(1)];
+        check(unsafe { ffi::cst_huffman_tree(probabilities.as_ptr(), probabilities.len(), f32_sums as i32, nodes.as_mut_ptr()) })?;
+        Ok(nodes)
+    }
+
+    pub fn from_probabilities(probabilities: &[f64], f32_sums: bool, stream: &Stream) -> Result<Self> {
+        let nodes = Self::tree(probabilities, f32_sums)?;
+        let mut raw: *mut c_void = core::ptr::null_mut();
+        check(unsafe { ffi::cst_huffman_codebook_create(nodes.as_ptr(), probabilities.len(), stream.as_raw(), &mut raw) })?;
+        Ok(HuffmanCodebook { raw, n_symbols: probabilities.len() })
+    }
+
+    pub fn n_symbols(&self) -> usize {
+        self.n_symbols
+    }
+
+    /// Slab stride that holds any stream of `n_per_stream` symbols.
+    pub fn max_words(&self, n_per_stream: usize, semantics: SymbolSemantics) -> usize {
+        unsafe { ffi::cst_huffman_max_words(self.raw, n_per_stream, semantics as i32) }
+    }
+
+    /// One container per row of the stream-major `symbols` matrix (`n_streams` rows of `n_per_stream`), each sealed / flushed.
+    pub fn encode(&self, symbols: &DeviceBuffer<i32>, n_streams: usize, n_per_stream: usize, semantics: SymbolSemantics,
+                  stream: &Stream) -> Result<HuffmanBatch> {
+        if symbols.len() < n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)? {
+            return Err(Error::InvalidArgument);
+        }
+        let stride_words = self.max_words(n_per_stream, semantics);
+        let mut out = HuffmanBatch {
+            words: DeviceBuffer::new(n_streams.checked_mul(stride_words).ok_or(Error::InvalidArgument)?)?,
+            n_words: DeviceBuffer::new(n_streams)?,
+            n_bits: DeviceBuffer::new(n_streams)?,
+            status: DeviceBuffer::new(n_streams)?,
+            stride_words,
+            n_streams,
+            semantics,
+        };
+        check(unsafe {
+            ffi::cst_huffman_encode_batch(self.raw, semantics as i32, symbols.as_ptr() as *const c_void, 4, n_streams, n_per_stream,
+                                          out.words.as_mut_ptr(), stride_words, out.n_words.as_mut_ptr(), out.n_bits.as_mut_ptr(),
+                                          core::ptr::null_mut(), out.status.as_mut_ptr(), stream.as_raw())
+        })?;
+        Ok(out)
+    }
+
+    /// `n_per_stream` symbols of every stream of `batch`; writes `symbols` (stream-major) and one status per stream.
+    pub fn decode(&self, batch: &HuffmanBatch, n_per_stream: usize, symbols: &mut DeviceBuffer<i32>, status: &mut DeviceBuffer<i32>,
+                  stream: &Stream) -> Result<()> {
+        if symbols.len() < batch.n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)? || status.len() < batch.n_streams {
+            return Err(Error::InvalidArgument);
+        }
+        check(unsafe {
+            ffi::cst_huffman_decode_batch(self.raw, batch.semantics as i32, batch.words.as_ptr(), core::ptr::null(), batch.stride_words,
+                                          batch.words.len(), batch.n_words.as_ptr(), symbols.as_mut_ptr() as *mut c_void, 4,
+                                          batch.n_streams, n_per_stream, core::ptr::null_mut(), core::ptr::null_mut(),
+                                          status.as_mut_ptr(), stream.as_raw())
+        })
+    }
+}
+
+impl Drop for HuffmanCodebook {
+    fn drop(&mut self) {
+        unsafe { ffi::cst_huffman_codebook_destroy(self.raw) };
+    }
+}

@@ -1,0 +1,170 @@
+"""Batched Huffman symbol codes (re-exported by `constriction_amd.batched`): one bit container per stream, one codebook shared by
+the batch, coded by the kernels of csrc/cst_huffman.hip (include/constriction_amd.h, "Huffman symbol codes").
+
+A stack batch row s holds what the reference's `StackCoder` holds after `encode_symbol` of symbols[s] last to first and
+`get_compressed_and_bitrate()` (src/pybindings/symbol/mod.rs:207-221); it decodes to symbols[s] in order, the convention of
+`ans_encode`.  A queue batch row holds `QueueEncoder` after `encode_symbol` of symbols[s] first to last."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _native as N
+from .batched import EncodedBatch, _ptr, _require_cuda, _stream_ptr
+
+_SEMANTICS = {"stack": N.HUFFMAN_STACK, "queue": N.HUFFMAN_QUEUE}
+_SYMBOL_BYTES = {torch.int32: 4, torch.uint8: 1}
+
+
+def _semantics(semantics) -> int:
+    if semantics not in _SEMANTICS:
+        raise ValueError(f"semantics must be 'stack' or 'queue', not {semantics!r}")
+    return _SEMANTICS[semantics]
+
+
+def huffman_tree(probabilities) -> np.ndarray:
+    """The reference's tree (src/symbol/huffman.rs:62-116) as its encoder representation, nodes[2n - 1] (uint64: parent << 1 |
+    bit, 0 at the root).  float32 probabilities are added in float32, float64 in float64, as the reference does.
+    NaN raises FloatingPointError (src/pybindings/mod.rs:245-250); negative or infinite values, which the reference documents as
+    invalid (src/pybindings/symbol/huffman.rs:35-45) without checking them, raise ValueError."""
+    if isinstance(probabilities, torch.Tensor):
+        probabilities = probabilities.detach().cpu().numpy()
+    p = np.asarray(probabilities)
+    if p.ndim != 1 or p.dtype not in (np.float32, np.float64):
+        raise TypeError("probabilities must be a rank-1 array of dtype float32 or float64")
+    if p.size == 0:
+        raise ValueError("a Huffman tree needs at least one symbol")
+    if np.isnan(p).any():
+        raise FloatingPointError("Floating point value is not a number (NaN).")
+    wide = np.ascontiguousarray(p, dtype=np.float64)
+    nodes = np.zeros(2 * p.size - 1, dtype=np.uint64)
+    st = N.load_library().cst_huffman_tree(wide.ctypes.data, p.size, int(p.dtype == np.float32), nodes.ctypes.data)
+    if st == N.CST_ERR_MODEL:
+        raise ValueError("probabilities must be nonnegative and finite")
+    N.check(st, "cst_huffman_tree")
+    return nodes
+
+
+class HuffmanCodebook:
+    """Device codebook (cst_huffman_codebook_create) shared by every stream of a batch: the encoder's codewords in both bit orders
+    and the decoder's table, from one tree."""
+
+    def __init__(self, nodes: np.ndarray):
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint64)
+        n = (nodes.size + 1) // 2
+        if nodes.ndim != 1 or nodes.size != 2 * n - 1 or n < 1:
+            raise ValueError("nodes must hold 2n - 1 entries")
+        if n > N.HUFFMAN_MAX_SYMBOLS:
+            raise ValueError(f"Huffman codebooks take at most {N.HUFFMAN_MAX_SYMBOLS} symbols")
+        L = N.lib()
+        h = C.c_void_p()
+        N.check(L.cst_huffman_codebook_create(nodes.ctypes.data, n, _stream_ptr(), C.byref(h)), "cst_huffman_codebook_create")
+        self._h = h
+        self.nodes = nodes
+        self.n_symbols = n
+
+    @classmethod
+    def from_probabilities(cls, probabilities) -> "HuffmanCodebook":
+        """float32 or float64 probabilities (the dtype selects the type the tree adds in)"""
+        return cls(huffman_tree(probabilities))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                N.load_library().cst_huffman_codebook_destroy(h)
+            except Exception:
+                pass
+
+    def max_words(self, n_per_stream: int, semantics="stack") -> int:
+        """slab stride that holds any stream of n_per_stream symbols (cst_huffman_max_words)"""
+        return N.load_library().cst_huffman_max_words(self._h, n_per_stream, _semantics(semantics))
+
+
+@dataclass
+class HuffmanBatch(EncodedBatch):
+    """Slabs of a batched Huffman encode: stream s is words[s, :n_words[s]], bitrate n_bits[s] (the written bits without a
+    stack's seal).  `stream(s)` is `get_compressed_and_bitrate()[0]` of the reference's coder for row s; `batched.compact`
+    packs the slabs."""
+    n_bits: Optional[torch.Tensor] = None
+    semantics: str = "stack"
+
+
+def _symbols_arg(symbols: torch.Tensor):
+    if not symbols.is_cuda:
+        raise ValueError("symbols must live in device memory (HBM)")
+    if symbols.dtype not in _SYMBOL_BYTES:
+        raise TypeError("Huffman symbols are int32 or uint8")
+    if symbols.dim() != 2:
+        raise ValueError("symbols must be a [n_streams, n_per_stream] matrix (stream-major)")
+    return symbols.contiguous(), _SYMBOL_BYTES[symbols.dtype]
+
+
+def huffman_encode(symbols: torch.Tensor, codebook: HuffmanCodebook, semantics="stack", stride: Optional[int] = None,
+                   out: Optional[HuffmanBatch] = None) -> HuffmanBatch:
+    """Row s of the int32 / uint8 matrix `symbols` into its own stack (`StackCoder`, rows consumed last to first, sealed) or
+    queue (`QueueEncoder`).  A symbol outside 0..n-1 leaves its stream with status IMPOSSIBLE_SYMBOL and 0 words, a slab that is
+    too small (`stride` below `codebook.max_words`) with CAPACITY.  `out` (a HuffmanBatch of an earlier call with as many streams)
+    is reused as it is: its slab stride holds, and `stride` is ignored, as for `ans_encode`."""
+    sem = _semantics(semantics)
+    symbols, sb = _symbols_arg(symbols)
+    n_streams, n_per = symbols.shape
+    dev = symbols.device
+    if out is None:
+        stride = stride if stride is not None else codebook.max_words(n_per, semantics)
+        out = HuffmanBatch(torch.empty((n_streams, stride), dtype=torch.int32, device=dev),
+                           torch.empty(n_streams, dtype=torch.int32, device=dev), torch.empty(n_streams, dtype=torch.int32, device=dev),
+                           config=None, n_bits=torch.empty(n_streams, dtype=torch.int64, device=dev), semantics=semantics)
+    else:
+        if out.words.dim() != 2 or out.words.shape[0] != n_streams or out.n_words.numel() != n_streams or \
+                out.status.numel() != n_streams or out.n_bits is None or out.n_bits.numel() != n_streams:
+            raise ValueError("out must be a HuffmanBatch with one row per stream")
+        for t, dt, name in ((out.words, torch.int32, "out.words"), (out.n_words, torch.int32, "out.n_words"),
+                            (out.status, torch.int32, "out.status"), (out.n_bits, torch.int64, "out.n_bits")):
+            if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous device tensor of dtype {dt}")
+        out.semantics = semantics
+    N.check(N.lib().cst_huffman_encode_batch(codebook._h, sem, _ptr(symbols), sb, n_streams, n_per, _ptr(out.words),
+                                             out.words.shape[1], _ptr(out.n_words), _ptr(out.n_bits), None, _ptr(out.status),
+                                             _stream_ptr()), "cst_huffman_encode_batch")
+    return out
+
+
+def huffman_decode(encoded, codebook: HuffmanCodebook, n_per_stream: int, semantics=None, offsets: Optional[torch.Tensor] = None,
+                   dtype=torch.int32):
+    """n_per_stream symbols of every stream -> (symbols [n_streams, n_per_stream] of `dtype` (int32 or uint8), status int32).
+
+    `encoded` is a HuffmanBatch (its semantics unless given) or (words, n_words): slabs [n_streams, stride], or with `offsets`
+    (int64 [n_streams + 1], `batched.compact`) the packed words.  A stack stream without its seal reports INVALID_DATA, a
+    stream that runs out of bits OUT_OF_DATA (its symbols from there on read 0)."""
+    if isinstance(encoded, HuffmanBatch):
+        words, n_words = encoded.words, encoded.n_words
+        semantics = semantics or encoded.semantics
+    else:
+        words, n_words = encoded
+    if semantics is None:
+        raise ValueError("semantics ('stack' or 'queue') is needed for plain words")
+    sem = _semantics(semantics)
+    if dtype not in _SYMBOL_BYTES:
+        raise TypeError("Huffman symbols are int32 or uint8")
+    words = _require_cuda(words, torch.int32, "words")
+    n_words = _require_cuda(n_words, torch.int32, "n_words")
+    if offsets is not None:
+        offsets = _require_cuda(offsets, torch.int64, "offsets")
+        if offsets.numel() < n_words.numel():
+            raise ValueError("offsets needs one entry per stream")
+    elif words.dim() != 2 or words.shape[0] < n_words.numel():
+        raise ValueError("slab words must be a [n_streams, stride] matrix (or give offsets for packed words)")
+    stride = 0 if offsets is not None else words.shape[1]
+    n_streams = n_words.numel()
+    dev = words.device
+    out = torch.empty((n_streams, n_per_stream), dtype=dtype, device=dev)
+    status = torch.empty(n_streams, dtype=torch.int32, device=dev)
+    N.check(N.lib().cst_huffman_decode_batch(codebook._h, sem, _ptr(words), _ptr(offsets), stride, words.numel(), _ptr(n_words),
+                                             _ptr(out), _SYMBOL_BYTES[dtype], n_streams, n_per_stream, None, None, _ptr(status),
+                                             _stream_ptr()), "cst_huffman_decode_batch")
+    return out, status

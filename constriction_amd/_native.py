@@ -35,6 +35,9 @@ FLAG_PACKED_W16 = 4
 
 CODER_ANS, CODER_RANGE = 0, 1
 
+HUFFMAN_STACK, HUFFMAN_QUEUE = 0, 1
+HUFFMAN_MAX_SYMBOLS = 65536
+
 
 class BackendUnavailable(RuntimeError):
     """The HIP extension (or a GPU) is missing.  The product path never falls back to the CPU."""
@@ -149,6 +152,12 @@ SIGNATURES = {
     "cst_debug_family_fn": (_i32, [_i32, _vp, _vp, _z, _vp]),
     "cst_debug_host_log1p": (_f64, [_f64]),
     "cst_release_scratch": (_i32, []),
+    "cst_huffman_tree": (_i32, [_vp, _z, _i32, _vp]),
+    "cst_huffman_codebook_create": (_i32, [_vp, _z, _vp, C.POINTER(_vp)]),
+    "cst_huffman_codebook_destroy": (_i32, [_vp]),
+    "cst_huffman_max_words": (_z, [_vp, _z, _i32]),
+    "cst_huffman_encode_batch": (_i32, [_vp, _i32, _vp, _i32, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_huffman_decode_batch": (_i32, [_vp, _i32, _vp, _vp, _z, _z, _vp, _vp, _i32, _z, _z, _vp, _vp, _vp, _vp]),
     "cst_debug_erf": (_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_tab": (_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_fast": (_i32, [_i32, _vp, _vp, _z, _vp]),

@@ -1409,3 +1409,10 @@ def ans_decode_gaussian_checkpointed(encoded: EncodedBatch, checkpoints: Checkpo
                                                  _ptr(checkpoints.state), _ptr(means), _ptr(stds), _ptr(out), n_streams, n_per, _ptr(scratch),
                                                  _ptr(status), _stream_ptr()), "cst_ans_decode_gaussian_batch_ckpt")
     return out, status
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Huffman symbol codes (constriction.symbol): one bit container per stream, a shared codebook (_huffman.py)
+# ---------------------------------------------------------------------------------------------------------------------
+
+from ._huffman import HuffmanBatch, HuffmanCodebook, huffman_decode, huffman_encode, huffman_tree  # noqa: E402,F401

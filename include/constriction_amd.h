@@ -779,6 +779,74 @@ cst_status cst_chain_decode_rows_batch(cst_coder_config cfg, const uint32_t *d_p
 cst_status cst_release_scratch(void);
 
 /* ------------------------------------------------------------------------------------------
+ * Huffman symbol codes: constriction.symbol (src/symbol/mod.rs, src/symbol/huffman.rs, src/pybindings/symbol/)
+ *
+ * The reference's StackCoder / QueueEncoder / QueueDecoder with huffman.EncoderHuffmanTree / DecoderHuffmanTree codebooks,
+ * one independent bit container per stream and ONE codebook shared by the batch.  Bits go into u32 words from bit 0
+ * upwards (mod.rs:376-393, 600-617).  A stack (CST_HUFFMAN_STACK) writes each codeword leaf to root (huffman.rs:128-155),
+ * consumes a stream's symbols BACK TO FRONT, ends with one seal bit `1` and is read from the last written bit downwards
+ * (mod.rs:642-655); row s then decodes to symbols[s, 0..n) in order, the convention of cst_ans_encode_batch.  A queue
+ * (CST_HUFFMAN_QUEUE) writes root to leaf (mod.rs:722-737), front to back, without a seal, and is read from bit 0 upwards
+ * (mod.rs:438-455).
+ * ---------------------------------------------------------------------------------------- */
+#define CST_HUFFMAN_STACK 0
+#define CST_HUFFMAN_QUEUE 1
+/* largest alphabet a codebook takes (cst_huffman_codebook_create: CST_ERR_INVALID_ARGUMENT beyond) */
+#define CST_HUFFMAN_MAX_SYMBOLS 65536
+
+/* HOST function: the reference's tree (huffman.rs:62-116, 200-230) for n probabilities: pop the two smallest
+ * (probability, index) pairs -- ties on the smaller index; the first popped becomes bit 0 -- and push their sum as inner
+ * node n, n+1, ... .  Writes h_nodes[2n - 1], the encoder representation: node i holds parent << 1 | bit, 0 marks the root.
+ * f32_sums != 0: probabilities are f32 values and every sum is an f32 addition (the reference adds in the input's float
+ * type, which changes trees).  CST_ERR_MODEL for n == 0 and for NaN, negative or infinite probabilities. */
+cst_status cst_huffman_tree(const double *h_probs, size_t n, int32_t f32_sums, uint64_t *h_nodes);
+
+/* Device codebook from h_nodes[2n - 1] (cst_huffman_tree), 1 <= n <= CST_HUFFMAN_MAX_SYMBOLS: codewords in both bit orders
+ * (codewords of more than 32 bits -- up to ~3000 for f64 probabilities -- in a bit pool the encoder reads out of line), the
+ * decode table of the first 12 bits and the inner nodes the decoder walks past it.  *out is an opaque handle (void *), for
+ * the coder calls below and cst_huffman_codebook_destroy.  CST_ERR_MODEL if h_nodes is not such a tree; synchronises
+ * `stream`. */
+cst_status cst_huffman_codebook_create(const uint64_t *h_nodes, size_t n, void *stream, void **out);
+cst_status cst_huffman_codebook_destroy(void *codebook);
+
+/* Slab stride (in words) that holds any stream of n_per_stream symbols: every codeword at the codebook's longest, the up to
+ * 31 bits a continued call (d_cont) starts with and the seal, rounded up to whole 64-byte units.  0 for a bad argument. */
+size_t cst_huffman_max_words(const void *codebook, size_t n_per_stream, int32_t semantics);
+
+/* Replaces, for every stream s:
+ *     coder = StackCoder(); for x in reversed(symbols[s]): coder.encode_symbol(x, tree)     (semantics CST_HUFFMAN_STACK)
+ *     coder = QueueEncoder(); for x in symbols[s]: coder.encode_symbol(x, tree)             (CST_HUFFMAN_QUEUE)
+ *     d_words[s*stride_words ..], d_n_bits[s] = coder.get_compressed_and_bitrate()           (pybindings/symbol/mod.rs:207-221)
+ * d_symbols    stream-major [n_streams][n_per_stream], int32 (symbol_bytes 4) or uint8 (1)
+ * d_n_bits     out (may be NULL): the bitrate, the written bits without the seal (mod.rs:205-220)
+ * d_cont       in/out (may be NULL): the container's partial word, partial | nbits << 32 with nbits < 32.  Given, the call
+ *              continues from it and neither seals nor flushes the partial word: d_words gets the completed words only and
+ *              d_cont the new partial word (what the single-coder drop-in keeps between calls).
+ * d_status     a symbol < 0 or >= n: CST_STREAM_IMPOSSIBLE_SYMBOL (huffman.rs:134-137); a slab too small: CST_STREAM_CAPACITY.
+ *              Either way n_words (and n_bits) are 0 and d_cont is left as it was.
+ * cst_last_kernel_name: "huffman_encode_kernel", or "huffman_encode_long_kernel" for a codebook with codewords of more than
+ * 32 bits. */
+cst_status cst_huffman_encode_batch(const void *codebook, int32_t semantics, const void *d_symbols, int32_t symbol_bytes,
+                                    size_t n_streams, size_t n_per_stream, uint32_t *d_words, size_t stride_words,
+                                    uint32_t *d_n_words, uint64_t *d_n_bits, uint64_t *d_cont, int32_t *d_status, void *stream);
+
+/* Replaces, for every stream s, StackCoder(words[s]) resp. QueueDecoder(words[s]) and n_per_stream decode_symbol calls.  The
+ * words of stream s are d_words[off(s) .. off(s) + d_n_words[s]) with off(s) = d_offsets ? d_offsets[s] : s * stride_words,
+ * and words_capacity bounds them as for cst_ans_decode_batch.  symbol_bytes 1 needs n <= 256.
+ * A stack stream is found by its seal, the HIGHEST set bit of its last word (the reference's from_compressed
+ * looks at the lowest); no words or a zero last word: CST_STREAM_INVALID_DATA.  Running out of bits inside a codeword:
+ * CST_STREAM_OUT_OF_DATA ("Ran out of bits in compressed data.", pybindings/symbol/mod.rs:386-395); the symbols from there on
+ * read 0 and, as in the reference, every bit counts as read.
+ * d_cont       in/out (may be NULL).  Queue: the read position in bits.  Stack: the partial word on top of the d_n_words[s]
+ *              full words, partial | nbits << 32 (nbits < 32), instead of the seal search.  Out: the same after decoding.
+ * d_n_words_out out (may be NULL).  Stack: the full words left below the partial word; queue: the words begun.
+ * cst_last_kernel_name: "huffman_decode_kernel", or "huffman_decode_long_kernel" for codewords of more than 12 bits. */
+cst_status cst_huffman_decode_batch(const void *codebook, int32_t semantics, const uint32_t *d_words, const uint64_t *d_offsets,
+                                    size_t stride_words, size_t words_capacity, const uint32_t *d_n_words, void *d_symbols,
+                                    int32_t symbol_bytes, size_t n_streams, size_t n_per_stream, uint64_t *d_cont,
+                                    uint32_t *d_n_words_out, int32_t *d_status, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * bit-exact f64 special functions on device (test hooks for the model kernels)
  * out[i] = erf(x[i]) resp. Gaussian cdf, evaluated by the same device code the table kernels use.
  * ---------------------------------------------------------------------------------------- */
