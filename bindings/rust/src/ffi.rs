@@ -989,6 +989,57 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    /// QuantizedLaplace / QuantizedCauchy with per-symbol parameters (src/pybindings/stream/model.rs:736-900): the Gaussian calls
+    /// above over another CDF -- the same kernels, routes, slabs, offsets, words_capacity, CST_FLAG_RAW_STATE and layouts; no jump
+    /// points.  family: CST_FAMILY_LAPLACE (d_a = means, d_b = scales) or CST_FAMILY_CAUCHY (d_a = locs, d_b = scales); d_a / d_b are
+    /// f64 matrices of the symbols' shape and layout.  A scale <= 0 or a non-finite parameter, and a symbol outside
+    /// [min_symbol, max_symbol], yield CST_STREAM_IMPOSSIBLE_SYMBOL for that stream.  The words are those of the tabulated route
+    /// (cst_family_cdf_rows + cst_*_encode_cp_batch / cst_*_decode_rows_batch), without the n_symbols + 1 words of table per symbol.
+    /// Any other family, a NULL matrix / words / counts / status pointer and max_symbol <= min_symbol return
+    /// CST_ERR_INVALID_ARGUMENT before the device is touched.
+    pub fn cst_ans_encode_family_batch(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_a: *const f64,
+        d_b: *const f64,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_state: *mut u64,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_family_batch(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const f64,
+        d_b: *const f64,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_state: *mut u64,
+        d_n_words_out: *mut u32,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// Per-symbol models given explicitly (any model family with per-symbol parameters, e.g.
     /// Categorical(perfect=False) with a probability matrix, src/pybindings/stream/model/internals.rs:188-249):
     ///   encode: d_left / d_prob hold EncoderModel::left_cumulative_and_probability of every symbol
@@ -1210,6 +1261,49 @@ extern "C" {
         d_n_words: *const u32,
         d_means: *const f64,
         d_stds: *const f64,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_rstate: *mut CstRangeState,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// ... and over QuantizedLaplace / QuantizedCauchy (see cst_ans_encode_family_batch)
+    pub fn cst_range_encode_family_batch(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_a: *const f64,
+        d_b: *const f64,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_rstate: *mut CstRangeState,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_family_batch(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const f64,
+        d_b: *const f64,
         d_symbols: *mut i32,
         n_streams: usize,
         n_per_stream: usize,

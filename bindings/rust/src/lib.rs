@@ -117,6 +117,25 @@ impl Layout {
     }
 }
 
+/// The model families with per-symbol parameters next to the Gaussian (`cst_family`; `constriction::stream::model`'s
+/// `LeakyQuantizer` over `probability::distribution::{Laplace, Cauchy}`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Family {
+    /// `QuantizedLaplace(lo, hi)`: parameters (mean, scale)
+    Laplace,
+    /// `QuantizedCauchy(lo, hi)`: parameters (loc, scale)
+    Cauchy,
+}
+
+impl Family {
+    fn raw(self) -> ffi::CstFamily {
+        match self {
+            Family::Laplace => ffi::CST_FAMILY_LAPLACE,
+            Family::Cauchy => ffi::CST_FAMILY_CAUCHY,
+        }
+    }
+}
+
 /// Number of visible gfx950 devices.
 pub fn device_count() -> Result<usize> {
     let n = unsafe { ffi::cst_device_count() };
@@ -866,6 +885,49 @@ impl BatchedAnsCoder {
         Ok(out)
     }
 
+    /// `encode_symbols_reverse` with one leakily quantized Laplace or Cauchy distribution per symbol (Python
+    /// `encode_reverse(symbols, QuantizedLaplace(lo, hi), means, scales)`, src/pybindings/stream/model.rs:736-900): `a` = mean / loc,
+    /// `b` = scale, of the shape of `symbols`.
+    pub fn encode_symbols_reverse_family(
+        &self,
+        family: Family,
+        symbols: &DeviceBuffer<i32>,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        n_streams: usize,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<EncodedBatch> {
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        if symbols.len() < count || a.len() < count || b.len() < count {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = EncodedBatch::allocate(n_streams, self.max_words(n_per_stream), self.config)?;
+        check(unsafe {
+            ffi::cst_ans_encode_family_batch(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                symbols.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                out.words.as_mut_ptr(),
+                out.stride_words,
+                out.n_words.as_mut_ptr(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
     /// `encode_symbols_reverse` + `pos()` in front of every chunk of `interval` symbols (a multiple of 16 that divides the row
     /// length; batches of at least 16 384 streams): the jump table of the reference's flagship call.
     pub fn encode_symbols_reverse_with_checkpoints(
@@ -1058,6 +1120,50 @@ impl BatchedAnsCoder {
                 encoded.n_words.as_ptr(),
                 means.as_ptr(),
                 stds.as_ptr(),
+                out.symbols.as_mut_ptr(),
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                core::ptr::null_mut(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
+    /// `decode_symbols` with one quantized Laplace or Cauchy distribution per symbol (see `encode_symbols_reverse_family`).
+    pub fn decode_symbols_family(
+        &self,
+        family: Family,
+        encoded: &EncodedBatch,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<DecodedBatch> {
+        let n_streams = encoded.n_streams;
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        if a.len() < count || b.len() < count {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = DecodedBatch { symbols: DeviceBuffer::new(count)?, status: DeviceBuffer::new(n_streams)? };
+        check(unsafe {
+            ffi::cst_ans_decode_family_batch(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                encoded.words.as_ptr(),
+                core::ptr::null(),
+                encoded.stride_words,
+                encoded.words.len(),
+                encoded.n_words.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
                 out.symbols.as_mut_ptr(),
                 n_streams,
                 n_per_stream,
@@ -1739,6 +1845,48 @@ impl BatchedRangeEncoder {
         Ok(out)
     }
 
+    /// `encode_symbols` with one leakily quantized Laplace or Cauchy distribution per symbol (Python
+    /// `RangeEncoder.encode(symbols, QuantizedCauchy(lo, hi), locs, scales)`): `a` = mean / loc, `b` = scale.
+    pub fn encode_symbols_family(
+        &self,
+        family: Family,
+        symbols: &DeviceBuffer<i32>,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        n_streams: usize,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<EncodedBatch> {
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        if symbols.len() < count || a.len() < count || b.len() < count {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = EncodedBatch::allocate(n_streams, self.max_words(n_per_stream), self.config)?;
+        check(unsafe {
+            ffi::cst_range_encode_family_batch(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                symbols.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                out.words.as_mut_ptr(),
+                out.stride_words,
+                out.n_words.as_mut_ptr(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
     /// `encode_symbols` that also notes `RangeEncoder::pos()` in front of every chunk of `interval` symbols (ABI 5,
     /// `cst_range_encode_gaussian_batch_ckpt`; src/stream/queue.rs:172-196): a multiple of 16 that divides `n_per_stream`, stream-major.
     /// The words are those of `encode_symbols`.  `auto_jump_interval_gaussian` is the library's own choice of `interval`.
@@ -2089,6 +2237,49 @@ impl BatchedRangeDecoder {
                 encoded.n_words.as_ptr(),
                 means.as_ptr(),
                 stds.as_ptr(),
+                out.symbols.as_mut_ptr(),
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
+    /// `decode_symbols` with one quantized Laplace or Cauchy distribution per symbol (see `encode_symbols_family`).
+    pub fn decode_symbols_family(
+        &self,
+        family: Family,
+        encoded: &EncodedBatch,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<DecodedBatch> {
+        let n_streams = encoded.n_streams;
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        if a.len() < count || b.len() < count {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = DecodedBatch { symbols: DeviceBuffer::new(count)?, status: DeviceBuffer::new(n_streams)? };
+        check(unsafe {
+            ffi::cst_range_decode_family_batch(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                encoded.words.as_ptr(),
+                core::ptr::null(),
+                encoded.stride_words,
+                encoded.words.len(),
+                encoded.n_words.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
                 out.symbols.as_mut_ptr(),
                 n_streams,
                 n_per_stream,

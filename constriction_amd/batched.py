@@ -922,7 +922,8 @@ def _gaussian_args(symbols_shape, means, stds):
     return means, stds
 
 
-def _encode_gaussian(fn_name, max_words_fn, symbols, min_symbol, max_symbol, means, stds, config, layout, stride, out):
+def _encode_gaussian(fn_name, max_words_fn, symbols, min_symbol, max_symbol, means, stds, config, layout, stride, out, family=()):
+    # family: () for the Gaussian entry points, (CST_FAMILY_*,) for cst_*_family_batch, which take it after the configuration
     symbols = _require_cuda(symbols, torch.int32, "symbols")
     n_streams, n_per, lay = _layout_shape(symbols, layout)
     means, stds = _gaussian_args(symbols.shape, means, stds)
@@ -932,7 +933,7 @@ def _encode_gaussian(fn_name, max_words_fn, symbols, min_symbol, max_symbol, mea
         out = EncodedBatch(torch.empty((n_streams, stride), dtype=torch.int32, device=dev),
                            torch.empty(n_streams, dtype=torch.int32, device=dev),
                            torch.empty(n_streams, dtype=torch.int32, device=dev), tuple(config))
-    N.check(getattr(N.lib(), fn_name)(_cfg(*config), int(min_symbol), int(max_symbol), _ptr(symbols), _ptr(means), _ptr(stds),
+    N.check(getattr(N.lib(), fn_name)(_cfg(*config), *family, int(min_symbol), int(max_symbol), _ptr(symbols), _ptr(means), _ptr(stds),
                                       n_streams, n_per, lay, _ptr(out.words), out.words.shape[1], _ptr(out.n_words), None,
                                       _ptr(out.status), N.FLAG_NONE, _stream_ptr()), fn_name)
     return out
@@ -986,7 +987,7 @@ def range_encode_gaussian(symbols, min_symbol, max_symbol, means, stds, config=(
     return out
 
 
-def _decode_gaussian(fn_name, ans, encoded, min_symbol, max_symbol, means, stds, layout, offsets, out, config):
+def _decode_gaussian(fn_name, ans, encoded, min_symbol, max_symbol, means, stds, layout, offsets, out, config, family=()):
     if isinstance(encoded, EncodedBatch):
         words, n_words, config = encoded.words, encoded.n_words, config or encoded.config
         stride = words.shape[1]
@@ -1004,7 +1005,7 @@ def _decode_gaussian(fn_name, ans, encoded, min_symbol, max_symbol, means, stds,
     if out is None:
         out = torch.empty(tuple(means.shape), dtype=torch.int32, device=dev)
     status = torch.empty(n_streams, dtype=torch.int32, device=dev)
-    args = [_cfg(*config), int(min_symbol), int(max_symbol), _ptr(words), _ptr(offsets), stride, words.numel(), _ptr(n_words), _ptr(means), _ptr(stds),
+    args = [_cfg(*config), *family, int(min_symbol), int(max_symbol), _ptr(words), _ptr(offsets), stride, words.numel(), _ptr(n_words), _ptr(means), _ptr(stds),
             _ptr(out), n_streams, n_per, lay, None]
     if ans:
         args.append(None)          # d_n_words_out
@@ -1101,6 +1102,65 @@ def range_decode_gaussian(encoded, min_symbol, max_symbol, means, stds, layout="
                 "cst_range_decode_gaussian_batch_ckpt")
         return out, _status_per_stream(part_status)
     return _decode_gaussian("cst_range_decode_gaussian_batch", False, encoded, min_symbol, max_symbol, means, stds, layout, offsets, out, config)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# per-symbol QuantizedLaplace / QuantizedCauchy: the same call with another family,
+#     coder.encode_reverse(symbols, QuantizedLaplace(lo, hi), means, scales) / coder.decode(QuantizedCauchy(lo, hi), locs, scales)
+# (src/pybindings/stream/model.rs:736-900), over the Gaussian's kernels and routes: the exact CDF is evaluated inside the coder
+# kernels, nothing is tabulated.  `a` / `b`: location and scale, float64 tensors of the symbols' shape (float32 is widened).
+# ---------------------------------------------------------------------------------------------------------------------
+
+FAMILIES = {"laplace": N.FAMILY_LAPLACE, "cauchy": N.FAMILY_CAUCHY}
+
+
+def _family_id(family) -> int:
+    fam = FAMILIES.get(family, family)
+    if fam not in (N.FAMILY_LAPLACE, N.FAMILY_CAUCHY):
+        raise ValueError("family must be 'laplace' or 'cauchy' (CST_FAMILY_LAPLACE / CST_FAMILY_CAUCHY)")
+    return int(fam)
+
+
+def ans_encode_family(family, symbols, lo, hi, a, b, config=(32, 64, 24), layout="stream_major", stride: Optional[int] = None,
+                      out: Optional[EncodedBatch] = None) -> EncodedBatch:
+    """One AnsCoder per stream: encode_reverse(symbols[s], Family(lo, hi), a[s], b[s]) + get_compressed."""
+    out = _encode_gaussian("cst_ans_encode_family_batch", max_words, symbols, lo, hi, a, b, config, layout, stride, out, (_family_id(family),))
+    out.jump = None
+    return out
+
+
+def range_encode_family(family, symbols, lo, hi, a, b, config=(32, 64, 24), layout="stream_major", stride: Optional[int] = None,
+                        out: Optional[EncodedBatch] = None) -> EncodedBatch:
+    """One RangeEncoder per stream: encode(symbols[s], Family(lo, hi), a[s], b[s]) + get_compressed."""
+    out = _encode_gaussian("cst_range_encode_family_batch", range_max_words, symbols, lo, hi, a, b, config, layout, stride, out,
+                           (_family_id(family),))
+    out.jump = None
+    return out
+
+
+def ans_decode_family(family, encoded, lo, hi, a, b, layout="stream_major", offsets=None, out=None, config=None):
+    """One AnsCoder per stream: AnsCoder(words[s]).decode(Family(lo, hi), a[s], b[s]).  `encoded`: an EncodedBatch, or
+    (packed, n_words) with offsets= (compact()).  Returns (symbols, status)."""
+    return _decode_gaussian("cst_ans_decode_family_batch", True, encoded, lo, hi, a, b, layout, offsets, out, config, (_family_id(family),))
+
+
+def range_decode_family(family, encoded, lo, hi, a, b, layout="stream_major", offsets=None, out=None, config=None):
+    """One RangeDecoder per stream: RangeDecoder(words[s]).decode(Family(lo, hi), a[s], b[s]).  Returns (symbols, status)."""
+    return _decode_gaussian("cst_range_decode_family_batch", False, encoded, lo, hi, a, b, layout, offsets, out, config, (_family_id(family),))
+
+
+def _named_family(fn, family):
+    def call(*args, **kwargs):
+        return fn(family, *args, **kwargs)
+    call.__name__ = fn.__name__.replace("family", family)
+    call.__doc__ = f"{fn.__name__}('{family}', ...)"
+    return call
+
+
+ans_encode_laplace, ans_encode_cauchy = _named_family(ans_encode_family, "laplace"), _named_family(ans_encode_family, "cauchy")
+ans_decode_laplace, ans_decode_cauchy = _named_family(ans_decode_family, "laplace"), _named_family(ans_decode_family, "cauchy")
+range_encode_laplace, range_encode_cauchy = _named_family(range_encode_family, "laplace"), _named_family(range_encode_family, "cauchy")
+range_decode_laplace, range_decode_cauchy = _named_family(range_decode_family, "laplace"), _named_family(range_decode_family, "cauchy")
 
 
 # ---------------------------------------------------------------------------------------------------------------------

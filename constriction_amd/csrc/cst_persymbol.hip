@@ -5,6 +5,8 @@
 //     (src/pybindings/stream/stack.rs:567-588, 733-751): every symbol gets its own
 //     LeakilyQuantizedDistribution (src/stream/model/quantize.rs:525-568), i.e. two bit-exact f64 erf on device
 //     per encoded symbol and a search over left cumulatives per decoded symbol;
+//   * per-symbol quantized Laplace and Cauchy distributions: the same call with another family, the same kernels over another
+//     policy (cst_family_policy.hpp; cst_*_family_batch at the end of this file);
 //   * explicit per-symbol models: (left, prob) pairs for encoding and cdf rows for decoding.
 //
 // Encoding is two passes: a fully parallel pass turns every symbol into a coder entry (c, p, 2^64/p), then one
@@ -13,9 +15,11 @@
 // support).
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 
 #include "cst_range_kernels.hpp"
 #include "cst_math.hpp"
+#include "cst_family_policy.hpp"
 
 namespace cst {
 
@@ -41,20 +45,28 @@ __global__ void cp_entries_kernel(const uint32_t* __restrict__ left, const uint3
     out[i] = make_entry(c, p);
 }
 
+// (the kernels below are named after the family they were written for; FAM is a policy of cst_family_policy.hpp, and only the
+// Gaussian stages the erf tables)
+template <class FAM = GaussianFamily>
 __global__ void gaussian_entries_kernel(int P, int32_t lo, int32_t hi, const int32_t* __restrict__ sym,
                                         const double* __restrict__ mu, const double* __restrict__ sd, size_t n,
                                         EncEntry* __restrict__ out) {
-    __shared__ double2 erf_tab[kErfTabEntries];
-    erf_tab_fill(erf_tab, threadIdx.x, blockDim.x);
-    __syncthreads();
+    const double2* erf_tab = nullptr;
+    if constexpr (FAM::kErfTab) {
+        __shared__ double2 erf_lds[kErfTabEntries];
+        erf_tab_fill(erf_lds, threadIdx.x, blockDim.x);
+        __syncthreads();
+        erf_tab = erf_lds;
+    }
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t c = 0, p = 0;
     const double m = mu[i], s = sd[i];
     // `assert!(std > 0.0)` and finite parameters (pybindings/stream/model.rs:654-657); out-of-support symbols
     // (quantize.rs:537-539) and degenerate distributions (quantize.rs:562-565) all end up with p = 0 = impossible
-    if (s > 0.0 && s <= 1.7976931348623157e308 && m == m && m <= 1.7976931348623157e308 && m >= -1.7976931348623157e308) {
-        if (!leaky_gaussian_lcp_quick(sym[i], lo, hi, P, 32, m, s, c, p, erf_tab)) p = 0;
+    if (FAM::valid(m, s)) {
+        if (!FAM::lcp(sym[i], lo, hi, P, m, s, c, p, erf_tab)) p = 0;
+        if (!FAM::kGaussian && (uint64_t)c + p > ((uint64_t)1 << P)) p = 0;      // (a left cumulative that ran backwards: degenerate)
     }
     out[i] = make_entry(c, p);
 }
@@ -355,8 +367,9 @@ __device__ __forceinline__ void encode_step_inv(EncLane<32, 64, SLOTS>& L, uint3
 // (6.60 GB counted against 5.57 GB algorithmic, profiles/r04_pmc_summary.md).  So the symbols of both tiles of a line are
 // requested together, a pair of tiles ahead, and parked lane by lane in the ring columns of lanes 32..63 (a wave codes
 // kFuStreams = 32 streams: no coder ever writes there), where the items pick them up one item ahead of their use.
-template <int W, int S, int KIND, bool PAIR = false>
+template <int W, int S, int KIND, bool PAIR = false, class FAM = GaussianFamily>
 __global__ __launch_bounds__(kFuBlock) void encode_gaussian_fused_kernel(const GaussianFusedArgs a) {
+    constexpr size_t kTabBytes = FAM::kErfTab ? kFuTabBytes : 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & (kWave - 1), wave_in_block = threadIdx.x >> 6;
     // LDS: [word rings, one per wave, aligned to their size: the hand-scheduled step forms slot addresses with and/or]
@@ -364,10 +377,12 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_fused_kernel(const G
     constexpr size_t kRingBytes = (size_t)kFuRingSlots * kWave * 4;
     uint32_t* ring = reinterpret_cast<uint32_t*>(smem + (size_t)wave_in_block * kRingBytes);
     double2* erf_tab = reinterpret_cast<double2*>(smem + (kFuBlock / kWave) * kRingBytes);
-    EncEntry* tile = reinterpret_cast<EncEntry*>(smem + (kFuBlock / kWave) * kRingBytes + kFuTabBytes + (size_t)wave_in_block * (kFuWaveBytes - kRingBytes));
+    EncEntry* tile = reinterpret_cast<EncEntry*>(smem + (kFuBlock / kWave) * kRingBytes + kTabBytes + (size_t)wave_in_block * (kFuWaveBytes - kRingBytes));
     if ((lds_addr(ring) & (uint32_t)(kRingBytes - 1)) != 0) __builtin_trap();
-    erf_tab_fill(erf_tab, threadIdx.x, blockDim.x);
-    __syncthreads();
+    if constexpr (FAM::kErfTab) {
+        erf_tab_fill(erf_tab, threadIdx.x, blockDim.x);
+        __syncthreads();
+    }
     const size_t s0 = ((size_t)blockIdx.x * (kFuBlock / kWave) + wave_in_block) * kFuStreams;
     if (s0 >= a.n_streams) return;
     const size_t N = a.n_per_stream;
@@ -498,8 +513,8 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_fused_kernel(const G
                 // `assert!(std > 0.0)` and finite parameters (pybindings/stream/model.rs:654-657); out-of-support symbols
                 // (quantize.rs:537-539) and degenerate distributions (quantize.rs:562-565) all end up with p = 0 = impossible.
                 // No branches: invalid parameters are evaluated as (0, 1) and thrown away.
-                const bool valid = sg > 0.0 && sg <= 1.7976931348623157e308 && fabs(m) <= 1.7976931348623157e308;
-                const bool inside = leaky_gaussian_lcp_quick(sy, a.lo, a.hi, P, 32, valid ? m : 0.0, valid ? sg : 1.0, c, p, erf_tab);
+                const bool valid = FAM::valid(m, sg);
+                const bool inside = FAM::lcp(sy, a.lo, a.hi, P, valid ? m : 0.0, valid ? sg : 1.0, c, p, erf_tab);
                 if (!valid || !inside || (uint64_t)c + p > ((uint64_t)1 << P)) p = 0;
                 EncEntry entry{c, p, 0u, 0u};                                   // (the range coder divides by nothing)
                 if constexpr (KIND == kAns) entry = use_inv ? make_entry_inv(c, p) : make_entry_f64(c, p);
@@ -786,6 +801,7 @@ struct DirectDecoder<W, S, kChain> {
 // to 64 candidate left cumulatives per round: two rounds for a 201-symbol support.  MODEL supplies left(element, i).
 struct GaussianLeft {
     static constexpr int32_t kBadModel = CST_STREAM_IMPOSSIBLE_SYMBOL;   // degenerate distribution (quantize.rs:562-565)
+    static constexpr bool kErfTab = true;
     const PerSymbolDecodeArgs& a;
     const double2* erf_tab;
     double mu, sd;
@@ -798,8 +814,24 @@ struct GaussianLeft {
         return leaky_gaussian_left_quick((int32_t)i, a.min_symbol, a.n_symbols, a.precision, 32, mu, sd, erf_tab);
     }
 };
+// QuantizedLaplace / QuantizedCauchy (a = mean / loc in `means`, b = scale in `stds`): 64 exact CDFs per round
+template <class FAM>
+struct FamilyLeft {
+    static constexpr int32_t kBadModel = CST_STREAM_IMPOSSIBLE_SYMBOL;
+    static constexpr bool kErfTab = false;
+    const PerSymbolDecodeArgs& a;
+    const double2* unused;
+    double pa, pb;
+    __device__ __forceinline__ bool load(size_t e) { pa = a.means[e]; pb = a.stds[e]; return FAM::valid(pa, pb); }
+    __device__ __forceinline__ uint32_t left(uint32_t i) const {
+        return FAM::template left<false>((int32_t)i, a.min_symbol, a.n_symbols, a.precision, pa, pb, nullptr);
+    }
+};
+using LaplaceLeft = FamilyLeft<LaplaceFamily>;
+using CauchyLeft = FamilyLeft<CauchyFamily>;
 struct RowLeft {                       // explicit cdf rows [n + 1] per coded symbol: 64 coalesced entries per round
     static constexpr int32_t kBadModel = CST_STREAM_INVALID_DATA;          // a row that is not a cdf for this quantile
+    static constexpr bool kErfTab = true;                                  // (unused by the rows; as staged since the kernel was written)
     const PerSymbolDecodeArgs& a;
     const double2* unused;
     const uint32_t* row;
@@ -809,9 +841,13 @@ struct RowLeft {                       // explicit cdf rows [n + 1] per coded sy
 
 template <int W, int S, int KIND, class MODEL>
 __global__ __launch_bounds__(kBlock) void decode_wave_kernel(const PerSymbolDecodeArgs a) {
-    __shared__ double2 erf_tab[kErfTabEntries];
-    erf_tab_fill(erf_tab, threadIdx.x, blockDim.x);
-    __syncthreads();
+    const double2* erf_tab = nullptr;
+    if constexpr (MODEL::kErfTab) {
+        __shared__ double2 erf_lds[kErfTabEntries];
+        erf_tab_fill(erf_lds, threadIdx.x, blockDim.x);
+        __syncthreads();
+        erf_tab = erf_lds;
+    }
     const int lane = threadIdx.x & (kWave - 1);
     const size_t s = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (s >= a.n_streams) return;
@@ -863,37 +899,6 @@ __global__ __launch_bounds__(kBlock) void decode_wave_kernel(const PerSymbolDeco
 // the 64 to 128 of a wave-wide search.  Any search returns the same symbol: the one with left(sym) <= q < left(sym + 1)
 // (quantize.rs:580-779).
 
-// Acklam's rational approximation of the inverse normal CDF in f32 with the hardware's approximate log, sqrt and
-// reciprocal: a STARTING POINT for the search (a guess that is off costs probes, never correctness).
-// `tail` = min(p, 1 - p) in (0, 0.5]; returns the (negative) quantile of the lower tail.
-__device__ __forceinline__ float ndtri_lower_f32(float tail) {
-    constexpr float a1 = -3.969683028665376e+01f, a2 = 2.209460984245205e+02f, a3 = -2.759285104469687e+02f, a4 = 1.383577518672690e+02f,
-        a5 = -3.066479806614716e+01f, a6 = 2.506628277459239e+00f, b1 = -5.447609879822406e+01f, b2 = 1.615858368580409e+02f,
-        b3 = -1.556989798598866e+02f, b4 = 6.680131188771972e+01f, b5 = -1.328068155288572e+01f, c1 = -7.784894002430293e-03f,
-        c2 = -3.223964580411365e-01f, c3 = -2.400758277161838e+00f, c4 = -2.549732539343734e+00f, c5 = 4.374664141464968e+00f,
-        c6 = 2.938163982698783e+00f, d1 = 7.784695709041462e-03f, d2 = 3.224671290700398e-01f, d3 = 2.445134137142996e+00f,
-        d4 = 3.754408661907416e+00f;
-    // both branches, then a select: cheaper than diverging over 25 instructions
-    // (explicit fused multiply-adds: the library is built with -ffp-contract=off for its bit-exact f64 paths, and a guess
-    // has no bits to keep)
-    auto f = [](float a, float b, float c) { return __builtin_fmaf(a, b, c); };
-    const float q = __builtin_amdgcn_sqrtf(-1.3862943611f * __builtin_amdgcn_logf(tail));          // sqrt(-2 ln(tail))
-    const float zt = f(f(f(f(f(c1, q, c2), q, c3), q, c4), q, c5), q, c6) * __builtin_amdgcn_rcpf(f(f(f(f(d1, q, d2), q, d3), q, d4), q, 1.0f));
-    const float u = tail - 0.5f, r = u * u;
-    const float zc = f(f(f(f(f(a1, r, a2), r, a3), r, a4), r, a5), r, a6) * u * __builtin_amdgcn_rcpf(f(f(f(f(f(b1, r, b2), r, b3), r, b4), r, b5), r, 1.0f));
-    return tail < 0.02425f ? zt : zc;
-}
-
-// The same quantile from Abramowitz & Stegun 26.2.23 (|error| < 4.5e-4 over the whole lower half): a third of the instructions.
-// Good for a first probe as long as 4.5e-4 sigma stays well below half a symbol; the lane decoder uses it when no lane of the
-// wave has sigma >= 200.
-__device__ __forceinline__ float ndtri_lower_coarse_f32(float tail) {
-    const float t = __builtin_amdgcn_sqrtf(-1.3862943611f * __builtin_amdgcn_logf(tail));          // sqrt(-2 ln(tail))
-    const float num = __builtin_fmaf(__builtin_fmaf(0.010328f, t, 0.802853f), t, 2.515517f);
-    const float den = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(0.001308f, t, 0.189269f), t, 1.432788f), t, 1.0f);
-    return __builtin_fmaf(num, __builtin_amdgcn_rcpf(den), -t);
-}
-
 // Out of line ON PURPOSE: inlined, the compiler hoists the 32 + 8 row addresses of both variants out of the symbol loop
 // into 130 VGPRs and then spills the erf's registers around every call of it.
 __device__ __noinline__ void store_symbol_tile(int32_t* sym, size_t n_streams, size_t N, size_t s0, size_t t0, int lane, const int32_t* tile, bool vec) {
@@ -920,6 +925,7 @@ template <bool SMALL> struct LaneGeo {
     static constexpr int kThreads = SMALL ? 512 : kBlock;
     static constexpr size_t kWaveBytes = (size_t)kWave * kOutStride * 4 + 2 * (size_t)kParTile * kParStride * 8 + (size_t)kWordWindow * kWave * 4;
     static constexpr size_t kLdsBytes = kErfTabBytes + (size_t)(kThreads / kWave) * kWaveBytes;
+    static constexpr size_t kLdsBytesNoTab = (size_t)(kThreads / kWave) * kWaveBytes;      // families without erf tables
 };
 
 // 16-symbol output tile of the SMALL geometry -> HBM: piece (lane & 3) of rows (lane >> 2) + 16 k, 64-byte row segments
@@ -940,17 +946,19 @@ __device__ __noinline__ void store_symbol_tile16(int32_t* sym, size_t n_streams,
     }
 }
 
-template <int W, int S, int KIND, bool SMALL = false>
+template <int W, int S, int KIND, bool SMALL = false, class FAM = GaussianFamily>
 __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane_kernel(const PerSymbolDecodeArgs a) {
     using G = LaneGeo<SMALL>;
     constexpr int kParTile = G::kParTile, kWordWindow = G::kWordWindow, kOutSyms = G::kOutSyms, kOutStride = G::kOutStride;
     constexpr size_t kLaneDecWaveBytes = G::kWaveBytes;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double2* erf_tab = reinterpret_cast<double2*>(smem);
-    erf_tab_fill(erf_tab, threadIdx.x, blockDim.x);
-    __syncthreads();
+    if constexpr (FAM::kErfTab) {
+        erf_tab_fill(erf_tab, threadIdx.x, blockDim.x);
+        __syncthreads();
+    }
     const int lane = threadIdx.x & (kWave - 1);
-    unsigned char* mine = smem + kErfTabBytes + (size_t)(threadIdx.x >> 6) * kLaneDecWaveBytes;
+    unsigned char* mine = smem + (FAM::kErfTab ? kErfTabBytes : 0) + (size_t)(threadIdx.x >> 6) * kLaneDecWaveBytes;
     int32_t* tile = reinterpret_cast<int32_t*>(mine);
     double* par_mu = reinterpret_cast<double*>(mine + (size_t)kWave * kOutStride * 4);
     double* par_sd = par_mu + kParTile * kParStride;
@@ -1098,19 +1106,19 @@ __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane
             D.ahead = win[(((uint32_t)D.next_index()) & (kWordWindow - 1)) * kWave + lane];
             if (status == CST_STREAM_OK) {
                 // the reference panics on an invalid model (pybindings/stream/model.rs:654-657)
-                const bool model_ok = sd > 0.0 && sd <= 1.7976931348623157e308 && fabs(mu) <= 1.7976931348623157e308;
+                const bool model_ok = FAM::valid(mu, sd);
                 const uint32_t q = model_ok ? D.quantile(P) : 0u;
                 if (!model_ok) status = CST_STREAM_IMPOSSIBLE_SYMBOL;
                 else if (D.status != CST_STREAM_OK) status = D.status;
                 else {
                     // guess: ignore the leak (one quantile per symbol) first, then account for the guessed symbol's share of it
                     const float below = (float)q + 0.5f, above = total_f - below;
-                    const bool coarse = !__any(sd >= 200.0);          // (wave-uniform: the cheap quantile is good enough)
-                    float z = coarse ? ndtri_lower_coarse_f32(fminf(below, above) * inv_total_f) : ndtri_lower_f32(fminf(below, above) * inv_total_f);
+                    const bool coarse = FAM::kGaussian && !__any(sd >= 200.0);          // (wave-uniform: the cheap quantile is good enough)
+                    float z = coarse ? FAM::guess_z_coarse(fminf(below, above) * inv_total_f) : FAM::guess_z(fminf(below, above) * inv_total_f);
                     double x = mu + sd * (double)(below < above ? z : -z) + guess_shift;
                     if (two_step_guess) {
                         const float b1 = below - (float)fmin(fmax(x, 0.0), (double)(n - 1u)), a1 = free_f - b1;
-                        z = ndtri_lower_f32(fmaxf(fminf(b1, a1), 0.25f) * inv_free_f);
+                        z = FAM::guess_z(fmaxf(fminf(b1, a1), 0.25f) * inv_free_f);
                         x = mu + sd * (double)(b1 < a1 ? z : -z) + guess_shift;
                     }
                     // first probe: the bin BOUNDARY nearest to the guess (boundary i lies at x = i) -- whichever side of it the
@@ -1126,7 +1134,7 @@ __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane
                         // ... and its two neighbours in the same breath: the three evaluations share their LDS latency, and a
                         // guess within half a symbol -- almost every one -- is bracketed without a second look
                         uint32_t v3[3];
-                        leaky_gaussian_left3_quick(g, a.min_symbol, n, P, mu, sd, erf_tab, v3);
+                        FAM::left3(g, a.min_symbol, n, P, mu, sd, erf_tab, v3);
                         if (v3[1] <= q) {
                             up = true;
                             if (q < v3[2]) { lo_i = g; lo_v = v3[1]; hi_i = g + 1u; hi_v = v3[2]; }
@@ -1139,7 +1147,7 @@ __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane
                     }
                     while (hi_i - lo_i > 1) {
                         // (every probe lies strictly inside (lo_i, hi_i), a subset of (0, n))
-                        const uint32_t v = leaky_gaussian_left_quick<true>((int32_t)probe, a.min_symbol, (int32_t)n, P, 32, mu, sd, erf_tab);
+                        const uint32_t v = FAM::template left<true>((int32_t)probe, a.min_symbol, (int32_t)n, P, mu, sd, erf_tab);
                         if (v <= q) { lo_i = probe; lo_v = v; up = true; } else { hi_i = probe; hi_v = v; down = true; }
                         if (up && down) probe = lo_i + (hi_i - lo_i) / 2;
                         else if (up) probe = min(lo_i + step, hi_i - 1u);
@@ -1187,12 +1195,17 @@ __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane
 constexpr int kRowEntries = 256;
 constexpr int kRowsAhead = 16;
 
+template <class FAM = GaussianFamily>
 __global__ __launch_bounds__(kRowEntries) void gaussian_rows_kernel(int P, int32_t lo, int32_t n, const double* __restrict__ means,
                                                                    const double* __restrict__ stds, int32_t layout, size_t n_streams,
                                                                    size_t N, size_t t0, size_t count, uint32_t* __restrict__ rows) {
-    __shared__ double2 erf_tab[kErfTabEntries];
-    erf_tab_fill(erf_tab, threadIdx.x, blockDim.x);
-    __syncthreads();
+    const double2* erf_tab = nullptr;
+    if constexpr (FAM::kErfTab) {
+        __shared__ double2 erf_lds[kErfTabEntries];
+        erf_tab_fill(erf_lds, threadIdx.x, blockDim.x);
+        __syncthreads();
+        erf_tab = erf_lds;
+    }
     const size_t row = blockIdx.x;                     // = stream * count + (t - t0)
     const size_t s = row / count, t = t0 + row % count;
     const size_t e = layout == CST_LAYOUT_SYMBOL_MAJOR ? t * n_streams + s : s * N + t;
@@ -1200,8 +1213,8 @@ __global__ __launch_bounds__(kRowEntries) void gaussian_rows_kernel(int P, int32
     const int32_t i = (int32_t)threadIdx.x;
     const uint32_t total = 1u << P;
     uint32_t v;
-    if (sd > 0.0 && sd <= 1.7976931348623157e308 && fabs(mu) <= 1.7976931348623157e308)
-        v = i <= n ? leaky_gaussian_left_quick(i, lo, n, P, 32, mu, sd, erf_tab) : total;
+    if (FAM::valid(mu, sd))
+        v = i <= n ? FAM::template left<false>(i, lo, n, P, mu, sd, erf_tab) : total;
     else v = i == 0 ? 0xffffffffu : total;             // invalid model (a valid row starts with 0)
     rows[row * kRowEntries + i] = v;
 }
@@ -1575,7 +1588,24 @@ static bool fused_encode_usable(size_t n_streams, size_t n_per_stream) {
     return n_streams >= knobs().fused_min_streams && n_per_stream >= 1;
 }
 
-template <int KIND>
+// what note_kernel() reports for a family's routes
+template <class FAM> struct FamilyNames;
+#define CST_FAMILY_NAMES(FAM, word)                                                                                                       \
+    template <> struct FamilyNames<FAM> {                                                                                                 \
+        static constexpr const char* fused[2] = {"ans_encode_" word "_fused_kernel", "range_encode_" word "_fused_kernel"};               \
+        static constexpr const char* two_pass[2] = {"ans_encode_" word "_two_pass", "range_encode_" word "_two_pass"};                    \
+        static constexpr const char* lane[3] = {"ans_decode_" word "_lane_kernel", "range_decode_" word "_lane_kernel",                   \
+                                                "chain_decode_" word "_lane_kernel"};                                                     \
+        static constexpr const char* lane_small[2] = {"ans_decode_" word "_lane_kernel<small>", "range_decode_" word "_lane_kernel<small>"}; \
+        static constexpr const char* wave[2] = {"ans_decode_" word "_wave_kernel", "range_decode_" word "_wave_kernel"};                  \
+        static constexpr const char* by_rows = "decode_" word "_by_rows";                                                                 \
+    }
+CST_FAMILY_NAMES(GaussianFamily, "gaussian");
+CST_FAMILY_NAMES(LaplaceFamily, "laplace");
+CST_FAMILY_NAMES(CauchyFamily, "cauchy");
+#undef CST_FAMILY_NAMES
+
+template <int KIND, class FAM = GaussianFamily>
 static cst_status encode_gaussian_fused(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
                                         const double* d_means, const double* d_stds, size_t n_streams, size_t n_per_stream, cst_layout layout,
                                         uint32_t* d_words, size_t stride_words, uint32_t* d_n_words, uint64_t* d_state,
@@ -1596,24 +1626,28 @@ static cst_status encode_gaussian_fused(cst_coder_config cfg, int32_t min_symbol
     a.status = d_status; a.flags = flags;
     const size_t per_block = (size_t)(kFuBlock / kWave) * kFuStreams;
     const size_t blocks = (n_streams + per_block - 1) / per_block;
-    const size_t lds = kFuTabBytes + (size_t)(kFuBlock / kWave) * kFuWaveBytes;
-    const bool pair = layout == CST_LAYOUT_STREAM_MAJOR && n_streams % kFuStreams == 0 && n_per_stream % kFuTile == 0 && n_per_stream > 0;
+    const size_t lds = (FAM::kErfTab ? kFuTabBytes : 0) + (size_t)(kFuBlock / kWave) * kFuWaveBytes;
+    // (PAIR saves a second fetch of the symbols' lines -- a fifth of the Gaussian's traffic.  The exact CDFs of the other families
+    // are arithmetic, not traffic, and the pair's sixteen parked symbols do not survive their calls without scratch.)
+    const bool pair = FAM::kGaussian && layout == CST_LAYOUT_STREAM_MAJOR && n_streams % kFuStreams == 0 && n_per_stream % kFuTile == 0 && n_per_stream > 0;
     if (cfg.word_bits == 32 && pair) {
-        CST_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_gaussian_fused_kernel<32, 64, KIND, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((encode_gaussian_fused_kernel<32, 64, KIND, true>), dim3((unsigned)blocks), dim3(kFuBlock), lds, hs, a);
+        if constexpr (FAM::kGaussian) {
+            CST_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_gaussian_fused_kernel<32, 64, KIND, true, FAM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL((encode_gaussian_fused_kernel<32, 64, KIND, true, FAM>), dim3((unsigned)blocks), dim3(kFuBlock), lds, hs, a);
+        }
     } else if (cfg.word_bits == 32) {
-        CST_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_gaussian_fused_kernel<32, 64, KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((encode_gaussian_fused_kernel<32, 64, KIND>), dim3((unsigned)blocks), dim3(kFuBlock), lds, hs, a);
+        CST_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_gaussian_fused_kernel<32, 64, KIND, false, FAM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((encode_gaussian_fused_kernel<32, 64, KIND, false, FAM>), dim3((unsigned)blocks), dim3(kFuBlock), lds, hs, a);
     } else {
-        CST_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_gaussian_fused_kernel<16, 32, KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((encode_gaussian_fused_kernel<16, 32, KIND>), dim3((unsigned)blocks), dim3(kFuBlock), lds, hs, a);
+        CST_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_gaussian_fused_kernel<16, 32, KIND, false, FAM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((encode_gaussian_fused_kernel<16, 32, KIND, false, FAM>), dim3((unsigned)blocks), dim3(kFuBlock), lds, hs, a);
     }
     CST_HIP_TRY(hipGetLastError());
     return CST_OK;
 }
 
 // few streams: cdf rows at full occupancy, then a lookup per symbol; in pieces of at most 64 MiB of rows
-template <int KIND>
+template <int KIND, class FAM = GaussianFamily>
 static cst_status decode_gaussian_by_rows(cst_coder_config cfg, const PerSymbolDecodeArgs& a, hipStream_t hs) {
     const size_t N = a.n_per_stream;
     // 65 536 rows = 64 MiB of rows per piece (the piece size makes no measurable difference from 4096 rows up: the
@@ -1626,7 +1660,7 @@ static cst_status decode_gaussian_by_rows(cst_coder_config cfg, const PerSymbolD
     hipError_t err = scratch_alloc((void**)&resume, a.n_streams * sizeof(DecodeResume), hs);
     for (size_t t0 = 0; t0 < N && err == hipSuccess; t0 += piece) {
         const size_t count = N - t0 < piece ? N - t0 : piece;
-        hipLaunchKernelGGL(gaussian_rows_kernel, dim3((unsigned)(a.n_streams * count)), dim3(kRowEntries), 0, hs, a.precision, a.min_symbol,
+        hipLaunchKernelGGL(gaussian_rows_kernel<FAM>, dim3((unsigned)(a.n_streams * count)), dim3(kRowEntries), 0, hs, a.precision, a.min_symbol,
                            a.n_symbols, a.means, a.stds, a.layout, a.n_streams, N, t0, count, rows);
         RowsDecodeArgs ra{a, reinterpret_cast<const uint4*>(rows), t0, count, resume, t0 == 0, t0 + count == N};
         if (cfg.word_bits == 32) hipLaunchKernelGGL((decode_rows_wave_kernel<32, 64, KIND>), dim3((unsigned)a.n_streams), dim3(kWave), 0, hs, ra);
@@ -1661,8 +1695,13 @@ static cst_status decode_chains_in_three(cst_coder_config cfg, const PerSymbolDe
     return CST_OK;
 }
 
-template <int KIND>
+// `gaussian`: per-symbol parameters of family FAM in a.means / a.stds (else explicit cdf rows)
+template <int KIND, class FAM = GaussianFamily>
 static cst_status decode_per_symbol(cst_coder_config cfg, const PerSymbolDecodeArgs& a, bool gaussian, hipStream_t hs) {
+    using WaveModel = std::conditional_t<FAM::kGaussian, GaussianLeft, FamilyLeft<FAM>>;
+    using Names = FamilyNames<FAM>;
+    constexpr size_t kLdsBig = FAM::kErfTab ? LaneGeo<false>::kLdsBytes : LaneGeo<false>::kLdsBytesNoTab;
+    constexpr size_t kLdsSmall = FAM::kErfTab ? LaneGeo<true>::kLdsBytes : LaneGeo<true>::kLdsBytesNoTab;
     if (a.n_streams == 0) return CST_OK;
     const size_t blocks = (a.n_streams * kWave + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
@@ -1682,23 +1721,23 @@ static cst_status decode_per_symbol(cst_coder_config cfg, const PerSymbolDecodeA
         };
         cst_status rc;
         if constexpr (KIND != kChain) {
-            if (small) rc = cfg.word_bits == 32 ? go(decode_gaussian_lane_kernel<32, 64, KIND, true>, LaneGeo<true>::kThreads, LaneGeo<true>::kLdsBytes)
-                                                : go(decode_gaussian_lane_kernel<16, 32, KIND, true>, LaneGeo<true>::kThreads, LaneGeo<true>::kLdsBytes);
-            else rc = cfg.word_bits == 32 ? go(decode_gaussian_lane_kernel<32, 64, KIND, false>, LaneGeo<false>::kThreads, LaneGeo<false>::kLdsBytes)
-                                          : go(decode_gaussian_lane_kernel<16, 32, KIND, false>, LaneGeo<false>::kThreads, LaneGeo<false>::kLdsBytes);
+            if (small) rc = cfg.word_bits == 32 ? go(decode_gaussian_lane_kernel<32, 64, KIND, true, FAM>, LaneGeo<true>::kThreads, kLdsSmall)
+                                                : go(decode_gaussian_lane_kernel<16, 32, KIND, true, FAM>, LaneGeo<true>::kThreads, kLdsSmall);
+            else rc = cfg.word_bits == 32 ? go(decode_gaussian_lane_kernel<32, 64, KIND, false, FAM>, LaneGeo<false>::kThreads, kLdsBig)
+                                          : go(decode_gaussian_lane_kernel<16, 32, KIND, false, FAM>, LaneGeo<false>::kThreads, kLdsBig);
         } else {
-            rc = cfg.word_bits == 32 ? go(decode_gaussian_lane_kernel<32, 64, KIND, false>, LaneGeo<false>::kThreads, LaneGeo<false>::kLdsBytes)
-                                     : go(decode_gaussian_lane_kernel<16, 32, KIND, false>, LaneGeo<false>::kThreads, LaneGeo<false>::kLdsBytes);
+            rc = cfg.word_bits == 32 ? go(decode_gaussian_lane_kernel<32, 64, KIND, false, FAM>, LaneGeo<false>::kThreads, kLdsBig)
+                                     : go(decode_gaussian_lane_kernel<16, 32, KIND, false, FAM>, LaneGeo<false>::kThreads, kLdsBig);
         }
         if (rc != CST_OK) return rc;
-        note_kernel(KIND == kChain ? "chain_decode_gaussian_lane_kernel" : KIND == kRange ? (small ? "range_decode_gaussian_lane_kernel<small>" : "range_decode_gaussian_lane_kernel")
-                                   : (small ? "ans_decode_gaussian_lane_kernel<small>" : "ans_decode_gaussian_lane_kernel"), CST_OK);
+        note_kernel(KIND == kChain || !small ? Names::lane[KIND] : Names::lane_small[KIND == kRange], CST_OK);
     } else if (KIND != kChain && gaussian && a.n_symbols < kRowEntries && a.n_per_stream >= 32) {
-        note_kernel("decode_gaussian_by_rows", CST_OK);
-        if constexpr (KIND != kChain) return decode_gaussian_by_rows<KIND>(cfg, a, hs);
+        note_kernel(Names::by_rows, CST_OK);
+        if constexpr (KIND != kChain) return decode_gaussian_by_rows<KIND, FAM>(cfg, a, hs);
     } else if (gaussian) {
-        if (cfg.word_bits == 32) hipLaunchKernelGGL((decode_wave_kernel<32, 64, KIND, GaussianLeft>), dim3((unsigned)blocks), dim3(kBlock), 0, hs, a);
-        else hipLaunchKernelGGL((decode_wave_kernel<16, 32, KIND, GaussianLeft>), dim3((unsigned)blocks), dim3(kBlock), 0, hs, a);
+        if (cfg.word_bits == 32) hipLaunchKernelGGL((decode_wave_kernel<32, 64, KIND, WaveModel>), dim3((unsigned)blocks), dim3(kBlock), 0, hs, a);
+        else hipLaunchKernelGGL((decode_wave_kernel<16, 32, KIND, WaveModel>), dim3((unsigned)blocks), dim3(kBlock), 0, hs, a);
+        if (!FAM::kGaussian) note_kernel(Names::wave[KIND == kRange], CST_OK);
     } else {
         if (cfg.word_bits == 32) hipLaunchKernelGGL((decode_wave_kernel<32, 64, KIND, RowLeft>), dim3((unsigned)blocks), dim3(kBlock), 0, hs, a);
         else hipLaunchKernelGGL((decode_wave_kernel<16, 32, KIND, RowLeft>), dim3((unsigned)blocks), dim3(kBlock), 0, hs, a);
@@ -2085,6 +2124,107 @@ cst_status cst_chain_encode_gaussian_batch(cst_coder_config cfg, int32_t min_sym
         hipLaunchKernelGGL(gaussian_entries_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hs, cfg.precision, min_symbol,
                            max_symbol, d_symbols, d_means, d_stds, n, out);
     });
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// QuantizedLaplace / QuantizedCauchy with per-symbol parameters: the Gaussian calls' routes, kernels and dispatch over another
+// policy (cst_family_policy.hpp).  No jump points for these families.
+// ------------------------------------------------------------------------------------------------
+namespace cst {
+
+template <int KIND, class FAM>
+static cst_status encode_family(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols, const double* d_a,
+                                const double* d_b, size_t n_streams, size_t n_per_stream, cst_layout layout, uint32_t* d_words,
+                                size_t stride_words, uint32_t* d_n_words, uint64_t* d_state, cst_range_state* d_rstate, int32_t* d_status,
+                                uint32_t flags, hipStream_t hs) {
+    if (fused_encode_usable(n_streams, n_per_stream))
+        return note_kernel(FamilyNames<FAM>::fused[KIND == kRange],
+                           encode_gaussian_fused<KIND, FAM>(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, n_streams, n_per_stream, layout, d_words,
+                                                            stride_words, d_n_words, d_state, d_rstate, d_status, flags, hs));
+    note_kernel(FamilyNames<FAM>::two_pass[KIND == kRange], CST_OK);
+    return encode_two_pass<KIND>(cfg, n_streams, n_per_stream, layout, d_words, stride_words, d_n_words, d_state, d_rstate, d_status, flags, hs,
+                                 [&](EncEntry* out, size_t n) {
+        hipLaunchKernelGGL(gaussian_entries_kernel<FAM>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hs, cfg.precision, min_symbol, max_symbol,
+                           d_symbols, d_a, d_b, n, out);
+    });
+}
+
+// everything that can be said about the arguments without the device, the same for all four calls
+static cst_status check_family_args(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, cst_layout layout,
+                                    const void* d_symbols, const void* d_a, const void* d_b, const void* d_words, const void* d_n_words,
+                                    const void* d_status, const void* raw_state, uint32_t flags) {
+    if (family != CST_FAMILY_LAPLACE && family != CST_FAMILY_CAUCHY) return CST_ERR_INVALID_ARGUMENT;
+    if (max_symbol <= min_symbol) return CST_ERR_INVALID_ARGUMENT;
+    if (!d_symbols || !d_a || !d_b || !d_words || !d_n_words || !d_status) return CST_ERR_INVALID_ARGUMENT;
+    if ((flags & CST_FLAG_RAW_STATE) && !raw_state) return CST_ERR_INVALID_ARGUMENT;
+    if (cst_status st = check_common(cfg, layout)) return st;
+    if ((int64_t)max_symbol - min_symbol + 1 > ((int64_t)1 << cfg.precision)) return CST_ERR_MODEL;      // LeakyQuantizer::new asserts this
+    return CST_OK;
+}
+
+template <int KIND>
+static cst_status decode_family(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const double* d_a,
+                                const double* d_b, int32_t* d_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout, uint64_t* d_state,
+                                uint32_t* d_n_words_out, cst_range_state* d_rstate, int32_t* d_status, uint32_t flags, hipStream_t hs) {
+    if (cst_status st = check_family_args(cfg, family, min_symbol, max_symbol, layout, d_symbols, d_a, d_b, d_words, d_n_words, d_status,
+                                          KIND == kAns ? (const void*)d_state : (const void*)d_rstate, flags)) return st;
+    PerSymbolDecodeArgs a{};
+    if (cst_status st = fill_decode_args(a, cfg, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_symbols, n_streams, n_per_stream, layout,
+                                         min_symbol, (int64_t)max_symbol - min_symbol + 1, d_status, flags)) return st;
+    a.means = d_a; a.stds = d_b; a.state = d_state; a.n_words_out = d_n_words_out; a.rstate = d_rstate;
+    return family == CST_FAMILY_LAPLACE ? decode_per_symbol<KIND, LaplaceFamily>(cfg, a, true, hs)
+                                        : decode_per_symbol<KIND, CauchyFamily>(cfg, a, true, hs);
+}
+
+} // namespace cst
+
+extern "C" {
+
+cst_status cst_ans_encode_family_batch(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                       const double* d_a, const double* d_b, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                       uint32_t* d_words, size_t stride_words, uint32_t* d_n_words, uint64_t* d_state, int32_t* d_status,
+                                       uint32_t flags, void* stream) {
+    if (cst_status st = check_family_args(cfg, family, min_symbol, max_symbol, layout, d_symbols, d_a, d_b, d_words, d_n_words, d_status, d_state, flags))
+        return st;
+    hipStream_t hs = (hipStream_t)stream;
+    return family == CST_FAMILY_LAPLACE
+        ? encode_family<kAns, LaplaceFamily>(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, n_streams, n_per_stream, layout, d_words, stride_words,
+                                             d_n_words, d_state, nullptr, d_status, flags, hs)
+        : encode_family<kAns, CauchyFamily>(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, n_streams, n_per_stream, layout, d_words, stride_words,
+                                            d_n_words, d_state, nullptr, d_status, flags, hs);
+}
+
+cst_status cst_range_encode_family_batch(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                         const double* d_a, const double* d_b, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                         uint32_t* d_words, size_t stride_words, uint32_t* d_n_words, cst_range_state* d_rstate, int32_t* d_status,
+                                         uint32_t flags, void* stream) {
+    if (cst_status st = check_family_args(cfg, family, min_symbol, max_symbol, layout, d_symbols, d_a, d_b, d_words, d_n_words, d_status, d_rstate, flags))
+        return st;
+    hipStream_t hs = (hipStream_t)stream;
+    return family == CST_FAMILY_LAPLACE
+        ? encode_family<kRange, LaplaceFamily>(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, n_streams, n_per_stream, layout, d_words, stride_words,
+                                               d_n_words, nullptr, d_rstate, d_status, flags, hs)
+        : encode_family<kRange, CauchyFamily>(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, n_streams, n_per_stream, layout, d_words, stride_words,
+                                              d_n_words, nullptr, d_rstate, d_status, flags, hs);
+}
+
+cst_status cst_ans_decode_family_batch(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                       const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                       const double* d_a, const double* d_b, int32_t* d_symbols, size_t n_streams, size_t n_per_stream,
+                                       cst_layout layout, uint64_t* d_state, uint32_t* d_n_words_out, int32_t* d_status, uint32_t flags, void* stream) {
+    return decode_family<kAns>(cfg, family, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_a, d_b, d_symbols,
+                               n_streams, n_per_stream, layout, d_state, d_n_words_out, nullptr, d_status, flags, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_family_batch(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                         const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                         const double* d_a, const double* d_b, int32_t* d_symbols, size_t n_streams, size_t n_per_stream,
+                                         cst_layout layout, cst_range_state* d_rstate, int32_t* d_status, uint32_t flags, void* stream) {
+    return decode_family<kRange>(cfg, family, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_a, d_b, d_symbols,
+                                 n_streams, n_per_stream, layout, nullptr, nullptr, d_rstate, d_status, flags, (hipStream_t)stream);
 }
 
 } // extern "C"

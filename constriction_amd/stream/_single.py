@@ -57,12 +57,15 @@ def raise_for_status(status: int):
     raise RuntimeError(f"stream status {status}")
 
 
-def model_args(model, params, n_expected=None):
+def model_args(model, params, n_expected=None, families=False):
     """Classifies an (model, *params) call.  Returns one of
        ("table", device_model)                         concrete model, iid symbols
        ("gaussian", lo, hi, means, stds)               QuantizedGaussian family with per-symbol parameters
        ("rows", cdf_rows, min_symbol)                  one tabulated cdf row per symbol position (Categorical family with
                                                        a probability matrix; CustomModel / ScipyModel with parameters)
+       ("family", lo, hi, a, b, family)                QuantizedLaplace / QuantizedCauchy with per-symbol parameters, for the
+                                                       coders that ask for it (families=True: cst_*_family_batch); the others
+                                                       get these two as "rows"
     """
     if not isinstance(model, M.Model):
         raise TypeError("model must be a constriction_amd.stream.model.Model")
@@ -81,6 +84,9 @@ def model_args(model, params, n_expected=None):
         if len(means) != len(stds):
             raise ValueError("Model parameters have unequal lengths.")
         return ("gaussian", model.min_symbol, model.max_symbol, means, stds)
+    if families and isinstance(model, M._LeakyFamily):
+        a, b = model.family_params(params)
+        return ("family", model.min_symbol, model.max_symbol, a, b, model._family)
     if hasattr(model, "family_rows"):      # tabulated families: one cdf row per symbol position
         return ("rows", model.family_rows(params), model.min_symbol)
     raise TypeError("unsupported model family")

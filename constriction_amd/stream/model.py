@@ -424,16 +424,22 @@ class _LeakyFamily(Model):
             self._dev = batched.Model.from_cdf(self.cdf_table(), self.min_symbol, PRECISION)
         return self._dev
 
-    def family_rows(self, params):
+    def family_params(self, params):
+        """the checked per-symbol parameter arrays (a, b) of a call with parameters"""
         if len(params) != 2:
             raise ValueError(f"Wrong number of model parameters: expected ({self._names[0]}, {self._names[1]}).")
         a, b = _as_float_params(params[0], self._names[0]), _as_float_params(params[1], self._names[1])
         if len(a) != len(b):
             raise ValueError("Model parameters have unequal lengths.")
+        if len(a):
+            self._check(a, b)
+        return a, b
+
+    def family_rows(self, params):
+        a, b = self.family_params(params)
         n = self.max_symbol - self.min_symbol + 1
         if len(a) == 0:
             return np.zeros((0, n + 1), np.uint32)
-        self._check(a, b)
         from .. import batched
         return batched.family_cdf_rows(self._family, self.min_symbol, self.max_symbol, a, b)
 

@@ -100,9 +100,9 @@ class RangeEncoder:
             raise ValueError("To encode a single symbol, use a concrete model, i.e., pass the\n"
                              "model parameters directly to the constructor of the model and not to the\n"
                              "`encode` method of the entropy coder.")
-        kind = S.model_args(model, optional_model_params)
+        kind = S.model_args(model, optional_model_params, families=True)
         n = len(sym)
-        if kind[0] == "gaussian" and len(kind[3]) != n or kind[0] == "rows" and len(kind[1]) != n:
+        if kind[0] in ("gaussian", "family") and len(kind[3]) != n or kind[0] == "rows" and len(kind[1]) != n:
             raise ValueError("`symbols` argument has wrong length.")
         if n == 0:
             return
@@ -122,6 +122,12 @@ class RangeEncoder:
             st = L.cst_range_encode_gaussian_batch(S.cfg(), lo, hi, S.ptr(d_sym), S.ptr(d_mu), S.ptr(d_sd), 1, n,
                                                    N.LAYOUT_STREAM_MAJOR, S.ptr(d_words), cap, d_n, d_rs,
                                                    d_status, N.FLAG_RAW_STATE, sp)
+        elif kind[0] == "family":
+            _, lo, hi, pa, pb, fam = kind
+            d_sym, d_a, d_b = S.dev(sym), S.dev(pa), S.dev(pb)
+            st = L.cst_range_encode_family_batch(S.cfg(), fam, lo, hi, S.ptr(d_sym), S.ptr(d_a), S.ptr(d_b), 1, n,
+                                                 N.LAYOUT_STREAM_MAJOR, S.ptr(d_words), cap, d_n, d_rs,
+                                                 d_status, N.FLAG_RAW_STATE, sp)
         else:
             rows = kind[1]
             idx = sym.astype(np.int64) - kind[2]
@@ -196,8 +202,8 @@ class RangeDecoder:
             amt = int(params[0])
             kind = S.model_args(model, ())
         else:
-            kind = S.model_args(model, params)
-            amt = len(kind[3]) if kind[0] == "gaussian" else len(kind[1])
+            kind = S.model_args(model, params, families=True)
+            amt = len(kind[3]) if kind[0] in ("gaussian", "family") else len(kind[1])
         if amt == 0:
             return np.zeros(0, dtype=np.int32)
         L = N.lib()
@@ -218,6 +224,12 @@ class RangeDecoder:
             st = L.cst_range_decode_gaussian_batch(S.cfg(), lo, hi, S.ptr(d_words), None, max(nwin, 1), d_words.numel(), d_n, S.ptr(d_mu),
                                                    S.ptr(d_sd), S.ptr(d_sym), 1, amt, N.LAYOUT_STREAM_MAJOR, d_rs,
                                                    d_status, N.FLAG_RAW_STATE, sp)
+        elif kind[0] == "family":
+            _, lo, hi, pa, pb, fam = kind
+            d_a, d_b = S.dev(pa), S.dev(pb)
+            st = L.cst_range_decode_family_batch(S.cfg(), fam, lo, hi, S.ptr(d_words), None, max(nwin, 1), d_words.numel(), d_n, S.ptr(d_a),
+                                                 S.ptr(d_b), S.ptr(d_sym), 1, amt, N.LAYOUT_STREAM_MAJOR, d_rs,
+                                                 d_status, N.FLAG_RAW_STATE, sp)
         else:
             rows = kind[1]
             d_rows = S.dev(rows.view(np.int32))

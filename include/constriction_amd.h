@@ -596,6 +596,27 @@ cst_status cst_ans_decode_gaussian_batch(cst_coder_config cfg, int32_t min_symbo
                                          cst_layout layout, uint64_t *d_state, uint32_t *d_n_words_out,
                                          int32_t *d_status, uint32_t flags, void *stream);
 
+/* QuantizedLaplace / QuantizedCauchy with per-symbol parameters (src/pybindings/stream/model.rs:736-900): the Gaussian calls
+ * above over another CDF -- the same kernels, routes, slabs, offsets, words_capacity, CST_FLAG_RAW_STATE and layouts; no jump
+ * points.  family: CST_FAMILY_LAPLACE (d_a = means, d_b = scales) or CST_FAMILY_CAUCHY (d_a = locs, d_b = scales); d_a / d_b are
+ * f64 matrices of the symbols' shape and layout.  A scale <= 0 or a non-finite parameter, and a symbol outside
+ * [min_symbol, max_symbol], yield CST_STREAM_IMPOSSIBLE_SYMBOL for that stream.  The words are those of the tabulated route
+ * (cst_family_cdf_rows + cst_*_encode_cp_batch / cst_*_decode_rows_batch), without the n_symbols + 1 words of table per symbol.
+ * Any other family, a NULL matrix / words / counts / status pointer and max_symbol <= min_symbol return
+ * CST_ERR_INVALID_ARGUMENT before the device is touched. */
+cst_status cst_ans_encode_family_batch(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                       const int32_t *d_symbols, const double *d_a, const double *d_b,
+                                       size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                       uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                       uint64_t *d_state, int32_t *d_status, uint32_t flags, void *stream);
+
+cst_status cst_ans_decode_family_batch(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                       const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
+                                       const uint32_t *d_n_words, const double *d_a, const double *d_b,
+                                       int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
+                                       cst_layout layout, uint64_t *d_state, uint32_t *d_n_words_out,
+                                       int32_t *d_status, uint32_t flags, void *stream);
+
 /* Per-symbol models given explicitly (any model family with per-symbol parameters, e.g.
  * Categorical(perfect=False) with a probability matrix, src/pybindings/stream/model/internals.rs:188-249):
  *   encode: d_left / d_prob hold EncoderModel::left_cumulative_and_probability of every symbol
@@ -693,6 +714,20 @@ cst_status cst_range_decode_gaussian_batch(cst_coder_config cfg, int32_t min_sym
                                            int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
                                            cst_layout layout, cst_range_state *d_rstate, int32_t *d_status,
                                            uint32_t flags, void *stream);
+
+/* ... and over QuantizedLaplace / QuantizedCauchy (see cst_ans_encode_family_batch) */
+cst_status cst_range_encode_family_batch(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                         const int32_t *d_symbols, const double *d_a, const double *d_b,
+                                         size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                         uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                         cst_range_state *d_rstate, int32_t *d_status, uint32_t flags, void *stream);
+
+cst_status cst_range_decode_family_batch(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                         const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
+                                         const uint32_t *d_n_words, const double *d_a, const double *d_b,
+                                         int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
+                                         cst_layout layout, cst_range_state *d_rstate, int32_t *d_status,
+                                         uint32_t flags, void *stream);
 
 /* ABI 5: jump points for the per-symbol Gaussian calls of the RANGE coder (RangeEncoder::pos / RangeDecoder::seek, src/stream/queue.rs:172-196,
  * 900-926), as cst_ans_{encode,decode}_gaussian_batch_ckpt are for ANS: the fused encoder notes (words emitted including held-back ones,

@@ -1,15 +1,37 @@
 #!/usr/bin/env python3
-"""Per-symbol quantized Gaussians (the reference's flagship call, src/pybindings/stream/stack.rs:567-588, 733-751) batched:
-n_streams x n_per symbols, every symbol with its own (mean, std) in f64; both coders; round trip checked."""
+"""Per-symbol quantized models (the reference's flagship call, src/pybindings/stream/stack.rs:567-588, 733-751) batched:
+n_streams x n_per symbols, every symbol with its own two f64 parameters; both coders; round trip checked.
+
+    bench_per_symbol.py [n_streams [n_per]] [--family gaussian laplace cauchy] [--support LO HI] [--rows] [--reps N] [--rounds K]
+
+--family: one or more of gaussian (mean, std), laplace (mean, scale), cauchy (loc, scale); several families are timed in the
+          same process on the same parameter matrices, alternating, `--rounds` times over: compare medians, look at the spread.
+          Next to another family the Gaussian is also timed without jump points, which the other families do not have.
+--rows:   also times what a caller of Laplace / Cauchy had before the family calls: one tabulated cdf row per symbol
+          (family_cdf_rows) + cst_ans_encode_cp_batch / cst_ans_decode_rows_batch.  n_symbols + 1 words of row per symbol: keep
+          the batch small (4096 x 256 at a 201-symbol support is 850 MB of rows)."""
+import argparse
+import statistics
 import sys
 from pathlib import Path
 import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from constriction_amd import batched as B
+from constriction_amd import _native as N
+
+ap = argparse.ArgumentParser()
+ap.add_argument("n_streams", nargs="?", type=int, default=65536)
+ap.add_argument("n_per", nargs="?", type=int, default=4096)
+ap.add_argument("--family", nargs="+", choices=["gaussian", "laplace", "cauchy"], default=["gaussian"])
+ap.add_argument("--support", nargs=2, type=int, default=[-127, 127], metavar=("LO", "HI"))
+ap.add_argument("--rows", action="store_true")
+ap.add_argument("--reps", type=int, default=3, help="calls per timed window")
+ap.add_argument("--rounds", type=int, default=1, help="timed windows per entry (the median and the range are printed)")
+args = ap.parse_args()
+n_streams, n_per, (lo, hi) = args.n_streams, args.n_per, args.support
 
 
-def timed(f, reps=3):
-    f(); torch.cuda.synchronize()
+def timed(f, reps):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(reps):
@@ -18,15 +40,80 @@ def timed(f, reps=3):
     return e0.elapsed_time(e1) / reps, out
 
 
-n_streams = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
-n_per = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 g = torch.Generator(device="cuda").manual_seed(1)
 means = (torch.rand((n_streams, n_per), generator=g, device="cuda", dtype=torch.float64) * 20 - 10)
 stds = torch.exp(torch.rand((n_streams, n_per), generator=g, device="cuda", dtype=torch.float64) * 3.4 - 0.7)
-sym = torch.clamp(torch.round(torch.randn((n_streams, n_per), generator=g, device="cuda", dtype=torch.float64) * stds + means), -127, 127).to(torch.int32)
-for name, enc_f, dec_f in (("ans", B.ans_encode_gaussian, B.ans_decode_gaussian), ("range", B.range_encode_gaussian, B.range_decode_gaussian)):
-    e, enc = timed(lambda: enc_f(sym, -127, 127, means, stds))
-    d, (dec, st) = timed(lambda: dec_f(enc, -127, 127, means, stds))
-    ok = bool(torch.equal(dec, sym)) and int(st.abs().sum()) == 0
-    ns = n_streams * n_per
-    print(f"{name:5s} per-symbol Gaussians {n_streams} x {n_per}: encode {e:8.3f} ms ({ns / e / 1e6:6.1f} Gsym/s)  decode {d:8.3f} ms ({ns / d / 1e6:6.1f} Gsym/s)  roundtrip_ok={ok}")
+sym = torch.clamp(torch.round(torch.randn((n_streams, n_per), generator=g, device="cuda", dtype=torch.float64) * stds + means), lo, hi).to(torch.int32)
+
+
+def family_calls(family, coder, jump_points="auto"):
+    if family == "gaussian":
+        enc_f, dec_f = getattr(B, f"{coder}_encode_gaussian"), getattr(B, f"{coder}_decode_gaussian")
+        return (lambda: enc_f(sym, lo, hi, means, stds, jump_points=jump_points)), (lambda enc: dec_f(enc, lo, hi, means, stds))
+    enc_f, dec_f = getattr(B, f"{coder}_encode_family"), getattr(B, f"{coder}_decode_family")
+    return (lambda: enc_f(family, sym, lo, hi, means, stds)), (lambda enc: dec_f(family, enc, lo, hi, means, stds))
+
+
+def rows_calls(family, coder):
+    """the tabulated route, rows built inside the timed call (they are part of what the caller pays)"""
+    fam = B.FAMILIES[family]
+    n = hi - lo + 1
+    L, cfg = N.lib(), B._cfg(32, 64, 24)
+    a, b = means.reshape(-1), stds.reshape(-1)
+    rows = torch.empty((n_streams * n_per, n + 1), dtype=torch.int32, device="cuda")
+    idx = (sym.reshape(-1).to(torch.int64) - lo)
+    ar = torch.arange(n_streams * n_per, device="cuda")
+    stride = (B.max_words if coder == "ans" else B.range_max_words)(n_per, (32, 64, 24))
+    out = B._new_batch(n_streams, stride, sym.device, (32, 64, 24))
+    dec = torch.empty_like(sym)
+    status = torch.empty(n_streams, dtype=torch.int32, device="cuda")
+    p, sp = B._ptr, B._stream_ptr
+
+    def tabulate():
+        N.check(L.cst_family_cdf_rows(fam, 24, lo, hi, p(a), p(b), None, a.numel(), p(rows), None, sp()), "cst_family_cdf_rows")
+
+    def encode():
+        tabulate()
+        left = rows[ar, idx].contiguous()
+        prob = (rows[ar, idx + 1] - left).contiguous()
+        fn = getattr(L, f"cst_{coder}_encode_cp_batch")
+        N.check(fn(cfg, p(left), p(prob), n_streams, n_per, N.LAYOUT_STREAM_MAJOR, p(out.words), stride, p(out.n_words), None, p(out.status),
+                   N.FLAG_NONE, sp()), "encode_cp")
+        return out
+
+    def decode(enc):
+        tabulate()
+        args_ = [cfg, p(enc.words), None, stride, enc.words.numel(), p(enc.n_words), p(rows), n, lo, p(dec), n_streams, n_per, N.LAYOUT_STREAM_MAJOR, None]
+        if coder == "ans":
+            args_.append(None)
+        N.check(getattr(L, f"cst_{coder}_decode_rows_batch")(*args_, p(status), N.FLAG_NONE, sp()), "decode_rows")
+        return dec, status
+    return encode, decode
+
+
+entries = []
+for coder in ("ans", "range"):
+    for family in args.family:
+        entries.append((coder, family, "", *family_calls(family, coder)))
+        if family == "gaussian" and len(args.family) > 1:      # the other families have no jump points: like for like
+            entries.append((coder, family, " without jump points", *family_calls(family, coder, 0)))
+        if args.rows and family != "gaussian":
+            entries.append((coder, family, " by rows", *rows_calls(family, coder)))
+results = {i: ([], []) for i in range(len(entries))}
+encoded, checked = {}, {}
+for i, (coder, family, how, enc_f, dec_f) in enumerate(entries):          # warm-up of every shape and route, and the check
+    encoded[i] = enc_f()
+    dec, st = dec_f(encoded[i])
+    torch.cuda.synchronize()
+    checked[i] = bool(torch.equal(dec, sym)) and int(st.abs().sum()) == 0
+for _ in range(args.rounds):                                                # alternating: every entry once per round
+    for i, (coder, family, how, enc_f, dec_f) in enumerate(entries):
+        e, enc = timed(enc_f, args.reps)
+        d, _ = timed(lambda: dec_f(enc), args.reps)
+        results[i][0].append(e); results[i][1].append(d)
+ns = n_streams * n_per
+for i, (coder, family, how, _, _) in enumerate(entries):
+    es, ds = results[i]
+    e, d = statistics.median(es), statistics.median(ds)
+    print(f"{coder:5s} per-symbol {family}{how} {n_streams} x {n_per} [{lo}, {hi}]: encode {e:8.3f} ms ({ns / e / 1e6:6.1f} Gsym/s, {min(es):.3f}..{max(es):.3f})  "
+          f"decode {d:8.3f} ms ({ns / d / 1e6:6.1f} Gsym/s, {min(ds):.3f}..{max(ds):.3f})  roundtrip_ok={checked[i]}")
