@@ -790,7 +790,7 @@ extern "C" {
     ///   CST_SMALL_KERNELS=0|enc|dec   never / only the encoder / only the decoder of the small-footprint kernels
     ///   CST_DQ_DECODER=1         the lane-quad decoder without CST_FLAG_COLD_WORDS CST_PT_SUB_WAVES=8 sub-lane decoder: never sixteen waves
     ///   CST_SUB_ORDER=0          range sub-lane decoder: chunks side by side      CST_LANE_GEO=big|small   per-symbol lane decoder geometry
-    ///   CST_FUSED_MIN_STREAMS=n  from how many streams the fused per-symbol encoder runs
+    ///   CST_FUSED_MIN_STREAMS=n  from how many streams the fused per-symbol encoder runs         CST_CATEGORICAL_ROUTE=fused|rows   per-symbol Categorical decoders: the route
     ///   CST_AUTO_JUMP=0          cst_jump_points_auto* answer 0                  CST_RAGGED_GROUP=8|16|32   ragged encoder: symbols per memory point
     /// (CST_RCCL_LIB=<path>, read at the first collective call, names the RCCL library to open.)
     /// cst_debug_reload_knobs re-reads them: for tests that drive several paths inside one process; not thread-safe against
@@ -1038,6 +1038,82 @@ extern "C" {
         d_status: *mut i32,
         flags: u32,
         stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// Categorical models with per-symbol probability vectors (Categorical(perfect=False) / Categorical(lazy=True) with a rank-2 array of
+    /// probabilities, src/pybindings/stream/model/internals.rs:399-514): symbol (s, t) is coded with the "fast" quantisation
+    /// (src/stream/model/categorical.rs:16-54 = LazyContiguousCategoricalEntropyModel, lazy_contiguous.rs:131-331) of row (s, t) of
+    /// d_probs, a float (prob_bytes = 4) or double (prob_bytes = 8) matrix of the symbol matrix's shape and layout with the n_symbols
+    /// entries of a row innermost.  The arithmetic is done in the type of the matrix -- float stays float -- by one sequential sum per
+    /// row; symbols are 0 .. n_symbols - 1.  The same slabs, offsets, words_capacity, CST_FLAG_RAW_STATE and layouts as the Gaussian
+    /// calls; no jump points.
+    /// Before the device is touched: a NULL symbols / probabilities / words / counts / status pointer and prob_bytes outside {4, 8}
+    /// return CST_ERR_INVALID_ARGUMENT, n_symbols < 2 or n_symbols >= 2^precision - 1 returns CST_ERR_MODEL.
+    /// Per stream: a row whose sum is not a positive normal number or that holds a negative or NaN entry, a symbol outside
+    /// [0, n_symbols) and a symbol whose interval comes out empty (an f32 row can end in one) yield CST_STREAM_IMPOSSIBLE_SYMBOL.
+    /// CST_CATEGORICAL_ROUTE=fused|rows (debug switch) forces the decoders' route: one lane per stream walking its rows (default
+    /// from 64 streams on), or rows tabulated in pieces and looked up by one wave per stream.
+    pub fn cst_ans_encode_categorical_batch(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_state: *mut u64,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_categorical_batch(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_state: *mut u64,
+        d_n_words_out: *mut u32,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// The quantised rows themselves: d_rows[r][0 .. n_symbols] = left cumulatives of row r of d_probs [n_rows][n_symbols], then
+    /// 2^precision (1 <= precision <= 31).  A bad row (see above) is written as 0xffffffff followed by 2^precision, and d_bad[r]
+    /// (optional) is 1 for it, else 0.  cst_categorical_fast_cdf_host is the same row walk on the CPU over host buffers.
+    pub fn cst_categorical_fast_cdf_rows(
+        precision: i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_rows: usize,
+        n_symbols: i32,
+        d_rows: *mut u32,
+        d_bad: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_categorical_fast_cdf_host(
+        precision: i32,
+        h_probs: *const c_void,
+        prob_bytes: i32,
+        n_rows: usize,
+        n_symbols: i32,
+        h_rows: *mut u32,
+        h_bad: *mut i32,
     ) -> CstStatus;
 
     /// Per-symbol models given explicitly (any model family with per-symbol parameters, e.g.
@@ -1304,6 +1380,45 @@ extern "C" {
         d_n_words: *const u32,
         d_a: *const f64,
         d_b: *const f64,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_rstate: *mut CstRangeState,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// ... and over Categorical probability matrices (see cst_ans_encode_categorical_batch)
+    pub fn cst_range_encode_categorical_batch(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_rstate: *mut CstRangeState,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_categorical_batch(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
         d_symbols: *mut i32,
         n_streams: usize,
         n_per_stream: usize,

@@ -186,6 +186,73 @@ pub fn last_kernel_name() -> String {
 // entropy models
 // ---------------------------------------------------------------------------------------------------------------------
 
+/// Element types of a Categorical probability matrix (`cst_*_categorical_batch`): the quantisation runs in this type, `f32` stays `f32`.
+pub trait Probability: Copy {
+    const BYTES: i32;
+}
+impl Probability for f32 {
+    const BYTES: i32 = 4;
+}
+impl Probability for f64 {
+    const BYTES: i32 = 8;
+}
+
+/// The "fast" quantisation of `n_rows` probability vectors of `n_symbols` entries on the device
+/// (`Categorical(perfect=False)` / `lazy=True`, src/stream/model/categorical.rs:16-54): rows of `n_symbols + 1` cumulatives, and a
+/// flag per row that is 1 where the vector is not normalizable.
+pub fn categorical_fast_cdf_rows<F: Probability>(
+    precision: u32,
+    probabilities: &DeviceBuffer<F>,
+    n_rows: usize,
+    n_symbols: usize,
+    stream: &Stream,
+) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>)> {
+    let count = n_rows.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+    if probabilities.len() < count || n_symbols > i32::MAX as usize {
+        return Err(Error::InvalidArgument);
+    }
+    let mut rows: DeviceBuffer<u32> = DeviceBuffer::new(count + n_rows)?;
+    let mut bad: DeviceBuffer<i32> = DeviceBuffer::new(n_rows)?;
+    check(unsafe {
+        ffi::cst_categorical_fast_cdf_rows(
+            precision as i32,
+            probabilities.as_ptr() as *const c_void,
+            F::BYTES,
+            n_rows,
+            n_symbols as i32,
+            rows.as_mut_ptr(),
+            bad.as_mut_ptr(),
+            stream.as_raw(),
+        )
+    })?;
+    Ok((rows, bad))
+}
+
+/// The same row walk on the CPU over host slices: `rows` takes `n_symbols + 1` cumulatives per vector.  Returns one flag per row,
+/// `true` where the vector is not normalizable.
+pub fn categorical_fast_cdf_host<F: Probability>(precision: u32, probabilities: &[F], n_symbols: usize, rows: &mut [u32]) -> Result<Vec<bool>> {
+    if n_symbols == 0 || probabilities.len() % n_symbols != 0 || n_symbols > i32::MAX as usize {
+        return Err(Error::InvalidArgument);
+    }
+    let n_rows = probabilities.len() / n_symbols;
+    if rows.len() < n_rows * (n_symbols + 1) {
+        return Err(Error::InvalidArgument);
+    }
+    let mut bad = vec![0i32; n_rows];
+    check(unsafe {
+        ffi::cst_categorical_fast_cdf_host(
+            precision as i32,
+            probabilities.as_ptr() as *const c_void,
+            F::BYTES,
+            n_rows,
+            n_symbols as i32,
+            rows.as_mut_ptr(),
+            bad.as_mut_ptr(),
+        )
+    })?;
+    Ok(bad.into_iter().map(|b| b != 0).collect())
+}
+
 /// A device-resident entropy model over a contiguous `i32` support: the encoder side is
 /// `EncoderModel::left_cumulative_and_probability` as a table (ContiguousCategoricalEntropyModel,
 /// src/stream/model/categorical/contiguous.rs:673-700), the decoder side `ContiguousLookupDecoderModel`
@@ -928,6 +995,45 @@ impl BatchedAnsCoder {
         Ok(out)
     }
 
+    /// `encode_symbols_reverse` with one Categorical model per symbol, given as probabilities (Python `encode_reverse(symbols, Categorical(perfect=False), probabilities)`, src/pybindings/stream/model/internals.rs:399-514).
+    /// `probabilities`: one vector of `n_symbols` entries per symbol, of the symbol matrix's shape and layout.
+    pub fn encode_symbols_reverse_categorical<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_streams: usize,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<EncodedBatch> {
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        let entries = count.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if symbols.len() < count || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = EncodedBatch::allocate(n_streams, self.max_words(n_per_stream), self.config)?;
+        check(unsafe {
+            ffi::cst_ans_encode_categorical_batch(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                out.words.as_mut_ptr(),
+                out.stride_words,
+                out.n_words.as_mut_ptr(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
     /// `encode_symbols_reverse` + `pos()` in front of every chunk of `interval` symbols (a multiple of 16 that divides the row
     /// length; batches of at least 16 384 streams): the jump table of the reference's flagship call.
     pub fn encode_symbols_reverse_with_checkpoints(
@@ -1164,6 +1270,47 @@ impl BatchedAnsCoder {
                 encoded.n_words.as_ptr(),
                 a.as_ptr(),
                 b.as_ptr(),
+                out.symbols.as_mut_ptr(),
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                core::ptr::null_mut(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
+    /// `decode_symbols` with one Categorical model per symbol (see `encode_symbols_reverse_categorical`).
+    pub fn decode_symbols_categorical<F: Probability>(
+        &self,
+        encoded: &EncodedBatch,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<DecodedBatch> {
+        let n_streams = encoded.n_streams;
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        let entries = count.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = DecodedBatch { symbols: DeviceBuffer::new(count)?, status: DeviceBuffer::new(n_streams)? };
+        check(unsafe {
+            ffi::cst_ans_decode_categorical_batch(
+                self.config,
+                encoded.words.as_ptr(),
+                core::ptr::null(),
+                encoded.stride_words,
+                encoded.words.len(),
+                encoded.n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
                 out.symbols.as_mut_ptr(),
                 n_streams,
                 n_per_stream,
@@ -1887,6 +2034,45 @@ impl BatchedRangeEncoder {
         Ok(out)
     }
 
+    /// `encode_symbols` with one Categorical model per symbol, given as probabilities (Python `RangeEncoder.encode(symbols, Categorical(lazy=True), probabilities)`).
+    /// `probabilities`: one vector of `n_symbols` entries per symbol, of the symbol matrix's shape and layout.
+    pub fn encode_symbols_categorical<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_streams: usize,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<EncodedBatch> {
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        let entries = count.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if symbols.len() < count || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = EncodedBatch::allocate(n_streams, self.max_words(n_per_stream), self.config)?;
+        check(unsafe {
+            ffi::cst_range_encode_categorical_batch(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                out.words.as_mut_ptr(),
+                out.stride_words,
+                out.n_words.as_mut_ptr(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
     /// `encode_symbols` that also notes `RangeEncoder::pos()` in front of every chunk of `interval` symbols (ABI 5,
     /// `cst_range_encode_gaussian_batch_ckpt`; src/stream/queue.rs:172-196): a multiple of 16 that divides `n_per_stream`, stream-major.
     /// The words are those of `encode_symbols`.  `auto_jump_interval_gaussian` is the library's own choice of `interval`.
@@ -2280,6 +2466,46 @@ impl BatchedRangeDecoder {
                 encoded.n_words.as_ptr(),
                 a.as_ptr(),
                 b.as_ptr(),
+                out.symbols.as_mut_ptr(),
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
+    /// `decode_symbols` with one Categorical model per symbol (see `encode_symbols_categorical`).
+    pub fn decode_symbols_categorical<F: Probability>(
+        &self,
+        encoded: &EncodedBatch,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<DecodedBatch> {
+        let n_streams = encoded.n_streams;
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        let entries = count.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = DecodedBatch { symbols: DeviceBuffer::new(count)?, status: DeviceBuffer::new(n_streams)? };
+        check(unsafe {
+            ffi::cst_range_decode_categorical_batch(
+                self.config,
+                encoded.words.as_ptr(),
+                core::ptr::null(),
+                encoded.stride_words,
+                encoded.words.len(),
+                encoded.n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
                 out.symbols.as_mut_ptr(),
                 n_streams,
                 n_per_stream,

@@ -1164,6 +1164,111 @@ range_decode_laplace, range_decode_cauchy = _named_family(range_decode_family, "
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# per-symbol Categorical models from a matrix of probabilities: the reference's
+#     coder.encode_reverse(symbols, Categorical(perfect=False), probabilities) / coder.decode(Categorical(lazy=True), probabilities)
+# (src/pybindings/stream/model/internals.rs:399-514) -- what an autoregressive model on the GPU puts out.  `probabilities`: a
+# float32 or float64 tensor of shape symbols.shape + (K,), contiguous in the chosen layout; the "fast" quantisation runs in its
+# dtype inside the coder kernels (float32 is NOT widened: the reference's tables differ between the two), symbols are 0 .. K - 1.
+# ---------------------------------------------------------------------------------------------------------------------
+
+_PROB_BYTES = {torch.float32: 4, torch.float64: 8}
+
+
+def _categorical_args(matrix_shape, probabilities, precision):
+    if not isinstance(probabilities, torch.Tensor) or not probabilities.is_cuda:
+        raise ValueError("probabilities must live in device memory (HBM)")
+    if probabilities.dtype not in _PROB_BYTES:
+        raise TypeError("probabilities must have dtype torch.float32 or torch.float64")
+    if matrix_shape is not None and tuple(probabilities.shape[:-1]) != tuple(matrix_shape):
+        raise ValueError("probabilities must have the shape of the symbol matrix plus one axis of K entries")
+    k = int(probabilities.shape[-1]) if probabilities.dim() else 0
+    if k < 2 or k >= (1 << precision) - 1:
+        raise ValueError("a Categorical model needs 2 <= K < 2**precision - 1 entries")
+    return probabilities.contiguous(), _PROB_BYTES[probabilities.dtype], k
+
+
+def categorical_cdf_rows(probabilities, precision: int = 24) -> torch.Tensor:
+    """The fast-quantised cdf rows of `probabilities` [..., K], tabulated on the GPU (cst_categorical_fast_cdf_rows): an int32
+    tensor [..., K + 1] holding uint32 left cumulatives and 2^precision, the rows that cst_*_decode_rows_batch and
+    model.Categorical(perfect=False) use.  Raises the reference's ValueError if a row is not normalizable."""
+    if probabilities.dim() < 1:
+        raise ValueError("probabilities must have at least one axis")
+    probs, nbytes, k = _categorical_args(None, probabilities, precision)
+    n_rows = probs.numel() // k
+    rows = torch.empty(tuple(probs.shape[:-1]) + (k + 1,), dtype=torch.int32, device=probs.device)
+    bad = torch.empty(max(n_rows, 1), dtype=torch.int32, device=probs.device)
+    if n_rows:
+        N.check(N.lib().cst_categorical_fast_cdf_rows(int(precision), _ptr(probs), nbytes, n_rows, k, _ptr(rows), _ptr(bad), _stream_ptr()),
+                "cst_categorical_fast_cdf_rows")
+        if bool(bad[:n_rows].any().item()):
+            raise ValueError("Probability distribution not normalizable (the array of probabilities\n"
+                             "might be empty, contain negative values or NaNs, or sum to infinity).")
+    return rows
+
+
+def _encode_categorical(fn_name, max_words_fn, symbols, probabilities, config, layout, stride, out):
+    symbols = _require_cuda(symbols, torch.int32, "symbols")
+    n_streams, n_per, lay = _layout_shape(symbols, layout)
+    probs, nbytes, k = _categorical_args(symbols.shape, probabilities, config[2])
+    if out is None:
+        out = _new_batch(n_streams, stride or max_words_fn(n_per, config), symbols.device, config)
+    N.check(getattr(N.lib(), fn_name)(_cfg(*config), _ptr(symbols), _ptr(probs), nbytes, k, n_streams, n_per, lay, _ptr(out.words),
+                                      out.words.shape[1], _ptr(out.n_words), None, _ptr(out.status), N.FLAG_NONE, _stream_ptr()), fn_name)
+    out.jump = None
+    return out
+
+
+def ans_encode_categorical(symbols, probabilities, config=(32, 64, 24), layout="stream_major", stride: Optional[int] = None,
+                           out: Optional[EncodedBatch] = None) -> EncodedBatch:
+    """One AnsCoder per stream: encode_reverse(symbols[s], Categorical(perfect=False), probabilities[s]) + get_compressed."""
+    return _encode_categorical("cst_ans_encode_categorical_batch", max_words, symbols, probabilities, config, layout, stride, out)
+
+
+def range_encode_categorical(symbols, probabilities, config=(32, 64, 24), layout="stream_major", stride: Optional[int] = None,
+                             out: Optional[EncodedBatch] = None) -> EncodedBatch:
+    """One RangeEncoder per stream: encode(symbols[s], Categorical(perfect=False), probabilities[s]) + get_compressed."""
+    return _encode_categorical("cst_range_encode_categorical_batch", range_max_words, symbols, probabilities, config, layout, stride, out)
+
+
+def _decode_categorical(fn_name, ans, encoded, probabilities, layout, offsets, out, config):
+    if isinstance(encoded, EncodedBatch):
+        words, n_words, config = encoded.words, encoded.n_words, config or encoded.config
+        stride = words.shape[1]
+    else:
+        words, n_words = encoded
+        stride = words.shape[1] if words.dim() == 2 else 0
+        config = config or (32, 64, 24)
+    if not isinstance(probabilities, torch.Tensor) or probabilities.dim() != 3:
+        raise ValueError("probabilities must be 3-d: the symbol matrix's two axes and one of K entries")
+    n_streams, n_per, lay = _layout_shape(probabilities[..., 0], layout)
+    if n_streams != n_words.numel():
+        raise ValueError("probabilities do not match the number of streams")
+    probs, nbytes, k = _categorical_args(probabilities.shape[:2], probabilities, config[2])
+    dev = words.device
+    if out is None:
+        out = torch.empty(tuple(probs.shape[:2]), dtype=torch.int32, device=dev)
+    status = torch.empty(n_streams, dtype=torch.int32, device=dev)
+    args = [_cfg(*config), _ptr(words), _ptr(offsets), stride, words.numel(), _ptr(n_words), _ptr(probs), nbytes, k, _ptr(out), n_streams, n_per,
+            lay, None]
+    if ans:
+        args.append(None)          # d_n_words_out
+    N.check(getattr(N.lib(), fn_name)(*args, _ptr(status), N.FLAG_NONE, _stream_ptr()), fn_name)
+    return out, status
+
+
+def ans_decode_categorical(encoded, probabilities, layout="stream_major", offsets=None, out=None, config=None):
+    """One AnsCoder per stream: AnsCoder(words[s]).decode(Categorical(perfect=False), probabilities[s]).  `encoded`: an
+    EncodedBatch, or (packed, n_words) with offsets= (compact()).  Returns (symbols, status)."""
+    return _decode_categorical("cst_ans_decode_categorical_batch", True, encoded, probabilities, layout, offsets, out, config)
+
+
+def range_decode_categorical(encoded, probabilities, layout="stream_major", offsets=None, out=None, config=None):
+    """One RangeDecoder per stream: RangeDecoder(words[s]).decode(Categorical(perfect=False), probabilities[s]).  Returns
+    (symbols, status)."""
+    return _decode_categorical("cst_range_decode_categorical_batch", False, encoded, probabilities, layout, offsets, out, config)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # checkpointed streams (the reference's Pos / Seek jump tables, src/stream/stack.rs:1107-1139): one long stream decodes
 # on as many lanes as it has chunks
 # ---------------------------------------------------------------------------------------------------------------------

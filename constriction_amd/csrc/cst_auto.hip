@@ -38,6 +38,7 @@ static Knobs read_knobs() {
     if (const char* e = env("CST_FUSED_MIN_STREAMS")) k.fused_min_streams = (size_t)strtoull(e, nullptr, 10);
     if (const char* e = env("CST_AUTO_JUMP")) k.auto_jump = e[0] == '0' ? 0 : 1;
     if (const char* e = env("CST_RAGGED_GROUP")) k.ragged_group = e[0] == '8' ? 8 : e[0] == '3' ? 32 : 16;
+    if (const char* e = env("CST_CATEGORICAL_ROUTE")) k.categorical_route = e[0] == 'f' ? 1 : e[0] == 'r' ? 2 : 0;
     return k;
 }
 

@@ -156,6 +156,7 @@ struct Knobs {
     size_t fused_min_streams = 16384; // CST_FUSED_MIN_STREAMS: from how many streams the fused per-symbol encoder runs
     int auto_jump = 1;                // CST_AUTO_JUMP=0: cst_jump_points_auto answers 0 (the plain decoders everywhere)
     int ragged_group = 16;            // CST_RAGGED_GROUP=8|16|32: symbols per memory point of the ragged encoder (cst_ans_ragged.hip)
+    int categorical_route = 0;        // CST_CATEGORICAL_ROUTE=fused|rows: 1 / 2 forces a route of the per-symbol Categorical decoders (0: by shape)
 };
 const Knobs& knobs();
 

@@ -66,6 +66,10 @@ def model_args(model, params, n_expected=None, families=False):
        ("family", lo, hi, a, b, family)                QuantizedLaplace / QuantizedCauchy with per-symbol parameters, for the
                                                        coders that ask for it (families=True: cst_*_family_batch); the others
                                                        get these two as "rows"
+       ("categorical", matrix)                         Categorical(perfect=False) / Categorical(lazy=True) / Bernoulli(perfect=False)
+                                                       with per-symbol probabilities, as the checked float32 / float64 matrix
+                                                       [symbols][K] (families=True: cst_*_categorical_batch); perfect=True
+                                                       and the other coders get "rows"
     """
     if not isinstance(model, M.Model):
         raise TypeError("model must be a constriction_amd.stream.model.Model")
@@ -84,6 +88,8 @@ def model_args(model, params, n_expected=None, families=False):
         if len(means) != len(stds):
             raise ValueError("Model parameters have unequal lengths.")
         return ("gaussian", model.min_symbol, model.max_symbol, means, stds)
+    if families and isinstance(model, (M.Categorical, M.Bernoulli)) and not model.perfect:
+        return ("categorical", model.family_matrix(params))
     if families and isinstance(model, M._LeakyFamily):
         a, b = model.family_params(params)
         return ("family", model.min_symbol, model.max_symbol, a, b, model._family)

@@ -70,6 +70,23 @@ def fast_quantized_cdf(probabilities: np.ndarray, precision: int = PRECISION) ->
     return cdf
 
 
+def check_probability_matrix(m: np.ndarray, precision: int = PRECISION) -> np.ndarray:
+    """What `fast_quantized_cdf` refuses, for every row of a probability matrix at once: entries that are not finite or
+    negative, and a sequential row sum (in the matrix's dtype) that is not a positive normal number -- the reference's
+    ValueError, raised before anything is uploaded."""
+    err = ValueError("Probability distribution not normalizable (the array of probabilities\n"
+                     "might be empty, contain negative values or NaNs, or sum to infinity).")
+    n = m.shape[1]
+    if n < 2 or n >= (1 << precision) - 1:
+        raise err
+    if len(m):
+        with np.errstate(over="ignore", invalid="ignore"):
+            norm = np.cumsum(m, axis=1, dtype=m.dtype)[:, -1]          # sequential accumulation, like Iterator::sum
+        if not (np.isfinite(m).all() and (m >= 0).all() and np.isfinite(norm).all() and (norm >= np.finfo(m.dtype).tiny).all()):
+            raise err
+    return m
+
+
 _warned = set()
 
 
@@ -200,6 +217,10 @@ class Categorical(Model):
 
     def family_rows(self, params) -> np.ndarray:
         """One quantised cdf row per symbol for the family form (a rank-2 array of probabilities)."""
+        m = self._matrix(params)
+        return np.stack([self._quantize(row) for row in m]) if len(m) else np.zeros((0, m.shape[1] + 1), np.uint32)
+
+    def _matrix(self, params):
         if len(params) != 1:
             raise ValueError("Wrong number of model parameters: Categorical expects one rank-2 array of probabilities.")
         m = np.asarray(params[0])
@@ -207,7 +228,11 @@ class Categorical(Model):
             raise ValueError("expected a rank-2 array of probabilities (one row per symbol)")
         if m.dtype not in (np.float32, np.float64):
             raise TypeError("probabilities must have dtype float32 or float64")
-        return np.stack([self._quantize(row) for row in m]) if len(m) else np.zeros((0, m.shape[1] + 1), np.uint32)
+        return np.ascontiguousarray(m)
+
+    def family_matrix(self, params) -> np.ndarray:
+        """the checked probability matrix of a call with parameters (fast quantisation: the coder kernels quantise it)"""
+        return check_probability_matrix(self._matrix(params))
 
     @staticmethod
     def cdf_rows(prob_matrix) -> np.ndarray:
@@ -252,6 +277,16 @@ class Bernoulli(Model):
             from .. import batched
             self._dev = batched.Model.from_cdf(self.cdf, 0, PRECISION)
         return self._dev
+
+    def family_matrix(self, params) -> np.ndarray:
+        """the f64 probability matrix [1 - p, p] of a call with parameters (fast quantisation)"""
+        if len(params) != 1:
+            raise ValueError("Wrong number of model parameters: Bernoulli expects one array `p`.")
+        ps = _as_float_params(params[0], "p")
+        try:
+            return check_probability_matrix(np.stack([1.0 - ps, ps], axis=1))
+        except ValueError:
+            raise ValueError("`p` must be >= 0.0 and <= 1.0.") from None
 
     def family_rows(self, params):
         if len(params) != 1:

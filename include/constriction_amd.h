@@ -485,7 +485,7 @@ size_t cst_jump_points_auto_gaussian(cst_coder_config cfg, int32_t coder, size_t
  *   CST_SMALL_KERNELS=0|enc|dec   never / only the encoder / only the decoder of the small-footprint kernels
  *   CST_DQ_DECODER=1         the lane-quad decoder without CST_FLAG_COLD_WORDS CST_PT_SUB_WAVES=8 sub-lane decoder: never sixteen waves
  *   CST_SUB_ORDER=0          range sub-lane decoder: chunks side by side      CST_LANE_GEO=big|small   per-symbol lane decoder geometry
- *   CST_FUSED_MIN_STREAMS=n  from how many streams the fused per-symbol encoder runs
+ *   CST_FUSED_MIN_STREAMS=n  from how many streams the fused per-symbol encoder runs         CST_CATEGORICAL_ROUTE=fused|rows   per-symbol Categorical decoders: the route
  *   CST_AUTO_JUMP=0          cst_jump_points_auto* answer 0                  CST_RAGGED_GROUP=8|16|32   ragged encoder: symbols per memory point
  * (CST_RCCL_LIB=<path>, read at the first collective call, names the RCCL library to open.)
  * cst_debug_reload_knobs re-reads them: for tests that drive several paths inside one process; not thread-safe against
@@ -617,6 +617,38 @@ cst_status cst_ans_decode_family_batch(cst_coder_config cfg, int32_t family, int
                                        cst_layout layout, uint64_t *d_state, uint32_t *d_n_words_out,
                                        int32_t *d_status, uint32_t flags, void *stream);
 
+/* Categorical models with per-symbol probability vectors (Categorical(perfect=False) / Categorical(lazy=True) with a rank-2 array of
+ * probabilities, src/pybindings/stream/model/internals.rs:399-514): symbol (s, t) is coded with the "fast" quantisation
+ * (src/stream/model/categorical.rs:16-54 = LazyContiguousCategoricalEntropyModel, lazy_contiguous.rs:131-331) of row (s, t) of
+ * d_probs, a float (prob_bytes = 4) or double (prob_bytes = 8) matrix of the symbol matrix's shape and layout with the n_symbols
+ * entries of a row innermost.  The arithmetic is done in the type of the matrix -- float stays float -- by one sequential sum per
+ * row; symbols are 0 .. n_symbols - 1.  The same slabs, offsets, words_capacity, CST_FLAG_RAW_STATE and layouts as the Gaussian
+ * calls; no jump points.
+ * Before the device is touched: a NULL symbols / probabilities / words / counts / status pointer and prob_bytes outside {4, 8}
+ * return CST_ERR_INVALID_ARGUMENT, n_symbols < 2 or n_symbols >= 2^precision - 1 returns CST_ERR_MODEL.
+ * Per stream: a row whose sum is not a positive normal number or that holds a negative or NaN entry, a symbol outside
+ * [0, n_symbols) and a symbol whose interval comes out empty (an f32 row can end in one) yield CST_STREAM_IMPOSSIBLE_SYMBOL.
+ * CST_CATEGORICAL_ROUTE=fused|rows (debug switch) forces the decoders' route: one lane per stream walking its rows (default
+ * from 64 streams on), or rows tabulated in pieces and looked up by one wave per stream. */
+cst_status cst_ans_encode_categorical_batch(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs, int32_t prob_bytes,
+                                            int32_t n_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                            uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                            uint64_t *d_state, int32_t *d_status, uint32_t flags, void *stream);
+
+cst_status cst_ans_decode_categorical_batch(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words,
+                                            size_t words_capacity, const uint32_t *d_n_words, const void *d_probs, int32_t prob_bytes,
+                                            int32_t n_symbols, int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
+                                            cst_layout layout, uint64_t *d_state, uint32_t *d_n_words_out,
+                                            int32_t *d_status, uint32_t flags, void *stream);
+
+/* The quantised rows themselves: d_rows[r][0 .. n_symbols] = left cumulatives of row r of d_probs [n_rows][n_symbols], then
+ * 2^precision (1 <= precision <= 31).  A bad row (see above) is written as 0xffffffff followed by 2^precision, and d_bad[r]
+ * (optional) is 1 for it, else 0.  cst_categorical_fast_cdf_host is the same row walk on the CPU over host buffers. */
+cst_status cst_categorical_fast_cdf_rows(int32_t precision, const void *d_probs, int32_t prob_bytes, size_t n_rows, int32_t n_symbols,
+                                         uint32_t *d_rows, int32_t *d_bad, void *stream);
+cst_status cst_categorical_fast_cdf_host(int32_t precision, const void *h_probs, int32_t prob_bytes, size_t n_rows, int32_t n_symbols,
+                                         uint32_t *h_rows, int32_t *h_bad);
+
 /* Per-symbol models given explicitly (any model family with per-symbol parameters, e.g.
  * Categorical(perfect=False) with a probability matrix, src/pybindings/stream/model/internals.rs:188-249):
  *   encode: d_left / d_prob hold EncoderModel::left_cumulative_and_probability of every symbol
@@ -728,6 +760,18 @@ cst_status cst_range_decode_family_batch(cst_coder_config cfg, int32_t family, i
                                          int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
                                          cst_layout layout, cst_range_state *d_rstate, int32_t *d_status,
                                          uint32_t flags, void *stream);
+
+/* ... and over Categorical probability matrices (see cst_ans_encode_categorical_batch) */
+cst_status cst_range_encode_categorical_batch(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs, int32_t prob_bytes,
+                                              int32_t n_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                              uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                              cst_range_state *d_rstate, int32_t *d_status, uint32_t flags, void *stream);
+
+cst_status cst_range_decode_categorical_batch(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words,
+                                              size_t words_capacity, const uint32_t *d_n_words, const void *d_probs, int32_t prob_bytes,
+                                              int32_t n_symbols, int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
+                                              cst_layout layout, cst_range_state *d_rstate, int32_t *d_status,
+                                              uint32_t flags, void *stream);
 
 /* ABI 5: jump points for the per-symbol Gaussian calls of the RANGE coder (RangeEncoder::pos / RangeDecoder::seek, src/stream/queue.rs:172-196,
  * 900-926), as cst_ans_{encode,decode}_gaussian_batch_ckpt are for ANS: the fused encoder notes (words emitted including held-back ones,

@@ -3,13 +3,19 @@
 n_streams x n_per symbols, every symbol with its own two f64 parameters; both coders; round trip checked.
 
     bench_per_symbol.py [n_streams [n_per]] [--family gaussian laplace cauchy] [--support LO HI] [--rows] [--reps N] [--rounds K]
+    bench_per_symbol.py [n_streams [n_per]] --categorical K [--f64] [--reps N] [--rounds K]
 
 --family: one or more of gaussian (mean, std), laplace (mean, scale), cauchy (loc, scale); several families are timed in the
           same process on the same parameter matrices, alternating, `--rounds` times over: compare medians, look at the spread.
           Next to another family the Gaussian is also timed without jump points, which the other families do not have.
 --rows:   also times what a caller of Laplace / Cauchy had before the family calls: one tabulated cdf row per symbol
           (family_cdf_rows) + cst_ans_encode_cp_batch / cst_ans_decode_rows_batch.  n_symbols + 1 words of row per symbol: keep
-          the batch small (4096 x 256 at a 201-symbol support is 850 MB of rows)."""
+          the batch small (4096 x 256 at a 201-symbol support is 850 MB of rows).
+--categorical K: per-symbol Categorical models instead, from a [n_streams, n_per, K] matrix of float32 (--f64: float64) probabilities
+          (default 4096 x 256; at K = 256 that is 1 GiB of float32): encode and decode of both coders through the categorical calls
+          (the decoder by both of its routes), the probability bytes per second of each against the 8 TB/s of HBM, and the same
+          batch through the tabulated device route -- categorical_cdf_rows + cst_*_encode_cp_batch / cst_*_decode_rows_batch --
+          in the same run."""
 import argparse
 import statistics
 import sys
@@ -20,15 +26,19 @@ from constriction_amd import batched as B
 from constriction_amd import _native as N
 
 ap = argparse.ArgumentParser()
-ap.add_argument("n_streams", nargs="?", type=int, default=65536)
-ap.add_argument("n_per", nargs="?", type=int, default=4096)
+ap.add_argument("n_streams", nargs="?", type=int, default=None)
+ap.add_argument("n_per", nargs="?", type=int, default=None)
+ap.add_argument("--categorical", type=int, default=0, metavar="K")
+ap.add_argument("--f64", action="store_true")
 ap.add_argument("--family", nargs="+", choices=["gaussian", "laplace", "cauchy"], default=["gaussian"])
 ap.add_argument("--support", nargs=2, type=int, default=[-127, 127], metavar=("LO", "HI"))
 ap.add_argument("--rows", action="store_true")
 ap.add_argument("--reps", type=int, default=3, help="calls per timed window")
 ap.add_argument("--rounds", type=int, default=1, help="timed windows per entry (the median and the range are printed)")
 args = ap.parse_args()
-n_streams, n_per, (lo, hi) = args.n_streams, args.n_per, args.support
+n_streams = args.n_streams or (4096 if args.categorical else 65536)
+n_per = args.n_per or (256 if args.categorical else 4096)
+lo, hi = args.support
 
 
 def timed(f, reps):
@@ -39,6 +49,79 @@ def timed(f, reps):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps, out
 
+
+def categorical_bench(K):
+    import os
+    dtype = torch.float64 if args.f64 else torch.float32
+    g = torch.Generator(device="cuda").manual_seed(1)
+    probs = torch.softmax(torch.randn((n_streams, n_per, K), generator=g, device="cuda", dtype=torch.float32) * 3.0, dim=-1).to(dtype)
+    sym = torch.randint(0, K, (n_streams, n_per), generator=g, device="cuda", dtype=torch.int32)
+    prob_bytes = probs.numel() * probs.element_size()
+    cfg = (32, 64, 24)
+    L, p, sp = N.lib(), B._ptr, B._stream_ptr
+
+    def route(name):
+        os.environ["CST_CATEGORICAL_ROUTE"] = name
+        N.reload_knobs()
+
+    def tabulated(coder):
+        """the tabulated device route, rows built inside the timed call (they are part of what the caller pays)"""
+        flat = sym.reshape(-1).to(torch.int64)
+        ar = torch.arange(n_streams * n_per, device="cuda")
+        stride = (B.max_words if coder == "ans" else B.range_max_words)(n_per, cfg)
+        out = B._new_batch(n_streams, stride, sym.device, cfg)
+        dec = torch.empty_like(sym)
+        status = torch.empty(n_streams, dtype=torch.int32, device="cuda")
+
+        def encode():
+            rows = B.categorical_cdf_rows(probs).reshape(-1, K + 1)
+            left = rows[ar, flat].contiguous()
+            prob = (rows[ar, flat + 1] - left).contiguous()
+            N.check(getattr(L, f"cst_{coder}_encode_cp_batch")(B._cfg(*cfg), p(left), p(prob), n_streams, n_per, N.LAYOUT_STREAM_MAJOR, p(out.words), stride,
+                                                               p(out.n_words), None, p(out.status), N.FLAG_NONE, sp()), "encode_cp")
+            return out
+
+        def decode(enc):
+            rows = B.categorical_cdf_rows(probs)
+            a = [B._cfg(*cfg), p(enc.words), None, stride, enc.words.numel(), p(enc.n_words), p(rows), K, 0, p(dec), n_streams, n_per,
+                 N.LAYOUT_STREAM_MAJOR, None]
+            if coder == "ans":
+                a.append(None)
+            N.check(getattr(L, f"cst_{coder}_decode_rows_batch")(*a, p(status), N.FLAG_NONE, sp()), "decode_rows")
+            return dec, status
+        return encode, decode
+
+    entries = []
+    for coder in ("ans", "range"):
+        enc_f, dec_f = getattr(B, f"{coder}_encode_categorical"), getattr(B, f"{coder}_decode_categorical")
+        entries.append((coder, "in-kernel, lane decoder", "fused", (lambda enc_f=enc_f: enc_f(sym, probs, cfg)), (lambda enc, dec_f=dec_f: dec_f(enc, probs))))
+        entries.append((coder, "in-kernel, rows in pieces", "rows", (lambda enc_f=enc_f: enc_f(sym, probs, cfg)), (lambda enc, dec_f=dec_f: dec_f(enc, probs))))
+        entries.append((coder, "tabulated device route", "", *tabulated(coder)))
+    times = {i: ([], []) for i in range(len(entries))}
+    ok = {}
+    for i, (coder, how, r, enc_f, dec_f) in enumerate(entries):
+        route(r)
+        enc = enc_f()
+        dec, st = dec_f(enc)
+        torch.cuda.synchronize()
+        ok[i] = bool(torch.equal(dec, sym)) and int(st.abs().sum()) == 0
+    for _ in range(args.rounds):
+        for i, (coder, how, r, enc_f, dec_f) in enumerate(entries):
+            route(r)
+            e, enc = timed(enc_f, args.reps)
+            d, _ = timed(lambda: dec_f(enc), args.reps)
+            times[i][0].append(e); times[i][1].append(d)
+    route("")
+    print(f"per-symbol Categorical, {n_streams} x {n_per} symbols, K = {K}, {str(dtype).split('.')[-1]}: {prob_bytes / 2**30:.2f} GiB of probabilities")
+    for i, (coder, how, r, _, _) in enumerate(entries):
+        e, d = statistics.median(times[i][0]), statistics.median(times[i][1])
+        print(f"{coder:5s} {how:26s}: encode {e:9.3f} ms ({prob_bytes / e / 1e9:6.3f} TB/s of probabilities, {100 * prob_bytes / e / 1e9 / 8:5.1f} % of 8 TB/s)  "
+              f"decode {d:9.3f} ms ({prob_bytes / d / 1e9:6.3f} TB/s, {100 * prob_bytes / d / 1e9 / 8:5.1f} %)  roundtrip_ok={ok[i]}")
+
+
+if args.categorical:
+    categorical_bench(args.categorical)
+    sys.exit(0)
 
 g = torch.Generator(device="cuda").manual_seed(1)
 means = (torch.rand((n_streams, n_per), generator=g, device="cuda", dtype=torch.float64) * 20 - 10)
