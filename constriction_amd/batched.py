@@ -1105,6 +1105,95 @@ def range_decode_gaussian(encoded, min_symbol, max_symbol, means, stds, layout="
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# per-symbol quantized Gaussians for streams of DIFFERENT lengths: a batch of images, crops or tensors of different sizes, every
+# latent with its own (mean, std) -- the ragged calls' indexing (flat arrays + sym_offsets) on the Gaussian calls' models
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _gaussian_ragged_args(sym_offsets, n_elements, means, stds):
+    sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
+    n_streams = sym_offsets.numel() - 1
+    if sym_offsets.dim() != 1 or n_streams < 0:
+        raise ValueError("sym_offsets must be 1-d and hold n_streams + 1 entries")
+    if means.dim() != 1 or stds.dim() != 1:
+        raise ValueError("means and stds must be flat")
+    if n_elements is None:
+        n_elements = means.numel()
+    means, stds = _gaussian_args((n_elements,), means, stds)
+    return sym_offsets, n_streams, means, stds
+
+
+def _never_null(t):
+    """a one-element stand-in for an empty tensor (a batch of empty streams): the entry points refuse NULL and read nothing"""
+    return t if t.numel() > 0 else torch.zeros(1, dtype=t.dtype, device=t.device)
+
+
+def ans_encode_gaussian_ragged(symbols, sym_offsets, min_symbol, max_symbol, means, stds, config=(32, 64, 24), order="auto") -> RaggedBatch:
+    """One AnsCoder per stream, streams of different lengths: encode_reverse(symbols[lo:hi], QuantizedGaussian(min, max), means[lo:hi],
+    stds[lo:hi]) + get_compressed with (lo, hi) = sym_offsets[s], sym_offsets[s + 1], for all streams in ONE launch.  `symbols` flat
+    int32; `means` / `stds` flat float64 of the same numel (float32 is widened); `sym_offsets` int64 [n + 1] as `ragged` returns it.
+    Every stream's words are those of ans_encode_gaussian for that stream alone.  The slabs are sized as in ans_encode_ragged; the
+    batch carries no jump points (`.jump` is None) and the schedule it ran with in `.order` (see _ragged_order).
+    One kernel for every batch size: built for many streams (16 384 and more); a few streams are coded correctly, but slowly --
+    rectangular batches of few streams have ans_encode_gaussian's two-pass route."""
+    symbols = _require_cuda(symbols, torch.int32, "symbols")
+    if symbols.dim() != 1:
+        raise ValueError("symbols must be flat")
+    sym_offsets, n_streams, means, stds = _gaussian_ragged_args(sym_offsets, symbols.numel(), means, stds)
+    W, S, P = config
+    dev = symbols.device
+    lengths = sym_offsets[1:] - sym_offsets[:-1]
+    # a stream of n symbols fills at most min(n, ceil(n P / W)) + S / W words (see ans_encode_ragged); 16-byte slabs
+    bound = torch.minimum(lengths, (lengths * P + (W - 1)) // W) + S // W
+    slabs = (bound + 3) // 4 * 4
+    word_offsets = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(slabs, 0, out=word_offsets[1:])
+    total = int(word_offsets[-1].item()) if n_streams else 0
+    order = _ragged_order(order, n_streams, lengths)
+    out = RaggedBatch(torch.empty(max(total, 4), dtype=torch.int32, device=dev), word_offsets,
+                      torch.empty(n_streams, dtype=torch.int32, device=dev), torch.empty(n_streams, dtype=torch.int32, device=dev), tuple(config),
+                      order)
+    if n_streams == 0:
+        return out
+    N.check(N.lib().cst_ans_encode_gaussian_ragged(_cfg(*config), int(min_symbol), int(max_symbol), _ptr(_never_null(symbols)),
+                                                   _ptr(_never_null(means)), _ptr(_never_null(stds)), _ptr(sym_offsets), n_streams,
+                                                   _ptr(order) if order is not None else None, _ptr(out.words), _ptr(word_offsets), 0,
+                                                   _ptr(out.n_words), _ptr(out.status), _stream_ptr()), "cst_ans_encode_gaussian_ragged")
+    return out
+
+
+def ans_decode_gaussian_ragged(encoded: RaggedBatch, sym_offsets, min_symbol, max_symbol, means, stds, out: Optional[torch.Tensor] = None,
+                               order="auto"):
+    """AnsCoder(words of stream s).decode(QuantizedGaussian(min, max), means[lo:hi], stds[lo:hi]) for every stream of a RaggedBatch:
+    stream s yields sym_offsets[s + 1] - sym_offsets[s] symbols at out[sym_offsets[s]:].  Returns (symbols flat, status per stream).
+    `order`: "auto" reuses the encoder's schedule, or keys on the word counts (see _ragged_order).  One kernel for every batch size, as
+    the encoder: few streams decode correctly, but slowly."""
+    sym_offsets, n_streams, means, stds = _gaussian_ragged_args(sym_offsets, None, means, stds)
+    if encoded.n_words.numel() != n_streams:
+        raise ValueError("sym_offsets does not match the number of streams of the batch")
+    if isinstance(order, str) and order == "auto" and encoded.order is not None and encoded.order.numel() == n_streams:
+        order = encoded.order
+    order = _ragged_order(order, n_streams, encoded.n_words)
+    dev = encoded.words.device
+    total = means.numel()
+    if out is None:
+        out = torch.empty(total, dtype=torch.int32, device=dev)
+    else:
+        out = _require_cuda(out, torch.int32, "out")
+        if out.dim() != 1 or out.numel() != total:
+            raise ValueError("out must be flat and hold one symbol per parameter")
+    status = torch.empty(n_streams, dtype=torch.int32, device=dev)
+    if n_streams == 0:
+        return out, status
+    target = _never_null(out)
+    N.check(N.lib().cst_ans_decode_gaussian_ragged(_cfg(*encoded.config), int(min_symbol), int(max_symbol), _ptr(encoded.words),
+                                                   _ptr(encoded.word_offsets), 0, encoded.words.numel(), _ptr(encoded.n_words),
+                                                   _ptr(_never_null(means)), _ptr(_never_null(stds)), _ptr(target), _ptr(sym_offsets), n_streams,
+                                                   _ptr(order) if order is not None else None, _ptr(status), _stream_ptr()),
+            "cst_ans_decode_gaussian_ragged")
+    return out, status
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # per-symbol QuantizedLaplace / QuantizedCauchy: the same call with another family,
 #     coder.encode_reverse(symbols, QuantizedLaplace(lo, hi), means, scales) / coder.decode(QuantizedCauchy(lo, hi), locs, scales)
 # (src/pybindings/stream/model.rs:736-900), over the Gaussian's kernels and routes: the exact CDF is evaluated inside the coder

@@ -368,6 +368,33 @@ cst_status cst_ans_count_until_ordered(const cst_model *model, cst_coder_config 
                                        int32_t eof_symbol, size_t max_symbols, uint64_t *d_lengths, int32_t *d_status,
                                        void *stream);
 
+/* Per-symbol quantized Gaussians for streams of DIFFERENT lengths: cst_ans_{encode,decode}_gaussian_batch with the indexing of
+ * the ragged calls above -- what a learned codec has in a batch of images, crops or tensors of different sizes, every latent with
+ * its own (mean, std).
+ *     symbols, means, stds of stream s = d_symbols / d_means / d_stds [d_sym_offsets[s] .. d_sym_offsets[s + 1])   (all three flat,
+ *                                        f64 parameters, d_sym_offsets: uint64 [n_streams + 1])
+ *     slabs, d_word_offsets / stride_words / words_capacity / d_n_words: exactly as in cst_ans_{encode,decode}_ragged (the bounds
+ *                                        check included; a slab whose offsets run backwards reports CST_STREAM_CAPACITY).  A slab of
+ *                                        min(n, ceil(n P / W)) + S / W words always suffices for a stream of n symbols.
+ *     d_order                            as in the *_ragged_ordered calls: lane slot i codes stream d_order[i]; NULL = the identity.
+ * Words, count and status of every stream are those of the reference coder -- and of cst_ans_encode_gaussian_batch -- for that
+ * stream alone, bit for bit; std <= 0, a non-finite parameter or a symbol outside [min_symbol, max_symbol] flags that one stream
+ * CST_STREAM_IMPOSSIBLE_SYMBOL (n_words = 0); a stream of length 0 yields 0 words and CST_STREAM_OK.  Presets (32,64) and (16,32),
+ * any precision the rectangular calls take.  CST_ERR_INVALID_ARGUMENT, before the device is touched: a NULL symbols / means / stds /
+ * sym_offsets / words / n_words / status pointer, an unsupported configuration, max_symbol <= min_symbol, d_word_offsets == NULL
+ * with stride_words == 0.  n_streams == 0: CST_OK, nothing is launched.  One kernel each for every batch size: built for many
+ * streams (from ~16 000 on); a handful of streams is coded correctly but leaves most of the device idle. */
+cst_status cst_ans_encode_gaussian_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                          const int32_t *d_symbols, const double *d_means, const double *d_stds,
+                                          const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                          uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                          uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_gaussian_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                          const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                          size_t words_capacity, const uint32_t *d_n_words, const double *d_means,
+                                          const double *d_stds, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                          size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
+
 /* Checkpointed streams -- the reference's Pos / Seek jump tables (src/stream/stack.rs:1107-1139; test :1456-1548) for the
  * batched coder.  The encoder notes, in front of every chunk of `ckpt_interval` symbols, what `AnsCoder::pos()` returns
  * there: d_ckpt_pos[s][j] = words in the bulk, d_ckpt_state[s][j] = coder state once symbols [j * interval, n) are
