@@ -602,6 +602,130 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    /// ... the same pair for the range coder (a queue: the decoder reads the symbols in the order they were written), and both coders
+    /// over QuantizedLaplace / QuantizedCauchy.  Arguments, checks, statuses and the order / word_offsets conventions are those of
+    /// cst_ans_{encode,decode}_gaussian_ragged; words, count and status of every stream are those of the reference RangeEncoder /
+    /// AnsCoder -- and of the rectangular cst_{ans,range}_{encode,decode}_{gaussian,family}_batch -- for that stream alone.
+    ///     range coder slabs                  min(n, ceil(n P / W)) + 2 words always suffice for a stream of n symbols (the bound inside
+    ///                                        cst_range_max_words); a stream of length 0 yields 0 words and CST_STREAM_OK.
+    ///     family                             CST_FAMILY_LAPLACE (d_a = means, d_b = scales) or CST_FAMILY_CAUCHY (d_a = locs, d_b =
+    ///                                        scales), as in cst_ans_encode_family_batch; anything else: CST_ERR_INVALID_ARGUMENT.
+    /// No jump points for any of these.
+    pub fn cst_range_encode_gaussian_ragged(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_means: *const f64,
+        d_stds: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_gaussian_ragged(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_means: *const f64,
+        d_stds: *const f64,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_encode_family_ragged(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_a: *const f64,
+        d_b: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_family_ragged(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const f64,
+        d_b: *const f64,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_encode_family_ragged(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_a: *const f64,
+        d_b: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_family_ragged(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const f64,
+        d_b: *const f64,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// Checkpointed streams -- the reference's Pos / Seek jump tables (src/stream/stack.rs:1107-1139; test :1456-1548) for the
     /// batched coder.  The encoder notes, in front of every chunk of `ckpt_interval` symbols, what `AnsCoder::pos()` returns
     /// there: d_ckpt_pos[s][j] = words in the bulk, d_ckpt_state[s][j] = coder state once symbols [j * interval, n) are

@@ -1550,6 +1550,111 @@ impl BatchedAnsCoder {
         Ok(status)
     }
 
+    /// `encode_symbols_reverse_ragged` with one leakily quantized Laplace or Cauchy distribution per symbol
+    /// (`cst_ans_encode_family_ragged`): `a` = mean / loc, `b` = scale, flat as `symbols`.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_reverse_ragged`: the offsets are DEVICE memory and cannot be checked here.  Every `sym_offsets` pair must
+    /// lie inside `symbols`, `a` and `b`, every slab inside `words`.
+    pub unsafe fn encode_symbols_reverse_family_ragged(
+        &self,
+        family: Family,
+        symbols: &DeviceBuffer<i32>,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || a.len() != symbols.len() || b.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_ans_encode_family_ragged(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                symbols.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status))
+    }
+
+    /// The decoder of [`BatchedAnsCoder::encode_symbols_reverse_family_ragged`] (`cst_ans_decode_family_ragged`).
+    ///
+    /// # Safety
+    /// As for `decode_symbols_ragged` of the ANS coder: `sym_offsets` (device memory) must delimit ranges inside `symbols`, `a` and
+    /// `b`.  The word slices ARE checked on the device against `words.len()`.
+    pub unsafe fn decode_symbols_family_ragged(
+        &self,
+        family: Family,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        symbols: &mut DeviceBuffer<i32>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if a.len() != symbols.len() || b.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_ans_decode_family_ragged(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok(status)
+    }
+
     /// `encode_ragged` that also notes `AnsCoder::pos()` in front of every `jump_interval` symbols of every stream (ABI 5,
     /// `cst_ans_encode_ragged_jump`; `Pos`, src/stream/stack.rs:1107-1116): chunk `j` of stream `s` is entry `chunk_offsets[s] + j` of
     /// the returned `(pos, state)` arrays, `chunk_offsets[n_streams + 1]` the exclusive prefix sum of `ceil(length / jump_interval)`
@@ -2139,6 +2244,109 @@ impl BatchedRangeEncoder {
         Ok(out)
     }
 
+    /// `encode_symbols` -- one leakily quantized Gaussian per SYMBOL -- for streams of different lengths in one launch
+    /// (`cst_range_encode_gaussian_ragged`): stream `s` owns elements `[sym_offsets[s], sym_offsets[s + 1])` of the flat `symbols`,
+    /// `means` and `stds`, and writes into the slab `[word_offsets[s], word_offsets[s + 1])` of `words`
+    /// (`min(n, ceil(n P / W)) + 2` words always suffice for `n` symbols).  `order`: a schedule as for the ordered ragged calls, or
+    /// `None`.  Every stream's words are those of `encode_symbols` for that stream alone.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_reverse_ragged`: the offsets are DEVICE memory and cannot be checked here.  Every `sym_offsets` pair must
+    /// lie inside `symbols`, `means` and `stds`, every slab inside `words`.
+    pub unsafe fn encode_symbols_ragged(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        support: RangeInclusive<i32>,
+        means: &DeviceBuffer<f64>,
+        stds: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || means.len() != symbols.len() || stds.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_range_encode_gaussian_ragged(
+                self.config,
+                *support.start(),
+                *support.end(),
+                symbols.as_ptr(),
+                means.as_ptr(),
+                stds.as_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status))
+    }
+
+    /// `encode_symbols_ragged` with one leakily quantized Laplace or Cauchy distribution per symbol
+    /// (`cst_range_encode_family_ragged`): `a` = mean / loc, `b` = scale, flat as `symbols`.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_reverse_ragged`: the offsets are DEVICE memory and cannot be checked here.  Every `sym_offsets` pair must
+    /// lie inside `symbols`, `a` and `b`, every slab inside `words`.
+    pub unsafe fn encode_symbols_family_ragged(
+        &self,
+        family: Family,
+        symbols: &DeviceBuffer<i32>,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || a.len() != symbols.len() || b.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_range_encode_family_ragged(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                symbols.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status))
+    }
+
     /// `encode_symbols` with one Categorical model per symbol, given as probabilities (Python `RangeEncoder.encode(symbols, Categorical(lazy=True), probabilities)`).
     /// `probabilities`: one vector of `n_symbols` entries per symbol, of the symbol matrix's shape and layout.
     pub fn encode_symbols_categorical<F: Probability>(
@@ -2582,6 +2790,113 @@ impl BatchedRangeDecoder {
             )
         })?;
         Ok(out)
+    }
+
+    /// The decoder of [`BatchedRangeEncoder::encode_symbols_ragged`] (`cst_range_decode_gaussian_ragged`): stream `s` yields
+    /// `sym_offsets[s + 1] - sym_offsets[s]` symbols at `symbols[sym_offsets[s]..]`.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_ragged` of the ANS coder: `sym_offsets` (device memory) must delimit ranges inside `symbols`, `means` and
+    /// `stds`.  The word slices ARE checked on the device against `words.len()`.
+    pub unsafe fn decode_symbols_ragged(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        support: RangeInclusive<i32>,
+        means: &DeviceBuffer<f64>,
+        stds: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        symbols: &mut DeviceBuffer<i32>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if means.len() != symbols.len() || stds.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_range_decode_gaussian_ragged(
+                self.config,
+                *support.start(),
+                *support.end(),
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                means.as_ptr(),
+                stds.as_ptr(),
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok(status)
+    }
+
+    /// The decoder of [`BatchedRangeEncoder::encode_symbols_family_ragged`] (`cst_range_decode_family_ragged`).
+    ///
+    /// # Safety
+    /// As for `decode_symbols_ragged` of the ANS coder: `sym_offsets` (device memory) must delimit ranges inside `symbols`, `a` and
+    /// `b`.  The word slices ARE checked on the device against `words.len()`.
+    pub unsafe fn decode_symbols_family_ragged(
+        &self,
+        family: Family,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        symbols: &mut DeviceBuffer<i32>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if a.len() != symbols.len() || b.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_range_decode_family_ragged(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok(status)
     }
 
     /// `decode_symbols` with one Categorical model per symbol (see `encode_symbols_categorical`).

@@ -572,6 +572,7 @@ class RaggedBatch:
     config: tuple
     order: Optional[torch.Tensor] = None   # int32 [n_streams]: the schedule the encoder ran with (the decoders reuse it)
     jump: Optional["RaggedJump"] = None    # jump points the encoder noted (ans_encode_ragged, jump_every): ans_decode_ragged decodes the chunks side by side
+    coder: str = "ans"                     # "ans" (a stack) or "range" (a queue): which coder wrote the words -- the other one's decoders refuse them
 
     def stream(self, s: int) -> np.ndarray:
         """get_compressed() of stream s (uint32, host)."""
@@ -623,6 +624,11 @@ def _ragged_order(order, n_streams, keys):
     if order.numel() != n_streams:
         raise ValueError("order must hold one stream index per stream")
     return order
+
+
+def _require_coder(encoded: RaggedBatch, coder: str) -> None:
+    if encoded.coder != coder:
+        raise ValueError(f"the batch holds the words of the {encoded.coder!r} coder: a {coder!r} decoder cannot read them")
 
 
 def ans_encode_ragged(symbols: torch.Tensor, sym_offsets: torch.Tensor, model: Model, config=(32, 64, 24), order="auto",
@@ -685,6 +691,7 @@ def ans_decode_ragged(encoded: RaggedBatch, model: Model, sym_offsets: torch.Ten
     sym_offsets[s + 1] - sym_offsets[s] symbols at out[sym_offsets[s]:].  Returns (symbols flat, status per stream).
     `order`: the schedule (see _ragged_order); "auto" reuses the encoder's, or sorts by word count from RAGGED_BALANCE_FROM
     streams on."""
+    _require_coder(encoded, "ans")
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
     n_streams = sym_offsets.numel() - 1
     # a batch with jump points decodes its chunks side by side (they are all at most `interval` symbols long: no schedule needed) --
@@ -1127,23 +1134,18 @@ def _never_null(t):
     return t if t.numel() > 0 else torch.zeros(1, dtype=t.dtype, device=t.device)
 
 
-def ans_encode_gaussian_ragged(symbols, sym_offsets, min_symbol, max_symbol, means, stds, config=(32, 64, 24), order="auto") -> RaggedBatch:
-    """One AnsCoder per stream, streams of different lengths: encode_reverse(symbols[lo:hi], QuantizedGaussian(min, max), means[lo:hi],
-    stds[lo:hi]) + get_compressed with (lo, hi) = sym_offsets[s], sym_offsets[s + 1], for all streams in ONE launch.  `symbols` flat
-    int32; `means` / `stds` flat float64 of the same numel (float32 is widened); `sym_offsets` int64 [n + 1] as `ragged` returns it.
-    Every stream's words are those of ans_encode_gaussian for that stream alone.  The slabs are sized as in ans_encode_ragged; the
-    batch carries no jump points (`.jump` is None) and the schedule it ran with in `.order` (see _ragged_order).
-    One kernel for every batch size: built for many streams (16 384 and more); a few streams are coded correctly, but slowly --
-    rectangular batches of few streams have ans_encode_gaussian's two-pass route."""
+def _encode_persymbol_ragged(fn_name, coder, symbols, sym_offsets, lo, hi, a, b, config, order, family=()) -> RaggedBatch:
+    """the body of every {ans,range}_encode_{gaussian,family}_ragged: `family` is () or (id,), the argument that follows cfg"""
     symbols = _require_cuda(symbols, torch.int32, "symbols")
     if symbols.dim() != 1:
         raise ValueError("symbols must be flat")
-    sym_offsets, n_streams, means, stds = _gaussian_ragged_args(sym_offsets, symbols.numel(), means, stds)
+    sym_offsets, n_streams, a, b = _gaussian_ragged_args(sym_offsets, symbols.numel(), a, b)
     W, S, P = config
     dev = symbols.device
     lengths = sym_offsets[1:] - sym_offsets[:-1]
-    # a stream of n symbols fills at most min(n, ceil(n P / W)) + S / W words (see ans_encode_ragged); 16-byte slabs
-    bound = torch.minimum(lengths, (lengths * P + (W - 1)) // W) + S // W
+    # a stream of n symbols fills at most min(n, ceil(n P / W)) words plus the S / W words of the ANS state (see ans_encode_ragged), or
+    # plus the 2 words that seal a range coder (the bound inside cst_range_max_words, without its rounding to 64 bytes); 16-byte slabs
+    bound = torch.minimum(lengths, (lengths * P + (W - 1)) // W) + (S // W if coder == "ans" else 2)
     slabs = (bound + 3) // 4 * 4
     word_offsets = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
     torch.cumsum(slabs, 0, out=word_offsets[1:])
@@ -1151,30 +1153,26 @@ def ans_encode_gaussian_ragged(symbols, sym_offsets, min_symbol, max_symbol, mea
     order = _ragged_order(order, n_streams, lengths)
     out = RaggedBatch(torch.empty(max(total, 4), dtype=torch.int32, device=dev), word_offsets,
                       torch.empty(n_streams, dtype=torch.int32, device=dev), torch.empty(n_streams, dtype=torch.int32, device=dev), tuple(config),
-                      order)
+                      order, None, coder)
     if n_streams == 0:
         return out
-    N.check(N.lib().cst_ans_encode_gaussian_ragged(_cfg(*config), int(min_symbol), int(max_symbol), _ptr(_never_null(symbols)),
-                                                   _ptr(_never_null(means)), _ptr(_never_null(stds)), _ptr(sym_offsets), n_streams,
-                                                   _ptr(order) if order is not None else None, _ptr(out.words), _ptr(word_offsets), 0,
-                                                   _ptr(out.n_words), _ptr(out.status), _stream_ptr()), "cst_ans_encode_gaussian_ragged")
+    N.check(getattr(N.lib(), fn_name)(_cfg(*config), *family, int(lo), int(hi), _ptr(_never_null(symbols)), _ptr(_never_null(a)),
+                                      _ptr(_never_null(b)), _ptr(sym_offsets), n_streams, _ptr(order) if order is not None else None,
+                                      _ptr(out.words), _ptr(word_offsets), 0, _ptr(out.n_words), _ptr(out.status), _stream_ptr()), fn_name)
     return out
 
 
-def ans_decode_gaussian_ragged(encoded: RaggedBatch, sym_offsets, min_symbol, max_symbol, means, stds, out: Optional[torch.Tensor] = None,
-                               order="auto"):
-    """AnsCoder(words of stream s).decode(QuantizedGaussian(min, max), means[lo:hi], stds[lo:hi]) for every stream of a RaggedBatch:
-    stream s yields sym_offsets[s + 1] - sym_offsets[s] symbols at out[sym_offsets[s]:].  Returns (symbols flat, status per stream).
-    `order`: "auto" reuses the encoder's schedule, or keys on the word counts (see _ragged_order).  One kernel for every batch size, as
-    the encoder: few streams decode correctly, but slowly."""
-    sym_offsets, n_streams, means, stds = _gaussian_ragged_args(sym_offsets, None, means, stds)
+def _decode_persymbol_ragged(fn_name, coder, encoded: RaggedBatch, sym_offsets, lo, hi, a, b, out, order, family=()):
+    """the body of every {ans,range}_decode_{gaussian,family}_ragged"""
+    _require_coder(encoded, coder)
+    sym_offsets, n_streams, a, b = _gaussian_ragged_args(sym_offsets, None, a, b)
     if encoded.n_words.numel() != n_streams:
         raise ValueError("sym_offsets does not match the number of streams of the batch")
     if isinstance(order, str) and order == "auto" and encoded.order is not None and encoded.order.numel() == n_streams:
         order = encoded.order
     order = _ragged_order(order, n_streams, encoded.n_words)
     dev = encoded.words.device
-    total = means.numel()
+    total = a.numel()
     if out is None:
         out = torch.empty(total, dtype=torch.int32, device=dev)
     else:
@@ -1185,12 +1183,47 @@ def ans_decode_gaussian_ragged(encoded: RaggedBatch, sym_offsets, min_symbol, ma
     if n_streams == 0:
         return out, status
     target = _never_null(out)
-    N.check(N.lib().cst_ans_decode_gaussian_ragged(_cfg(*encoded.config), int(min_symbol), int(max_symbol), _ptr(encoded.words),
-                                                   _ptr(encoded.word_offsets), 0, encoded.words.numel(), _ptr(encoded.n_words),
-                                                   _ptr(_never_null(means)), _ptr(_never_null(stds)), _ptr(target), _ptr(sym_offsets), n_streams,
-                                                   _ptr(order) if order is not None else None, _ptr(status), _stream_ptr()),
-            "cst_ans_decode_gaussian_ragged")
+    N.check(getattr(N.lib(), fn_name)(_cfg(*encoded.config), *family, int(lo), int(hi), _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
+                                      encoded.words.numel(), _ptr(encoded.n_words), _ptr(_never_null(a)), _ptr(_never_null(b)), _ptr(target),
+                                      _ptr(sym_offsets), n_streams, _ptr(order) if order is not None else None, _ptr(status), _stream_ptr()),
+            fn_name)
     return out, status
+
+
+def ans_encode_gaussian_ragged(symbols, sym_offsets, min_symbol, max_symbol, means, stds, config=(32, 64, 24), order="auto") -> RaggedBatch:
+    """One AnsCoder per stream, streams of different lengths: encode_reverse(symbols[lo:hi], QuantizedGaussian(min, max), means[lo:hi],
+    stds[lo:hi]) + get_compressed with (lo, hi) = sym_offsets[s], sym_offsets[s + 1], for all streams in ONE launch.  `symbols` flat
+    int32; `means` / `stds` flat float64 of the same numel (float32 is widened); `sym_offsets` int64 [n + 1] as `ragged` returns it.
+    Every stream's words are those of ans_encode_gaussian for that stream alone.  The slabs are sized as in ans_encode_ragged; the
+    batch carries no jump points (`.jump` is None) and the schedule it ran with in `.order` (see _ragged_order).
+    One kernel for every batch size: built for many streams (16 384 and more); a few streams are coded correctly, but slowly --
+    rectangular batches of few streams have ans_encode_gaussian's two-pass route."""
+    return _encode_persymbol_ragged("cst_ans_encode_gaussian_ragged", "ans", symbols, sym_offsets, min_symbol, max_symbol, means, stds, config, order)
+
+
+def ans_decode_gaussian_ragged(encoded: RaggedBatch, sym_offsets, min_symbol, max_symbol, means, stds, out: Optional[torch.Tensor] = None,
+                               order="auto"):
+    """AnsCoder(words of stream s).decode(QuantizedGaussian(min, max), means[lo:hi], stds[lo:hi]) for every stream of a RaggedBatch:
+    stream s yields sym_offsets[s + 1] - sym_offsets[s] symbols at out[sym_offsets[s]:].  Returns (symbols flat, status per stream).
+    `order`: "auto" reuses the encoder's schedule, or keys on the word counts (see _ragged_order).  One kernel for every batch size, as
+    the encoder: few streams decode correctly, but slowly."""
+    return _decode_persymbol_ragged("cst_ans_decode_gaussian_ragged", "ans", encoded, sym_offsets, min_symbol, max_symbol, means, stds, out, order)
+
+
+def range_encode_gaussian_ragged(symbols, sym_offsets, min_symbol, max_symbol, means, stds, config=(32, 64, 24), order="auto") -> RaggedBatch:
+    """One RangeEncoder per stream, streams of different lengths: encode(symbols[lo:hi], QuantizedGaussian(min, max), means[lo:hi],
+    stds[lo:hi]) + get_compressed -- ans_encode_gaussian_ragged for the queue.  Every stream's words are those of range_encode_gaussian
+    for that stream alone; a slab holds min(n, ceil(n P / W)) + 2 words, rounded up to 4; the batch says `.coder == "range"`."""
+    return _encode_persymbol_ragged("cst_range_encode_gaussian_ragged", "range", symbols, sym_offsets, min_symbol, max_symbol, means, stds, config,
+                                    order)
+
+
+def range_decode_gaussian_ragged(encoded: RaggedBatch, sym_offsets, min_symbol, max_symbol, means, stds, out: Optional[torch.Tensor] = None,
+                                 order="auto"):
+    """RangeDecoder(words of stream s).decode(QuantizedGaussian(min, max), means[lo:hi], stds[lo:hi]) for every stream of a RaggedBatch
+    that a range encoder wrote.  Returns (symbols flat, status per stream); see ans_decode_gaussian_ragged."""
+    return _decode_persymbol_ragged("cst_range_decode_gaussian_ragged", "range", encoded, sym_offsets, min_symbol, max_symbol, means, stds, out,
+                                    order)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1250,6 +1283,36 @@ ans_encode_laplace, ans_encode_cauchy = _named_family(ans_encode_family, "laplac
 ans_decode_laplace, ans_decode_cauchy = _named_family(ans_decode_family, "laplace"), _named_family(ans_decode_family, "cauchy")
 range_encode_laplace, range_encode_cauchy = _named_family(range_encode_family, "laplace"), _named_family(range_encode_family, "cauchy")
 range_decode_laplace, range_decode_cauchy = _named_family(range_decode_family, "laplace"), _named_family(range_decode_family, "cauchy")
+
+
+# ... and for streams of DIFFERENT lengths: the ragged Gaussian calls over another family (flat symbols / a / b + sym_offsets)
+
+def ans_encode_family_ragged(family, symbols, sym_offsets, lo, hi, a, b, config=(32, 64, 24), order="auto") -> RaggedBatch:
+    """One AnsCoder per stream: encode_reverse(symbols[s], Family(lo, hi), a[s], b[s]) + get_compressed (see ans_encode_gaussian_ragged)."""
+    return _encode_persymbol_ragged("cst_ans_encode_family_ragged", "ans", symbols, sym_offsets, lo, hi, a, b, config, order, (_family_id(family),))
+
+
+def range_encode_family_ragged(family, symbols, sym_offsets, lo, hi, a, b, config=(32, 64, 24), order="auto") -> RaggedBatch:
+    """One RangeEncoder per stream: encode(symbols[s], Family(lo, hi), a[s], b[s]) + get_compressed (see range_encode_gaussian_ragged)."""
+    return _encode_persymbol_ragged("cst_range_encode_family_ragged", "range", symbols, sym_offsets, lo, hi, a, b, config, order,
+                                    (_family_id(family),))
+
+
+def ans_decode_family_ragged(family, encoded: RaggedBatch, sym_offsets, lo, hi, a, b, out: Optional[torch.Tensor] = None, order="auto"):
+    """One AnsCoder per stream: AnsCoder(words of stream s).decode(Family(lo, hi), a[s], b[s]).  Returns (symbols flat, status)."""
+    return _decode_persymbol_ragged("cst_ans_decode_family_ragged", "ans", encoded, sym_offsets, lo, hi, a, b, out, order, (_family_id(family),))
+
+
+def range_decode_family_ragged(family, encoded: RaggedBatch, sym_offsets, lo, hi, a, b, out: Optional[torch.Tensor] = None, order="auto"):
+    """One RangeDecoder per stream: RangeDecoder(words of stream s).decode(Family(lo, hi), a[s], b[s]).  Returns (symbols flat, status)."""
+    return _decode_persymbol_ragged("cst_range_decode_family_ragged", "range", encoded, sym_offsets, lo, hi, a, b, out, order,
+                                    (_family_id(family),))
+
+
+ans_encode_laplace_ragged, ans_encode_cauchy_ragged = (_named_family(ans_encode_family_ragged, f) for f in ("laplace", "cauchy"))
+ans_decode_laplace_ragged, ans_decode_cauchy_ragged = (_named_family(ans_decode_family_ragged, f) for f in ("laplace", "cauchy"))
+range_encode_laplace_ragged, range_encode_cauchy_ragged = (_named_family(range_encode_family_ragged, f) for f in ("laplace", "cauchy"))
+range_decode_laplace_ragged, range_decode_cauchy_ragged = (_named_family(range_decode_family_ragged, f) for f in ("laplace", "cauchy"))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

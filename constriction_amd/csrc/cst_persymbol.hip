@@ -1234,11 +1234,13 @@ struct GaussianRaggedEncodeArgs {
 constexpr size_t kRgMetaBytes = (size_t)kFuStreams * sizeof(uint4);
 constexpr size_t kRgEncWaveBytes = kFuWaveBytes + kRgMetaBytes;
 
-// encode_gaussian_fused_kernel<W, S, kAns> in its general form (per-item index and ok_q; walking by adding and PAIR need whole
+// encode_gaussian_fused_kernel<W, S, KIND> in its general form (per-item index and ok_q; walking by adding and PAIR need whole
 // tiles of one matrix).  Tile k of stream j covers symbols [16 k, 16 k + 16) of its row; the wave codes max_j ceil(len_j / 16)
-// tiles, last to first; whole-tile or symbol-by-symbol steps are each lane's own decision.
-template <int W, int S, class FAM = GaussianFamily>
+// tiles, last to first (ANS, a stack) or first to last (the range coder, a queue); whole-tile or symbol-by-symbol steps are
+// each lane's own decision.
+template <int W, int S, int KIND, class FAM = GaussianFamily>
 __global__ __launch_bounds__(kFuBlock) void encode_gaussian_ragged_kernel(const GaussianRaggedEncodeArgs a) {
+    static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
     constexpr size_t kTabBytes = FAM::kErfTab ? kFuTabBytes : 0;
     constexpr int kWaves = kFuBlock / kWave;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1257,7 +1259,7 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_ragged_kernel(const 
     const size_t slot0 = ((size_t)blockIdx.x * kWaves + wave_in_block) * kFuStreams;
     if (slot0 >= a.n_streams) return;
     const int P = a.precision;
-    const bool use_inv = W == 32 && S == 64 && P >= kInvMinPrecision;      // entries with 1 / p (make_entry_inv)
+    const bool use_inv = KIND == kAns && W == 32 && S == 64 && P >= kInvMinPrecision;      // entries with 1 / p (make_entry_inv)
     bool active = false;
     size_t s = 0;
     if (lane < kFuStreams) s = persymbol_ragged_stream(a.order, slot0 + (size_t)lane, a.n_streams, active);   // this lane codes a stream in phase B
@@ -1292,15 +1294,17 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_ragged_kernel(const 
     const uint64_t slab_hi = !active ? 0 : (a.word_offsets ? a.word_offsets[s + 1] : 0);
     const uint64_t slab_n = !active ? 0 : (a.word_offsets ? (slab_hi >= slab_lo ? slab_hi - slab_lo : 0) : (uint64_t)a.stride_words);
     EncLane<W, S, kFuRingSlots> LA;
-    LA.init(a.words + slab_lo, (uint32_t)(slab_n > 0xffffffffull ? 0xffffffffull : slab_n), ring, lane);
+    RangeEncLane<W, S, kFuRingSlots> LR;
+    if constexpr (KIND == kAns) LA.init(a.words + slab_lo, (uint32_t)(slab_n > 0xffffffffull ? 0xffffffffull : slab_n), ring, lane);
+    else LR.init(a.words + slab_lo, (uint32_t)(slab_n > 0xffffffffull ? 0xffffffffull : slab_n), ring, lane);
     uint32_t bad = 0;
 
     if (n_tiles > 0) {
 #pragma unroll
-        for (int q = 0; q < kFuAhead; ++q) request(q, n_tiles - 1u, q);
+        for (int q = 0; q < kFuAhead; ++q) request(q, KIND == kAns ? n_tiles - 1u : 0u, q);
     }
     for (uint32_t step = 0; step < n_tiles; ++step) {
-        const uint32_t k = n_tiles - 1u - step;                // ANS codes last to first
+        const uint32_t k = KIND == kAns ? n_tiles - 1u - step : step;      // ANS codes last to first, the range coder first to last
         wave_lds_fence();                                      // (the previous tile has been read)
         // ---- phase A: entries of tile k ----
 #pragma unroll 1
@@ -1311,50 +1315,75 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_ragged_kernel(const 
                 const int32_t sy = ok_q[q] ? sy_q[q] : a.lo;       // (items past their stream's end: never coded)
                 const double m = ok_q[q] ? mu_q[q] : 0.0, sg = ok_q[q] ? sd_q[q] : 1.0;
                 if (it + kFuAhead < kFuIters) request(q, k, it + kFuAhead);
-                else if (step + 1 < n_tiles) request(q, k - 1u, it + kFuAhead - kFuIters);
+                else if (step + 1 < n_tiles) request(q, KIND == kAns ? k - 1u : k + 1u, it + kFuAhead - kFuIters);
                 uint32_t c = 0, p = 0;
                 // invalid parameters, out-of-support symbols and degenerate distributions all end up with p = 0 = impossible
                 // (see the fused kernel); no branches: invalid parameters are evaluated as (0, 1) and thrown away
                 const bool valid = FAM::valid(m, sg);
                 const bool inside = FAM::lcp(sy, a.lo, a.hi, P, valid ? m : 0.0, valid ? sg : 1.0, c, p, erf_tab);
                 if (!valid || !inside || (uint64_t)c + p > ((uint64_t)1 << P)) p = 0;
-                tile[item_t * kFuRowStride + it * (kWave / kFuTile) + item_j0] = use_inv ? make_entry_inv(c, p) : make_entry_f64(c, p);
+                EncEntry entry{c, p, 0u, 0u};                                   // (the range coder divides by nothing)
+                if constexpr (KIND == kAns) entry = use_inv ? make_entry_inv(c, p) : make_entry_f64(c, p);
+                tile[item_t * kFuRowStride + it * (kWave / kFuTile) + item_j0] = entry;
             }
         }
         wave_lds_fence();
         // ---- phase B: every stream's lane over what its row has of this tile ----
         const uint64_t t0 = (uint64_t)k * kFuTile;
         const int n_here = !active || t0 >= (uint64_t)len ? 0 : ((uint64_t)len - t0 < (uint64_t)kFuTile ? (int)((uint64_t)len - t0) : kFuTile);
-        constexpr bool FAST = W == 32 && S == 64;               // the 32-bit-halves step (8 <= P)
-        if (FAST && P >= 8 && n_here == kFuTile) {
-            // a whole tile: all sixteen entries first (one LDS wait), then sixteen hand-scheduled steps.  An impossible symbol
-            // is coded as (0, 1) -- its stream is flagged and its words are never used.
-            EncEntry e[kFuTile];
+        if constexpr (KIND == kAns) {
+            constexpr bool FAST = W == 32 && S == 64;               // the 32-bit-halves step (8 <= P)
+            if (FAST && P >= 8 && n_here == kFuTile) {
+                // a whole tile: all sixteen entries first (one LDS wait), then sixteen hand-scheduled steps.  An impossible symbol
+                // is coded as (0, 1) -- its stream is flagged and its words are never used.
+                EncEntry e[kFuTile];
 #pragma unroll
-            for (int tl = 0; tl < kFuTile; ++tl) e[tl] = tile[tl * kFuRowStride + lane];
+                for (int tl = 0; tl < kFuTile; ++tl) e[tl] = tile[tl * kFuRowStride + lane];
 #pragma unroll
-            for (int tl = kFuTile - 1; tl >= 0; --tl) {
-                const bool none = e[tl].p == 0;
-                bad |= none ? 1u : 0u;
-                if constexpr (FAST) {
-                    if (use_inv) encode_step_inv(LA, none ? 0u : e[tl].c, none ? 1u : e[tl].p, none ? 1.0 : f64_from(e[tl].m_lo, e[tl].m_hi), P);
-                    else LA.template step<FAST>(EncEntry{none ? 0u : e[tl].c, none ? 1u : e[tl].p, none ? 0xffffffffu : e[tl].m_lo, none ? 0xffffffffu : e[tl].m_hi}, P);
+                for (int tl = kFuTile - 1; tl >= 0; --tl) {
+                    const bool none = e[tl].p == 0;
+                    bad |= none ? 1u : 0u;
+                    if constexpr (FAST) {
+                        if (use_inv) encode_step_inv(LA, none ? 0u : e[tl].c, none ? 1u : e[tl].p, none ? 1.0 : f64_from(e[tl].m_lo, e[tl].m_hi), P);
+                        else LA.template step<FAST>(EncEntry{none ? 0u : e[tl].c, none ? 1u : e[tl].p, none ? 0xffffffffu : e[tl].m_lo, none ? 0xffffffffu : e[tl].m_hi}, P);
+                    }
+                }
+            } else {
+                // (other presets, P < 8, the end of a row; n_here = 0: this lane's stream has nothing in the tile)
+                for (int tl = n_here - 1; tl >= 0; --tl) {
+                    const EncEntry e = tile[tl * kFuRowStride + lane];
+                    if (e.p == 0) bad = 1;
+                    else if (!bad) LA.template step<false>(use_inv ? make_entry(e.c, e.p) : e, P);
                 }
             }
+        } else if (n_here == kFuTile) {
+            // a whole tile: all sixteen (c, p) first (one LDS wait), then sixteen steps in coding order; an impossible symbol is
+            // coded as (0, 1) -- its stream is flagged and its words are never used
+            uint2 e[kFuTile];
+#pragma unroll
+            for (int tl = 0; tl < kFuTile; ++tl) e[tl] = *reinterpret_cast<const uint2*>(&tile[tl * kFuRowStride + lane]);
+#pragma unroll
+            for (int tl = 0; tl < kFuTile; ++tl) {
+                const bool none = e[tl].y == 0;
+                bad |= none ? 1u : 0u;
+                LR.step(none ? 0u : e[tl].x, none ? 1u : e[tl].y, P);
+            }
         } else {
-            // (other presets, P < 8, the end of a row; n_here = 0: this lane's stream has nothing in the tile)
-            for (int tl = n_here - 1; tl >= 0; --tl) {
+            // (the end of a row; n_here = 0: this lane's stream has nothing in the tile)
+            for (int tl = 0; tl < n_here; ++tl) {
                 const EncEntry e = tile[tl * kFuRowStride + lane];
                 if (e.p == 0) bad = 1;
-                else if (!bad) LA.template step<false>(use_inv ? make_entry(e.c, e.p) : e, P);
+                else if (!bad) LR.step(e.c, e.p, P);
             }
         }
         // at most kFuTile new words per stream and tile: whole chunks leave here (<= 19 pending before, < 4 after)
-        LA.flush_chunks();
+        if constexpr (KIND == kAns) LA.flush_chunks(); else LR.out.flush_chunks();
     }
 
     uint32_t n_words = 0;
-    int32_t status = LA.finish(true, 1u, n_words);
+    int32_t status;
+    if constexpr (KIND == kAns) status = LA.finish(true, 1u, n_words);
+    else status = LR.finish(1u, n_words);               // (no symbols: `range` is still all ones and nothing is sealed)
     if (!active) return;
     if (bad) status = CST_STREAM_IMPOSSIBLE_SYMBOL;
     if (too_long) status = CST_STREAM_CAPACITY;
@@ -1405,12 +1434,13 @@ __device__ __noinline__ void store_symbol_tile_ragged(int32_t* sym, uint32_t off
     }
 }
 
-// decode_gaussian_lane_kernel<W, S, kAns> for ragged rows: one lane per stream, parameters one tile ahead in the item mapping
+// decode_gaussian_lane_kernel<W, S, KIND> for ragged rows: one lane per stream, parameters one tile ahead in the item mapping
 // that puts consecutive lanes on consecutive addresses, the word window, FAM::left3 and the bracket search as they are.  The
 // loop runs to the wave's longest stream; a lane past its own length decodes and stores nothing but goes on taking part in the
 // wave-wide loads and fences.
-template <int W, int S, class FAM = GaussianFamily>
+template <int W, int S, int KIND, class FAM = GaussianFamily>
 __global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(const GaussianRaggedDecodeArgs ra) {
+    static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
     using G = LaneGeo<true>;
     constexpr int kParTile = G::kParTile, kWordWindow = G::kWordWindow, kOutSyms = G::kOutSyms, kOutStride = G::kOutStride;
     static_assert(kOutSyms == 16 && kOutStride == 20, "store_symbol_tile_ragged's tile");
@@ -1444,7 +1474,7 @@ __global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(c
     const double guess_shift = 0.5 - (double)a.min_symbol;            // symbol index of the real number x: x - min_symbol + 0.5
     const bool two_step_guess = (double)n * 64.0 > free_weight;      // the leak moves the guess by more than 1/64 quantile
 
-    DirectDecoder<W, S, kAns> D;
+    DirectDecoder<W, S, KIND> D;
     D.init(a, se, false);
     int32_t status = D.status;
 
@@ -1472,29 +1502,48 @@ __global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(c
             par_sd[item_t * kParStride + it * (kWave / kParTile) + item_j0] = sd_r[it];
         }
     };
-    // ---- word window: as in the lane kernel (a tile of 8 symbols takes at most 8 words) ----
+    // ---- word window: as in the lane kernel (a tile of 8 symbols takes at most 8 words; the range coder's first S / W words
+    // are taken by init, before the window starts).  ANS reads downwards from its position: every index from 0 up to it exists.
+    // The range coder reads upwards: an index exists below the stream's length. ----
+    constexpr bool kDownward = DirectDecoder<W, S, KIND>::kDownward;
     uint32_t w_r[kParTile];
     int64_t w_first = 0;                                      // index of w_r[0]
     auto win_request = [&](int64_t first) {
         w_first = first;
-        if (!__any(first < 0)) {                              // every lane's words exist: one pointer, eight offsets
-            const uint32_t* pw = D.in + first;
+        if constexpr (kDownward) {
+            if (!__any(first < 0)) {                              // every lane's words exist: one pointer, eight offsets
+                const uint32_t* pw = D.in + first;
 #pragma unroll
-            for (int i = 0; i < kParTile; ++i) w_r[i] = pw[i];
-            return;
-        }
+                for (int i = 0; i < kParTile; ++i) w_r[i] = pw[i];
+                return;
+            }
 #pragma unroll
-        for (int i = 0; i < kParTile; ++i) {
-            const int64_t p = first + i;
-            w_r[i] = *(p >= 0 ? D.in + p : D.idle);
+            for (int i = 0; i < kParTile; ++i) {
+                const int64_t p = first + i;
+                w_r[i] = *(p >= 0 ? D.in + p : D.idle);
+            }
+        } else {
+            const int64_t len = (int64_t)D.length();
+            if (!__any(first < 0 || first + kParTile > len)) {
+                const uint32_t* pw = D.in + first;
+#pragma unroll
+                for (int i = 0; i < kParTile; ++i) w_r[i] = pw[i];
+                return;
+            }
+#pragma unroll
+            for (int i = 0; i < kParTile; ++i) {
+                const int64_t p = first + i;
+                w_r[i] = *(p >= 0 && p < len ? D.in + p : D.idle);
+            }
         }
     };
     auto win_land = [&]() {
 #pragma unroll
         for (int i = 0; i < kParTile; ++i) win[(((uint32_t)(w_first + i)) & (kWordWindow - 1)) * kWave + lane] = w_r[i];
     };
-    const auto window_of = [&](int ahead_tiles) -> int64_t {  // first index of the 8 words `ahead_tiles` tiles ahead (ANS reads downwards)
-        return (int64_t)D.position() - (int64_t)kParTile * (ahead_tiles + 1);
+    const auto window_of = [&](int ahead_tiles) -> int64_t {  // first index of the 8 words `ahead_tiles` tiles ahead
+        if constexpr (kDownward) return (int64_t)D.position() - (int64_t)kParTile * (ahead_tiles + 1);
+        else return (int64_t)D.position() + (int64_t)kParTile * ahead_tiles;
     };
 
     if (mx > 0) {
@@ -1998,7 +2047,8 @@ template <class FAM> struct FamilyNames;
         static constexpr const char* lane_small[2] = {"ans_decode_" word "_lane_kernel<small>", "range_decode_" word "_lane_kernel<small>"}; \
         static constexpr const char* wave[2] = {"ans_decode_" word "_wave_kernel", "range_decode_" word "_wave_kernel"};                  \
         static constexpr const char* by_rows = "decode_" word "_by_rows";                                                                 \
-        static constexpr const char* ragged[2] = {"ans_encode_" word "_ragged_kernel", "ans_decode_" word "_ragged_kernel"};              \
+        static constexpr const char* ragged[2][2] = {{"ans_encode_" word "_ragged_kernel", "ans_decode_" word "_ragged_kernel"},          \
+                                                     {"range_encode_" word "_ragged_kernel", "range_decode_" word "_ragged_kernel"}};     \
     }
 CST_FAMILY_NAMES(GaussianFamily, "gaussian");
 CST_FAMILY_NAMES(LaplaceFamily, "laplace");
@@ -2546,8 +2596,8 @@ static cst_status check_ragged_gaussian_args(cst_coder_config cfg, int32_t min_s
     return CST_OK;
 }
 
-template <class FAM = GaussianFamily>
-static cst_status encode_gaussian_ragged(cst_coder_config cfg, const GaussianRaggedEncodeArgs& a, hipStream_t hs) {
+template <int KIND, class FAM>
+static cst_status launch_encode_ragged(cst_coder_config cfg, const GaussianRaggedEncodeArgs& a, hipStream_t hs) {
     const size_t per_block = (size_t)(kFuBlock / kWave) * kFuStreams;
     const size_t blocks = (a.n_streams + per_block - 1) / per_block;
     if (blocks > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
@@ -2558,11 +2608,11 @@ static cst_status encode_gaussian_ragged(cst_coder_config cfg, const GaussianRag
         CST_HIP_TRY(hipGetLastError());
         return CST_OK;
     };
-    return cfg.word_bits == 32 ? go(encode_gaussian_ragged_kernel<32, 64, FAM>) : go(encode_gaussian_ragged_kernel<16, 32, FAM>);
+    return cfg.word_bits == 32 ? go(encode_gaussian_ragged_kernel<32, 64, KIND, FAM>) : go(encode_gaussian_ragged_kernel<16, 32, KIND, FAM>);
 }
 
-template <class FAM = GaussianFamily>
-static cst_status decode_gaussian_ragged(cst_coder_config cfg, const GaussianRaggedDecodeArgs& a, hipStream_t hs) {
+template <int KIND, class FAM>
+static cst_status launch_decode_ragged(cst_coder_config cfg, const GaussianRaggedDecodeArgs& a, hipStream_t hs) {
     const size_t blocks = (a.p.n_streams + kRgDecThreads - 1) / kRgDecThreads;
     if (blocks > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
     const size_t lds = FAM::kErfTab ? kRgDecLdsBytes : kRgDecLdsBytesNoTab;
@@ -2572,8 +2622,45 @@ static cst_status decode_gaussian_ragged(cst_coder_config cfg, const GaussianRag
         CST_HIP_TRY(hipGetLastError());
         return CST_OK;
     };
-    return cfg.word_bits == 32 ? go(decode_gaussian_ragged_kernel<32, 64, FAM>) : go(decode_gaussian_ragged_kernel<16, 32, FAM>);
+    return cfg.word_bits == 32 ? go(decode_gaussian_ragged_kernel<32, 64, KIND, FAM>) : go(decode_gaussian_ragged_kernel<16, 32, KIND, FAM>);
 }
+
+// the checks, the arguments and the launch of every (coder, family) ragged encode call; d_a / d_b are the family's two parameters
+template <int KIND, class FAM>
+static cst_status encode_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols, const double* d_a,
+                                const double* d_b, const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order, uint32_t* d_words,
+                                const uint64_t* d_word_offsets, size_t stride_words, uint32_t* d_n_words, int32_t* d_status, hipStream_t hs) {
+    if (cst_status st = check_ragged_gaussian_args(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, d_sym_offsets, d_words, d_word_offsets,
+                                                   stride_words, d_n_words, d_status, d_order, n_streams)) return st;
+    if (n_streams == 0) return CST_OK;
+    GaussianRaggedEncodeArgs a{};
+    a.symbols = d_symbols; a.means = d_a; a.stds = d_b; a.sym_offsets = d_sym_offsets; a.n_streams = n_streams; a.order = d_order;
+    a.precision = cfg.precision; a.lo = min_symbol; a.hi = max_symbol;
+    a.words = d_words; a.word_offsets = d_word_offsets; a.stride_words = stride_words; a.n_words = d_n_words; a.status = d_status;
+    return note_kernel(FamilyNames<FAM>::ragged[KIND == kRange][0], launch_encode_ragged<KIND, FAM>(cfg, a, hs));
+}
+
+template <int KIND, class FAM>
+static cst_status decode_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                const double* d_a, const double* d_b, int32_t* d_symbols, const uint64_t* d_sym_offsets, size_t n_streams,
+                                const uint32_t* d_order, int32_t* d_status, hipStream_t hs) {
+    if (cst_status st = check_ragged_gaussian_args(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, d_sym_offsets, d_words, d_word_offsets,
+                                                   stride_words, d_n_words, d_status, d_order, n_streams)) return st;
+    if (n_streams == 0) return CST_OK;
+    GaussianRaggedDecodeArgs a{};
+    a.p.words = d_words; a.p.offsets = d_word_offsets; a.p.stride_words = stride_words; a.p.n_words = d_n_words; a.p.words_capacity = words_capacity;
+    a.p.symbols = d_symbols; a.p.n_streams = n_streams; a.p.precision = cfg.precision;
+    a.p.min_symbol = min_symbol; a.p.n_symbols = (int32_t)((int64_t)max_symbol - min_symbol + 1);
+    a.p.means = d_a; a.p.stds = d_b; a.p.status = d_status;
+    a.sym_offsets = d_sym_offsets; a.order = d_order;
+    return note_kernel(FamilyNames<FAM>::ragged[KIND == kRange][1], launch_decode_ragged<KIND, FAM>(cfg, a, hs));
+}
+
+// the family calls: the Gaussian's checks first, then the family (Laplace or Cauchy, nothing else)
+#define CST_RAGGED_FAMILY(call, KIND, ...)                                                                                      \
+    (family == CST_FAMILY_LAPLACE ? call<KIND, LaplaceFamily>(__VA_ARGS__)                                                      \
+     : family == CST_FAMILY_CAUCHY ? call<KIND, CauchyFamily>(__VA_ARGS__) : CST_ERR_INVALID_ARGUMENT)
 
 } // namespace cst
 
@@ -2583,31 +2670,67 @@ cst_status cst_ans_encode_gaussian_ragged(cst_coder_config cfg, int32_t min_symb
                                           const double* d_means, const double* d_stds, const uint64_t* d_sym_offsets, size_t n_streams,
                                           const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
                                           uint32_t* d_n_words, int32_t* d_status, void* stream) {
-    if (cst_status st = check_ragged_gaussian_args(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, d_sym_offsets, d_words, d_word_offsets,
-                                                   stride_words, d_n_words, d_status, d_order, n_streams)) return st;
-    if (n_streams == 0) return CST_OK;
-    GaussianRaggedEncodeArgs a{};
-    a.symbols = d_symbols; a.means = d_means; a.stds = d_stds; a.sym_offsets = d_sym_offsets; a.n_streams = n_streams; a.order = d_order;
-    a.precision = cfg.precision; a.lo = min_symbol; a.hi = max_symbol;
-    a.words = d_words; a.word_offsets = d_word_offsets; a.stride_words = stride_words; a.n_words = d_n_words; a.status = d_status;
-    return note_kernel(FamilyNames<GaussianFamily>::ragged[0], encode_gaussian_ragged(cfg, a, (hipStream_t)stream));
+    return encode_ragged<kAns, GaussianFamily>(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, d_sym_offsets, n_streams, d_order, d_words,
+                                               d_word_offsets, stride_words, d_n_words, d_status, (hipStream_t)stream);
 }
 
 cst_status cst_ans_decode_gaussian_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
                                           const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
                                           const double* d_means, const double* d_stds, int32_t* d_symbols, const uint64_t* d_sym_offsets,
                                           size_t n_streams, const uint32_t* d_order, int32_t* d_status, void* stream) {
-    if (cst_status st = check_ragged_gaussian_args(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, d_sym_offsets, d_words, d_word_offsets,
-                                                   stride_words, d_n_words, d_status, d_order, n_streams)) return st;
-    if (n_streams == 0) return CST_OK;
-    GaussianRaggedDecodeArgs a{};
-    a.p.words = d_words; a.p.offsets = d_word_offsets; a.p.stride_words = stride_words; a.p.n_words = d_n_words; a.p.words_capacity = words_capacity;
-    a.p.symbols = d_symbols; a.p.n_streams = n_streams; a.p.precision = cfg.precision;
-    a.p.min_symbol = min_symbol; a.p.n_symbols = (int32_t)((int64_t)max_symbol - min_symbol + 1);
-    a.p.means = d_means; a.p.stds = d_stds; a.p.status = d_status;
-    a.sym_offsets = d_sym_offsets; a.order = d_order;
-    return note_kernel(FamilyNames<GaussianFamily>::ragged[1], decode_gaussian_ragged(cfg, a, (hipStream_t)stream));
+    return decode_ragged<kAns, GaussianFamily>(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_means,
+                                               d_stds, d_symbols, d_sym_offsets, n_streams, d_order, d_status, (hipStream_t)stream);
 }
+
+cst_status cst_range_encode_gaussian_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                            const double* d_means, const double* d_stds, const uint64_t* d_sym_offsets, size_t n_streams,
+                                            const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                            uint32_t* d_n_words, int32_t* d_status, void* stream) {
+    return encode_ragged<kRange, GaussianFamily>(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, d_sym_offsets, n_streams, d_order, d_words,
+                                                 d_word_offsets, stride_words, d_n_words, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_gaussian_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                            const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                            const double* d_means, const double* d_stds, int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                            size_t n_streams, const uint32_t* d_order, int32_t* d_status, void* stream) {
+    return decode_ragged<kRange, GaussianFamily>(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_means,
+                                                 d_stds, d_symbols, d_sym_offsets, n_streams, d_order, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_ans_encode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                        const double* d_a, const double* d_b, const uint64_t* d_sym_offsets, size_t n_streams,
+                                        const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                        uint32_t* d_n_words, int32_t* d_status, void* stream) {
+    return CST_RAGGED_FAMILY(encode_ragged, kAns, cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, d_sym_offsets, n_streams, d_order, d_words,
+                             d_word_offsets, stride_words, d_n_words, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                        const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                        const double* d_a, const double* d_b, int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                        size_t n_streams, const uint32_t* d_order, int32_t* d_status, void* stream) {
+    return CST_RAGGED_FAMILY(decode_ragged, kAns, cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_a,
+                             d_b, d_symbols, d_sym_offsets, n_streams, d_order, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_encode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                          const double* d_a, const double* d_b, const uint64_t* d_sym_offsets, size_t n_streams,
+                                          const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                          uint32_t* d_n_words, int32_t* d_status, void* stream) {
+    return CST_RAGGED_FAMILY(encode_ragged, kRange, cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, d_sym_offsets, n_streams, d_order, d_words,
+                             d_word_offsets, stride_words, d_n_words, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                          const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                          const double* d_a, const double* d_b, int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                          size_t n_streams, const uint32_t* d_order, int32_t* d_status, void* stream) {
+    return CST_RAGGED_FAMILY(decode_ragged, kRange, cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_a,
+                             d_b, d_symbols, d_sym_offsets, n_streams, d_order, d_status, (hipStream_t)stream);
+}
+
+#undef CST_RAGGED_FAMILY
 
 } // extern "C"
 

@@ -395,6 +395,46 @@ cst_status cst_ans_decode_gaussian_ragged(cst_coder_config cfg, int32_t min_symb
                                           const double *d_stds, int32_t *d_symbols, const uint64_t *d_sym_offsets,
                                           size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
 
+/* ... the same pair for the range coder (a queue: the decoder reads the symbols in the order they were written), and both coders
+ * over QuantizedLaplace / QuantizedCauchy.  Arguments, checks, statuses and the order / word_offsets conventions are those of
+ * cst_ans_{encode,decode}_gaussian_ragged; words, count and status of every stream are those of the reference RangeEncoder /
+ * AnsCoder -- and of the rectangular cst_{ans,range}_{encode,decode}_{gaussian,family}_batch -- for that stream alone.
+ *     range coder slabs                  min(n, ceil(n P / W)) + 2 words always suffice for a stream of n symbols (the bound inside
+ *                                        cst_range_max_words); a stream of length 0 yields 0 words and CST_STREAM_OK.
+ *     family                             CST_FAMILY_LAPLACE (d_a = means, d_b = scales) or CST_FAMILY_CAUCHY (d_a = locs, d_b =
+ *                                        scales), as in cst_ans_encode_family_batch; anything else: CST_ERR_INVALID_ARGUMENT.
+ * No jump points for any of these. */
+cst_status cst_range_encode_gaussian_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                            const int32_t *d_symbols, const double *d_means, const double *d_stds,
+                                            const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                            uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                            uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_range_decode_gaussian_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                            const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                            size_t words_capacity, const uint32_t *d_n_words, const double *d_means,
+                                            const double *d_stds, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                            size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
+cst_status cst_ans_encode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                        const int32_t *d_symbols, const double *d_a, const double *d_b,
+                                        const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                        uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                        uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                        const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                        size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
+                                        const double *d_b, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                        size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
+cst_status cst_range_encode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                          const int32_t *d_symbols, const double *d_a, const double *d_b,
+                                          const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                          uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                          uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_range_decode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                          const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                          size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
+                                          const double *d_b, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                          size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
+
 /* Checkpointed streams -- the reference's Pos / Seek jump tables (src/stream/stack.rs:1107-1139; test :1456-1548) for the
  * batched coder.  The encoder notes, in front of every chunk of `ckpt_interval` symbols, what `AnsCoder::pos()` returns
  * there: d_ckpt_pos[s][j] = words in the bulk, d_ckpt_state[s][j] = coder state once symbols [j * interval, n) are

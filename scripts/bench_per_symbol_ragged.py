@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Per-symbol Gaussians for streams of different lengths: 16 384 streams of 256 .. 8192 symbols (uniform) at (32,64,24), support
+"""Per-symbol models for streams of different lengths: 16 384 streams of 256 .. 8192 symbols (uniform) at (32,64,24), support
 -100 .. 100, parameters drawn as in tests/test_gpu_per_symbol_batch.py::workload, through
-  (a) batched.ans_{encode,decode}_gaussian_ragged: one launch each (as the streams come, and once more sorted by length);
-  (b) the bit-exact alternative without them: the streams grouped by length, one ans_{encode,decode}_gaussian call per distinct
+  (a) batched.{coder}_{encode,decode}_{family}_ragged: one launch each (as the streams come, and once more sorted by length);
+  (b) the bit-exact alternative without them: the streams grouped by length, one {coder}_{encode,decode}_{family} call per distinct
       length (the groups' matrices are built beforehand and not timed);
   (c) the price of raggedness: the rectangular calls on a 16 384 x 4224 matrix (the same number of symbols) beside the ragged calls
       on that same matrix expressed with equal lengths.
+--coder ans|range and --family gaussian|laplace|cauchy choose the form (default: ans, gaussian); --skip-grouped leaves (b) out (it
+takes seconds per alternation and minutes to set up; its condition is then not judged).
 Device events on the launch stream, warmed up, in one process, the candidates alternating, medians of the alternations.  Every
 stream is checked by the decode round trip.  The one condition: (a) is faster than (b) in every alternation (exit status 1 otherwise);
 (c) is a recorded ratio."""
@@ -20,20 +22,31 @@ ap.add_argument("--streams", type=int, default=16384)
 ap.add_argument("--min-len", type=int, default=256)
 ap.add_argument("--max-len", type=int, default=8192)
 ap.add_argument("--alternations", type=int, default=5)
+ap.add_argument("--coder", choices=["ans", "range"], default="ans")
+ap.add_argument("--family", choices=["gaussian", "laplace", "cauchy"], default="gaussian")
+ap.add_argument("--skip-grouped", action="store_true", help="leave (b), one rectangular call per distinct length, out")
 args = ap.parse_args()
 assert args.alternations >= 5 or args.streams < 16384, "the recorded figures are medians of at least five alternations"
 
 CFG, LO, HI = (32, 64, 24), -100, 100
 torch.manual_seed(1)
 dev = "cuda"
+enc_ragged, dec_ragged = getattr(B, f"{args.coder}_encode_{args.family}_ragged"), getattr(B, f"{args.coder}_decode_{args.family}_ragged")
+enc_rect, dec_rect = getattr(B, f"{args.coder}_encode_{args.family}"), getattr(B, f"{args.coder}_decode_{args.family}")
+NO_JUMP = {"jump_points": 0} if args.family == "gaussian" else {}      # (the family calls have no jump points to switch off)
 
 
 def draw(*shape):
-    """mu uniform in 0.6 [lo, hi], sd log-uniform in 0.3 .. 40, symbols = clipped rounded draws"""
+    """mu uniform in 0.6 [lo, hi], sd log-uniform in 0.3 .. 40, symbols = clipped rounded draws from the family"""
     mu = (torch.rand(*shape, dtype=torch.float64, device=dev) * 2 - 1) * (0.6 * HI)
     sd = torch.exp(torch.log(torch.tensor(0.3, dtype=torch.float64, device=dev))
                    + torch.rand(*shape, dtype=torch.float64, device=dev) * torch.log(torch.tensor(40.0 / 0.3, dtype=torch.float64, device=dev)))
-    sym = torch.clamp(torch.round(mu + sd * torch.randn(*shape, dtype=torch.float64, device=dev)), LO, HI).to(torch.int32)
+    if args.family == "gaussian":
+        noise = torch.randn(*shape, dtype=torch.float64, device=dev)
+    else:
+        u = torch.rand(*shape, dtype=torch.float64, device=dev) - 0.5
+        noise = -torch.sign(u) * torch.log1p(-2 * u.abs()) if args.family == "laplace" else torch.tan(torch.pi * u)
+    sym = torch.clamp(torch.round(mu + sd * noise), LO, HI).to(torch.int32)
     return sym, mu, sd
 
 
@@ -65,17 +78,17 @@ torch.cumsum(lengths, 0, out=offsets[1:])
 total = int(offsets[-1])
 sym, mu, sd = draw(total)
 
-enc = B.ans_encode_gaussian_ragged(sym, offsets, LO, HI, mu, sd, CFG)
-dec, st = B.ans_decode_gaussian_ragged(enc, offsets, LO, HI, mu, sd)
+enc = enc_ragged(sym, offsets, LO, HI, mu, sd, CFG)
+dec, st = dec_ragged(enc, offsets, LO, HI, mu, sd)
 torch.cuda.synchronize()
 ok_a = bool(torch.equal(dec, sym)) and int(enc.status.abs().sum()) == 0 and int(st.abs().sum()) == 0
 
 # ---- (b): one rectangular batch per distinct length ----
 order = torch.argsort(lengths, stable=True)
-sorted_len = lengths[order].cpu().tolist()
+sorted_len = lengths[order].cpu().tolist() if not args.skip_grouped else []
 order_h, off_h = order.cpu().tolist(), offsets.cpu().tolist()
 groups = []          # (streams, symbols, means, stds) per distinct length
-i = 0
+i = 0 if not args.skip_grouped else n
 while i < n:
     j = i
     while j < n and sorted_len[j] == sorted_len[i]:
@@ -91,12 +104,12 @@ group_dec = [None] * len(groups)
 
 def b_encode():
     for g, (_, s_, m_, d_) in enumerate(groups):
-        group_enc[g] = B.ans_encode_gaussian(s_, LO, HI, m_, d_, CFG, jump_points=0)
+        group_enc[g] = enc_rect(s_, LO, HI, m_, d_, CFG, **NO_JUMP)
 
 
 def b_decode():
     for g, (_, s_, m_, d_) in enumerate(groups):
-        group_dec[g] = B.ans_decode_gaussian(group_enc[g], LO, HI, m_, d_)
+        group_dec[g] = dec_rect(group_enc[g], LO, HI, m_, d_)
 
 
 b_encode(); b_decode()
@@ -107,22 +120,23 @@ ok_b = all(bool(torch.equal(group_dec[g][0], groups[g][1])) and int(group_dec[g]
 n_words_b = torch.zeros(n, dtype=torch.int32, device=dev)
 for g, (rows, *_rest) in enumerate(groups):
     n_words_b[torch.tensor(rows, device=dev)] = group_enc[g].n_words
-ok_b = ok_b and bool(torch.equal(n_words_b, enc.n_words))
+ok_b = ok_b and (args.skip_grouped or bool(torch.equal(n_words_b, enc.n_words)))
 
 # (a) once more with a schedule (streams of similar length side by side, the sort itself not timed): recorded, no condition on it
 by_length = B.ragged_order(lengths)
-enc_s = B.ans_encode_gaussian_ragged(sym, offsets, LO, HI, mu, sd, CFG, order=by_length)
-dec_s, st_s = B.ans_decode_gaussian_ragged(enc_s, offsets, LO, HI, mu, sd)
+enc_s = enc_ragged(sym, offsets, LO, HI, mu, sd, CFG, order=by_length)
+dec_s, st_s = dec_ragged(enc_s, offsets, LO, HI, mu, sd)
 torch.cuda.synchronize()
 ok_a = ok_a and bool(torch.equal(dec_s, sym)) and int(st_s.abs().sum()) == 0 and bool(torch.equal(enc_s.n_words, enc.n_words))
 
-t_ab = alternate({"a_encode": lambda: B.ans_encode_gaussian_ragged(sym, offsets, LO, HI, mu, sd, CFG),
+t_ab = alternate({"a_encode": lambda: enc_ragged(sym, offsets, LO, HI, mu, sd, CFG),
                   "b_encode": b_encode,
-                  "a_sorted_encode": lambda: B.ans_encode_gaussian_ragged(sym, offsets, LO, HI, mu, sd, CFG, order=by_length),
-                  "a_decode": lambda: B.ans_decode_gaussian_ragged(enc, offsets, LO, HI, mu, sd, out=dec),
+                  "a_sorted_encode": lambda: enc_ragged(sym, offsets, LO, HI, mu, sd, CFG, order=by_length),
+                  "a_decode": lambda: dec_ragged(enc, offsets, LO, HI, mu, sd, out=dec),
                   "b_decode": b_decode,
-                  "a_sorted_decode": lambda: B.ans_decode_gaussian_ragged(enc_s, offsets, LO, HI, mu, sd, out=dec_s)}, args.alternations)
-faster = all(a < b for a, b in zip(t_ab["a_encode"], t_ab["b_encode"])) and all(a < b for a, b in zip(t_ab["a_decode"], t_ab["b_decode"]))
+                  "a_sorted_decode": lambda: dec_ragged(enc_s, offsets, LO, HI, mu, sd, out=dec_s)}, args.alternations)
+faster = args.skip_grouped or (all(a < b for a, b in zip(t_ab["a_encode"], t_ab["b_encode"]))
+                               and all(a < b for a, b in zip(t_ab["a_decode"], t_ab["b_decode"])))
 del groups, group_enc, group_dec
 
 # ---- (c): a rectangular matrix of the same size, both ways ----
@@ -130,31 +144,35 @@ n_per = (args.min_len + args.max_len) // 2
 sym_r, mu_r, sd_r = draw(n, n_per)
 off_r = torch.arange(n + 1, dtype=torch.int64, device=dev) * n_per
 flat_r, mu_f, sd_f = sym_r.reshape(-1), mu_r.reshape(-1), sd_r.reshape(-1)
-enc_r = B.ans_encode_gaussian(sym_r, LO, HI, mu_r, sd_r, CFG, jump_points=0)
-dec_r, st_r = B.ans_decode_gaussian(enc_r, LO, HI, mu_r, sd_r)
-enc_e = B.ans_encode_gaussian_ragged(flat_r, off_r, LO, HI, mu_f, sd_f, CFG)
-dec_e, st_e = B.ans_decode_gaussian_ragged(enc_e, off_r, LO, HI, mu_f, sd_f)
+enc_r = enc_rect(sym_r, LO, HI, mu_r, sd_r, CFG, **NO_JUMP)
+dec_r, st_r = dec_rect(enc_r, LO, HI, mu_r, sd_r)
+enc_e = enc_ragged(flat_r, off_r, LO, HI, mu_f, sd_f, CFG)
+dec_e, st_e = dec_ragged(enc_e, off_r, LO, HI, mu_f, sd_f)
 torch.cuda.synchronize()
 ok_c = bool(torch.equal(dec_r, sym_r)) and bool(torch.equal(dec_e, flat_r)) and int(st_r.abs().sum()) == 0 and int(st_e.abs().sum()) == 0 \
     and bool(torch.equal(enc_r.n_words, enc_e.n_words))
-t_c = alternate({"rect_encode": lambda: B.ans_encode_gaussian(sym_r, LO, HI, mu_r, sd_r, CFG, jump_points=0, out=enc_r),
-                 "ragged_encode": lambda: B.ans_encode_gaussian_ragged(flat_r, off_r, LO, HI, mu_f, sd_f, CFG),
-                 "rect_decode": lambda: B.ans_decode_gaussian(enc_r, LO, HI, mu_r, sd_r, out=dec_r),
-                 "ragged_decode": lambda: B.ans_decode_gaussian_ragged(enc_e, off_r, LO, HI, mu_f, sd_f, out=dec_e)}, args.alternations)
+t_c = alternate({"rect_encode": lambda: enc_rect(sym_r, LO, HI, mu_r, sd_r, CFG, out=enc_r, **NO_JUMP),
+                 "ragged_encode": lambda: enc_ragged(flat_r, off_r, LO, HI, mu_f, sd_f, CFG),
+                 "rect_decode": lambda: dec_rect(enc_r, LO, HI, mu_r, sd_r, out=dec_r),
+                 "ragged_decode": lambda: dec_ragged(enc_e, off_r, LO, HI, mu_f, sd_f, out=dec_e)}, args.alternations)
 
 med = lambda xs: statistics.median(xs)
 m_ab = {k: med(v) for k, v in t_ab.items()}
 m_c = {k: med(v) for k, v in t_c.items()}
-print(f"{n} streams of {args.min_len} .. {args.max_len} symbols ({total / 1e6:.1f} M symbols), (32,64,24), medians of {args.alternations}:")
+print(f"{args.coder} x {args.family}: {n} streams of {args.min_len} .. {args.max_len} symbols ({total / 1e6:.1f} M symbols), (32,64,24), "
+      f"medians of {args.alternations}:")
 print(f"  (a) ragged calls:               encode {m_ab['a_encode']:9.3f} ms ({total / m_ab['a_encode'] / 1e6:.2f} Gsym/s)  "
       f"decode {m_ab['a_decode']:9.3f} ms ({total / m_ab['a_decode'] / 1e6:.2f} Gsym/s)  round trip ok={ok_a}")
 print(f"      ... sorted by length:       encode {m_ab['a_sorted_encode']:9.3f} ms ({total / m_ab['a_sorted_encode'] / 1e6:.2f} Gsym/s)  "
       f"decode {m_ab['a_sorted_decode']:9.3f} ms ({total / m_ab['a_sorted_decode'] / 1e6:.2f} Gsym/s)")
-print(f"  (b) one call per length:       encode {m_ab['b_encode']:9.3f} ms  decode {m_ab['b_decode']:9.3f} ms  round trip ok={ok_b}")
-print(f"      (a) faster than (b) in every alternation: {faster}")
+if args.skip_grouped:
+    print("  (b) one call per length:       left out (--skip-grouped)")
+else:
+    print(f"  (b) one call per length:       encode {m_ab['b_encode']:9.3f} ms  decode {m_ab['b_decode']:9.3f} ms  round trip ok={ok_b}")
+    print(f"      (a) faster than (b) in every alternation: {faster}")
 print(f"  (c) {n} x {n_per} rectangular:  encode {m_c['rect_encode']:9.3f} ms  decode {m_c['rect_decode']:9.3f} ms")
 print(f"      the same through the ragged calls: encode {m_c['ragged_encode']:9.3f} ms ({m_c['ragged_encode'] / m_c['rect_encode']:.2f}x)  "
       f"decode {m_c['ragged_decode']:9.3f} ms ({m_c['ragged_decode'] / m_c['rect_decode']:.2f}x)  round trips ok={ok_c}")
-print(json.dumps({"streams": n, "symbols": total, "alternations": args.alternations, "ms": {**m_ab, **m_c}, "all_ms": {**t_ab, **t_c},
+print(json.dumps({"coder": args.coder, "family": args.family, "grouped": not args.skip_grouped, "streams": n, "symbols": total, "alternations": args.alternations, "ms": {**m_ab, **m_c}, "all_ms": {**t_ab, **t_c},
                   "a_faster_than_b": faster, "round_trips_ok": ok_a and ok_b and ok_c}))
 sys.exit(0 if faster and ok_a and ok_b and ok_c else 1)
