@@ -1293,6 +1293,68 @@ extern "C" {
         h_bad: *mut i32,
     ) -> CstStatus;
 
+    pub fn cst_categorical_perfect_cdf_rows(
+        precision: i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_rows: usize,
+        n_symbols: i32,
+        d_rows: *mut u32,
+        d_bad: *mut i32,
+        d_moves: *mut u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_categorical_perfect_cdf_host(
+        precision: i32,
+        h_probs: *const c_void,
+        prob_bytes: i32,
+        n_rows: usize,
+        n_symbols: i32,
+        h_rows: *mut u32,
+        h_bad: *mut i32,
+        h_moves: *mut u32,
+    ) -> CstStatus;
+
+    pub fn cst_ans_encode_categorical_perfect_batch(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_state: *mut u64,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_categorical_perfect_batch(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_state: *mut u64,
+        d_n_words_out: *mut u32,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// Per-symbol models given explicitly (any model family with per-symbol parameters, e.g.
     /// Categorical(perfect=False) with a probability matrix, src/pybindings/stream/model/internals.rs:188-249):
     ///   encode: d_left / d_prob hold EncoderModel::left_cumulative_and_probability of every symbol
@@ -1587,6 +1649,45 @@ extern "C" {
     ) -> CstStatus;
 
     pub fn cst_range_decode_categorical_batch(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_rstate: *mut CstRangeState,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// ... and with the perfect quantisation (see cst_ans_encode_categorical_perfect_batch)
+    pub fn cst_range_encode_categorical_perfect_batch(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_rstate: *mut CstRangeState,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_categorical_perfect_batch(
         cfg: CstCoderConfig,
         d_words: *const u32,
         d_offsets: *const u64,

@@ -253,6 +253,71 @@ pub fn categorical_fast_cdf_host<F: Probability>(precision: u32, probabilities: 
     Ok(bad.into_iter().map(|b| b != 0).collect())
 }
 
+/// The cross-entropy-optimal quantisation of `n_rows` probability vectors of `n_symbols <= 1024` entries on the device
+/// (`Categorical(perfect=True)`, src/stream/model/categorical.rs:56-177, one wave per row): rows of `n_symbols + 1` cumulatives, a code
+/// per row (0 good, 1 not normalizable, 2 the search was stopped) and the number of unit moves of every row's search.
+pub fn categorical_perfect_cdf_rows<F: Probability>(
+    precision: u32,
+    probabilities: &DeviceBuffer<F>,
+    n_rows: usize,
+    n_symbols: usize,
+    stream: &Stream,
+) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>, DeviceBuffer<u32>)> {
+    let count = n_rows.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+    if probabilities.len() < count || n_symbols > i32::MAX as usize {
+        return Err(Error::InvalidArgument);
+    }
+    let mut rows: DeviceBuffer<u32> = DeviceBuffer::new(count + n_rows)?;
+    let mut bad: DeviceBuffer<i32> = DeviceBuffer::new(n_rows)?;
+    let mut moves: DeviceBuffer<u32> = DeviceBuffer::new(n_rows)?;
+    check(unsafe {
+        ffi::cst_categorical_perfect_cdf_rows(
+            precision as i32,
+            probabilities.as_ptr() as *const c_void,
+            F::BYTES,
+            n_rows,
+            n_symbols as i32,
+            rows.as_mut_ptr(),
+            bad.as_mut_ptr(),
+            moves.as_mut_ptr(),
+            stream.as_raw(),
+        )
+    })?;
+    Ok((rows, bad, moves))
+}
+
+/// The device quantiser's formulation on the CPU over host slices: `rows` takes `n_symbols + 1` cumulatives per vector.  Returns
+/// the code and the number of unit moves of every row.
+pub fn categorical_perfect_cdf_host<F: Probability>(
+    precision: u32,
+    probabilities: &[F],
+    n_symbols: usize,
+    rows: &mut [u32],
+) -> Result<(Vec<i32>, Vec<u32>)> {
+    if n_symbols == 0 || probabilities.len() % n_symbols != 0 || n_symbols > i32::MAX as usize {
+        return Err(Error::InvalidArgument);
+    }
+    let n_rows = probabilities.len() / n_symbols;
+    if rows.len() < n_rows * (n_symbols + 1) {
+        return Err(Error::InvalidArgument);
+    }
+    let mut bad = vec![0i32; n_rows];
+    let mut moves = vec![0u32; n_rows];
+    check(unsafe {
+        ffi::cst_categorical_perfect_cdf_host(
+            precision as i32,
+            probabilities.as_ptr() as *const c_void,
+            F::BYTES,
+            n_rows,
+            n_symbols as i32,
+            rows.as_mut_ptr(),
+            bad.as_mut_ptr(),
+            moves.as_mut_ptr(),
+        )
+    })?;
+    Ok((bad, moves))
+}
+
 /// A device-resident entropy model over a contiguous `i32` support: the encoder side is
 /// `EncoderModel::left_cumulative_and_probability` as a table (ContiguousCategoricalEntropyModel,
 /// src/stream/model/categorical/contiguous.rs:673-700), the decoder side `ContiguousLookupDecoderModel`
@@ -1034,6 +1099,45 @@ impl BatchedAnsCoder {
         Ok(out)
     }
 
+    /// The same with `Categorical(perfect=True)`: every row quantised on the device by `perfectly_quantized_probabilities`
+    /// (src/stream/model/categorical.rs:56-177; at most 1024 symbols, `f32` rows are widened to `f64`).
+    pub fn encode_symbols_reverse_categorical_perfect<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_streams: usize,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<EncodedBatch> {
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        let entries = count.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if symbols.len() < count || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = EncodedBatch::allocate(n_streams, self.max_words(n_per_stream), self.config)?;
+        check(unsafe {
+            ffi::cst_ans_encode_categorical_perfect_batch(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                out.words.as_mut_ptr(),
+                out.stride_words,
+                out.n_words.as_mut_ptr(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
     /// `encode_symbols_reverse` + `pos()` in front of every chunk of `interval` symbols (a multiple of 16 that divides the row
     /// length; batches of at least 16 384 streams): the jump table of the reference's flagship call.
     pub fn encode_symbols_reverse_with_checkpoints(
@@ -1302,6 +1406,47 @@ impl BatchedAnsCoder {
         let mut out = DecodedBatch { symbols: DeviceBuffer::new(count)?, status: DeviceBuffer::new(n_streams)? };
         check(unsafe {
             ffi::cst_ans_decode_categorical_batch(
+                self.config,
+                encoded.words.as_ptr(),
+                core::ptr::null(),
+                encoded.stride_words,
+                encoded.words.len(),
+                encoded.n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                out.symbols.as_mut_ptr(),
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                core::ptr::null_mut(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
+    /// The decoder of the `_perfect` encoder: rows tabulated in pieces by the device quantiser, then looked up.
+    pub fn decode_symbols_categorical_perfect<F: Probability>(
+        &self,
+        encoded: &EncodedBatch,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<DecodedBatch> {
+        let n_streams = encoded.n_streams;
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        let entries = count.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = DecodedBatch { symbols: DeviceBuffer::new(count)?, status: DeviceBuffer::new(n_streams)? };
+        check(unsafe {
+            ffi::cst_ans_decode_categorical_perfect_batch(
                 self.config,
                 encoded.words.as_ptr(),
                 core::ptr::null(),
@@ -2386,6 +2531,45 @@ impl BatchedRangeEncoder {
         Ok(out)
     }
 
+    /// The same with `Categorical(perfect=True)`: every row quantised on the device by `perfectly_quantized_probabilities`
+    /// (src/stream/model/categorical.rs:56-177; at most 1024 symbols, `f32` rows are widened to `f64`).
+    pub fn encode_symbols_categorical_perfect<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_streams: usize,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<EncodedBatch> {
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        let entries = count.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if symbols.len() < count || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = EncodedBatch::allocate(n_streams, self.max_words(n_per_stream), self.config)?;
+        check(unsafe {
+            ffi::cst_range_encode_categorical_perfect_batch(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                out.words.as_mut_ptr(),
+                out.stride_words,
+                out.n_words.as_mut_ptr(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
     /// `encode_symbols` that also notes `RangeEncoder::pos()` in front of every chunk of `interval` symbols (ABI 5,
     /// `cst_range_encode_gaussian_batch_ckpt`; src/stream/queue.rs:172-196): a multiple of 16 that divides `n_per_stream`, stream-major.
     /// The words are those of `encode_symbols`.  `auto_jump_interval_gaussian` is the library's own choice of `interval`.
@@ -2917,6 +3101,46 @@ impl BatchedRangeDecoder {
         let mut out = DecodedBatch { symbols: DeviceBuffer::new(count)?, status: DeviceBuffer::new(n_streams)? };
         check(unsafe {
             ffi::cst_range_decode_categorical_batch(
+                self.config,
+                encoded.words.as_ptr(),
+                core::ptr::null(),
+                encoded.stride_words,
+                encoded.words.len(),
+                encoded.n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                out.symbols.as_mut_ptr(),
+                n_streams,
+                n_per_stream,
+                self.layout.raw(),
+                core::ptr::null_mut(),
+                out.status.as_mut_ptr(),
+                ffi::CST_FLAG_NONE,
+                stream.as_raw(),
+            )
+        })?;
+        Ok(out)
+    }
+
+    /// The decoder of the `_perfect` encoder: rows tabulated in pieces by the device quantiser, then looked up.
+    pub fn decode_symbols_categorical_perfect<F: Probability>(
+        &self,
+        encoded: &EncodedBatch,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_per_stream: usize,
+        stream: &Stream,
+    ) -> Result<DecodedBatch> {
+        let n_streams = encoded.n_streams;
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        let entries = count.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = DecodedBatch { symbols: DeviceBuffer::new(count)?, status: DeviceBuffer::new(n_streams)? };
+        check(unsafe {
+            ffi::cst_range_decode_categorical_perfect_batch(
                 self.config,
                 encoded.words.as_ptr(),
                 core::ptr::null(),

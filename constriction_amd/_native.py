@@ -37,6 +37,7 @@ CODER_ANS, CODER_RANGE = 0, 1
 
 HUFFMAN_STACK, HUFFMAN_QUEUE = 0, 1
 HUFFMAN_MAX_SYMBOLS = 65536
+CATEGORICAL_PERFECT_MAX_K = 1024   # CST_CATEGORICAL_PERFECT_MAX_K: the slots of the device quantiser
 
 
 class BackendUnavailable(RuntimeError):
@@ -155,6 +156,13 @@ SIGNATURES = {
     "cst_range_decode_categorical_batch": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _vp, _z, _z, _i32, _vp, _vp, _u32, _vp]),
     "cst_categorical_fast_cdf_rows": (_i32, [_i32, _vp, _i32, _z, _i32, _vp, _vp, _vp]),
     "cst_categorical_fast_cdf_host": (_i32, [_i32, _vp, _i32, _z, _i32, _vp, _vp]),
+    "cst_ans_encode_categorical_perfect_batch": (_i32, [CoderConfig, _vp, _vp, _i32, _i32, _z, _z, _i32, _vp, _z, _vp, _vp, _vp, _u32, _vp]),
+    "cst_ans_decode_categorical_perfect_batch": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _vp, _z, _z, _i32, _vp, _vp, _vp, _u32,
+                                                        _vp]),
+    "cst_range_encode_categorical_perfect_batch": (_i32, [CoderConfig, _vp, _vp, _i32, _i32, _z, _z, _i32, _vp, _z, _vp, _vp, _vp, _u32, _vp]),
+    "cst_range_decode_categorical_perfect_batch": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _vp, _z, _z, _i32, _vp, _vp, _u32, _vp]),
+    "cst_categorical_perfect_cdf_rows": (_i32, [_i32, _vp, _i32, _z, _i32, _vp, _vp, _vp, _vp]),
+    "cst_categorical_perfect_cdf_host": (_i32, [_i32, _vp, _i32, _z, _i32, _vp, _vp, _vp]),
     "cst_range_encode_gaussian_batch": (_i32, [CoderConfig, _i32, _i32, _vp, _vp, _vp, _z, _z, _i32, _vp, _z, _vp, _vp, _vp, _u32, _vp]),
     "cst_range_decode_gaussian_batch": (_i32, [CoderConfig, _i32, _i32, _vp, _vp, _z, _z, _vp, _vp, _vp, _vp, _z, _z, _i32, _vp, _vp, _u32, _vp]),
     "cst_range_decode_rows_batch": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _vp, _z, _z, _i32, _vp, _vp, _u32, _vp]),

@@ -1321,47 +1321,76 @@ range_decode_laplace_ragged, range_decode_cauchy_ragged = (_named_family(range_d
 # (src/pybindings/stream/model/internals.rs:399-514) -- what an autoregressive model on the GPU puts out.  `probabilities`: a
 # float32 or float64 tensor of shape symbols.shape + (K,), contiguous in the chosen layout; the "fast" quantisation runs in its
 # dtype inside the coder kernels (float32 is NOT widened: the reference's tables differ between the two), symbols are 0 .. K - 1.
+# perfect=True: Categorical(perfect=True), the reference's default -- `perfectly_quantized_probabilities` in f64 (float32 IS widened,
+# as the reference does), one wave per row on the device (csrc/cst_categorical_perfect.hip), K <= 1024.
 # ---------------------------------------------------------------------------------------------------------------------
 
 _PROB_BYTES = {torch.float32: 4, torch.float64: 8}
 
 
-def _categorical_args(matrix_shape, probabilities, precision):
-    if not isinstance(probabilities, torch.Tensor) or not probabilities.is_cuda:
+def _categorical_args(matrix_shape, probabilities, precision, perfect=False):
+    if not isinstance(probabilities, torch.Tensor):
         raise ValueError("probabilities must live in device memory (HBM)")
     if probabilities.dtype not in _PROB_BYTES:
         raise TypeError("probabilities must have dtype torch.float32 or torch.float64")
     if matrix_shape is not None and tuple(probabilities.shape[:-1]) != tuple(matrix_shape):
         raise ValueError("probabilities must have the shape of the symbol matrix plus one axis of K entries")
     k = int(probabilities.shape[-1]) if probabilities.dim() else 0
-    if k < 2 or k >= (1 << precision) - 1:
+    if perfect:
+        if k < 2 or k > min(N.CATEGORICAL_PERFECT_MAX_K, 1 << precision):
+            raise ValueError(f"a Categorical(perfect=True) model on the device needs 2 <= K <= min({N.CATEGORICAL_PERFECT_MAX_K}, 2**precision) entries")
+    elif k < 2 or k >= (1 << precision) - 1:
         raise ValueError("a Categorical model needs 2 <= K < 2**precision - 1 entries")
+    if not probabilities.is_cuda:
+        raise ValueError("probabilities must live in device memory (HBM)")
     return probabilities.contiguous(), _PROB_BYTES[probabilities.dtype], k
 
 
-def categorical_cdf_rows(probabilities, precision: int = 24) -> torch.Tensor:
-    """The fast-quantised cdf rows of `probabilities` [..., K], tabulated on the GPU (cst_categorical_fast_cdf_rows): an int32
-    tensor [..., K + 1] holding uint32 left cumulatives and 2^precision, the rows that cst_*_decode_rows_batch and
-    model.Categorical(perfect=False) use.  Raises the reference's ValueError if a row is not normalizable."""
+def categorical_cdf_rows(probabilities, precision: int = 24, perfect: bool = False, return_moves: bool = False):
+    """The quantised cdf rows of `probabilities` [..., K], tabulated on the GPU: an int32 tensor [..., K + 1] holding uint32 left
+    cumulatives and 2^precision, the rows that cst_*_decode_rows_batch use.  perfect=False: the fast quantisation in the dtype of
+    the input (cst_categorical_fast_cdf_rows), the rows of model.Categorical(perfect=False).  perfect=True: the cross-entropy-
+    optimal one in f64 (cst_categorical_perfect_cdf_rows, one wave per row, K <= 1024), the rows of model.Categorical(perfect=True);
+    return_moves=True then returns (rows, moves), `moves` an int32 tensor [...] of the unit moves of every row's search.
+    Raises the reference's ValueError if a row is not normalizable, and a RuntimeError naming the row if a search was stopped."""
     if probabilities.dim() < 1:
         raise ValueError("probabilities must have at least one axis")
-    probs, nbytes, k = _categorical_args(None, probabilities, precision)
+    if return_moves and not perfect:
+        raise ValueError("return_moves needs perfect=True: the fast quantisation does not search")
+    probs, nbytes, k = _categorical_args(None, probabilities, precision, perfect)
     n_rows = probs.numel() // k
     rows = torch.empty(tuple(probs.shape[:-1]) + (k + 1,), dtype=torch.int32, device=probs.device)
-    bad = torch.empty(max(n_rows, 1), dtype=torch.int32, device=probs.device)
+    bad = torch.zeros(max(n_rows, 1), dtype=torch.int32, device=probs.device)
+    moves = torch.zeros(max(n_rows, 1), dtype=torch.int32, device=probs.device) if perfect else None
     if n_rows:
-        N.check(N.lib().cst_categorical_fast_cdf_rows(int(precision), _ptr(probs), nbytes, n_rows, k, _ptr(rows), _ptr(bad), _stream_ptr()),
-                "cst_categorical_fast_cdf_rows")
-        if bool(bad[:n_rows].any().item()):
+        if perfect:
+            N.check(N.lib().cst_categorical_perfect_cdf_rows(int(precision), _ptr(probs), nbytes, n_rows, k, _ptr(rows), _ptr(bad), _ptr(moves),
+                                                             _stream_ptr()), "cst_categorical_perfect_cdf_rows")
+        else:
+            N.check(N.lib().cst_categorical_fast_cdf_rows(int(precision), _ptr(probs), nbytes, n_rows, k, _ptr(rows), _ptr(bad), _stream_ptr()),
+                    "cst_categorical_fast_cdf_rows")
+        codes = bad[:n_rows]
+        if bool(codes.any().item()):
+            stopped = (codes == 2).nonzero()
+            if stopped.numel():
+                raise RuntimeError(f"Categorical(perfect=True): the search of row {int(stopped[0].item())} did not converge "
+                                   f"within {16 * k + 1024} unit moves")
             raise ValueError("Probability distribution not normalizable (the array of probabilities\n"
                              "might be empty, contain negative values or NaNs, or sum to infinity).")
+    if return_moves:
+        return rows, moves[:n_rows].reshape(tuple(probs.shape[:-1]))
     return rows
 
 
-def _encode_categorical(fn_name, max_words_fn, symbols, probabilities, config, layout, stride, out):
+def _perfect_name(fn_name, perfect):
+    return fn_name.replace("_categorical_batch", "_categorical_perfect_batch") if perfect else fn_name
+
+
+def _encode_categorical(fn_name, max_words_fn, symbols, probabilities, config, layout, stride, out, perfect=False):
+    fn_name = _perfect_name(fn_name, perfect)
     symbols = _require_cuda(symbols, torch.int32, "symbols")
     n_streams, n_per, lay = _layout_shape(symbols, layout)
-    probs, nbytes, k = _categorical_args(symbols.shape, probabilities, config[2])
+    probs, nbytes, k = _categorical_args(symbols.shape, probabilities, config[2], perfect)
     if out is None:
         out = _new_batch(n_streams, stride or max_words_fn(n_per, config), symbols.device, config)
     N.check(getattr(N.lib(), fn_name)(_cfg(*config), _ptr(symbols), _ptr(probs), nbytes, k, n_streams, n_per, lay, _ptr(out.words),
@@ -1371,18 +1400,21 @@ def _encode_categorical(fn_name, max_words_fn, symbols, probabilities, config, l
 
 
 def ans_encode_categorical(symbols, probabilities, config=(32, 64, 24), layout="stream_major", stride: Optional[int] = None,
-                           out: Optional[EncodedBatch] = None) -> EncodedBatch:
-    """One AnsCoder per stream: encode_reverse(symbols[s], Categorical(perfect=False), probabilities[s]) + get_compressed."""
-    return _encode_categorical("cst_ans_encode_categorical_batch", max_words, symbols, probabilities, config, layout, stride, out)
+                           out: Optional[EncodedBatch] = None, perfect: bool = False) -> EncodedBatch:
+    """One AnsCoder per stream: encode_reverse(symbols[s], Categorical(perfect=perfect), probabilities[s]) + get_compressed.
+    perfect=True: every row quantised by one wave (cst_ans_encode_categorical_perfect_batch, K <= 1024)."""
+    return _encode_categorical("cst_ans_encode_categorical_batch", max_words, symbols, probabilities, config, layout, stride, out, perfect)
 
 
 def range_encode_categorical(symbols, probabilities, config=(32, 64, 24), layout="stream_major", stride: Optional[int] = None,
-                             out: Optional[EncodedBatch] = None) -> EncodedBatch:
-    """One RangeEncoder per stream: encode(symbols[s], Categorical(perfect=False), probabilities[s]) + get_compressed."""
-    return _encode_categorical("cst_range_encode_categorical_batch", range_max_words, symbols, probabilities, config, layout, stride, out)
+                             out: Optional[EncodedBatch] = None, perfect: bool = False) -> EncodedBatch:
+    """One RangeEncoder per stream: encode(symbols[s], Categorical(perfect=perfect), probabilities[s]) + get_compressed."""
+    return _encode_categorical("cst_range_encode_categorical_batch", range_max_words, symbols, probabilities, config, layout, stride, out,
+                               perfect)
 
 
-def _decode_categorical(fn_name, ans, encoded, probabilities, layout, offsets, out, config):
+def _decode_categorical(fn_name, ans, encoded, probabilities, layout, offsets, out, config, perfect=False):
+    fn_name = _perfect_name(fn_name, perfect)
     if isinstance(encoded, EncodedBatch):
         words, n_words, config = encoded.words, encoded.n_words, config or encoded.config
         stride = words.shape[1]
@@ -1395,7 +1427,7 @@ def _decode_categorical(fn_name, ans, encoded, probabilities, layout, offsets, o
     n_streams, n_per, lay = _layout_shape(probabilities[..., 0], layout)
     if n_streams != n_words.numel():
         raise ValueError("probabilities do not match the number of streams")
-    probs, nbytes, k = _categorical_args(probabilities.shape[:2], probabilities, config[2])
+    probs, nbytes, k = _categorical_args(probabilities.shape[:2], probabilities, config[2], perfect)
     dev = words.device
     if out is None:
         out = torch.empty(tuple(probs.shape[:2]), dtype=torch.int32, device=dev)
@@ -1408,16 +1440,16 @@ def _decode_categorical(fn_name, ans, encoded, probabilities, layout, offsets, o
     return out, status
 
 
-def ans_decode_categorical(encoded, probabilities, layout="stream_major", offsets=None, out=None, config=None):
-    """One AnsCoder per stream: AnsCoder(words[s]).decode(Categorical(perfect=False), probabilities[s]).  `encoded`: an
+def ans_decode_categorical(encoded, probabilities, layout="stream_major", offsets=None, out=None, config=None, perfect: bool = False):
+    """One AnsCoder per stream: AnsCoder(words[s]).decode(Categorical(perfect=perfect), probabilities[s]).  `encoded`: an
     EncodedBatch, or (packed, n_words) with offsets= (compact()).  Returns (symbols, status)."""
-    return _decode_categorical("cst_ans_decode_categorical_batch", True, encoded, probabilities, layout, offsets, out, config)
+    return _decode_categorical("cst_ans_decode_categorical_batch", True, encoded, probabilities, layout, offsets, out, config, perfect)
 
 
-def range_decode_categorical(encoded, probabilities, layout="stream_major", offsets=None, out=None, config=None):
-    """One RangeDecoder per stream: RangeDecoder(words[s]).decode(Categorical(perfect=False), probabilities[s]).  Returns
+def range_decode_categorical(encoded, probabilities, layout="stream_major", offsets=None, out=None, config=None, perfect: bool = False):
+    """One RangeDecoder per stream: RangeDecoder(words[s]).decode(Categorical(perfect=perfect), probabilities[s]).  Returns
     (symbols, status)."""
-    return _decode_categorical("cst_range_decode_categorical_batch", False, encoded, probabilities, layout, offsets, out, config)
+    return _decode_categorical("cst_range_decode_categorical_batch", False, encoded, probabilities, layout, offsets, out, config, perfect)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

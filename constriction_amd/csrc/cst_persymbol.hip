@@ -23,6 +23,7 @@
 #include "cst_math.hpp"
 #include "cst_family_policy.hpp"
 #include "cst_categorical.hpp"
+#include "cst_categorical_perfect.hpp"
 
 namespace cst {
 
@@ -3285,6 +3286,100 @@ static cst_status decode_categorical(cst_coder_config cfg, const uint32_t* d_wor
     return note_kernel(kCatLaneNames[KIND == kRange], CST_OK);
 }
 
+// ---- Categorical(perfect=True): the quantiser is categorical_perfect_kernel (cst_categorical_perfect.hip); host glue only ----
+
+static constexpr const char* kCatPerfectEncodeNames[2] = {"ans_encode_categorical_perfect_two_pass", "range_encode_categorical_perfect_two_pass"};
+static constexpr const char* kCatPerfectRowsName = "decode_categorical_perfect_by_rows";
+
+static cst_status check_categorical_perfect_args(cst_coder_config cfg, cst_layout layout, const void* d_symbols, const void* d_probs, int32_t prob_bytes,
+                                                 int32_t n_symbols, const void* d_words, const void* d_n_words, const void* d_status,
+                                                 const void* raw_state, uint32_t flags) {
+    if (!d_symbols || !d_probs || !d_words || !d_n_words || !d_status) return CST_ERR_INVALID_ARGUMENT;
+    if (prob_bytes != 4 && prob_bytes != 8) return CST_ERR_INVALID_ARGUMENT;
+    if ((flags & CST_FLAG_RAW_STATE) && !raw_state) return CST_ERR_INVALID_ARGUMENT;
+    if (cst_status st = check_common(cfg, layout)) return st;
+    // perfectly_quantized_probabilities: at least two symbols and a unit of weight for each; the kernel's slots
+    if (n_symbols < 2 || n_symbols > kCatPerfectMaxK || (uint64_t)n_symbols > ((uint64_t)1 << cfg.precision)) return CST_ERR_MODEL;
+    return CST_OK;
+}
+
+template <int KIND>
+static cst_status encode_categorical_perfect(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes,
+                                             int32_t n_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout, uint32_t* d_words,
+                                             size_t stride_words, uint32_t* d_n_words, uint64_t* d_state, cst_range_state* d_rstate,
+                                             int32_t* d_status, uint32_t flags, hipStream_t hs) {
+    if (cst_status st = check_categorical_perfect_args(cfg, layout, d_symbols, d_probs, prob_bytes, n_symbols, d_words, d_n_words, d_status,
+                                                       KIND == kAns ? (const void*)d_state : (const void*)d_rstate, flags)) return st;
+    if (n_streams * n_per_stream > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
+    note_kernel(kCatPerfectEncodeNames[KIND == kRange], CST_OK);
+    return encode_two_pass<KIND>(cfg, n_streams, n_per_stream, layout, d_words, stride_words, d_n_words, d_state, d_rstate, d_status, flags, hs,
+                                 [&](EncEntry* out, size_t) {
+        CatPerfectArgs r{};
+        r.probs = d_probs; r.prob_bytes = prob_bytes; r.K = (uint32_t)n_symbols; r.P = cfg.precision; r.layout = layout;
+        r.n_streams = n_streams; r.N = n_per_stream; r.t0 = 0; r.count = n_per_stream;
+        r.symbols = d_symbols; r.entries = out;
+        (void)launch_categorical_perfect(r, hs);                         // (its launch error is read by encode_two_pass)
+    });
+}
+
+// the route of decode_categorical_by_rows with the perfect tabulator: rows in pieces of at most 64 MiB, then a lookup per symbol
+template <int KIND>
+static cst_status decode_categorical_perfect(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_offsets, size_t stride_words,
+                                             size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                             int32_t n_symbols, int32_t* d_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                             uint64_t* d_state, uint32_t* d_n_words_out, cst_range_state* d_rstate, int32_t* d_status,
+                                             uint32_t flags, hipStream_t hs) {
+    if (cst_status st = check_categorical_perfect_args(cfg, layout, d_symbols, d_probs, prob_bytes, n_symbols, d_words, d_n_words, d_status,
+                                                       KIND == kAns ? (const void*)d_state : (const void*)d_rstate, flags)) return st;
+    PerSymbolDecodeArgs a{};
+    if (cst_status st = fill_decode_args(a, cfg, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_symbols, n_streams, n_per_stream,
+                                         layout, 0, n_symbols, d_status, flags)) return st;
+    a.state = d_state; a.n_words_out = d_n_words_out; a.rstate = d_rstate;
+    if (n_streams == 0) return CST_OK;
+    if (n_streams > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
+    const size_t N = n_per_stream, K = (size_t)n_symbols;
+    // Every batch comes this way, not only the few-stream ones: decode_rows_wave_kernel's 256-entry rows (K < 256) are taken
+    // while the 64 positions per stream that its pieces are made of fit the 64 MiB, the K + 1 word rows of the piece decoder
+    // otherwise (and for N == 0, where one empty piece initialises and finishes the decoders).
+    const size_t budget = (size_t)16 << 20;
+    const bool packed = K < (size_t)kRowEntries && N > 0 && n_streams * 64 * (size_t)kRowEntries <= budget;
+    const size_t pitch = packed ? (size_t)kRowEntries : K + 1;
+    size_t piece = budget / (n_streams * pitch);
+    if (packed) piece &= ~(size_t)63;
+    else if (piece == 0) piece = 1;
+    if (piece > N) piece = N;
+    if (piece == 0) piece = 1;
+    uint32_t* rows = nullptr;
+    DecodeResume* resume = nullptr;
+    CST_HIP_TRY(scratch_alloc((void**)&rows, n_streams * piece * pitch * sizeof(uint32_t), hs));
+    hipError_t err = scratch_alloc((void**)&resume, n_streams * sizeof(DecodeResume), hs);
+    cst_status rc = CST_OK;
+    for (size_t t0 = 0; (t0 < N || (N == 0 && t0 == 0)) && err == hipSuccess && rc == CST_OK; t0 += piece) {
+        const size_t count = N - t0 < piece ? N - t0 : piece;
+        CatPerfectArgs r{};
+        r.probs = d_probs; r.prob_bytes = prob_bytes; r.K = (uint32_t)K; r.P = cfg.precision; r.layout = layout;
+        r.n_streams = n_streams; r.N = N; r.t0 = t0; r.count = count; r.rows = rows; r.pitch = pitch;
+        rc = launch_categorical_perfect(r, hs);
+        if (rc != CST_OK) break;
+        const int32_t first = t0 == 0, last = t0 + count == N;
+        if (packed) {
+            RowsDecodeArgs ra{a, reinterpret_cast<const uint4*>(rows), t0, count, resume, first, last};
+            if (cfg.word_bits == 32) hipLaunchKernelGGL((decode_rows_wave_kernel<32, 64, KIND>), dim3((unsigned)n_streams), dim3(kWave), 0, hs, ra);
+            else hipLaunchKernelGGL((decode_rows_wave_kernel<16, 32, KIND>), dim3((unsigned)n_streams), dim3(kWave), 0, hs, ra);
+        } else {
+            CatPieceArgs ra{a, rows, t0, count, resume, first, last};
+            const dim3 grid((unsigned)((n_streams * kWave + kBlock - 1) / kBlock));
+            if (cfg.word_bits == 32) hipLaunchKernelGGL((decode_rows_piece_wave_kernel<32, 64, KIND>), grid, dim3(kBlock), 0, hs, ra);
+            else hipLaunchKernelGGL((decode_rows_piece_wave_kernel<16, 32, KIND>), grid, dim3(kBlock), 0, hs, ra);
+        }
+        err = hipGetLastError();
+    }
+    if (resume) (void)hipFreeAsync(resume, hs);
+    (void)hipFreeAsync(rows, hs);
+    CST_HIP_TRY(err);
+    return note_kernel(kCatPerfectRowsName, rc);
+}
+
 } // namespace cst
 
 extern "C" {
@@ -3338,6 +3433,38 @@ cst_status cst_range_decode_categorical_batch(cst_coder_config cfg, const uint32
                                               int32_t* d_status, uint32_t flags, void* stream) {
     return decode_categorical<kRange>(cfg, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes, n_symbols, d_symbols, n_streams,
                                       n_per_stream, layout, nullptr, nullptr, d_rstate, d_status, flags, (hipStream_t)stream);
+}
+
+cst_status cst_ans_encode_categorical_perfect_batch(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes,
+                                                    int32_t n_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout, uint32_t* d_words,
+                                                    size_t stride_words, uint32_t* d_n_words, uint64_t* d_state, int32_t* d_status, uint32_t flags,
+                                                    void* stream) {
+    return encode_categorical_perfect<kAns>(cfg, d_symbols, d_probs, prob_bytes, n_symbols, n_streams, n_per_stream, layout, d_words, stride_words,
+                                            d_n_words, d_state, nullptr, d_status, flags, (hipStream_t)stream);
+}
+
+cst_status cst_range_encode_categorical_perfect_batch(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes,
+                                                      int32_t n_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout, uint32_t* d_words,
+                                                      size_t stride_words, uint32_t* d_n_words, cst_range_state* d_rstate, int32_t* d_status,
+                                                      uint32_t flags, void* stream) {
+    return encode_categorical_perfect<kRange>(cfg, d_symbols, d_probs, prob_bytes, n_symbols, n_streams, n_per_stream, layout, d_words, stride_words,
+                                              d_n_words, nullptr, d_rstate, d_status, flags, (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_categorical_perfect_batch(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_offsets, size_t stride_words,
+                                                    size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                                    int32_t n_symbols, int32_t* d_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                                    uint64_t* d_state, uint32_t* d_n_words_out, int32_t* d_status, uint32_t flags, void* stream) {
+    return decode_categorical_perfect<kAns>(cfg, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes, n_symbols, d_symbols,
+                                            n_streams, n_per_stream, layout, d_state, d_n_words_out, nullptr, d_status, flags, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_categorical_perfect_batch(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_offsets, size_t stride_words,
+                                                      size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                                      int32_t n_symbols, int32_t* d_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                                      cst_range_state* d_rstate, int32_t* d_status, uint32_t flags, void* stream) {
+    return decode_categorical_perfect<kRange>(cfg, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes, n_symbols, d_symbols,
+                                              n_streams, n_per_stream, layout, nullptr, nullptr, d_rstate, d_status, flags, (hipStream_t)stream);
 }
 
 } // extern "C"

@@ -57,7 +57,7 @@ def raise_for_status(status: int):
     raise RuntimeError(f"stream status {status}")
 
 
-def model_args(model, params, n_expected=None, families=False):
+def model_args(model, params, n_expected=None, families=False, device_perfect=False):
     """Classifies an (model, *params) call.  Returns one of
        ("table", device_model)                         concrete model, iid symbols
        ("gaussian", lo, hi, means, stds)               QuantizedGaussian family with per-symbol parameters
@@ -68,8 +68,14 @@ def model_args(model, params, n_expected=None, families=False):
                                                        get these two as "rows"
        ("categorical", matrix)                         Categorical(perfect=False) / Categorical(lazy=True) / Bernoulli(perfect=False)
                                                        with per-symbol probabilities, as the checked float32 / float64 matrix
-                                                       [symbols][K] (families=True: cst_*_categorical_batch); perfect=True
-                                                       and the other coders get "rows"
+                                                       [symbols][K] (families=True: cst_*_categorical_batch); the other
+                                                       coders get "rows"
+       ("categorical_perfect", matrix)                 Categorical(perfect=True) / Bernoulli(perfect=True) with per-symbol
+                                                       probabilities and K <= 1024, as the checked matrix, for the coders that
+                                                       ask for it on top of families=True (device_perfect=True: the stack and
+                                                       queue coders; cst_*_categorical_perfect_batch quantise it on the
+                                                       device); more symbols and every other caller get "rows" from the host
+                                                       quantiser
     """
     if not isinstance(model, M.Model):
         raise TypeError("model must be a constriction_amd.stream.model.Model")
@@ -90,6 +96,10 @@ def model_args(model, params, n_expected=None, families=False):
         return ("gaussian", model.min_symbol, model.max_symbol, means, stds)
     if families and isinstance(model, (M.Categorical, M.Bernoulli)) and not model.perfect:
         return ("categorical", model.family_matrix(params))
+    if families and device_perfect and isinstance(model, (M.Categorical, M.Bernoulli)) and model.perfect:
+        m = model.family_matrix(params, device_limit=N.CATEGORICAL_PERFECT_MAX_K)
+        if m is not None:
+            return ("categorical_perfect", m)
     if families and isinstance(model, M._LeakyFamily):
         a, b = model.family_params(params)
         return ("family", model.min_symbol, model.max_symbol, a, b, model._family)

@@ -70,19 +70,21 @@ def fast_quantized_cdf(probabilities: np.ndarray, precision: int = PRECISION) ->
     return cdf
 
 
-def check_probability_matrix(m: np.ndarray, precision: int = PRECISION) -> np.ndarray:
-    """What `fast_quantized_cdf` refuses, for every row of a probability matrix at once: entries that are not finite or
-    negative, and a sequential row sum (in the matrix's dtype) that is not a positive normal number -- the reference's
-    ValueError, raised before anything is uploaded."""
+def check_probability_matrix(m: np.ndarray, precision: int = PRECISION, perfect: bool = False) -> np.ndarray:
+    """What the quantisers refuse, for every row of a probability matrix at once -- the reference's ValueError, raised before
+    anything is uploaded.  `fast_quantized_cdf`: entries that are not finite or negative, and a sequential row sum (in the
+    matrix's dtype) that is not a positive normal number.  perfect=True, `perfectly_quantized_probabilities`: the same with the
+    entries widened to f64 first (`F: Into<f64>`), for 2 <= n <= 2^precision symbols."""
     err = ValueError("Probability distribution not normalizable (the array of probabilities\n"
                      "might be empty, contain negative values or NaNs, or sum to infinity).")
     n = m.shape[1]
-    if n < 2 or n >= (1 << precision) - 1:
+    if n < 2 or (n > (1 << precision) if perfect else n >= (1 << precision) - 1):
         raise err
     if len(m):
+        wide = m.astype(np.float64) if perfect else m
         with np.errstate(over="ignore", invalid="ignore"):
-            norm = np.cumsum(m, axis=1, dtype=m.dtype)[:, -1]          # sequential accumulation, like Iterator::sum
-        if not (np.isfinite(m).all() and (m >= 0).all() and np.isfinite(norm).all() and (norm >= np.finfo(m.dtype).tiny).all()):
+            norm = np.cumsum(wide, axis=1, dtype=wide.dtype)[:, -1]    # sequential accumulation, like Iterator::sum
+        if not (np.isfinite(wide).all() and (wide >= 0).all() and np.isfinite(norm).all() and (norm >= np.finfo(wide.dtype).tiny).all()):
             raise err
     return m
 
@@ -230,9 +232,13 @@ class Categorical(Model):
             raise TypeError("probabilities must have dtype float32 or float64")
         return np.ascontiguousarray(m)
 
-    def family_matrix(self, params) -> np.ndarray:
-        """the checked probability matrix of a call with parameters (fast quantisation: the coder kernels quantise it)"""
-        return check_probability_matrix(self._matrix(params))
+    def family_matrix(self, params, device_limit=None):
+        """the checked probability matrix of a call with parameters (the coder kernels quantise it); None for a perfect model over
+        more than `device_limit` symbols (the device quantiser's slots: the host's family_rows then)"""
+        m = self._matrix(params)
+        if self.perfect and device_limit is not None and m.shape[1] > device_limit:
+            return None
+        return check_probability_matrix(m, perfect=self.perfect)
 
     @staticmethod
     def cdf_rows(prob_matrix) -> np.ndarray:
@@ -278,13 +284,13 @@ class Bernoulli(Model):
             self._dev = batched.Model.from_cdf(self.cdf, 0, PRECISION)
         return self._dev
 
-    def family_matrix(self, params) -> np.ndarray:
-        """the f64 probability matrix [1 - p, p] of a call with parameters (fast quantisation)"""
+    def family_matrix(self, params, device_limit=None) -> np.ndarray:
+        """the f64 probability matrix [1 - p, p] of a call with parameters (the coder kernels quantise it)"""
         if len(params) != 1:
             raise ValueError("Wrong number of model parameters: Bernoulli expects one array `p`.")
         ps = _as_float_params(params[0], "p")
         try:
-            return check_probability_matrix(np.stack([1.0 - ps, ps], axis=1))
+            return check_probability_matrix(np.stack([1.0 - ps, ps], axis=1), perfect=self.perfect)
         except ValueError:
             raise ValueError("`p` must be >= 0.0 and <= 1.0.") from None
 

@@ -100,9 +100,9 @@ class RangeEncoder:
             raise ValueError("To encode a single symbol, use a concrete model, i.e., pass the\n"
                              "model parameters directly to the constructor of the model and not to the\n"
                              "`encode` method of the entropy coder.")
-        kind = S.model_args(model, optional_model_params, families=True)
+        kind = S.model_args(model, optional_model_params, families=True, device_perfect=True)
         n = len(sym)
-        if kind[0] in ("gaussian", "family") and len(kind[3]) != n or kind[0] in ("rows", "categorical") and len(kind[1]) != n:
+        if kind[0] in ("gaussian", "family") and len(kind[3]) != n or kind[0] in ("rows", "categorical", "categorical_perfect") and len(kind[1]) != n:
             raise ValueError("`symbols` argument has wrong length.")
         if n == 0:
             return
@@ -128,12 +128,13 @@ class RangeEncoder:
             st = L.cst_range_encode_family_batch(S.cfg(), fam, lo, hi, S.ptr(d_sym), S.ptr(d_a), S.ptr(d_b), 1, n,
                                                  N.LAYOUT_STREAM_MAJOR, S.ptr(d_words), cap, d_n, d_rs,
                                                  d_status, N.FLAG_RAW_STATE, sp)
-        elif kind[0] == "categorical":
+        elif kind[0] in ("categorical", "categorical_perfect"):
             probs = kind[1]
             d_sym, d_probs = S.dev(sym), S.dev(probs)
-            st = L.cst_range_encode_categorical_batch(S.cfg(), S.ptr(d_sym), S.ptr(d_probs), probs.itemsize, probs.shape[1], 1, n,
-                                                    N.LAYOUT_STREAM_MAJOR, S.ptr(d_words), cap, d_n, d_rs,
-                                                    d_status, N.FLAG_RAW_STATE, sp)
+            fn = L.cst_range_encode_categorical_perfect_batch if kind[0] == "categorical_perfect" else L.cst_range_encode_categorical_batch
+            st = fn(S.cfg(), S.ptr(d_sym), S.ptr(d_probs), probs.itemsize, probs.shape[1], 1, n,
+                    N.LAYOUT_STREAM_MAJOR, S.ptr(d_words), cap, d_n, d_rs,
+                    d_status, N.FLAG_RAW_STATE, sp)
         else:
             rows = kind[1]
             idx = sym.astype(np.int64) - kind[2]
@@ -208,7 +209,7 @@ class RangeDecoder:
             amt = int(params[0])
             kind = S.model_args(model, ())
         else:
-            kind = S.model_args(model, params, families=True)
+            kind = S.model_args(model, params, families=True, device_perfect=True)
             amt = len(kind[3]) if kind[0] in ("gaussian", "family") else len(kind[1])
         if amt == 0:
             return np.zeros(0, dtype=np.int32)
@@ -236,12 +237,13 @@ class RangeDecoder:
             st = L.cst_range_decode_family_batch(S.cfg(), fam, lo, hi, S.ptr(d_words), None, max(nwin, 1), d_words.numel(), d_n, S.ptr(d_a),
                                                  S.ptr(d_b), S.ptr(d_sym), 1, amt, N.LAYOUT_STREAM_MAJOR, d_rs,
                                                  d_status, N.FLAG_RAW_STATE, sp)
-        elif kind[0] == "categorical":
+        elif kind[0] in ("categorical", "categorical_perfect"):
             probs = kind[1]
             d_probs = S.dev(probs)
-            st = L.cst_range_decode_categorical_batch(S.cfg(), S.ptr(d_words), None, max(nwin, 1), d_words.numel(), d_n, S.ptr(d_probs),
-                                                      probs.itemsize, probs.shape[1], S.ptr(d_sym), 1, amt, N.LAYOUT_STREAM_MAJOR, d_rs,
-                                                      d_status, N.FLAG_RAW_STATE, sp)
+            fn = L.cst_range_decode_categorical_perfect_batch if kind[0] == "categorical_perfect" else L.cst_range_decode_categorical_batch
+            st = fn(S.cfg(), S.ptr(d_words), None, max(nwin, 1), d_words.numel(), d_n, S.ptr(d_probs),
+                    probs.itemsize, probs.shape[1], S.ptr(d_sym), 1, amt, N.LAYOUT_STREAM_MAJOR, d_rs,
+                    d_status, N.FLAG_RAW_STATE, sp)
         else:
             rows = kind[1]
             d_rows = S.dev(rows.view(np.int32))

@@ -716,6 +716,40 @@ cst_status cst_categorical_fast_cdf_rows(int32_t precision, const void *d_probs,
 cst_status cst_categorical_fast_cdf_host(int32_t precision, const void *h_probs, int32_t prob_bytes, size_t n_rows, int32_t n_symbols,
                                          uint32_t *h_rows, int32_t *h_bad);
 
+/* Categorical(perfect=True) / Bernoulli(perfect=True) with per-symbol probability vectors, quantised ON THE DEVICE: one wave runs
+ * `perfectly_quantized_probabilities` (src/stream/model/categorical.rs:56-177; f32 rows are widened to f64 first) for one row --
+ * the words of cst_categorical_perfect_cdf, row by row.  2 <= n_symbols <= CST_CATEGORICAL_PERFECT_MAX_K.
+ *
+ * cst_categorical_perfect_cdf_rows: the rows in the format of cst_categorical_fast_cdf_rows (1 <= precision <= 31).  d_bad[r]
+ * (optional): 0 a good row, 1 a bad one (the host function's CST_ERR_MODEL: a sum that is not a positive normal number, a negative
+ * or NaN entry, a share beyond the weight that is left), 2 a row whose search had not ended after 16 * n_symbols + 1024 unit
+ * moves (a safety stop; no input is known to come near it).  Rows with a nonzero code are written as 0xffffffff followed by
+ * 2^precision.  d_moves[r] (optional): the unit moves of the row's search.  cst_categorical_perfect_cdf_host is the same
+ * formulation (ranks instead of a sorted vector, the same stop) on the CPU over host buffers.
+ *
+ * cst_{ans,range}_{encode,decode}_categorical_perfect_batch: the argument lists, layouts, slabs, offsets, words_capacity and
+ * CST_FLAG_RAW_STATE of cst_*_categorical_batch.  The encoders quantise a row and keep only the entry of its symbol; the decoders
+ * tabulate rows in pieces of at most 64 MiB and look them up with one wave per stream.  A row with a nonzero code and a symbol
+ * outside [0, n_symbols) yield CST_STREAM_IMPOSSIBLE_SYMBOL for their stream only.
+ * Before the device is touched: NULL pointers and prob_bytes outside {4, 8} return CST_ERR_INVALID_ARGUMENT; n_symbols < 2,
+ * n_symbols > CST_CATEGORICAL_PERFECT_MAX_K and n_symbols > 2^precision return CST_ERR_MODEL. */
+#define CST_CATEGORICAL_PERFECT_MAX_K 1024
+cst_status cst_categorical_perfect_cdf_rows(int32_t precision, const void *d_probs, int32_t prob_bytes, size_t n_rows, int32_t n_symbols,
+                                            uint32_t *d_rows, int32_t *d_bad, uint32_t *d_moves, void *stream);
+cst_status cst_categorical_perfect_cdf_host(int32_t precision, const void *h_probs, int32_t prob_bytes, size_t n_rows, int32_t n_symbols,
+                                            uint32_t *h_rows, int32_t *h_bad, uint32_t *h_moves);
+
+cst_status cst_ans_encode_categorical_perfect_batch(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs, int32_t prob_bytes,
+                                                    int32_t n_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                                    uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                                    uint64_t *d_state, int32_t *d_status, uint32_t flags, void *stream);
+
+cst_status cst_ans_decode_categorical_perfect_batch(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words,
+                                                    size_t words_capacity, const uint32_t *d_n_words, const void *d_probs, int32_t prob_bytes,
+                                                    int32_t n_symbols, int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
+                                                    cst_layout layout, uint64_t *d_state, uint32_t *d_n_words_out,
+                                                    int32_t *d_status, uint32_t flags, void *stream);
+
 /* Per-symbol models given explicitly (any model family with per-symbol parameters, e.g.
  * Categorical(perfect=False) with a probability matrix, src/pybindings/stream/model/internals.rs:188-249):
  *   encode: d_left / d_prob hold EncoderModel::left_cumulative_and_probability of every symbol
@@ -839,6 +873,18 @@ cst_status cst_range_decode_categorical_batch(cst_coder_config cfg, const uint32
                                               int32_t n_symbols, int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
                                               cst_layout layout, cst_range_state *d_rstate, int32_t *d_status,
                                               uint32_t flags, void *stream);
+
+/* ... and with the perfect quantisation (see cst_ans_encode_categorical_perfect_batch) */
+cst_status cst_range_encode_categorical_perfect_batch(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs, int32_t prob_bytes,
+                                                      int32_t n_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                                      uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                                      cst_range_state *d_rstate, int32_t *d_status, uint32_t flags, void *stream);
+
+cst_status cst_range_decode_categorical_perfect_batch(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words,
+                                                      size_t words_capacity, const uint32_t *d_n_words, const void *d_probs, int32_t prob_bytes,
+                                                      int32_t n_symbols, int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
+                                                      cst_layout layout, cst_range_state *d_rstate, int32_t *d_status,
+                                                      uint32_t flags, void *stream);
 
 /* ABI 5: jump points for the per-symbol Gaussian calls of the RANGE coder (RangeEncoder::pos / RangeDecoder::seek, src/stream/queue.rs:172-196,
  * 900-926), as cst_ans_{encode,decode}_gaussian_batch_ckpt are for ANS: the fused encoder notes (words emitted including held-back ones,

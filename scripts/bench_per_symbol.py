@@ -4,6 +4,7 @@ n_streams x n_per symbols, every symbol with its own two f64 parameters; both co
 
     bench_per_symbol.py [n_streams [n_per]] [--family gaussian laplace cauchy] [--support LO HI] [--rows] [--reps N] [--rounds K]
     bench_per_symbol.py [n_streams [n_per]] --categorical K [--f64] [--reps N] [--rounds K]
+    bench_per_symbol.py [n_streams [n_per]] --categorical K --perfect [--f64] [--reps N] [--rounds K]
 
 --family: one or more of gaussian (mean, std), laplace (mean, scale), cauchy (loc, scale); several families are timed in the
           same process on the same parameter matrices, alternating, `--rounds` times over: compare medians, look at the spread.
@@ -15,7 +16,11 @@ n_streams x n_per symbols, every symbol with its own two f64 parameters; both co
           (default 4096 x 256; at K = 256 that is 1 GiB of float32): encode and decode of both coders through the categorical calls
           (the decoder by both of its routes), the probability bytes per second of each against the 8 TB/s of HBM, and the same
           batch through the tabulated device route -- categorical_cdf_rows + cst_*_encode_cp_batch / cst_*_decode_rows_batch --
-          in the same run."""
+          in the same run.
+--perfect: with --categorical K (K <= 1024), Categorical(perfect=True) instead: the rows kernel alone (rows per second, the maximum
+          and the mean of its move counts), the four coder calls of `*_categorical(..., perfect=True)`, and -- in the same run --
+          the host route they replace, Categorical(perfect=True).family_rows on a slice of at most 4096 rows, scaled to the
+          batch and labelled as scaled."""
 import argparse
 import statistics
 import sys
@@ -30,6 +35,7 @@ ap.add_argument("n_streams", nargs="?", type=int, default=None)
 ap.add_argument("n_per", nargs="?", type=int, default=None)
 ap.add_argument("--categorical", type=int, default=0, metavar="K")
 ap.add_argument("--f64", action="store_true")
+ap.add_argument("--perfect", action="store_true")
 ap.add_argument("--family", nargs="+", choices=["gaussian", "laplace", "cauchy"], default=["gaussian"])
 ap.add_argument("--support", nargs=2, type=int, default=[-127, 127], metavar=("LO", "HI"))
 ap.add_argument("--rows", action="store_true")
@@ -119,6 +125,55 @@ def categorical_bench(K):
               f"decode {d:9.3f} ms ({prob_bytes / d / 1e9:6.3f} TB/s, {100 * prob_bytes / d / 1e9 / 8:5.1f} %)  roundtrip_ok={ok[i]}")
 
 
+def categorical_perfect_bench(K):
+    import time
+    import numpy as np
+    from constriction_amd.stream import model as M
+    dtype = torch.float64 if args.f64 else torch.float32
+    g = torch.Generator(device="cuda").manual_seed(1)
+    probs = torch.softmax(torch.randn((n_streams, n_per, K), generator=g, device="cuda", dtype=torch.float32) * 3.0, dim=-1).to(dtype)
+    sym = torch.randint(0, K, (n_streams, n_per), generator=g, device="cuda", dtype=torch.int32)
+    cfg, n_rows = (32, 64, 24), n_streams * n_per
+    rows_ms, moves = [], None
+    _, moves = B.categorical_cdf_rows(probs, cfg[2], perfect=True, return_moves=True)          # (warm-up; raises for a stopped row)
+    for _ in range(args.rounds):
+        t, _ = timed(lambda: B.categorical_cdf_rows(probs, cfg[2], perfect=True), args.reps)
+        rows_ms.append(t)
+    ok, times = {}, {}
+    for coder in ("ans", "range"):
+        enc_f, dec_f = getattr(B, f"{coder}_encode_categorical"), getattr(B, f"{coder}_decode_categorical")
+        enc = enc_f(sym, probs, cfg, perfect=True)
+        dec, st = dec_f(enc, probs, perfect=True)
+        torch.cuda.synchronize()
+        ok[coder] = bool(torch.equal(dec, sym)) and int(st.abs().sum()) == 0
+        times[coder] = ([], [])
+        for _ in range(args.rounds):
+            e, enc = timed(lambda: enc_f(sym, probs, cfg, perfect=True), args.reps)
+            d, _ = timed(lambda: dec_f(enc, probs, perfect=True), args.reps)
+            times[coder][0].append(e); times[coder][1].append(d)
+    # the host route: one sequential search per row in the library's host code, behind a Python loop
+    n_host = min(n_rows, 4096)
+    host_probs = probs.reshape(-1, K)[:n_host].cpu().numpy()
+    t0 = time.perf_counter()
+    host_rows = M.Categorical(perfect=True).family_rows((host_probs,))
+    host_s = time.perf_counter() - t0
+    same = np.array_equal(host_rows, B.categorical_cdf_rows(probs.reshape(-1, K)[:n_host], cfg[2], perfect=True).cpu().numpy().view(np.uint32))
+    r = statistics.median(rows_ms)
+    print(f"per-symbol Categorical(perfect=True), {n_streams} x {n_per} symbols, K = {K}, {str(dtype).split('.')[-1]}")
+    print(f"rows kernel              : {r:9.3f} ms for {n_rows} rows ({n_rows / r / 1e3:8.3f} M rows/s)  moves: max {int(moves.max())}, "
+          f"mean {float(moves.double().mean()):.2f} (cap {16 * K + 1024})")
+    for coder in ("ans", "range"):
+        e, d = statistics.median(times[coder][0]), statistics.median(times[coder][1])
+        print(f"{coder:5s} device quantiser   : encode {e:9.3f} ms  decode {d:9.3f} ms  roundtrip_ok={ok[coder]}")
+    print(f"host route (family_rows) : {host_s * 1e3:9.3f} ms for {n_host} rows = {host_s * 1e3 * n_rows / n_host:11.3f} ms SCALED to {n_rows} rows "
+          f"({n_host / host_s / 1e6:8.5f} M rows/s; rows only, before any upload or coding)  same_rows={same}")
+
+
+if args.perfect and not args.categorical:
+    ap.error("--perfect needs --categorical K")
+if args.categorical and args.perfect:
+    categorical_perfect_bench(args.categorical)
+    sys.exit(0)
 if args.categorical:
     categorical_bench(args.categorical)
     sys.exit(0)
