@@ -726,6 +726,77 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    /// The range coder with ONE SHARED TABLE for streams of different lengths: cst_ans_{encode,decode}_ragged / cst_ans_count_until for the
+    /// reference's queue -- one RangeEncoder / RangeDecoder per document (src/stream/queue.rs), the symbols decoded in the order they were
+    /// encoded, so that a terminator is simply written last.  Symbols, slabs, d_word_offsets / stride_words / words_capacity / d_n_words
+    /// and d_order (NULL = the identity; an entry that is no stream index idles its slot) are those of the ragged calls above.
+    ///   - Words, count and status of every stream are those of the reference RangeEncoder / RangeDecoder for that stream alone, bit for
+    ///     bit -- and those of cst_range_{encode,decode}_batch.
+    ///   - A slab of min(n, ceil(n P / W)) + 2 words always suffices for a stream of n symbols (checked against the CPU oracle for
+    ///     n = 0 .. 70, 255 .. 257 and 700 at about P bits per symbol on six presets: the oracle stays one word below the bound).  A slab
+    ///     whose offsets run backwards is a slab of no words: CST_STREAM_CAPACITY, nothing written.
+    ///   - A stream of length 0 yields 0 words and CST_STREAM_OK.
+    ///   - An impossible symbol flags its stream only: CST_STREAM_IMPOSSIBLE_SYMBOL, n_words = 0.
+    ///   - Corrupt counts or offsets on the decoder side give CST_STREAM_INVALID_DATA and nothing outside words_capacity is read (the
+    ///     bounds check of cst_range_decode_batch).
+    ///   - cst_range_count_until: every stream is decoded until `eof_symbol` appears; d_lengths[s] = symbols decoded, terminator included.
+    ///     A range decoder that has run out of words keeps decoding (the reference shifts in zeros), so `max_symbols` is the only stop
+    ///     for a stream without a terminator: it reports CST_STREAM_CAPACITY and max_symbols.  An exclusive prefix sum of d_lengths is the
+    ///     d_sym_offsets of cst_range_decode_ragged.
+    ///   - CST_ERR_INVALID_ARGUMENT, before the device is touched: a NULL model or a NULL sym_offsets / words (encoder) / n_words /
+    ///     lengths / status pointer, an unsupported configuration, cfg.precision != the model's (as cst_range_encode_batch refuses it), a
+    ///     per-stream-table model, d_word_offsets == NULL with stride_words == 0, n_streams > 2^32 - 1 with an order.
+    ///   - n_streams == 0: CST_OK, nothing is launched.
+    /// Presets (32,64) and (16,32), every precision cst_range_encode_batch takes.  No jump points (RangeEncoder::pos / RangeDecoder::seek)
+    /// for these batches yet.
+    pub fn cst_range_encode_ragged(
+        model: *const CstModel,
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_ragged(
+        model: *const CstModel,
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_count_until(
+        model: *const CstModel,
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        n_streams: usize,
+        d_order: *const u32,
+        eof_symbol: i32,
+        max_symbols: usize,
+        d_lengths: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// Checkpointed streams -- the reference's Pos / Seek jump tables (src/stream/stack.rs:1107-1139; test :1456-1548) for the
     /// batched coder.  The encoder notes, in front of every chunk of `ckpt_interval` symbols, what `AnsCoder::pos()` returns
     /// there: d_ckpt_pos[s][j] = words in the bulk, d_ckpt_state[s][j] = coder state once symbols [j * interval, n) are

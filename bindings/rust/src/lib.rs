@@ -2389,6 +2389,53 @@ impl BatchedRangeEncoder {
         Ok(out)
     }
 
+    /// `encode_iid_symbols` for streams of different lengths in one launch -- one `DefaultRangeEncoder` per document with a shared
+    /// model (`cst_range_encode_ragged`; the queue form of [`BatchedAnsCoder::encode_ragged`]).  `sym_offsets[n_streams + 1]` delimits
+    /// the symbols of every stream, `word_offsets[n_streams + 1]` its slab (`min(n, ceil(n P / W)) + 2` words always suffice for `n`
+    /// symbols).  `order`: a schedule as for the ordered ragged calls, or `None`.  Every stream's words are those of
+    /// `encode_iid_symbols` for that stream alone.  No jump points.
+    ///
+    /// # Safety
+    /// The offsets are DEVICE memory: this wrapper cannot check them.  Every `sym_offsets` pair must lie inside `symbols`, every
+    /// slab `[word_offsets[s], word_offsets[s + 1])` inside `words`.
+    pub unsafe fn encode_iid_symbols_ragged(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        model: &DeviceModel,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_range_encode_ragged(
+                model.as_raw(),
+                self.config,
+                symbols.as_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status))
+    }
+
     /// `encode_symbols` -- one leakily quantized Gaussian per SYMBOL -- for streams of different lengths in one launch
     /// (`cst_range_encode_gaussian_ragged`): stream `s` owns elements `[sym_offsets[s], sym_offsets[s + 1])` of the flat `symbols`,
     /// `means` and `stds`, and writes into the slab `[word_offsets[s], word_offsets[s + 1])` of `words`
@@ -2974,6 +3021,95 @@ impl BatchedRangeDecoder {
             )
         })?;
         Ok(out)
+    }
+
+    /// The decoder of [`BatchedRangeEncoder::encode_iid_symbols_ragged`] (`cst_range_decode_ragged`): `decode_iid_symbols` per
+    /// stream, stream `s` yields `sym_offsets[s + 1] - sym_offsets[s]` symbols at `symbols[sym_offsets[s]..]`, in the order they
+    /// were encoded.
+    ///
+    /// # Safety
+    /// `sym_offsets` (device memory) must delimit ranges inside `symbols`.  The word slices ARE checked on the device against
+    /// `words.len()` (`words_capacity` of the C ABI).
+    pub unsafe fn decode_iid_symbols_ragged(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        symbols: &mut DeviceBuffer<i32>,
+        model: &DeviceModel,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_range_decode_ragged(
+                model.as_raw(),
+                self.config,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok(status)
+    }
+
+    /// Streams whose length is not stored (`cst_range_count_until`): every stream is decoded until `eof_symbol` -- which a queue
+    /// writes last -- and only the number of symbols decoded, terminator included, is kept.  Returns (lengths, status); an exclusive
+    /// prefix sum of the lengths is the `sym_offsets` of `decode_iid_symbols_ragged`.  A range decoder never runs out of words, so
+    /// `max_symbols` is the only stop for a stream without a terminator (`StreamStatus::Capacity`).  The word slices are checked on
+    /// the device against `words.len()`.
+    pub fn count_iid_symbols_until(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        order: Option<&DeviceBuffer<u32>>,
+        eof_symbol: i32,
+        max_symbols: usize,
+        model: &DeviceModel,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u64>, DeviceBuffer<i32>)> {
+        let n_streams = n_words.len();
+        if word_offsets.len() < n_streams || order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut lengths: DeviceBuffer<u64> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_range_count_until(
+                model.as_raw(),
+                self.config,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                eof_symbol,
+                max_symbols,
+                lengths.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((lengths, status))
     }
 
     /// The decoder of [`BatchedRangeEncoder::encode_symbols_ragged`] (`cst_range_decode_gaussian_ragged`): stream `s` yields

@@ -749,6 +749,98 @@ def ans_decode_until(encoded: RaggedBatch, model: Model, eof_symbol: int, max_sy
     return symbols, sym_offsets, torch.where(status != 0, status, status2)
 
 
+# ... the same three for the range coder, the reference's QUEUE (one RangeEncoder / RangeDecoder per document, queue.rs): the symbols
+# come back in the order they were written, so a document's terminator is simply its last symbol
+
+def range_encode_ragged(symbols: torch.Tensor, sym_offsets: torch.Tensor, model: Model, config=(32, 64, 24), order="auto") -> RaggedBatch:
+    """One RangeEncoder per stream, streams of different lengths (`symbols` flat, stream s = symbols[sym_offsets[s]:sym_offsets[s+1]]):
+    encode_iid_symbols + get_compressed per stream (queue.rs:612-705, 458-523) in ONE launch.  Every stream's words are those of
+    range_encode for that stream alone; a slab holds min(n, ceil(n P / W)) + 2 words, rounded up to 4.  The batch says
+    `.coder == "range"`, carries no jump points (`.jump` is None) and the schedule it ran with in `.order` (see _ragged_order)."""
+    symbols = _to_indices(model, _require_cuda(symbols, torch.int32, "symbols"))
+    sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
+    n_streams = sym_offsets.numel() - 1
+    if symbols.dim() != 1 or sym_offsets.dim() != 1 or n_streams < 0:
+        raise ValueError("symbols must be flat and sym_offsets hold n_streams + 1 entries")
+    W, S, P = config
+    dev = symbols.device
+    lengths = sym_offsets[1:] - sym_offsets[:-1]
+    # a stream of n symbols fills at most min(n, ceil(n P / W)) words plus the 2 that seal it (the bound inside cst_range_max_words,
+    # without its rounding to 64 bytes: thousands of short streams); 16-byte slabs keep the chunk stores aligned
+    bound = torch.minimum(lengths, (lengths * P + (W - 1)) // W) + 2
+    slabs = (bound + 3) // 4 * 4
+    word_offsets = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(slabs, 0, out=word_offsets[1:])
+    total = int(word_offsets[-1].item()) if n_streams else 0
+    order = _ragged_order(order, n_streams, lengths)
+    out = RaggedBatch(torch.empty(max(total, 4), dtype=torch.int32, device=dev), word_offsets,
+                      torch.empty(n_streams, dtype=torch.int32, device=dev), torch.empty(n_streams, dtype=torch.int32, device=dev), tuple(config),
+                      order, None, "range")
+    if n_streams == 0:
+        return out
+    N.check(N.lib().cst_range_encode_ragged(model._h, _cfg(*config), _ptr(symbols), _ptr(sym_offsets), n_streams,
+                                            _ptr(order) if order is not None else None, _ptr(out.words), _ptr(word_offsets), 0,
+                                            _ptr(out.n_words), _ptr(out.status), _stream_ptr()), "cst_range_encode_ragged")
+    return out
+
+
+def range_decode_ragged(encoded: RaggedBatch, model: Model, sym_offsets: torch.Tensor, out: Optional[torch.Tensor] = None, order="auto"):
+    """from_compressed + decode_iid_symbols per stream (queue.rs:776-790, 968-1033): stream s yields
+    sym_offsets[s + 1] - sym_offsets[s] symbols at out[sym_offsets[s]:], in the order they were encoded.  Returns (symbols flat,
+    status per stream).  `order`: the schedule (see _ragged_order); "auto" reuses the encoder's, or sorts by word count from
+    RAGGED_BALANCE_FROM streams on."""
+    _require_coder(encoded, "range")
+    sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
+    n_streams = sym_offsets.numel() - 1
+    if sym_offsets.dim() != 1 or encoded.n_words.numel() != n_streams:
+        raise ValueError("sym_offsets does not match the number of streams of the batch")
+    if isinstance(order, str) and order == "auto" and encoded.order is not None and encoded.order.numel() == n_streams:
+        order = encoded.order
+    order = _ragged_order(order, n_streams, encoded.n_words)
+    dev = encoded.words.device
+    total = int(sym_offsets[-1].item()) if n_streams > 0 else 0
+    if out is None:
+        out = torch.empty(total, dtype=torch.int32, device=dev)
+    else:
+        out = _require_cuda(out, torch.int32, "out")
+        if out.dim() != 1 or out.numel() < total:
+            raise ValueError("out must be flat and hold every stream's symbols")
+    status = torch.empty(n_streams, dtype=torch.int32, device=dev)
+    if n_streams == 0:
+        return _to_symbols(model, out), status
+    N.check(N.lib().cst_range_decode_ragged(model._h, _cfg(*encoded.config), _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
+                                            encoded.words.numel(), _ptr(encoded.n_words), _ptr(out), _ptr(sym_offsets), n_streams,
+                                            _ptr(order) if order is not None else None, _ptr(status), _stream_ptr()),
+            "cst_range_decode_ragged")
+    return _to_symbols(model, out), status
+
+
+def range_decode_until(encoded: RaggedBatch, model: Model, eof_symbol: int, max_symbols: Optional[int] = None):
+    """Streams whose length is not stored: every stream is decoded until `eof_symbol`, which a queue writes LAST.  Two launches --
+    count, prefix sum, decode -- as ans_decode_until.  Returns (symbols flat, sym_offsets [n + 1], status); the terminator is the last
+    symbol of every stream.  A range decoder never runs out of words (the reference shifts in zeros), so `max_symbols` (default 2^20)
+    is the only stop for a stream without a terminator: status CAPACITY (2), and such a stream decodes to NO symbols (its length is 0
+    in sym_offsets).  Contiguous alphabets only."""
+    _require_coder(encoded, "range")
+    max_symbols = (1 << 20) if max_symbols is None else int(max_symbols)
+    if model.noncontiguous:
+        raise ValueError("range_decode_until: contiguous alphabets only")
+    n_streams = encoded.n_words.numel()
+    dev = encoded.words.device
+    lengths = torch.zeros(n_streams, dtype=torch.int64, device=dev)
+    status = torch.zeros(n_streams, dtype=torch.int32, device=dev)
+    order = encoded.order if encoded.order is not None and encoded.order.numel() == n_streams else _ragged_order("auto", n_streams, encoded.n_words)
+    N.check(N.lib().cst_range_count_until(model._h, _cfg(*encoded.config), _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
+                                          encoded.words.numel(), _ptr(encoded.n_words), n_streams,
+                                          _ptr(order) if order is not None else None, int(eof_symbol), int(max_symbols),
+                                          _ptr(lengths), _ptr(status), _stream_ptr()), "cst_range_count_until")
+    lengths = torch.where(status != 0, torch.zeros_like(lengths), lengths)      # (a stream without a terminator is not decoded)
+    sym_offsets = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(lengths, 0, out=sym_offsets[1:])
+    symbols, status2 = range_decode_ragged(encoded, model, sym_offsets, order=order)
+    return symbols, sym_offsets, torch.where(status != 0, status, status2)
+
+
 def _compact_scratch(device, n_streams):
     # (one scratch per device AND stream: two compactions on different streams must not share ticket / status words)
     need = N.load_library().cst_compact_scratch_bytes(n_streams)

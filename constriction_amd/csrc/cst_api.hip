@@ -451,6 +451,50 @@ cst_status cst_ans_count_until(const cst_model* model, cst_coder_config cfg, con
                                        eof_symbol, max_symbols, d_lengths, d_status, stream);
 }
 
+// ---- the range coder with a shared table over streams of different lengths (cst_range_ragged.hip) ----
+// every refusal comes before the device is touched, whatever the number of streams (as the per-symbol ragged calls do it)
+static bool range_ragged_args_ok(const cst_model* model, cst_coder_config cfg, const uint64_t* d_word_offsets, size_t stride_words,
+                                 const uint32_t* d_order, size_t n_streams) {
+    if (!model || !config_supported(cfg) || cfg.precision != model->precision || model->per_stream) return false;
+    if (!d_word_offsets && stride_words == 0) return false;
+    return ragged_order_ok(d_order, n_streams);
+}
+
+cst_status cst_range_encode_ragged(const cst_model* model, cst_coder_config cfg, const int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                   size_t n_streams, const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets,
+                                   size_t stride_words, uint32_t* d_n_words, int32_t* d_status, void* stream) {
+    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, d_order, n_streams)) return CST_ERR_INVALID_ARGUMENT;
+    if (!d_sym_offsets || !d_words || !d_n_words || !d_status) return CST_ERR_INVALID_ARGUMENT;
+    if (n_streams == 0) return CST_OK;
+    if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    return note_kernel("range_encode_ragged_kernel", range_encode_ragged(model, cfg, d_symbols, d_sym_offsets, n_streams, d_words, d_word_offsets,
+                                                                         stride_words, d_n_words, d_status, d_order, (hipStream_t)stream));
+}
+
+cst_status cst_range_decode_ragged(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                   size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, int32_t* d_symbols,
+                                   const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order, int32_t* d_status, void* stream) {
+    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, d_order, n_streams)) return CST_ERR_INVALID_ARGUMENT;
+    if (!d_sym_offsets || !d_n_words || !d_status) return CST_ERR_INVALID_ARGUMENT;
+    if (n_streams == 0) return CST_OK;
+    if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    return note_kernel("range_decode_ragged_kernel", range_decode_ragged(model, cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                                                                         d_symbols, d_sym_offsets, n_streams, d_status, d_order, (hipStream_t)stream));
+}
+
+cst_status cst_range_count_until(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                 size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, size_t n_streams,
+                                 const uint32_t* d_order, int32_t eof_symbol, size_t max_symbols, uint64_t* d_lengths, int32_t* d_status,
+                                 void* stream) {
+    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, d_order, n_streams)) return CST_ERR_INVALID_ARGUMENT;
+    if (!d_n_words || !d_lengths || !d_status) return CST_ERR_INVALID_ARGUMENT;
+    if (n_streams == 0) return CST_OK;
+    if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    return note_kernel("range_count_until_kernel", range_count_until(model, cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                                                                     n_streams, eof_symbol, max_symbols, d_lengths, d_status, d_order,
+                                                                     (hipStream_t)stream));
+}
+
 cst_status cst_words_reverse(const uint32_t* d_words_in, const uint64_t* d_offsets_in, size_t stride_in, const uint32_t* d_n_words,
                              size_t n_streams, uint32_t* d_words_out, const uint64_t* d_offsets_out, size_t stride_out, void* stream) {
     if (n_streams == 0) return CST_OK;

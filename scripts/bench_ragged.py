@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Many small coders (the reference's tests/issue52.rs pattern): 100 000 documents of 20 .. 2000 symbols with one categorical
 model at P = 24 through `batched.ans_{encode,decode}_ragged` (one launch each), beside the same documents one
-`stream.stack.AnsCoder` each through the drop-in (a device round trip per call; 200 documents, extrapolated)."""
-import sys, time
+`stream.stack.AnsCoder` each through the drop-in (a device round trip per call; 200 documents, extrapolated).
+`--coder range`: the same workloads through `batched.range_{encode,decode}_ragged` (one RangeEncoder / RangeDecoder per document), with
+`ans_encode_ragged(..., jump_every=0)` / `ans_decode_ragged` on the same documents in the same run beside them."""
+import argparse, sys, time
 from pathlib import Path
 import numpy as np, torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
@@ -10,6 +12,9 @@ import bench
 from constriction_amd import batched as B
 from constriction_amd.stream import model as M, stack
 
+args = argparse.ArgumentParser(description=__doc__)
+args.add_argument("--coder", choices=("ans", "range"), default="ans")
+coder = args.parse_args().coder
 rng = np.random.default_rng(1)
 n_docs, n_sym, P = 100_000, 64, 24
 probs = rng.dirichlet(np.ones(n_sym) * 0.5)
@@ -25,6 +30,24 @@ for label, lengths in (("20 .. 2000 symbols, shuffled", np.exp(rng.uniform(np.lo
     offsets = np.zeros(n_docs + 1, dtype=np.int64); np.cumsum(lengths, out=offsets[1:])
     flat = torch.from_numpy(rng.choice(n_sym, size=int(offsets[-1]), p=probs).astype(np.int32)).cuda()
     off_d = torch.from_numpy(offsets).cuda()
+    if coder == "range":
+        n = int(offsets[-1])
+        enc = B.range_encode_ragged(flat, off_d, model)
+        dec, st = B.range_decode_ragged(enc, model, off_d)
+        ok = bool(torch.equal(dec, flat)) and int(enc.status.abs().sum()) == 0 and int(st.abs().sum()) == 0
+        e = min(bench.event_ms(lambda: B.range_encode_ragged(flat, off_d, model), 5) for _ in range(3))
+        d = min(bench.event_ms(lambda: B.range_decode_ragged(enc, model, off_d, out=dec), 5) for _ in range(3))
+        # the comparison: the ANS coder without jump points (one chain per document, as the range coder's) on the same documents
+        ans = B.ans_encode_ragged(flat, off_d, model, jump_every=0)
+        adec, ast = B.ans_decode_ragged(ans, model, off_d)
+        ok = ok and bool(torch.equal(adec, flat)) and int(ans.status.abs().sum()) == 0
+        ae = min(bench.event_ms(lambda: B.ans_encode_ragged(flat, off_d, model, jump_every=0), 5) for _ in range(3))
+        ad = min(bench.event_ms(lambda: B.ans_decode_ragged(ans, model, off_d, out=adec), 5) for _ in range(3))
+        print(f"{n_docs} documents, {label} ({n / 1e6:.1f} M symbols): range encode {e:.3f} ms ({e * 1e3 / n_docs:.3f} us/doc, "
+              f"{n / e / 1e6:.1f} Gsym/s)  decode {d:.3f} ms ({d * 1e3 / n_docs:.3f} us/doc, {n / d / 1e6:.1f} Gsym/s)  |  "
+              f"ans, no jump points: encode {ae:.3f} ms  decode {ad:.3f} ms  |  range / ans: encode {e / ae:.2f}x  decode {d / ad:.2f}x  ok={ok}",
+              flush=True)
+        continue
     enc = B.ans_encode_ragged(flat, off_d, model)
     dec, st = B.ans_decode_ragged(enc, model, off_d)
     ok = bool(torch.equal(dec, flat)) and int(enc.status.abs().sum()) == 0
@@ -35,6 +58,18 @@ for label, lengths in (("20 .. 2000 symbols, shuffled", np.exp(rng.uniform(np.lo
           f"decode {d:.3f} ms ({d * 1e3 / n_docs:.3f} us/doc, {n / d / 1e6:.1f} Gsym/s)  ok={ok}")
 docs = [flat[offsets[s]: offsets[s + 1]].cpu().numpy() for s in range(200)]
 torch.cuda.synchronize()
+if coder == "range":
+    from constriction_amd.stream import queue
+    t0 = time.perf_counter()
+    words = []
+    for doc in docs:
+        c = queue.RangeEncoder(); c.encode(doc, single); words.append(c.get_compressed())
+    t1 = time.perf_counter()
+    for doc, w in zip(docs, words):
+        assert np.array_equal(queue.RangeDecoder(w).decode(single, len(doc)), doc)
+    t2 = time.perf_counter()
+    print(f"drop-in, one RangeEncoder / RangeDecoder per document: encode {(t1 - t0) / 200 * 1e6:.0f} us/doc, decode {(t2 - t1) / 200 * 1e6:.0f} us/doc")
+    sys.exit(0)
 t0 = time.perf_counter()
 words = []
 for doc in docs:
