@@ -73,13 +73,20 @@ def _compile(src: Path, force: bool) -> Path:
     return obj
 
 
+def _workers(n_sources: int) -> int:
+    """compile processes: MAX_JOBS where it is set (a job that may use only some of a machine's CPUs), else
+    every CPU; never more than there are sources"""
+    jobs = os.environ.get("MAX_JOBS", "")
+    return max(1, min(n_sources, int(jobs) if jobs.isdigit() and int(jobs) > 0 else os.cpu_count() or 1))
+
+
 def build_library(force: bool = False, verbose: bool = False) -> Path:
     if not force and not needs_build():
         return LIB
     LIB.parent.mkdir(parents=True, exist_ok=True)
     OBJ.mkdir(parents=True, exist_ok=True)
     srcs = sorted(CSRC.glob("*.hip"))
-    with ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 1)) as pool:
+    with ThreadPoolExecutor(max_workers=_workers(len(srcs))) as pool:
         objs = list(pool.map(lambda s: _compile(s, force), srcs))
     tmp = LIB.with_suffix(".so.tmp")
     res = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", *map(str, objs), *LINK_LIBS, "-o", str(tmp)],

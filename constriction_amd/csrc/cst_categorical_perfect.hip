@@ -41,7 +41,7 @@ CST_HD double perfect_cost(double prob, uint32_t weight) {
 }
 CST_HD bool perfect_norm_ok(double norm) { return norm >= CatFloat<double>::kMinNormal && norm <= CatFloat<double>::kMax; }
 
-// floor(2^64 / p) as the coders' entries carry it (make_entry of cst_persymbol.hip)
+// floor(2^64 / p) as the coders' entries carry it (make_entry of cst_persymbol.hpp)
 __device__ __forceinline__ EncEntry perfect_entry(uint32_t c, uint32_t p) {
     uint64_t m = 0;
     if (p == 1) m = ~0ull;

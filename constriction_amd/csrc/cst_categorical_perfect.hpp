@@ -1,5 +1,5 @@
 // cst_categorical_perfect.hpp -- the launcher of the device quantiser behind Categorical(perfect=True)
-// (cst_categorical_perfect.hip), for the per-symbol coders' host glue in cst_persymbol.hip.
+// (cst_categorical_perfect.hip), for the per-symbol coders' host glue in cst_persymbol_categorical.hip.
 #pragma once
 #include "cst_common.hpp"
 

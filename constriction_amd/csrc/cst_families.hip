@@ -7,7 +7,7 @@
 // The continuous distributions live in the un-vendored `probability` crate (0.20.3 -> special 0.10.3 -> libm 0.2.16,
 // Cargo.lock); what is evaluated here are its published formulas over the libm-crate (musl / FreeBSD msun)
 // elementary functions: log / log1p / atan in cst_family_math.hpp (with the Laplace and Cauchy CDFs, which the
-// per-symbol coders of cst_persymbol.hip evaluate too), lgamma_r below, exp in cst_math.hpp.  categorical.rs:11 imports
+// per-symbol coders of cst_persymbol*.hip evaluate too), lgamma_r below, exp in cst_math.hpp.  categorical.rs:11 imports
 // `libm::log1p` explicitly.  Like everything in cst_math.hpp this file needs -ffp-contract=off: each operation
 // rounds once, in the order written, so that the CPU checker under tests (a separate C restatement)
 // and the GPU agree bit for bit.

@@ -1,6 +1,6 @@
 // cst_family_math.hpp -- the libm-crate (musl / FreeBSD msun) elementary functions behind the Laplace and Cauchy families and the
 // `probability` crate's two CDFs over them, bit for bit.  Shared by the table builder (cst_families.hip, which names the sources
-// and keeps the Binomial's functions) and the per-symbol coders (cst_persymbol.hip).  Like everything in cst_math.hpp this needs
+// and keeps the Binomial's functions) and the per-symbol coders (cst_persymbol*.hip).  Like everything in cst_math.hpp this needs
 // -ffp-contract=off: each operation rounds once, in the order written.
 #pragma once
 #include "cst_math.hpp"

@@ -1,4 +1,4 @@
-// cst_family_policy.hpp -- what the per-symbol coders (cst_persymbol.hip) need to know about a model FAMILY, at compile time.
+// cst_family_policy.hpp -- what the per-symbol coders (cst_persymbol*.hip) need to know about a model FAMILY, at compile time.
 //
 // The reference's flagship call  coder.encode_reverse(symbols, Family(lo, hi), param_a, param_b)  is the same for
 // QuantizedGaussian, QuantizedLaplace and QuantizedCauchy (src/pybindings/stream/model.rs:600-900): every symbol gets its own

@@ -1,4 +1,4 @@
-// cst_range_kernels.hpp -- per-lane range coder state machines (shared by cst_range.hip and cst_persymbol.hip).
+// cst_range_kernels.hpp -- per-lane range coder state machines (shared by cst_range.hip and the per-symbol coders, cst_persymbol*.hip).
 //
 // Recurrences: RangeEncoder::encode_symbol (src/stream/queue.rs:612-705) with its lazy carry
 // (EncoderSituation::Inverted, queue.rs:126-142), seal_words (queue.rs:482-523), RangeDecoder::read_point

@@ -15,7 +15,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-CHUNK = 64                  # kCatChunk of csrc/cst_persymbol.hip: columns of a row staged at a time
+CHUNK = 64                  # kCatChunk of csrc/cst_persymbol_categorical.hip: columns of a row staged at a time
 ROUTES = {"fused": "{coder}_decode_categorical_lane_kernel", "rows": "decode_categorical_by_rows"}
 # (n_streams, n_per_stream, K): every n_streams of {1, 3, 63, 64, 65, 130}, every n_per_stream of {1, 31, 64, 65, 100} and every K of
 # {2, 5, 64, 65, 257, 1031} + {C - 1, C, C + 1, 2 C + 1} appears, and every case runs through both routes of the decoder
