@@ -747,8 +747,29 @@ extern "C" {
     ///     lengths / status pointer, an unsupported configuration, cfg.precision != the model's (as cst_range_encode_batch refuses it), a
     ///     per-stream-table model, d_word_offsets == NULL with stride_words == 0, n_streams > 2^32 - 1 with an order.
     ///   - n_streams == 0: CST_OK, nothing is launched.
-    /// Presets (32,64) and (16,32), every precision cst_range_encode_batch takes.  No jump points (RangeEncoder::pos / RangeDecoder::seek)
-    /// for these batches yet.
+    /// Presets (32,64) and (16,32), every precision cst_range_encode_batch takes.
+    ///
+    /// Jump points (RangeEncoder::pos / RangeDecoder::seek, src/stream/queue.rs:172-196, 900-926) -- cst_range_{encode,decode}_ragged_jump,
+    /// the counterparts of cst_ans_{encode,decode}_ragged_jump: a launch lasts as long as its longest document's chain, and a range step
+    /// (its quantile is a quotient) costs more than an ANS step.  The encoder notes RangeEncoder::pos() in front of every chunk of
+    /// `jump_interval` symbols (a multiple of 8) of every stream on its way; words, d_n_words and d_status are exactly those of
+    /// cst_range_encode_ragged.  The decoder runs every chunk as a coder of its own (seek + at most jump_interval symbols) on a lane of its
+    /// own: the longest chain is jump_interval steps.
+    ///   - Chunk j of stream s is entry d_chunk_offsets[s] + j of the three table arrays, d_chunk_offsets[n_streams + 1] (uint64, read by both
+    ///     calls) the exclusive prefix sum of ceil(length / jump_interval) -- the layout of the ANS calls.  A jump point is d_jump_pos (uint32:
+    ///     words emitted so far INCLUDING held-back ones, as d_ckpt_pos of cst_range_encode_batch_ckpt), d_jump_lower / d_jump_range (uint64
+    ///     for both presets: the RangeCoderState there).  Chunk 0 is (0, 0, all ones); no chunk starts at the end of a stream.  The table
+    ///     entries of a stream whose status is not CST_STREAM_OK are unspecified.
+    ///   - n_chunks_total: the entries of the table arrays; d_chunk_offsets[n_streams] or any upper bound of it (entries behind the last chunk
+    ///     decode nothing).  d_scratch: cst_range_ragged_jump_scratch_bytes(n_chunks_total) bytes.
+    ///   - A chunk reads forward from its jump point, on past its chunk if need be, never past its stream's d_n_words; the slice of every
+    ///     stream is checked as cst_range_decode_ragged checks it.  One status per STREAM: the worst of its chunks'.  A table that does not
+    ///     describe its stream (chunks != ceil(length / jump_interval), offsets beyond n_chunks_total) or a d_jump_pos beyond the stream's
+    ///     d_n_words reports CST_STREAM_INVALID_DATA for that stream; the others decode, and nothing outside words_capacity or the stream's
+    ///     own symbols is touched.
+    ///   - CST_ERR_INVALID_ARGUMENT, before the device is touched: every refusal of cst_range_{encode,decode}_ragged (the decoder takes no
+    ///     order), jump_interval 0, not a multiple of 8 or > 2^31 - 1, n_chunks_total > 2^32 - 1, a NULL d_chunk_offsets / d_jump_pos /
+    ///     d_jump_lower / d_jump_range / d_scratch.  n_streams == 0: CST_OK, nothing is launched.
     pub fn cst_range_encode_ragged(
         model: *const CstModel,
         cfg: CstCoderConfig,
@@ -793,6 +814,50 @@ extern "C" {
         eof_symbol: i32,
         max_symbols: usize,
         d_lengths: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_ragged_jump_scratch_bytes(n_chunks_total: usize) -> usize;
+
+    pub fn cst_range_encode_ragged_jump(
+        model: *const CstModel,
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32,
+        d_jump_lower: *mut u64,
+        d_jump_range: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_ragged_jump(
+        model: *const CstModel,
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_scratch: *mut c_void,
         d_status: *mut i32,
         stream: *mut c_void,
     ) -> CstStatus;

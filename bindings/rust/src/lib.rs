@@ -2393,7 +2393,7 @@ impl BatchedRangeEncoder {
     /// model (`cst_range_encode_ragged`; the queue form of [`BatchedAnsCoder::encode_ragged`]).  `sym_offsets[n_streams + 1]` delimits
     /// the symbols of every stream, `word_offsets[n_streams + 1]` its slab (`min(n, ceil(n P / W)) + 2` words always suffice for `n`
     /// symbols).  `order`: a schedule as for the ordered ragged calls, or `None`.  Every stream's words are those of
-    /// `encode_iid_symbols` for that stream alone.  No jump points.
+    /// `encode_iid_symbols` for that stream alone.  (With jump points: `encode_iid_symbols_ragged_with_jump_points`.)
     ///
     /// # Safety
     /// The offsets are DEVICE memory: this wrapper cannot check them.  Every `sym_offsets` pair must lie inside `symbols`, every
@@ -2434,6 +2434,64 @@ impl BatchedRangeEncoder {
             )
         })?;
         Ok((n_words, status))
+    }
+
+    /// `encode_iid_symbols_ragged` that also notes `RangeEncoder::pos()` in front of every `jump_interval` symbols of every stream
+    /// (`cst_range_encode_ragged_jump`; `Pos`, src/stream/queue.rs:172-196): chunk `j` of stream `s` is entry `chunk_offsets[s] + j` of
+    /// the returned `(pos, lower, range)` arrays, `chunk_offsets[n_streams + 1]` the exclusive prefix sum of
+    /// `ceil(length / jump_interval)` (device memory, `n_chunks_total` its last entry or an upper bound of it).  `pos` counts the
+    /// words emitted so far, held-back ones included; `(lower, range)` is the coder state there.  The words are those of
+    /// `encode_iid_symbols_ragged`.  Returns `(n_words, status, pos, lower, range)`.
+    ///
+    /// # Safety
+    /// As for `encode_iid_symbols_ragged`; `chunk_offsets` must be that prefix sum.
+    pub unsafe fn encode_iid_symbols_ragged_with_jump_points(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        model: &DeviceModel,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>, DeviceBuffer<u32>, DeviceBuffer<u64>, DeviceBuffer<u64>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 8 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut pos: DeviceBuffer<u32> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut lower: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut range: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        check(unsafe {
+            ffi::cst_range_encode_ragged_jump(
+                model.as_raw(),
+                self.config,
+                symbols.as_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                pos.as_mut_ptr(),
+                lower.as_mut_ptr(),
+                range.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status, pos, lower, range))
     }
 
     /// `encode_symbols` -- one leakily quantized Gaussian per SYMBOL -- for streams of different lengths in one launch
@@ -3066,6 +3124,67 @@ impl BatchedRangeDecoder {
                 stream.as_raw(),
             )
         })?;
+        Ok(status)
+    }
+
+    /// The decoder of [`BatchedRangeEncoder::encode_iid_symbols_ragged_with_jump_points`] (`cst_range_decode_ragged_jump`): every
+    /// chunk of every stream as a coder of its own (`RangeDecoder::seek`, src/stream/queue.rs:911-926, + at most `jump_interval`
+    /// symbols), so that a launch lasts as long as a chunk, not as its longest document.  One status per stream.
+    ///
+    /// # Safety
+    /// As for `decode_iid_symbols_ragged`.  The jump table is checked against the lengths and word counts on the device.
+    pub unsafe fn decode_iid_symbols_ragged_from_jump_points(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        sym_offsets: &DeviceBuffer<u64>,
+        symbols: &mut DeviceBuffer<i32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        pos: &DeviceBuffer<u32>,
+        lower: &DeviceBuffer<u64>,
+        range: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        model: &DeviceModel,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 8 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        if pos.len() < n_chunks_total || lower.len() < n_chunks_total || range.len() < n_chunks_total {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_range_ragged_jump_scratch_bytes(n_chunks_total) })?;
+        check(unsafe {
+            ffi::cst_range_decode_ragged_jump(
+                model.as_raw(),
+                self.config,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                n_chunks_total,
+                pos.as_ptr(),
+                lower.as_ptr(),
+                range.as_ptr(),
+                scratch.as_mut_ptr() as *mut c_void,
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
         Ok(status)
     }
 

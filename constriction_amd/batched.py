@@ -572,6 +572,7 @@ class RaggedBatch:
     config: tuple
     order: Optional[torch.Tensor] = None   # int32 [n_streams]: the schedule the encoder ran with (the decoders reuse it)
     jump: Optional["RaggedJump"] = None    # jump points the encoder noted (ans_encode_ragged, jump_every): ans_decode_ragged decodes the chunks side by side
+    #                                        (a range batch carries a RangeRaggedJump here: range_encode_ragged_jump / range_decode_ragged)
     coder: str = "ans"                     # "ans" (a stack) or "range" (a queue): which coder wrote the words -- the other one's decoders refuse them
 
     def stream(self, s: int) -> np.ndarray:
@@ -588,6 +589,17 @@ class RaggedJump:
     chunk_offsets: torch.Tensor   # int64 [n_streams + 1]: exclusive prefix sum of ceil(length / interval)
     pos: torch.Tensor             # int32 [>= total chunks]
     state: torch.Tensor           # int64 [>= total chunks]
+
+
+@dataclass
+class RangeRaggedJump:
+    """RangeEncoder.pos() in front of every `interval` symbols of every stream of a range RaggedBatch (queue.rs:172-196): chunk j of
+    stream s is entry chunk_offsets[s] + j of pos (words emitted so far, held-back ones included) / lower / range (the coder state there)."""
+    interval: int
+    chunk_offsets: torch.Tensor   # int64 [n_streams + 1]: exclusive prefix sum of ceil(length / interval)
+    pos: torch.Tensor             # int32 [>= total chunks]
+    lower: torch.Tensor           # int64 [>= total chunks]
+    range: torch.Tensor           # int64 [>= total chunks]
 
 
 RAGGED_JUMP_EVERY = 256            # jump_every="auto": symbols between the jump points of a ragged batch
@@ -752,11 +764,41 @@ def ans_decode_until(encoded: RaggedBatch, model: Model, eof_symbol: int, max_sy
 # ... the same three for the range coder, the reference's QUEUE (one RangeEncoder / RangeDecoder per document, queue.rs): the symbols
 # come back in the order they were written, so a document's terminator is simply its last symbol
 
+def _range_jump_every(jump_every) -> object:
+    """the `jump_every` argument, judged before any tensor is looked at: "auto", or an int that is 0 or a positive multiple of 8"""
+    if isinstance(jump_every, str):
+        if jump_every != "auto":
+            raise ValueError("jump_every: 'auto', 0 or a multiple of 8")
+        return "auto"
+    jump_every = int(jump_every or 0)
+    if jump_every < 0 or jump_every % 8 != 0:
+        raise ValueError("jump_every: 'auto', 0 or a multiple of 8")
+    return jump_every
+
+
 def range_encode_ragged(symbols: torch.Tensor, sym_offsets: torch.Tensor, model: Model, config=(32, 64, 24), order="auto") -> RaggedBatch:
     """One RangeEncoder per stream, streams of different lengths (`symbols` flat, stream s = symbols[sym_offsets[s]:sym_offsets[s+1]]):
     encode_iid_symbols + get_compressed per stream (queue.rs:612-705, 458-523) in ONE launch.  Every stream's words are those of
     range_encode for that stream alone; a slab holds min(n, ceil(n P / W)) + 2 words, rounded up to 4.  The batch says
     `.coder == "range"`, carries no jump points (`.jump` is None) and the schedule it ran with in `.order` (see _ragged_order)."""
+    return _range_encode_ragged(symbols, sym_offsets, model, config, order, 0)
+
+
+def range_encode_ragged_jump(symbols: torch.Tensor, sym_offsets: torch.Tensor, model: Model, config=(32, 64, 24), order="auto",
+                             jump_every="auto") -> RaggedBatch:
+    """range_encode_ragged that also notes RangeEncoder.pos() in front of every `jump_every` symbols of every stream (a multiple of 8; the
+    words, counts and statuses are unchanged).  The batch carries the table as `.jump` (a RangeRaggedJump), and range_decode_ragged then
+    decodes all chunks side by side: a launch lasts as long as its longest CHAIN, and a range step costs more than an ANS step.
+    "auto" (default): every RAGGED_JUMP_EVERY symbols if the streams average MORE than RAGGED_JUMP_EVERY symbols, i.e. more than one
+    chunk each (not the ANS rule of a quarter of that: 100 000 documents of 200 symbols, one chunk each, encode in 0.133 instead of
+    0.104 ms and decode in 0.142 instead of 0.126 ms with a table that buys them nothing, while documents of 20 .. 2000 symbols, 430 on
+    average, decode in 0.30 instead of 0.94 ms for 0.55 instead of 0.51 ms of encoding); 0: none -- the result is
+    exactly range_encode_ragged's."""
+    return _range_encode_ragged(symbols, sym_offsets, model, config, order, _range_jump_every(jump_every))
+
+
+def _range_encode_ragged(symbols, sym_offsets, model, config, order, jump_every) -> RaggedBatch:
+    """the body of range_encode_ragged (jump_every = 0) and range_encode_ragged_jump (jump_every as _range_jump_every returns it)"""
     symbols = _to_indices(model, _require_cuda(symbols, torch.int32, "symbols"))
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
     n_streams = sym_offsets.numel() - 1
@@ -778,6 +820,21 @@ def range_encode_ragged(symbols: torch.Tensor, sym_offsets: torch.Tensor, model:
                       order, None, "range")
     if n_streams == 0:
         return out
+    if jump_every == "auto":
+        jump_every = RAGGED_JUMP_EVERY if symbols.numel() > n_streams * RAGGED_JUMP_EVERY else 0
+    if jump_every:
+        chunk_offsets = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
+        torch.cumsum((lengths + (jump_every - 1)) // jump_every, 0, out=chunk_offsets[1:])
+        # (no read-back of the total: sum(ceil(len / I)) <= total / I + n_streams bounds it, entries behind the last chunk stay unused)
+        n_chunks = max(symbols.numel() // jump_every + n_streams, 1)
+        jump = RangeRaggedJump(jump_every, chunk_offsets, torch.empty(n_chunks, dtype=torch.int32, device=dev),
+                               torch.empty(n_chunks, dtype=torch.int64, device=dev), torch.empty(n_chunks, dtype=torch.int64, device=dev))
+        N.check(N.lib().cst_range_encode_ragged_jump(model._h, _cfg(*config), _ptr(symbols), _ptr(sym_offsets), n_streams,
+                                                     _ptr(order) if order is not None else None, _ptr(out.words), _ptr(word_offsets), 0,
+                                                     _ptr(out.n_words), jump_every, _ptr(chunk_offsets), _ptr(jump.pos), _ptr(jump.lower),
+                                                     _ptr(jump.range), _ptr(out.status), _stream_ptr()), "cst_range_encode_ragged_jump")
+        out.jump = jump
+        return out
     N.check(N.lib().cst_range_encode_ragged(model._h, _cfg(*config), _ptr(symbols), _ptr(sym_offsets), n_streams,
                                             _ptr(order) if order is not None else None, _ptr(out.words), _ptr(word_offsets), 0,
                                             _ptr(out.n_words), _ptr(out.status), _stream_ptr()), "cst_range_encode_ragged")
@@ -788,12 +845,17 @@ def range_decode_ragged(encoded: RaggedBatch, model: Model, sym_offsets: torch.T
     """from_compressed + decode_iid_symbols per stream (queue.rs:776-790, 968-1033): stream s yields
     sym_offsets[s + 1] - sym_offsets[s] symbols at out[sym_offsets[s]:], in the order they were encoded.  Returns (symbols flat,
     status per stream).  `order`: the schedule (see _ragged_order); "auto" reuses the encoder's, or sorts by word count from
-    RAGGED_BALANCE_FROM streams on."""
+    RAGGED_BALANCE_FROM streams on.  A batch with jump points (range_encode_ragged_jump) decodes its chunks side by side when `order` is
+    None or "auto"; a schedule handed in is honoured on the whole streams."""
     _require_coder(encoded, "range")
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
     n_streams = sym_offsets.numel() - 1
     if sym_offsets.dim() != 1 or encoded.n_words.numel() != n_streams:
         raise ValueError("sym_offsets does not match the number of streams of the batch")
+    jump = encoded.jump
+    if jump is not None and not isinstance(jump, RangeRaggedJump):
+        raise ValueError("the batch carries the jump points of another coder")
+    take_jump = jump is not None and (order is None or (isinstance(order, str) and order == "auto"))
     if isinstance(order, str) and order == "auto" and encoded.order is not None and encoded.order.numel() == n_streams:
         order = encoded.order
     order = _ragged_order(order, n_streams, encoded.n_words)
@@ -807,6 +869,17 @@ def range_decode_ragged(encoded: RaggedBatch, model: Model, sym_offsets: torch.T
             raise ValueError("out must be flat and hold every stream's symbols")
     status = torch.empty(n_streams, dtype=torch.int32, device=dev)
     if n_streams == 0:
+        return _to_symbols(model, out), status
+    if take_jump and jump.chunk_offsets.numel() == n_streams + 1:
+        # every chunk of every stream on a lane of its own (the table is checked against the lengths on the device: a stream it does not
+        # describe reports INVALID_DATA); an upper bound of the chunks is enough, entries behind the last chunk are empty
+        L = N.lib()
+        n_chunks = min(int(jump.pos.numel()), int(jump.lower.numel()), int(jump.range.numel()))
+        scratch = _ckpt_scratch("range_ragged_jump", dev, L.cst_range_ragged_jump_scratch_bytes(n_chunks))
+        N.check(L.cst_range_decode_ragged_jump(model._h, _cfg(*encoded.config), _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
+                                               encoded.words.numel(), _ptr(encoded.n_words), _ptr(out), _ptr(sym_offsets), n_streams,
+                                               jump.interval, _ptr(jump.chunk_offsets), n_chunks, _ptr(jump.pos), _ptr(jump.lower),
+                                               _ptr(jump.range), _ptr(scratch), _ptr(status), _stream_ptr()), "cst_range_decode_ragged_jump")
         return _to_symbols(model, out), status
     N.check(N.lib().cst_range_decode_ragged(model._h, _cfg(*encoded.config), _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
                                             encoded.words.numel(), _ptr(encoded.n_words), _ptr(out), _ptr(sym_offsets), n_streams,

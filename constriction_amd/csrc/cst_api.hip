@@ -495,6 +495,45 @@ cst_status cst_range_count_until(const cst_model* model, cst_coder_config cfg, c
                                                                      (hipStream_t)stream));
 }
 
+// ... with jump points (RangeEncoder::pos / RangeDecoder::seek per chunk of every stream)
+size_t cst_range_ragged_jump_scratch_bytes(size_t n_chunks_total) { return range_ragged_jump_scratch_bytes(n_chunks_total); }
+
+static bool ragged_jump_interval_ok(size_t jump_interval) { return jump_interval != 0 && jump_interval % 8 == 0 && jump_interval <= 0x7fffffffull; }
+
+cst_status cst_range_encode_ragged_jump(const cst_model* model, cst_coder_config cfg, const int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                        size_t n_streams, const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets,
+                                        size_t stride_words, uint32_t* d_n_words, size_t jump_interval, const uint64_t* d_chunk_offsets,
+                                        uint32_t* d_jump_pos, uint64_t* d_jump_lower, uint64_t* d_jump_range, int32_t* d_status, void* stream) {
+    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, d_order, n_streams) || !ragged_jump_interval_ok(jump_interval))
+        return CST_ERR_INVALID_ARGUMENT;
+    if (!d_sym_offsets || !d_words || !d_n_words || !d_status || !d_chunk_offsets || !d_jump_pos || !d_jump_lower || !d_jump_range)
+        return CST_ERR_INVALID_ARGUMENT;
+    if (n_streams == 0) return CST_OK;
+    if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    return note_kernel("range_encode_ragged_kernel<jump>", range_encode_ragged_jump(model, cfg, d_symbols, d_sym_offsets, n_streams, d_words, d_word_offsets,
+                                                                                     stride_words, d_n_words, d_status, d_order, (uint32_t)jump_interval,
+                                                                                     d_chunk_offsets, d_jump_pos, d_jump_lower, d_jump_range,
+                                                                                     (hipStream_t)stream));
+}
+
+cst_status cst_range_decode_ragged_jump(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                        size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, int32_t* d_symbols,
+                                        const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets,
+                                        size_t n_chunks_total, const uint32_t* d_jump_pos, const uint64_t* d_jump_lower,
+                                        const uint64_t* d_jump_range, void* d_scratch, int32_t* d_status, void* stream) {
+    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, nullptr, n_streams) || !ragged_jump_interval_ok(jump_interval) ||
+        n_chunks_total > 0xffffffffull)
+        return CST_ERR_INVALID_ARGUMENT;
+    if (!d_sym_offsets || !d_n_words || !d_status || !d_chunk_offsets || !d_jump_pos || !d_jump_lower || !d_jump_range || !d_scratch)
+        return CST_ERR_INVALID_ARGUMENT;
+    if (n_streams == 0) return CST_OK;
+    if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    return note_kernel("range_decode_ragged_kernel<jump>", range_decode_ragged_jump(model, cfg, d_words, d_word_offsets, stride_words, words_capacity,
+                                                                                     d_n_words, d_symbols, d_sym_offsets, n_streams,
+                                                                                     (uint32_t)jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos,
+                                                                                     d_jump_lower, d_jump_range, d_scratch, d_status, (hipStream_t)stream));
+}
+
 cst_status cst_words_reverse(const uint32_t* d_words_in, const uint64_t* d_offsets_in, size_t stride_in, const uint32_t* d_n_words,
                              size_t n_streams, uint32_t* d_words_out, const uint64_t* d_offsets_out, size_t stride_out, void* stream) {
     if (n_streams == 0) return CST_OK;

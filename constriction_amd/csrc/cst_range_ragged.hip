@@ -17,7 +17,9 @@
 // Decoder steps: RangeDecLane::step, whose quantile is an f64 quotient -- the cost of a range step over an ANS step.
 // Every stream's words, count and status are those of cst_range_{encode,decode}_batch for that stream alone (queue.rs:612-705,
 // 458-523, 847-868, 968-1033).
-// NOT here: jump points (RangeEncoder::pos / RangeDecoder::seek).  RangeDecLane::init_at is what a decoder of chunks would start from.
+// Jump points (RangeEncoder::pos / RangeDecoder::seek, queue.rs:172-196, 900-926) are a form of their own of the two coding kernels
+// (JUMP, a compile-time parameter of the shared bodies: the plain kernels keep their registers, LDS, occupancy and timings): see
+// RangeRaggedJump and RangeRaggedChunks below.
 #include "cst_range_kernels.hpp"
 
 namespace cst {
@@ -40,6 +42,30 @@ struct RangeRaggedArgs {
     int32_t* status;
     uint64_t words_capacity;
     const uint32_t* order;           // null, or [n_streams]: lane slot i codes stream order[i]
+};
+
+// The jump form of the encoder notes RangeEncoder::pos() in front of every chunk of `interval` symbols of every stream: chunk j of
+// stream s is entry chunk_offsets[s] + j of pos / lower / range, chunk_offsets the exclusive prefix sum of ceil(len / interval) (the
+// layout of cst_ans_ragged.hip).  pos = words emitted so far INCLUDING held-back ones, (lower, range) the RangeCoderState there.
+struct RangeRaggedJump {
+    uint32_t interval;               // a multiple of kRrGroup
+    const uint64_t* chunk_offsets;   // [n_streams + 1]
+    uint32_t* pos;
+    uint64_t* lower;
+    uint64_t* range;
+};
+
+// The jump form of the decoder runs every chunk as a coder of its own, one lane per chunk (`n_streams` of its RangeRaggedArgs is
+// the number of chunks, `status` one entry per chunk, `order` null).  A range chunk reads FORWARD from its jump point and may read on
+// past its chunk, never past its stream: a chunk carries its own symbol range and its STREAM's slice of the words.
+struct RangeRaggedChunks {
+    const uint64_t* sym_lo;          // first symbol of the chunk in the flat output
+    const uint32_t* len;             // symbols of the chunk (0: a table entry that belongs to no stream)
+    const uint64_t* word_off;        // the chunk's stream: offset and number of its words (already checked once, see rr_chunks_kernel)
+    const uint32_t* n_words;
+    const uint32_t* pos;             // the jump table
+    const uint64_t* lower;
+    const uint64_t* range;
 };
 
 // lane slot -> stream: the slot itself, or order[slot] (an entry that is not a stream leaves its lane idle)
@@ -75,10 +101,10 @@ constexpr size_t kRrEncRingBytes = (size_t)(kBlock / kWave) * kRrEncSlots * kWav
 static_assert(3 + 2 * kRrGroup < kRrEncSlots && kRrEncSlots / 2 + kRrGroup < kRrEncSlots && kRrEncSlots / 2 - 1 + kRrGroup <= 3 + 4 * kMaxChunksPerPoint,
               "the encoder's ring must hold a group's words, and a memory point must be able to move them out");
 
-template <int W, int S, bool STAGED>
-__global__ __launch_bounds__(kBlock) void range_encode_ragged_kernel(const RangeRaggedArgs a) {
+// the encoder: JUMP = false is range_encode_ragged_kernel, JUMP = true the form that notes the jump points of `jp` on its way
+template <int W, int S, bool STAGED, bool JUMP>
+__device__ __forceinline__ void rr_encode(const RangeRaggedArgs& a, const RangeRaggedJump& jp, unsigned char* smem) {
     constexpr int G = kRrGroup;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & (kWave - 1);
     uint32_t* ring = reinterpret_cast<uint32_t*>(smem) + (threadIdx.x >> 6) * (kRrEncSlots * kWave);
     const EncEntry* table = a.enc;
@@ -130,12 +156,38 @@ __global__ __launch_bounds__(kBlock) void range_encode_ragged_kernel(const Range
     const rr_v4i_unaligned* g4 = reinterpret_cast<const rr_v4i_unaligned*>(row);      // group g = pieces 2 g, 2 g + 1
     rr_v4i nx0 = rr_v4i{0, 0, 0, 0}, nx1 = rr_v4i{0, 0, 0, 0};
     if (ng > 0) { nx0 = g4[0].v; nx1 = g4[1].v; }
+    // RangeEncoder::pos() in front of every chunk (JUMP).  A queue codes first to last, so chunk j starts in front of group
+    // j * interval / 8 and is known AT that group's memory point: it is stored there, next to the word chunks (one memory point per
+    // group).  Between groups no quad is in flight, so a rolled-back quad never sees a jump point; pos counts the held-back words of an
+    // Inverted run as cst_range.hip does.  No division in the loop: the lane counts groups down to its next chunk (`to_jump`).
+    [[maybe_unused]] uint32_t to_jump = 0;
+    [[maybe_unused]] uint64_t next_chunk = 0;
+    [[maybe_unused]] bool jumps = false;
+    if constexpr (JUMP) {
+        jumps = active && len > 0;
+        if (jumps) next_chunk = jp.chunk_offsets[s];
+    }
+    auto store_jump_point = [&]() {
+        jp.pos[next_chunk] = L.out.wr + L.inv_n; jp.lower[next_chunk] = (uint64_t)L.lower; jp.range[next_chunk] = (uint64_t)L.range;
+        ++next_chunk;
+        to_jump = jp.interval / (uint32_t)G;
+    };
     for (uint32_t g = 0; g < mxg; ++g) {
         rr_consume(nx0, nx1);                  // group g's symbols (requested a group ago) -- and every older store
         const rr_v4i c0 = nx0, c1 = nx1;
         if (g + 1 < ng) { nx0 = g4[2 * (size_t)(g + 1)].v; nx1 = g4[2 * (size_t)(g + 1) + 1].v; }      // (only a group that exists)
         L.out.flush_chunks();                  // complete 16-byte chunks of the words of earlier groups: ring -> slab (at most 5)
+        if constexpr (JUMP) {
+            if (jumps && g < ng) {
+                if (to_jump == 0) store_jump_point();
+                --to_jump;
+            }
+        }
         if (g < ng) { quad(c0); quad(c1); }
+    }
+    if constexpr (JUMP) {
+        // a chunk that starts exactly at 8 ng, in front of the ragged end of the row (no chunk starts at len itself)
+        if (jumps && pre != 0 && to_jump == 0) store_jump_point();
     }
     if (__any(pre != 0)) {
 #pragma unroll
@@ -152,6 +204,18 @@ __global__ __launch_bounds__(kBlock) void range_encode_ragged_kernel(const Range
     if (!active) return;
     a.n_words_out[s] = status == CST_STREAM_OK ? n_words : 0u;
     a.status[s] = status;
+}
+
+template <int W, int S, bool STAGED>
+__global__ __launch_bounds__(kBlock) void range_encode_ragged_kernel(const RangeRaggedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rr_encode<W, S, STAGED, false>(a, RangeRaggedJump{}, smem);
+}
+
+template <int W, int S, bool STAGED>
+__global__ __launch_bounds__(kBlock) void range_encode_ragged_jump_kernel(const RangeRaggedArgs a, const RangeRaggedJump jp) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rr_encode<W, S, STAGED, true>(a, jp, smem);
 }
 
 // what both decoding kernels share: the tables (staged or not), the lane's coder on its slice of the words, its window primed.
@@ -195,20 +259,36 @@ struct RangeRaggedDecoder {
         L.in.prime();
         wave_lds_fence();
     }
+    // a chunk (the lane's `s` is a chunk index): RangeDecoder::seek to its jump point on its STREAM's slice of the words -- checked as
+    // start() checks it --, window primed at the read position.  init_at clamps a `pos` beyond the stream's words to their end.
+    __device__ __forceinline__ void start_at(const RangeRaggedArgs& a, const RangeRaggedChunks& v, uint32_t* ring) {
+        using st_t = typename StateT<S>::type;
+        ws = active ? word_slice(v.word_off, 0, v.n_words, s, a.words_capacity) : WordSlice{0, 0u, false};
+        L.init_at(a.words_in + ws.off, ws.n, active ? v.pos[s] : 0u, active ? (st_t)v.lower[s] : (st_t)0, active ? (st_t)v.range[s] : (st_t)0, ring, lane);
+        L.in.prime();
+        wave_lds_fence();
+    }
     __device__ __forceinline__ uint32_t step(const RangeRaggedArgs& a) {
         return L.template step<kDecBucket>(lut, cdf, bucket, a.precision - a.bucket_bits, a.n_symbols, a.precision);
     }
 };
 
-template <int W, int S, bool STAGED>
-__global__ __launch_bounds__(kBlock) void range_decode_ragged_kernel(const RangeRaggedArgs a) {
+// the decoder: JUMP = false is range_decode_ragged_kernel (a lane per stream), JUMP = true the form with a lane per chunk of `v`
+template <int W, int S, bool STAGED, bool JUMP>
+__device__ __forceinline__ void rr_decode(const RangeRaggedArgs& a, const RangeRaggedChunks& v, unsigned char* smem) {
     constexpr int G = kRrGroup;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     RangeRaggedDecoder<W, S, STAGED> D;
     D.stage(a, smem);
     if (!D.wave_has_streams(a)) return;
-    D.start(a, reinterpret_cast<uint32_t*>(smem) + (threadIdx.x >> 6) * (kRrDecSlots * kWave));
-    const uint64_t sym_lo = D.active ? a.sym_offsets[D.s] : 0, sym_hi = D.active ? a.sym_offsets[D.s + 1] : 0;
+    uint32_t* ring = reinterpret_cast<uint32_t*>(smem) + (threadIdx.x >> 6) * (kRrDecSlots * kWave);
+    uint64_t sym_lo = 0, sym_hi = 0;
+    if constexpr (JUMP) {
+        D.start_at(a, v, ring);
+        if (D.active) { sym_lo = v.sym_lo[D.s]; sym_hi = sym_lo + v.len[D.s]; }
+    } else {
+        D.start(a, ring);
+        sym_lo = D.active ? a.sym_offsets[D.s] : 0; sym_hi = D.active ? a.sym_offsets[D.s + 1] : 0;
+    }
     const bool too_long = sym_hi - sym_lo > 0xffffffffull || sym_hi < sym_lo;
     const uint32_t len = too_long ? 0u : (uint32_t)(sym_hi - sym_lo);
     int32_t* row = a.symbols_out + sym_lo;
@@ -240,6 +320,18 @@ __global__ __launch_bounds__(kBlock) void range_decode_ragged_kernel(const Range
     store_group((mx + G - 1) / G * G);
     if (!D.active) return;
     a.status[D.s] = D.ws.bad ? (int32_t)CST_STREAM_INVALID_DATA : (too_long ? (int32_t)CST_STREAM_CAPACITY : D.L.status);
+}
+
+template <int W, int S, bool STAGED>
+__global__ __launch_bounds__(kBlock) void range_decode_ragged_kernel(const RangeRaggedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rr_decode<W, S, STAGED, false>(a, RangeRaggedChunks{}, smem);
+}
+
+template <int W, int S, bool STAGED>
+__global__ __launch_bounds__(kBlock) void range_decode_ragged_jump_kernel(const RangeRaggedArgs a, const RangeRaggedChunks v) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rr_decode<W, S, STAGED, true>(a, v, smem);
 }
 
 // The reference's index stores no lengths: a document ends where its terminator is decoded, and a queue writes it LAST.  First pass of
@@ -354,6 +446,114 @@ cst_status range_count_until(const cst_model* model, cst_coder_config cfg, const
     const uint32_t eof_index = (uint32_t)eof_symbol - (uint32_t)model->min_symbol;
     const uint64_t mx = (uint64_t)max_symbols;
     CST_RANGE_RAGGED_DISPATCH(range_count_until_kernel, kRrDecRingBytes, rr_decode_table_bytes(model), eof_index, mx, d_lengths);
+}
+// ---- jump points ----
+cst_status range_encode_ragged_jump(const cst_model* model, cst_coder_config cfg, const int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                    size_t n_streams, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                    uint32_t* d_n_words, int32_t* d_status, const uint32_t* d_order, uint32_t interval,
+                                    const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos, uint64_t* d_jump_lower, uint64_t* d_jump_range,
+                                    hipStream_t hs) {
+    RangeRaggedArgs a{};
+    a.order = d_order;
+    a.symbols_in = d_symbols; a.sym_offsets = d_sym_offsets; a.n_streams = n_streams; a.enc = model->d_enc;
+    a.n_symbols = model->n_symbols; a.min_symbol = model->min_symbol; a.precision = model->precision;
+    a.words_out = d_words; a.word_offsets = d_word_offsets; a.stride_words = stride_words; a.n_words_out = d_n_words; a.status = d_status;
+    const RangeRaggedJump jp{interval, d_chunk_offsets, d_jump_pos, d_jump_lower, d_jump_range};
+    CST_RANGE_RAGGED_DISPATCH(range_encode_ragged_jump_kernel, kRrEncRingBytes, rr_encode_table_bytes(model), jp);
+}
+
+// The decoder's scratch: what RangeRaggedChunks points to, the stream every chunk belongs to, and one status per chunk.
+struct RangeRaggedScratch {
+    uint64_t *sym_lo, *word_off;
+    uint32_t *len, *n_words, *owner;
+    int32_t* status;
+    explicit RangeRaggedScratch(void* d_scratch, size_t n) {
+        unsigned char* b = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(d_scratch) + 15) & ~(uintptr_t)15);
+        sym_lo = reinterpret_cast<uint64_t*>(b); word_off = sym_lo + n;
+        len = reinterpret_cast<uint32_t*>(word_off + n); n_words = len + n; owner = n_words + n;
+        status = reinterpret_cast<int32_t*>(owner + n);
+    }
+};
+size_t range_ragged_jump_scratch_bytes(size_t n_chunks_total) { return 32 * n_chunks_total + 128; }
+constexpr uint32_t kRrNoOwner = 0xffffffffu;
+
+// The chunks of a batch as coders of their own, one thread per table entry: entry c belongs to the stream s with
+// chunk_offsets[s] <= c < chunk_offsets[s + 1] (found by bisection: the table is caller data, and whatever it holds, an entry gets a
+// symbol range inside ONE stream's symbols or none at all), and decodes symbols [j I, min(j I + I, len)) of it, j = c - chunk_offsets[s].
+// Entries that belong to no stream (behind the last chunk: n_chunks_total may be an upper bound) are empty.  The stream's slice of
+// the words is checked HERE as the plain decoder checks it (per-slab bound included); a bad one is handed on as the empty slice.
+__global__ void rr_chunks_kernel(const uint64_t* __restrict__ sym_offsets, const uint64_t* __restrict__ word_offsets, size_t stride_words,
+                                 uint64_t words_capacity, const uint32_t* __restrict__ n_words, const uint64_t* __restrict__ chunk_offsets,
+                                 size_t n_streams, size_t n_chunks_total, uint32_t interval, RangeRaggedScratch v) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_chunks_total) return;
+    size_t s = 0, hi = n_streams;          // the last stream with chunk_offsets[s] <= c
+    while (hi - s > 1) {
+        const size_t mid = s + (hi - s) / 2;
+        if (chunk_offsets[mid] <= c) s = mid; else hi = mid;
+    }
+    const uint64_t c0 = chunk_offsets[s], c1 = chunk_offsets[s + 1];
+    const uint64_t lo = sym_offsets[s], end = sym_offsets[s + 1];
+    const uint64_t start = (c - c0) * interval;
+    const bool mine = c >= c0 && c < c1 && end >= lo && end - lo <= 0xffffffffull && start < end - lo;
+    const WordSlice ws = mine ? word_slice(word_offsets, stride_words, n_words, s, words_capacity) : WordSlice{0, 0u, false};
+    const uint64_t left = mine ? end - lo - start : 0;
+    v.sym_lo[c] = mine ? lo + start : 0;
+    v.len[c] = (uint32_t)(left < interval ? left : interval);
+    v.word_off[c] = ws.off;
+    v.n_words[c] = ws.n;
+    v.owner[c] = mine ? (uint32_t)s : kRrNoOwner;
+}
+
+// a stream's status: the worst of its chunks'.  A table that does not describe the stream (chunks != ceil(len / I), entries beyond
+// n_chunks_total or given to another stream), a jump point beyond the stream's words, or words that leave the buffer, are caller data
+// gone wrong: CST_STREAM_INVALID_DATA.  (A stream too long for one coder: CST_STREAM_CAPACITY, as the plain decoder says.)
+__global__ void rr_chunk_status_kernel(RangeRaggedScratch v, const uint64_t* __restrict__ sym_offsets, const uint64_t* __restrict__ word_offsets,
+                                       size_t stride_words, uint64_t words_capacity, const uint64_t* __restrict__ chunk_offsets,
+                                       const uint32_t* __restrict__ jump_pos, const uint32_t* __restrict__ n_words, size_t n_streams,
+                                       size_t n_chunks_total, uint32_t interval, int32_t* __restrict__ status) {
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_streams) return;
+    const uint64_t lo = sym_offsets[s], end = sym_offsets[s + 1];
+    const uint64_t c0 = chunk_offsets[s], c1 = chunk_offsets[s + 1];
+    int32_t worst = CST_STREAM_OK;
+    if (word_slice(word_offsets, stride_words, n_words, s, words_capacity).bad) worst = CST_STREAM_INVALID_DATA;
+    else if (end < lo || end - lo > 0xffffffffull) worst = CST_STREAM_CAPACITY;
+    else if (c1 < c0 || c1 > n_chunks_total || c1 - c0 != (end - lo + interval - 1) / interval) worst = CST_STREAM_INVALID_DATA;
+    else
+        for (uint64_t c = c0; c < c1; ++c) {
+            worst = max(worst, v.status[c]);
+            if (v.owner[c] != (uint32_t)s || jump_pos[c] > n_words[s]) worst = CST_STREAM_INVALID_DATA;
+        }
+    status[s] = worst;
+}
+
+static cst_status rr_decode_chunks(const cst_model* model, cst_coder_config cfg, const RangeRaggedArgs& a, const RangeRaggedChunks& v, hipStream_t hs) {
+    CST_RANGE_RAGGED_DISPATCH(range_decode_ragged_jump_kernel, kRrDecRingBytes, rr_decode_table_bytes(model), v);
+}
+
+cst_status range_decode_ragged_jump(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                    size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, int32_t* d_symbols,
+                                    const uint64_t* d_sym_offsets, size_t n_streams, uint32_t interval, const uint64_t* d_chunk_offsets,
+                                    size_t n_chunks_total, const uint32_t* d_jump_pos, const uint64_t* d_jump_lower,
+                                    const uint64_t* d_jump_range, void* d_scratch, int32_t* d_status, hipStream_t hs) {
+    if (n_streams > ((size_t)0x7fffffff) * 256) return CST_ERR_INVALID_ARGUMENT;
+    const RangeRaggedScratch v(d_scratch, n_chunks_total);
+    if (n_chunks_total > 0) {
+        hipLaunchKernelGGL(rr_chunks_kernel, dim3((unsigned)((n_chunks_total + 255) / 256)), dim3(256), 0, hs, d_sym_offsets, d_word_offsets,
+                           stride_words, (uint64_t)words_capacity, d_n_words, d_chunk_offsets, n_streams, n_chunks_total, interval, v);
+        CST_HIP_TRY(hipGetLastError());
+        // (the slices handed on are absolute offsets that passed the check, or empty: `words_capacity` bounds them once more)
+        RangeRaggedArgs a = rr_decode_args(model, d_words, nullptr, 0, words_capacity, nullptr, n_chunks_total, v.status, nullptr);
+        a.symbols_out = d_symbols;
+        const RangeRaggedChunks ch{v.sym_lo, v.len, v.word_off, v.n_words, d_jump_pos, d_jump_lower, d_jump_range};
+        const cst_status rc = rr_decode_chunks(model, cfg, a, ch, hs);
+        if (rc != CST_OK) return rc;
+    }
+    hipLaunchKernelGGL(rr_chunk_status_kernel, dim3((unsigned)((n_streams + 255) / 256)), dim3(256), 0, hs, v, d_sym_offsets, d_word_offsets, stride_words,
+                       (uint64_t)words_capacity, d_chunk_offsets, d_jump_pos, d_n_words, n_streams, n_chunks_total, interval, d_status);
+    CST_HIP_TRY(hipGetLastError());
+    return CST_OK;
 }
 #undef CST_RANGE_RAGGED_DISPATCH
 

@@ -456,8 +456,29 @@ cst_status cst_range_decode_family_ragged(cst_coder_config cfg, int32_t family, 
  *     lengths / status pointer, an unsupported configuration, cfg.precision != the model's (as cst_range_encode_batch refuses it), a
  *     per-stream-table model, d_word_offsets == NULL with stride_words == 0, n_streams > 2^32 - 1 with an order.
  *   - n_streams == 0: CST_OK, nothing is launched.
- * Presets (32,64) and (16,32), every precision cst_range_encode_batch takes.  No jump points (RangeEncoder::pos / RangeDecoder::seek)
- * for these batches yet. */
+ * Presets (32,64) and (16,32), every precision cst_range_encode_batch takes.
+ *
+ * Jump points (RangeEncoder::pos / RangeDecoder::seek, src/stream/queue.rs:172-196, 900-926) -- cst_range_{encode,decode}_ragged_jump,
+ * the counterparts of cst_ans_{encode,decode}_ragged_jump: a launch lasts as long as its longest document's chain, and a range step
+ * (its quantile is a quotient) costs more than an ANS step.  The encoder notes RangeEncoder::pos() in front of every chunk of
+ * `jump_interval` symbols (a multiple of 8) of every stream on its way; words, d_n_words and d_status are exactly those of
+ * cst_range_encode_ragged.  The decoder runs every chunk as a coder of its own (seek + at most jump_interval symbols) on a lane of its
+ * own: the longest chain is jump_interval steps.
+ *   - Chunk j of stream s is entry d_chunk_offsets[s] + j of the three table arrays, d_chunk_offsets[n_streams + 1] (uint64, read by both
+ *     calls) the exclusive prefix sum of ceil(length / jump_interval) -- the layout of the ANS calls.  A jump point is d_jump_pos (uint32:
+ *     words emitted so far INCLUDING held-back ones, as d_ckpt_pos of cst_range_encode_batch_ckpt), d_jump_lower / d_jump_range (uint64
+ *     for both presets: the RangeCoderState there).  Chunk 0 is (0, 0, all ones); no chunk starts at the end of a stream.  The table
+ *     entries of a stream whose status is not CST_STREAM_OK are unspecified.
+ *   - n_chunks_total: the entries of the table arrays; d_chunk_offsets[n_streams] or any upper bound of it (entries behind the last chunk
+ *     decode nothing).  d_scratch: cst_range_ragged_jump_scratch_bytes(n_chunks_total) bytes.
+ *   - A chunk reads forward from its jump point, on past its chunk if need be, never past its stream's d_n_words; the slice of every
+ *     stream is checked as cst_range_decode_ragged checks it.  One status per STREAM: the worst of its chunks'.  A table that does not
+ *     describe its stream (chunks != ceil(length / jump_interval), offsets beyond n_chunks_total) or a d_jump_pos beyond the stream's
+ *     d_n_words reports CST_STREAM_INVALID_DATA for that stream; the others decode, and nothing outside words_capacity or the stream's
+ *     own symbols is touched.
+ *   - CST_ERR_INVALID_ARGUMENT, before the device is touched: every refusal of cst_range_{encode,decode}_ragged (the decoder takes no
+ *     order), jump_interval 0, not a multiple of 8 or > 2^31 - 1, n_chunks_total > 2^32 - 1, a NULL d_chunk_offsets / d_jump_pos /
+ *     d_jump_lower / d_jump_range / d_scratch.  n_streams == 0: CST_OK, nothing is launched. */
 cst_status cst_range_encode_ragged(const cst_model *model, cst_coder_config cfg, const int32_t *d_symbols,
                                    const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order, uint32_t *d_words,
                                    const uint64_t *d_word_offsets, size_t stride_words, uint32_t *d_n_words, int32_t *d_status,
@@ -470,6 +491,18 @@ cst_status cst_range_count_until(const cst_model *model, cst_coder_config cfg, c
                                  const uint64_t *d_word_offsets, size_t stride_words, size_t words_capacity,
                                  const uint32_t *d_n_words, size_t n_streams, const uint32_t *d_order, int32_t eof_symbol,
                                  size_t max_symbols, uint64_t *d_lengths, int32_t *d_status, void *stream);
+size_t cst_range_ragged_jump_scratch_bytes(size_t n_chunks_total);
+cst_status cst_range_encode_ragged_jump(const cst_model *model, cst_coder_config cfg, const int32_t *d_symbols,
+                                        const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order, uint32_t *d_words,
+                                        const uint64_t *d_word_offsets, size_t stride_words, uint32_t *d_n_words,
+                                        size_t jump_interval, const uint64_t *d_chunk_offsets, uint32_t *d_jump_pos,
+                                        uint64_t *d_jump_lower, uint64_t *d_jump_range, int32_t *d_status, void *stream);
+cst_status cst_range_decode_ragged_jump(const cst_model *model, cst_coder_config cfg, const uint32_t *d_words,
+                                        const uint64_t *d_word_offsets, size_t stride_words, size_t words_capacity,
+                                        const uint32_t *d_n_words, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                        size_t n_streams, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                        size_t n_chunks_total, const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
+                                        const uint64_t *d_jump_range, void *d_scratch, int32_t *d_status, void *stream);
 
 /* Checkpointed streams -- the reference's Pos / Seek jump tables (src/stream/stack.rs:1107-1139; test :1456-1548) for the
  * batched coder.  The encoder notes, in front of every chunk of `ckpt_interval` symbols, what `AnsCoder::pos()` returns

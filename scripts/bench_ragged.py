@@ -3,7 +3,9 @@
 model at P = 24 through `batched.ans_{encode,decode}_ragged` (one launch each), beside the same documents one
 `stream.stack.AnsCoder` each through the drop-in (a device round trip per call; 200 documents, extrapolated).
 `--coder range`: the same workloads through `batched.range_{encode,decode}_ragged` (one RangeEncoder / RangeDecoder per document), with
-`ans_encode_ragged(..., jump_every=0)` / `ans_decode_ragged` on the same documents in the same run beside them."""
+`ans_encode_ragged(..., jump_every=0)` / `ans_decode_ragged` on the same documents in the same run beside them.
+`--coder range --jump-every N`: also `range_encode_ragged_jump(..., jump_every=N)` and the decode of its chunks side by side, beside the
+plain pair on the same documents in the same run; every figure is measured twice (the second run shows the spread)."""
 import argparse, sys, time
 from pathlib import Path
 import numpy as np, torch
@@ -14,7 +16,10 @@ from constriction_amd.stream import model as M, stack
 
 args = argparse.ArgumentParser(description=__doc__)
 args.add_argument("--coder", choices=("ans", "range"), default="ans")
-coder = args.parse_args().coder
+args.add_argument("--jump-every", type=int, default=0, help="range coder: also time the pair with a jump point every N symbols")
+opts = args.parse_args()
+coder, jump_every = opts.coder, opts.jump_every
+best = lambda fn: min(bench.event_ms(fn, 5) for _ in range(3))      # best of three event timings of five calls
 rng = np.random.default_rng(1)
 n_docs, n_sym, P = 100_000, 64, 24
 probs = rng.dirichlet(np.ones(n_sym) * 0.5)
@@ -47,6 +52,19 @@ for label, lengths in (("20 .. 2000 symbols, shuffled", np.exp(rng.uniform(np.lo
               f"{n / e / 1e6:.1f} Gsym/s)  decode {d:.3f} ms ({d * 1e3 / n_docs:.3f} us/doc, {n / d / 1e6:.1f} Gsym/s)  |  "
               f"ans, no jump points: encode {ae:.3f} ms  decode {ad:.3f} ms  |  range / ans: encode {e / ae:.2f}x  decode {d / ad:.2f}x  ok={ok}",
               flush=True)
+        if jump_every:
+            jenc = B.range_encode_ragged_jump(flat, off_d, model, jump_every=jump_every)
+            jdec, jst = B.range_decode_ragged(jenc, model, off_d)
+            jok = (B.last_kernel() == "range_decode_ragged_kernel<jump>" and bool(torch.equal(jdec, flat)) and bool(torch.equal(jenc.n_words, enc.n_words))
+                   and int(jenc.status.abs().sum()) == 0 and int(jst.abs().sum()) == 0)
+            runs = [(best(lambda: B.range_encode_ragged(flat, off_d, model)), best(lambda: B.range_decode_ragged(enc, model, off_d, out=dec)),
+                     best(lambda: B.range_encode_ragged_jump(flat, off_d, model, jump_every=jump_every)),
+                     best(lambda: B.range_decode_ragged(jenc, model, off_d, out=jdec))) for _ in range(2)]
+            pair = lambda k: " / ".join(f"{r[k]:.3f}" for r in runs)
+            print(f"    jump point every {jump_every} symbols ({int(jenc.jump.chunk_offsets[-1])} chunks), two runs: plain encode {pair(0)} ms  "
+                  f"plain decode {pair(1)} ms  |  jump encode {pair(2)} ms  jump decode {pair(3)} ms  |  jump / plain: encode "
+                  f"{min(r[2] for r in runs) / min(r[0] for r in runs):.2f}x  decode {min(r[3] for r in runs) / min(r[1] for r in runs):.2f}x  ok={jok}",
+                  flush=True)
         continue
     enc = B.ans_encode_ragged(flat, off_d, model)
     dec, st = B.ans_decode_ragged(enc, model, off_d)
