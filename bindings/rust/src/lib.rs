@@ -1800,6 +1800,260 @@ impl BatchedAnsCoder {
         Ok(status)
     }
 
+    /// `encode_symbols_reverse_ragged` that also notes `AnsCoder::pos()` in front of every `jump_interval` symbols of every stream (`cst_ans_encode_gaussian_ragged_jump`): chunk `j` of
+    /// stream `s` is entry `chunk_offsets[s] + j` of the returned `(pos, state)` arrays, `chunk_offsets[n_streams + 1]` the exclusive prefix
+    /// sum of `ceil(length / jump_interval)` (device memory, `n_chunks_total` its last entry or an upper bound).  `jump_interval`: a
+    /// positive multiple of 16.  The words are those of `encode_symbols_reverse_ragged`.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_reverse_ragged`; `chunk_offsets` must be that prefix sum.
+    pub unsafe fn encode_symbols_reverse_ragged_with_jump_points(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        support: RangeInclusive<i32>,
+        means: &DeviceBuffer<f64>,
+        stds: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>, DeviceBuffer<u32>, DeviceBuffer<u64>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || means.len() != symbols.len() || stds.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut pos: DeviceBuffer<u32> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut state: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        check(unsafe {
+            ffi::cst_ans_encode_gaussian_ragged_jump(
+                self.config,
+                *support.start(),
+                *support.end(),
+                symbols.as_ptr(),
+                means.as_ptr(),
+                stds.as_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                pos.as_mut_ptr(),
+                state.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status, pos, state))
+    }
+
+    /// The decoder of the `_with_jump_points` encoder (`cst_ans_decode_gaussian_ragged_jump`): every chunk of every stream as a coder of its own (seek + at most
+    /// `jump_interval` symbols), so that a launch lasts as long as a chunk, not as its longest stream.  One status per stream.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_ragged`.  The jump table is checked against the lengths and word counts on the device.
+    pub unsafe fn decode_symbols_ragged_from_jump_points(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        support: RangeInclusive<i32>,
+        means: &DeviceBuffer<f64>,
+        stds: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        symbols: &mut DeviceBuffer<i32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        pos: &DeviceBuffer<u32>,
+        state: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if means.len() != symbols.len() || stds.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || pos.len() < n_chunks_total || state.len() < n_chunks_total || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) })?;
+        check(unsafe {
+            ffi::cst_ans_decode_gaussian_ragged_jump(
+                self.config,
+                *support.start(),
+                *support.end(),
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                means.as_ptr(),
+                stds.as_ptr(),
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                n_chunks_total,
+                pos.as_ptr(),
+                state.as_ptr(),
+                scratch.as_mut_ptr() as *mut c_void,
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
+        Ok(status)
+    }
+
+    /// `encode_symbols_reverse_family_ragged` that also notes `AnsCoder::pos()` in front of every `jump_interval` symbols of every stream (`cst_ans_encode_family_ragged_jump`): chunk `j` of
+    /// stream `s` is entry `chunk_offsets[s] + j` of the returned `(pos, state)` arrays, `chunk_offsets[n_streams + 1]` the exclusive prefix
+    /// sum of `ceil(length / jump_interval)` (device memory, `n_chunks_total` its last entry or an upper bound).  `jump_interval`: a
+    /// positive multiple of 16.  The words are those of `encode_symbols_reverse_family_ragged`.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_reverse_family_ragged`; `chunk_offsets` must be that prefix sum.
+    pub unsafe fn encode_symbols_reverse_family_ragged_with_jump_points(
+        &self,
+        family: Family,
+        symbols: &DeviceBuffer<i32>,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>, DeviceBuffer<u32>, DeviceBuffer<u64>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || a.len() != symbols.len() || b.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut pos: DeviceBuffer<u32> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut state: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        check(unsafe {
+            ffi::cst_ans_encode_family_ragged_jump(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                symbols.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                pos.as_mut_ptr(),
+                state.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status, pos, state))
+    }
+
+    /// The decoder of the `_with_jump_points` encoder (`cst_ans_decode_family_ragged_jump`): every chunk of every stream as a coder of its own (seek + at most
+    /// `jump_interval` symbols), so that a launch lasts as long as a chunk, not as its longest stream.  One status per stream.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_family_ragged`.  The jump table is checked against the lengths and word counts on the device.
+    pub unsafe fn decode_symbols_family_ragged_from_jump_points(
+        &self,
+        family: Family,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        symbols: &mut DeviceBuffer<i32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        pos: &DeviceBuffer<u32>,
+        state: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if a.len() != symbols.len() || b.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || pos.len() < n_chunks_total || state.len() < n_chunks_total || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) })?;
+        check(unsafe {
+            ffi::cst_ans_decode_family_ragged_jump(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                n_chunks_total,
+                pos.as_ptr(),
+                state.as_ptr(),
+                scratch.as_mut_ptr() as *mut c_void,
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
+        Ok(status)
+    }
+
     /// `encode_ragged` that also notes `AnsCoder::pos()` in front of every `jump_interval` symbols of every stream (ABI 5,
     /// `cst_ans_encode_ragged_jump`; `Pos`, src/stream/stack.rs:1107-1116): chunk `j` of stream `s` is entry `chunk_offsets[s] + j` of
     /// the returned `(pos, state)` arrays, `chunk_offsets[n_streams + 1]` the exclusive prefix sum of `ceil(length / jump_interval)`
@@ -2597,6 +2851,136 @@ impl BatchedRangeEncoder {
         Ok((n_words, status))
     }
 
+    /// `encode_symbols_ragged` that also notes `RangeEncoder::pos()` in front of every `jump_interval` symbols of every stream (`cst_range_encode_gaussian_ragged_jump`): chunk `j` of
+    /// stream `s` is entry `chunk_offsets[s] + j` of the returned `(pos, lower, range)` arrays, `chunk_offsets[n_streams + 1]` the exclusive prefix
+    /// sum of `ceil(length / jump_interval)` (device memory, `n_chunks_total` its last entry or an upper bound).  `jump_interval`: a
+    /// positive multiple of 16.  The words are those of `encode_symbols_ragged`.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_ragged`; `chunk_offsets` must be that prefix sum.
+    pub unsafe fn encode_symbols_ragged_with_jump_points(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        support: RangeInclusive<i32>,
+        means: &DeviceBuffer<f64>,
+        stds: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>, DeviceBuffer<u32>, DeviceBuffer<u64>, DeviceBuffer<u64>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || means.len() != symbols.len() || stds.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut pos: DeviceBuffer<u32> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut lower: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut range: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        check(unsafe {
+            ffi::cst_range_encode_gaussian_ragged_jump(
+                self.config,
+                *support.start(),
+                *support.end(),
+                symbols.as_ptr(),
+                means.as_ptr(),
+                stds.as_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                pos.as_mut_ptr(),
+                lower.as_mut_ptr(),
+                range.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status, pos, lower, range))
+    }
+
+    /// `encode_symbols_family_ragged` that also notes `RangeEncoder::pos()` in front of every `jump_interval` symbols of every stream (`cst_range_encode_family_ragged_jump`): chunk `j` of
+    /// stream `s` is entry `chunk_offsets[s] + j` of the returned `(pos, lower, range)` arrays, `chunk_offsets[n_streams + 1]` the exclusive prefix
+    /// sum of `ceil(length / jump_interval)` (device memory, `n_chunks_total` its last entry or an upper bound).  `jump_interval`: a
+    /// positive multiple of 16.  The words are those of `encode_symbols_family_ragged`.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_family_ragged`; `chunk_offsets` must be that prefix sum.
+    pub unsafe fn encode_symbols_family_ragged_with_jump_points(
+        &self,
+        family: Family,
+        symbols: &DeviceBuffer<i32>,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>, DeviceBuffer<u32>, DeviceBuffer<u64>, DeviceBuffer<u64>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || a.len() != symbols.len() || b.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut pos: DeviceBuffer<u32> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut lower: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut range: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        check(unsafe {
+            ffi::cst_range_encode_family_ragged_jump(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                symbols.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                pos.as_mut_ptr(),
+                lower.as_mut_ptr(),
+                range.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status, pos, lower, range))
+    }
+
     /// `encode_symbols` with one Categorical model per symbol, given as probabilities (Python `RangeEncoder.encode(symbols, Categorical(lazy=True), probabilities)`).
     /// `probabilities`: one vector of `n_symbols` entries per symbol, of the symbol matrix's shape and layout.
     pub fn encode_symbols_categorical<F: Probability>(
@@ -3335,6 +3719,138 @@ impl BatchedRangeDecoder {
                 stream.as_raw(),
             )
         })?;
+        Ok(status)
+    }
+
+    /// The decoder of the `_with_jump_points` encoder (`cst_range_decode_gaussian_ragged_jump`): every chunk of every stream as a coder of its own (seek + at most
+    /// `jump_interval` symbols), so that a launch lasts as long as a chunk, not as its longest stream.  One status per stream.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_ragged`.  The jump table is checked against the lengths and word counts on the device.
+    pub unsafe fn decode_symbols_ragged_from_jump_points(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        support: RangeInclusive<i32>,
+        means: &DeviceBuffer<f64>,
+        stds: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        symbols: &mut DeviceBuffer<i32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        pos: &DeviceBuffer<u32>,
+        lower: &DeviceBuffer<u64>,
+        range: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if means.len() != symbols.len() || stds.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || pos.len() < n_chunks_total || lower.len() < n_chunks_total || range.len() < n_chunks_total || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) })?;
+        check(unsafe {
+            ffi::cst_range_decode_gaussian_ragged_jump(
+                self.config,
+                *support.start(),
+                *support.end(),
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                means.as_ptr(),
+                stds.as_ptr(),
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                n_chunks_total,
+                pos.as_ptr(),
+                lower.as_ptr(),
+                range.as_ptr(),
+                scratch.as_mut_ptr() as *mut c_void,
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
+        Ok(status)
+    }
+
+    /// The decoder of the `_with_jump_points` encoder (`cst_range_decode_family_ragged_jump`): every chunk of every stream as a coder of its own (seek + at most
+    /// `jump_interval` symbols), so that a launch lasts as long as a chunk, not as its longest stream.  One status per stream.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_family_ragged`.  The jump table is checked against the lengths and word counts on the device.
+    pub unsafe fn decode_symbols_family_ragged_from_jump_points(
+        &self,
+        family: Family,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        support: RangeInclusive<i32>,
+        a: &DeviceBuffer<f64>,
+        b: &DeviceBuffer<f64>,
+        sym_offsets: &DeviceBuffer<u64>,
+        symbols: &mut DeviceBuffer<i32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        pos: &DeviceBuffer<u32>,
+        lower: &DeviceBuffer<u64>,
+        range: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if a.len() != symbols.len() || b.len() != symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || pos.len() < n_chunks_total || lower.len() < n_chunks_total || range.len() < n_chunks_total || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) })?;
+        check(unsafe {
+            ffi::cst_range_decode_family_ragged_jump(
+                self.config,
+                family.raw(),
+                *support.start(),
+                *support.end(),
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                a.as_ptr(),
+                b.as_ptr(),
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                n_chunks_total,
+                pos.as_ptr(),
+                lower.as_ptr(),
+                range.as_ptr(),
+                scratch.as_mut_ptr() as *mut c_void,
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
         Ok(status)
     }
 

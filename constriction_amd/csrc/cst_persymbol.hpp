@@ -3,6 +3,7 @@
 //   cst_persymbol.hip              what every family shares, the explicit models, every rectangular decoder but the Categorical ones
 //   cst_persymbol_encode.hip       Gaussian / Laplace / Cauchy encoders
 //   cst_persymbol_ragged.hip       streams of different lengths
+//   cst_persymbol_ragged_jump.hip  ... with jump points (both share their kernels through cst_persymbol_ragged.hpp)
 //   cst_persymbol_categorical.hip  Categorical models from probability matrices
 // EVERY KERNEL INSTANTIATION LIVES IN ONE FILE: nothing here is relocatable device code, so a second implicit instantiation would
 // compile and ship the kernel twice.  A kernel needed from another file is reached through a host launcher declared here and defined
@@ -330,6 +331,8 @@ template <class FAM> struct FamilyNames;
         static constexpr const char* by_rows = "decode_" word "_by_rows";                                                                 \
         static constexpr const char* ragged[2][2] = {{"ans_encode_" word "_ragged_kernel", "ans_decode_" word "_ragged_kernel"},          \
                                                      {"range_encode_" word "_ragged_kernel", "range_decode_" word "_ragged_kernel"}};     \
+        static constexpr const char* ragged_jump[2][2] = {{"ans_encode_" word "_ragged_kernel<jump>", "ans_decode_" word "_ragged_kernel<jump>"},      \
+                                                          {"range_encode_" word "_ragged_kernel<jump>", "range_decode_" word "_ragged_kernel<jump>"}}; \
     }
 CST_FAMILY_NAMES(GaussianFamily, "gaussian");
 CST_FAMILY_NAMES(LaplaceFamily, "laplace");

@@ -1,468 +1,11 @@
 // cst_persymbol_ragged.hip -- per-symbol Gaussian, Laplace and Cauchy models for streams of DIFFERENT lengths (cst_persymbol.hpp has the
-// map of the per-symbol files): encode_gaussian_ragged_kernel, decode_gaussian_ragged_kernel and their eight entry points.
-// (The kernels named "gaussian" are generic: FAM is a policy of cst_family_policy.hpp, and only the Gaussian stages the erf tables.)
-#include "cst_persymbol.hpp"
+// map of the per-symbol files): the plain forms of encode_gaussian_ragged_kernel and decode_gaussian_ragged_kernel
+// (cst_persymbol_ragged.hpp) and their eight entry points.  Their forms with jump points: cst_persymbol_ragged_jump.hip.
+#include "cst_persymbol_ragged.hpp"
 
 namespace cst {
 
-// ------------------------------------------------------------------------------------------------
-// per-symbol models for streams of DIFFERENT lengths (cst_ans_{encode,decode}_gaussian_ragged): the fused encoder and the
-// lane-per-stream decoder above with CSR-style indexing -- stream s owns elements [sym_offsets[s], sym_offsets[s + 1]) of the flat
-// symbols / means / stds, and its words go to / come from a slab of its own (cst_ans_ragged.hip's convention, word_slice's
-// bounds check).  Lane slot i codes stream order[i] (null: i).  A wave runs as many tiles as its longest stream has; the lanes of
-// shorter streams sit the others out.  One route for every batch size: few streams leave most of the chip idle (the
-// rectangular calls have their two-pass and by-rows forms for that; here it is a matter of speed, never of correctness).
-// Every stream's words, count and status are those of the rectangular kernels for that stream alone: the entries, the coder
-// steps and the bracket search are the same code.
-// ------------------------------------------------------------------------------------------------
-
-// lane slot -> stream: the slot itself, or order[slot] (an entry that is not a stream leaves its lane idle)
-__device__ __forceinline__ size_t persymbol_ragged_stream(const uint32_t* order, size_t slot, size_t n_streams, bool& active) {
-    active = slot < n_streams;
-    if (!active || !order) return slot;
-    const size_t s = order[slot];
-    active = s < n_streams;
-    return s;
-}
-
-__device__ __forceinline__ uint32_t persymbol_wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-
-struct GaussianRaggedEncodeArgs {
-    const int32_t* symbols;
-    const double* means;
-    const double* stds;
-    const uint64_t* sym_offsets;     // [n_streams + 1]
-    size_t n_streams;
-    const uint32_t* order;           // null, or [n_streams]
-    int32_t precision, lo, hi;
-    uint32_t* words;
-    const uint64_t* word_offsets;    // [n_streams + 1]: slab of stream s = [off[s], off[s + 1]), or null: s * stride_words
-    size_t stride_words;
-    uint32_t* n_words;
-    int32_t* status;
-};
-
-// LDS per wave on top of the fused kernel's ring and entry tile: (element offset, length) of the wave's kFuStreams streams,
-// staged once -- the sixteen lanes that build stream j's entries read j's pair from here, not from HBM per item
-constexpr size_t kRgMetaBytes = (size_t)kFuStreams * sizeof(uint4);
-constexpr size_t kRgEncWaveBytes = kFuWaveBytes + kRgMetaBytes;
-
-// encode_gaussian_fused_kernel<W, S, KIND> in its general form (per-item index and ok_q; walking by adding and PAIR need whole
-// tiles of one matrix).  Tile k of stream j covers symbols [16 k, 16 k + 16) of its row; the wave codes max_j ceil(len_j / 16)
-// tiles, last to first (ANS, a stack) or first to last (the range coder, a queue); whole-tile or symbol-by-symbol steps are
-// each lane's own decision.
-template <int W, int S, int KIND, class FAM = GaussianFamily>
-__global__ __launch_bounds__(kFuBlock) void encode_gaussian_ragged_kernel(const GaussianRaggedEncodeArgs a) {
-    static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
-    constexpr size_t kTabBytes = FAM::kErfTab ? kFuTabBytes : 0;
-    constexpr int kWaves = kFuBlock / kWave;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & (kWave - 1), wave_in_block = threadIdx.x >> 6;
-    // LDS: [word rings, one per wave, aligned to their size][erf tables][entry tiles, one per wave][stream offsets and lengths, per wave]
-    constexpr size_t kRingBytes = (size_t)kFuRingSlots * kWave * 4, kTileBytes = kFuWaveBytes - kRingBytes;
-    uint32_t* ring = reinterpret_cast<uint32_t*>(smem + (size_t)wave_in_block * kRingBytes);
-    double2* erf_tab = reinterpret_cast<double2*>(smem + kWaves * kRingBytes);
-    EncEntry* tile = reinterpret_cast<EncEntry*>(smem + kWaves * kRingBytes + kTabBytes + (size_t)wave_in_block * kTileBytes);
-    uint4* meta = reinterpret_cast<uint4*>(smem + kWaves * kRingBytes + kTabBytes + kWaves * kTileBytes + (size_t)wave_in_block * kRgMetaBytes);
-    if ((lds_addr(ring) & (uint32_t)(kRingBytes - 1)) != 0) __builtin_trap();
-    if constexpr (FAM::kErfTab) {
-        erf_tab_fill(erf_tab, threadIdx.x, blockDim.x);
-        __syncthreads();
-    }
-    const size_t slot0 = ((size_t)blockIdx.x * kWaves + wave_in_block) * kFuStreams;
-    if (slot0 >= a.n_streams) return;
-    const int P = a.precision;
-    const bool use_inv = KIND == kAns && W == 32 && S == 64 && P >= kInvMinPrecision;      // entries with 1 / p (make_entry_inv)
-    bool active = false;
-    size_t s = 0;
-    if (lane < kFuStreams) s = persymbol_ragged_stream(a.order, slot0 + (size_t)lane, a.n_streams, active);   // this lane codes a stream in phase B
-    const uint64_t sym_lo = active ? a.sym_offsets[s] : 0, sym_hi = active ? a.sym_offsets[s + 1] : 0;
-    const bool too_long = sym_hi - sym_lo > 0xffffffffull || sym_hi < sym_lo;
-    const uint32_t len = too_long ? 0u : (uint32_t)(sym_hi - sym_lo);
-    if (lane < kFuStreams) meta[lane] = uint4{(uint32_t)sym_lo, (uint32_t)(sym_lo >> 32), len, 0u};
-    const uint32_t n_tiles = persymbol_wave_max((len >> 4) + ((len & (uint32_t)(kFuTile - 1)) != 0 ? 1u : 0u));
-    static_assert(kFuTile == 16, "tile counts above shift by four");
-    wave_lds_fence();
-
-    // phase A's work items: item w = it * 64 + lane of a tile is (stream j = w / 16, symbol tl = w % 16): sixteen consecutive
-    // lanes on consecutive elements of one stream's row.  Requested kFuAhead items ahead of their use, as in the fused kernel.
-    int32_t sy_q[kFuAhead];
-    double mu_q[kFuAhead], sd_q[kFuAhead];
-    bool ok_q[kFuAhead];
-    const int item_t = lane & (kFuTile - 1), item_j0 = lane >> 4;
-    auto request = [&](int slot, uint32_t k, int it) {
-        const uint4 m = meta[it * (kWave / kFuTile) + item_j0];
-        const uint64_t t = (uint64_t)k * kFuTile + (uint64_t)item_t;
-        ok_q[slot] = t < (uint64_t)m.z;
-        // (unconditional loads from an address that is always valid -- a wave with a tile to code has a symbol, so element 0
-        //  exists: a conditional load is waited for at once)
-        const uint64_t e = ok_q[slot] ? ((((uint64_t)m.y) << 32) | (uint64_t)m.x) + t : 0;
-        sy_q[slot] = __builtin_nontemporal_load(a.symbols + e);
-        mu_q[slot] = __builtin_nontemporal_load(a.means + e);
-        sd_q[slot] = __builtin_nontemporal_load(a.stds + e);
-    };
-
-    const uint64_t slab_lo = !active ? 0 : (a.word_offsets ? a.word_offsets[s] : (uint64_t)s * a.stride_words);
-    // (offsets that run backwards give the stream a slab of NO words: it reports CST_STREAM_CAPACITY and writes nothing)
-    const uint64_t slab_hi = !active ? 0 : (a.word_offsets ? a.word_offsets[s + 1] : 0);
-    const uint64_t slab_n = !active ? 0 : (a.word_offsets ? (slab_hi >= slab_lo ? slab_hi - slab_lo : 0) : (uint64_t)a.stride_words);
-    EncLane<W, S, kFuRingSlots> LA;
-    RangeEncLane<W, S, kFuRingSlots> LR;
-    if constexpr (KIND == kAns) LA.init(a.words + slab_lo, (uint32_t)(slab_n > 0xffffffffull ? 0xffffffffull : slab_n), ring, lane);
-    else LR.init(a.words + slab_lo, (uint32_t)(slab_n > 0xffffffffull ? 0xffffffffull : slab_n), ring, lane);
-    uint32_t bad = 0;
-
-    if (n_tiles > 0) {
-#pragma unroll
-        for (int q = 0; q < kFuAhead; ++q) request(q, KIND == kAns ? n_tiles - 1u : 0u, q);
-    }
-    for (uint32_t step = 0; step < n_tiles; ++step) {
-        const uint32_t k = KIND == kAns ? n_tiles - 1u - step : step;      // ANS codes last to first, the range coder first to last
-        wave_lds_fence();                                      // (the previous tile has been read)
-        // ---- phase A: entries of tile k ----
-#pragma unroll 1
-        for (int it0 = 0; it0 < kFuIters; it0 += kFuAhead) {
-#pragma unroll
-            for (int q = 0; q < kFuAhead; ++q) {
-                const int it = it0 + q;
-                const int32_t sy = ok_q[q] ? sy_q[q] : a.lo;       // (items past their stream's end: never coded)
-                const double m = ok_q[q] ? mu_q[q] : 0.0, sg = ok_q[q] ? sd_q[q] : 1.0;
-                if (it + kFuAhead < kFuIters) request(q, k, it + kFuAhead);
-                else if (step + 1 < n_tiles) request(q, KIND == kAns ? k - 1u : k + 1u, it + kFuAhead - kFuIters);
-                uint32_t c = 0, p = 0;
-                // invalid parameters, out-of-support symbols and degenerate distributions all end up with p = 0 = impossible
-                // (see the fused kernel); no branches: invalid parameters are evaluated as (0, 1) and thrown away
-                const bool valid = FAM::valid(m, sg);
-                const bool inside = FAM::lcp(sy, a.lo, a.hi, P, valid ? m : 0.0, valid ? sg : 1.0, c, p, erf_tab);
-                if (!valid || !inside || (uint64_t)c + p > ((uint64_t)1 << P)) p = 0;
-                EncEntry entry{c, p, 0u, 0u};                                   // (the range coder divides by nothing)
-                if constexpr (KIND == kAns) entry = use_inv ? make_entry_inv(c, p) : make_entry_f64(c, p);
-                tile[item_t * kFuRowStride + it * (kWave / kFuTile) + item_j0] = entry;
-            }
-        }
-        wave_lds_fence();
-        // ---- phase B: every stream's lane over what its row has of this tile ----
-        const uint64_t t0 = (uint64_t)k * kFuTile;
-        const int n_here = !active || t0 >= (uint64_t)len ? 0 : ((uint64_t)len - t0 < (uint64_t)kFuTile ? (int)((uint64_t)len - t0) : kFuTile);
-        if constexpr (KIND == kAns) {
-            constexpr bool FAST = W == 32 && S == 64;               // the 32-bit-halves step (8 <= P)
-            if (FAST && P >= 8 && n_here == kFuTile) {
-                // a whole tile: all sixteen entries first (one LDS wait), then sixteen hand-scheduled steps.  An impossible symbol
-                // is coded as (0, 1) -- its stream is flagged and its words are never used.
-                EncEntry e[kFuTile];
-#pragma unroll
-                for (int tl = 0; tl < kFuTile; ++tl) e[tl] = tile[tl * kFuRowStride + lane];
-#pragma unroll
-                for (int tl = kFuTile - 1; tl >= 0; --tl) {
-                    const bool none = e[tl].p == 0;
-                    bad |= none ? 1u : 0u;
-                    if constexpr (FAST) {
-                        if (use_inv) encode_step_inv(LA, none ? 0u : e[tl].c, none ? 1u : e[tl].p, none ? 1.0 : f64_from(e[tl].m_lo, e[tl].m_hi), P);
-                        else LA.template step<FAST>(EncEntry{none ? 0u : e[tl].c, none ? 1u : e[tl].p, none ? 0xffffffffu : e[tl].m_lo, none ? 0xffffffffu : e[tl].m_hi}, P);
-                    }
-                }
-            } else {
-                // (other presets, P < 8, the end of a row; n_here = 0: this lane's stream has nothing in the tile)
-                for (int tl = n_here - 1; tl >= 0; --tl) {
-                    const EncEntry e = tile[tl * kFuRowStride + lane];
-                    if (e.p == 0) bad = 1;
-                    else if (!bad) LA.template step<false>(use_inv ? make_entry(e.c, e.p) : e, P);
-                }
-            }
-        } else if (n_here == kFuTile) {
-            // a whole tile: all sixteen (c, p) first (one LDS wait), then sixteen steps in coding order; an impossible symbol is
-            // coded as (0, 1) -- its stream is flagged and its words are never used
-            uint2 e[kFuTile];
-#pragma unroll
-            for (int tl = 0; tl < kFuTile; ++tl) e[tl] = *reinterpret_cast<const uint2*>(&tile[tl * kFuRowStride + lane]);
-#pragma unroll
-            for (int tl = 0; tl < kFuTile; ++tl) {
-                const bool none = e[tl].y == 0;
-                bad |= none ? 1u : 0u;
-                LR.step(none ? 0u : e[tl].x, none ? 1u : e[tl].y, P);
-            }
-        } else {
-            // (the end of a row; n_here = 0: this lane's stream has nothing in the tile)
-            for (int tl = 0; tl < n_here; ++tl) {
-                const EncEntry e = tile[tl * kFuRowStride + lane];
-                if (e.p == 0) bad = 1;
-                else if (!bad) LR.step(e.c, e.p, P);
-            }
-        }
-        // at most kFuTile new words per stream and tile: whole chunks leave here (<= 19 pending before, < 4 after)
-        if constexpr (KIND == kAns) LA.flush_chunks(); else LR.out.flush_chunks();
-    }
-
-    uint32_t n_words = 0;
-    int32_t status;
-    if constexpr (KIND == kAns) status = LA.finish(true, 1u, n_words);
-    else status = LR.finish(1u, n_words);               // (no symbols: `range` is still all ones and nothing is sealed)
-    if (!active) return;
-    if (bad) status = CST_STREAM_IMPOSSIBLE_SYMBOL;
-    if (too_long) status = CST_STREAM_CAPACITY;
-    a.status[s] = status;
-    a.n_words[s] = status == CST_STREAM_OK ? n_words : 0u;
-}
-
-struct GaussianRaggedDecodeArgs {
-    PerSymbolDecodeArgs p;           // words / offsets / stride_words / n_words / words_capacity, symbols (flat), means, stds (flat), the support
-    const uint64_t* sym_offsets;     // [n_streams + 1]
-    const uint32_t* order;           // null, or [n_streams]
-};
-
-typedef struct __attribute__((packed, aligned(4))) { v4i v; } v4i_at4;      // a 16-byte access at a 4-byte boundary
-
-// The decoder's geometry: the tiles of LaneGeo<true> (parameter tiles of 8, a 16-slot word window, a 16-symbol output tile:
-// 17 KiB per wave) in workgroups of FOUR waves -- two workgroups per CU, so two waves per SIMD cover each other's waits as
-// in the rectangular small geometry, which matters more here (a wave waits for its longest lane, and a row that starts
-// anywhere takes two cache lines for its eight doubles), while a batch spreads over twice as many CUs as with eight-wave
-// workgroups.  The pair requests of the rectangular small geometry need rows of one length and do not apply.
-constexpr int kRgDecThreads = kBlock;
-constexpr size_t kRgDecLdsBytes = kErfTabBytes + (size_t)(kRgDecThreads / kWave) * LaneGeo<true>::kWaveBytes;
-constexpr size_t kRgDecLdsBytesNoTab = (size_t)(kRgDecThreads / kWave) * LaneGeo<true>::kWaveBytes;
-
-// 16-symbol output tile -> HBM: piece (lane & 3) of rows (lane >> 2) + 16 k, as store_symbol_tile16 -- but every row has its
-// own start (4-byte aligned, nothing more) and its own end: the owner lane's (offset, length) come by cross-lane read, a
-// piece that lies wholly inside its row is one unaligned 16-byte store, the piece at a row's end goes word by word.
-__device__ __noinline__ void store_symbol_tile_ragged(int32_t* sym, uint32_t off_lo, uint32_t off_hi, uint32_t len, uint64_t t0, int lane,
-                                                      const int32_t* tile) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int r = (lane >> 2) + 16 * k;
-        const uint64_t off = ((uint64_t)(uint32_t)__shfl((int)off_hi, r) << 32) | (uint64_t)(uint32_t)__shfl((int)off_lo, r);
-        const uint64_t n = (uint64_t)(uint32_t)__shfl((int)len, r);
-        const uint64_t tp = t0 + 4u * (uint32_t)(lane & 3);
-        if (tp >= n) continue;
-        const int32_t* src = tile + r * 20 + 4 * (lane & 3);
-        int32_t* dst = sym + off + tp;
-        if (tp + 4 <= n) {
-            const int4 v = *reinterpret_cast<const int4*>(src);
-            v4i t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-            reinterpret_cast<v4i_at4*>(dst)->v = t;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                if (tp + (uint64_t)i < n) dst[i] = src[i];
-        }
-    }
-}
-
-// decode_gaussian_lane_kernel<W, S, KIND> for ragged rows: one lane per stream, parameters one tile ahead in the item mapping
-// that puts consecutive lanes on consecutive addresses, the word window, FAM::left3 and the bracket search as they are.  The
-// loop runs to the wave's longest stream; a lane past its own length decodes and stores nothing but goes on taking part in the
-// wave-wide loads and fences.
-template <int W, int S, int KIND, class FAM = GaussianFamily>
-__global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(const GaussianRaggedDecodeArgs ra) {
-    static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
-    using G = LaneGeo<true>;
-    constexpr int kParTile = G::kParTile, kWordWindow = G::kWordWindow, kOutSyms = G::kOutSyms, kOutStride = G::kOutStride;
-    static_assert(kOutSyms == 16 && kOutStride == 20, "store_symbol_tile_ragged's tile");
-    const PerSymbolDecodeArgs& a = ra.p;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double2* erf_tab = reinterpret_cast<double2*>(smem);
-    if constexpr (FAM::kErfTab) {
-        erf_tab_fill(erf_tab, threadIdx.x, blockDim.x);
-        __syncthreads();
-    }
-    const int lane = threadIdx.x & (kWave - 1);
-    unsigned char* mine = smem + (FAM::kErfTab ? kErfTabBytes : 0) + (size_t)(threadIdx.x >> 6) * G::kWaveBytes;
-    int32_t* tile = reinterpret_cast<int32_t*>(mine);
-    double* par_mu = reinterpret_cast<double*>(mine + (size_t)kWave * kOutStride * 4);
-    double* par_sd = par_mu + kParTile * kParStride;
-    uint32_t* win = reinterpret_cast<uint32_t*>(par_sd + kParTile * kParStride);
-    const size_t slot = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot - lane >= a.n_streams) return;
-    bool active;
-    const size_t s = persymbol_ragged_stream(ra.order, slot, a.n_streams, active);
-    const size_t se = active ? s : 0;                         // idle lanes look at stream 0's words and decode nothing
-    const uint64_t sym_lo = active ? ra.sym_offsets[s] : 0, sym_hi = active ? ra.sym_offsets[s + 1] : 0;
-    const bool too_long = sym_hi - sym_lo > 0xffffffffull || sym_hi < sym_lo;
-    const uint32_t len = too_long ? 0u : (uint32_t)(sym_hi - sym_lo);
-    const uint32_t off_lo = (uint32_t)sym_lo, off_hi = (uint32_t)(sym_lo >> 32);
-    const uint64_t mx = persymbol_wave_max(len);
-    const int P = a.precision;
-    const uint32_t n = (uint32_t)a.n_symbols;
-    const double free_weight = (double)((P >= 32 ? 0xffffffffu : ((1u << P) - 1u)) - (n - 1u));
-    const float total_f = (float)(1ull << P), free_f = (float)free_weight, inv_total_f = 1.0f / total_f, inv_free_f = 1.0f / free_f;
-    const double guess_shift = 0.5 - (double)a.min_symbol;            // symbol index of the real number x: x - min_symbol + 0.5
-    const bool two_step_guess = (double)n * 64.0 > free_weight;      // the leak moves the guess by more than 1/64 quantile
-
-    DirectDecoder<W, S, KIND> D;
-    D.init(a, se, false);
-    int32_t status = D.status;
-
-    // ---- parameter tiles: item w = it * 64 + lane of a tile is (stream j = w / 8, symbol tl = w % 8): eight consecutive lanes
-    // on consecutive doubles of one stream's row, element sym_offsets[sj] + t0 + tl, predicated on len_sj (lane j's values, by
-    // cross-lane read) ----
-    double mu_r[kParTile], sd_r[kParTile];
-    const int item_t = lane & (kParTile - 1), item_j0 = lane / kParTile;
-    auto par_request = [&](uint64_t t0) {
-#pragma unroll
-        for (int it = 0; it < kParTile; ++it) {
-            const int j = it * (kWave / kParTile) + item_j0;
-            const uint64_t off = ((uint64_t)(uint32_t)__shfl((int)off_hi, j) << 32) | (uint64_t)(uint32_t)__shfl((int)off_lo, j);
-            const uint64_t t = t0 + (uint64_t)item_t;
-            // (an element that does not exist: element 0, which does -- the wave has a symbol to decode)
-            const uint64_t e = t < (uint64_t)(uint32_t)__shfl((int)len, j) ? off + t : 0;
-            mu_r[it] = __builtin_nontemporal_load(a.means + e);
-            sd_r[it] = __builtin_nontemporal_load(a.stds + e);
-        }
-    };
-    auto par_land = [&]() {
-#pragma unroll
-        for (int it = 0; it < kParTile; ++it) {
-            par_mu[item_t * kParStride + it * (kWave / kParTile) + item_j0] = mu_r[it];
-            par_sd[item_t * kParStride + it * (kWave / kParTile) + item_j0] = sd_r[it];
-        }
-    };
-    // ---- word window: as in the lane kernel (a tile of 8 symbols takes at most 8 words; the range coder's first S / W words
-    // are taken by init, before the window starts).  ANS reads downwards from its position: every index from 0 up to it exists.
-    // The range coder reads upwards: an index exists below the stream's length. ----
-    constexpr bool kDownward = DirectDecoder<W, S, KIND>::kDownward;
-    uint32_t w_r[kParTile];
-    int64_t w_first = 0;                                      // index of w_r[0]
-    auto win_request = [&](int64_t first) {
-        w_first = first;
-        if constexpr (kDownward) {
-            if (!__any(first < 0)) {                              // every lane's words exist: one pointer, eight offsets
-                const uint32_t* pw = D.in + first;
-#pragma unroll
-                for (int i = 0; i < kParTile; ++i) w_r[i] = pw[i];
-                return;
-            }
-#pragma unroll
-            for (int i = 0; i < kParTile; ++i) {
-                const int64_t p = first + i;
-                w_r[i] = *(p >= 0 ? D.in + p : D.idle);
-            }
-        } else {
-            const int64_t len = (int64_t)D.length();
-            if (!__any(first < 0 || first + kParTile > len)) {
-                const uint32_t* pw = D.in + first;
-#pragma unroll
-                for (int i = 0; i < kParTile; ++i) w_r[i] = pw[i];
-                return;
-            }
-#pragma unroll
-            for (int i = 0; i < kParTile; ++i) {
-                const int64_t p = first + i;
-                w_r[i] = *(p >= 0 && p < len ? D.in + p : D.idle);
-            }
-        }
-    };
-    auto win_land = [&]() {
-#pragma unroll
-        for (int i = 0; i < kParTile; ++i) win[(((uint32_t)(w_first + i)) & (kWordWindow - 1)) * kWave + lane] = w_r[i];
-    };
-    const auto window_of = [&](int ahead_tiles) -> int64_t {  // first index of the 8 words `ahead_tiles` tiles ahead
-        if constexpr (kDownward) return (int64_t)D.position() - (int64_t)kParTile * (ahead_tiles + 1);
-        else return (int64_t)D.position() + (int64_t)kParTile * ahead_tiles;
-    };
-
-    if (mx > 0) {
-        par_request(0);
-        win_request(window_of(0));
-    }
-    for (uint64_t t0 = 0; t0 < mx; t0 += kParTile) {
-        wave_lds_fence();                                     // (the previous tile's parameters have been read)
-        par_land();
-        win_land();
-        if (t0 + kParTile < mx) par_request(t0 + kParTile);
-        win_request(window_of(1));                            // (the words one tile further: used from the next tile on)
-        wave_lds_fence();
-        const int n_wave = (int)(mx - t0 < (uint64_t)kParTile ? mx - t0 : (uint64_t)kParTile);
-#pragma unroll 1
-        for (int tl = 0; tl < n_wave; ++tl) {
-            const uint64_t t = t0 + (uint64_t)tl;
-            int32_t sym = 0;
-            const double mu = par_mu[tl * kParStride + lane], sd = par_sd[tl * kParStride + lane];
-            D.ahead = win[(((uint32_t)D.next_index()) & (kWordWindow - 1)) * kWave + lane];
-            if (t < (uint64_t)len && status == CST_STREAM_OK) {
-                // the reference panics on an invalid model (pybindings/stream/model.rs:654-657)
-                const bool model_ok = FAM::valid(mu, sd);
-                const uint32_t q = model_ok ? D.quantile(P) : 0u;
-                if (!model_ok) status = CST_STREAM_IMPOSSIBLE_SYMBOL;
-                else if (D.status != CST_STREAM_OK) status = D.status;
-                else {
-                    // the lane kernel's search, unchanged: guess, three left cumulatives around it, then the bracket
-                    const float below = (float)q + 0.5f, above = total_f - below;
-                    const bool coarse = FAM::kGaussian && !__any(sd >= 200.0);          // (wave-uniform: the cheap quantile is good enough)
-                    float z = coarse ? FAM::guess_z_coarse(fminf(below, above) * inv_total_f) : FAM::guess_z(fminf(below, above) * inv_total_f);
-                    double x = mu + sd * (double)(below < above ? z : -z) + guess_shift;
-                    if (two_step_guess) {
-                        const float b1 = below - (float)fmin(fmax(x, 0.0), (double)(n - 1u)), a1 = free_f - b1;
-                        z = FAM::guess_z(fmaxf(fminf(b1, a1), 0.25f) * inv_free_f);
-                        x = mu + sd * (double)(b1 < a1 ? z : -z) + guess_shift;
-                    }
-                    const uint32_t g = (uint32_t)fmin(fmax(x + 0.5, 1.0), (double)(n - 1u));
-                    // bracket [lo_i, hi_i): left(lo_i) = lo_v <= q < hi_v = left(hi_i)
-                    uint32_t lo_i = 0, hi_i = n, lo_v = 0, hi_v = P >= 32 ? 0u : (1u << P);
-                    uint32_t probe = g, step = 1;
-                    bool up = false, down = false;
-                    {
-                        uint32_t v3[3];
-                        FAM::left3(g, a.min_symbol, n, P, mu, sd, erf_tab, v3);
-                        if (v3[1] <= q) {
-                            up = true;
-                            if (q < v3[2]) { lo_i = g; lo_v = v3[1]; hi_i = g + 1u; hi_v = v3[2]; }
-                            else { lo_i = g + 1u; lo_v = v3[2]; probe = min(g + 2u, n - 1u); step = 2; }
-                        } else {
-                            down = true;
-                            if (v3[0] <= q) { lo_i = g - 1u; lo_v = v3[0]; hi_i = g; hi_v = v3[1]; }
-                            else { hi_i = g - 1u; hi_v = v3[0]; probe = max(g - 1u, 2u) - 1u; step = 2; }
-                        }
-                    }
-                    while (hi_i - lo_i > 1) {
-                        // (every probe lies strictly inside (lo_i, hi_i), a subset of (0, n))
-                        const uint32_t v = FAM::template left<true>((int32_t)probe, a.min_symbol, (int32_t)n, P, mu, sd, erf_tab);
-                        if (v <= q) { lo_i = probe; lo_v = v; up = true; } else { hi_i = probe; hi_v = v; down = true; }
-                        if (up && down) probe = lo_i + (hi_i - lo_i) / 2;
-                        else if (up) probe = min(lo_i + step, hi_i - 1u);
-                        else probe = max(hi_i - min(step, hi_i - 1u), lo_i + 1u);
-                        step *= 2;
-                    }
-                    const uint32_t c = lo_v, p = hi_v - lo_v;
-                    if (p == 0 || c > q || (uint64_t)c + p > ((uint64_t)1 << P)) status = CST_STREAM_IMPOSSIBLE_SYMBOL;   // degenerate distribution (quantize.rs:562-565)
-                    else {
-                        sym = a.min_symbol + (int32_t)lo_i;
-                        D.advance(q, c, p, P);
-                    }
-                }
-            }
-            // (a lane past its length writes a zero into its own LDS row: never stored)
-            tile[lane * kOutStride + (int)(t % kOutSyms)] = sym;
-            if (t % kOutSyms == kOutSyms - 1) {
-                wave_lds_fence();
-                store_symbol_tile_ragged(a.symbols, off_lo, off_hi, len, t - (kOutSyms - 1), lane, tile);
-                wave_lds_fence();
-            }
-        }
-    }
-    if (mx % kOutSyms != 0) {
-        wave_lds_fence();
-        store_symbol_tile_ragged(a.symbols, off_lo, off_hi, len, mx - mx % kOutSyms, lane, tile);
-    }
-    if (!active) return;
-    a.status[s] = too_long ? (int32_t)CST_STREAM_CAPACITY : status;
-}
-
 // ---- host side: one route whatever the batch ----
-// what both calls refuse before they touch the device
-static cst_status check_ragged_gaussian_args(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const void* d_symbols, const void* d_means,
-                                             const void* d_stds, const void* d_sym_offsets, const void* d_words, const void* d_word_offsets,
-                                             size_t stride_words, const void* d_n_words, const void* d_status, const void* d_order, size_t n_streams) {
-    if (!d_symbols || !d_means || !d_stds || !d_sym_offsets || !d_words || !d_n_words || !d_status) return CST_ERR_INVALID_ARGUMENT;
-    if (!config_supported(cfg) || max_symbol <= min_symbol) return CST_ERR_INVALID_ARGUMENT;
-    if (!d_word_offsets && stride_words == 0) return CST_ERR_INVALID_ARGUMENT;
-    if (d_order && n_streams > 0xffffffffull) return CST_ERR_INVALID_ARGUMENT;
-    if (support_too_large(cfg, min_symbol, max_symbol)) return CST_ERR_MODEL;      // (the support limit of the rectangular calls)
-    return CST_OK;
-}
-
 template <int KIND, class FAM>
 static cst_status launch_encode_ragged(cst_coder_config cfg, const GaussianRaggedEncodeArgs& a, hipStream_t hs) {
     const size_t per_block = (size_t)(kFuBlock / kWave) * kFuStreams;

@@ -403,7 +403,7 @@ cst_status cst_ans_decode_gaussian_ragged(cst_coder_config cfg, int32_t min_symb
  *                                        cst_range_max_words); a stream of length 0 yields 0 words and CST_STREAM_OK.
  *     family                             CST_FAMILY_LAPLACE (d_a = means, d_b = scales) or CST_FAMILY_CAUCHY (d_a = locs, d_b =
  *                                        scales), as in cst_ans_encode_family_batch; anything else: CST_ERR_INVALID_ARGUMENT.
- * No jump points for any of these. */
+ * Jump points: cst_{ans,range}_{encode,decode}_{gaussian,family}_ragged_jump below. */
 cst_status cst_range_encode_gaussian_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                             const int32_t *d_symbols, const double *d_means, const double *d_stds,
                                             const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
@@ -434,6 +434,95 @@ cst_status cst_range_decode_family_ragged(cst_coder_config cfg, int32_t family, 
                                           size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
                                           const double *d_b, int32_t *d_symbols, const uint64_t *d_sym_offsets,
                                           size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
+
+/* Jump points (the reference's Pos / Seek: src/stream/stack.rs:1107-1139, src/stream/queue.rs:172-196, 900-926) for the eight calls above.
+ * Their decoders are chains -- one lane walks one stream, a launch lasts as long as its longest stream -- so the encoder notes the
+ * coder's pos() in front of every chunk of `jump_interval` symbols of every stream on its way, and the decoder runs every chunk as a
+ * coder of its own (seek + at most jump_interval symbols) on a lane of its own: the longest chain is jump_interval steps.
+ *   - jump_interval: a positive multiple of 16 (the encoder codes in tiles of 16 symbols), at most 2^31 - 1.
+ *   - Chunk j of stream s is entry d_chunk_offsets[s] + j of the table arrays; d_chunk_offsets[n_streams + 1] (uint64, read by both calls)
+ *     is the exclusive prefix sum of ceil(length / jump_interval) -- the layout of cst_{ans,range}_{encode,decode}_ragged_jump.  Table
+ *     arrays are uint32 d_jump_pos and uint64 d_jump_state (ANS) or uint64 d_jump_lower / d_jump_range (range) for both presets.
+ *       ANS    d_jump_pos = words in the bulk, d_jump_state = the coder state once the symbols from the chunk's first on are encoded
+ *              (AnsCoder::pos()): chunk 0 is (the words in the bulk: n_words - S / W where the state fills S / W words, the final state).
+ *       range  d_jump_pos = words emitted so far INCLUDING held-back ones, d_jump_lower / d_jump_range = the RangeCoderState before the
+ *              chunk's first symbol is encoded (RangeEncoder::pos()): chunk 0 is (0, 0, all ones of the state width).
+ *     No chunk starts at the end of a stream.  The entries of a stream whose status is not CST_STREAM_OK are unspecified.
+ *   - Encoder: the arguments of the plain call (d_order included), then the interval and the table; words, d_n_words and d_status are
+ *     exactly those of the plain call.
+ *   - Decoder: the arguments of the plain call WITHOUT d_order (chunks are at most jump_interval long: nothing to schedule), then the
+ *     interval, the table (const) and d_scratch of cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) bytes.  n_chunks_total: the
+ *     entries of the table arrays; d_chunk_offsets[n_streams] or any upper bound of it (entries behind the last chunk decode nothing).
+ *   - An ANS chunk reads the words in front of its jump point.  A range chunk reads forward from its jump point, on past its chunk if
+ *     need be, never past its stream's d_n_words.  The slice of every stream is checked as the plain decoder checks it.
+ *   - One status per STREAM: the worst of its chunks'.  A table that does not describe its stream (chunks != ceil(length /
+ *     jump_interval), offsets beyond n_chunks_total) or a d_jump_pos beyond the stream's d_n_words reports CST_STREAM_INVALID_DATA for
+ *     that stream; the others decode, and nothing outside words_capacity or the stream's own symbols is touched, whatever the table holds.
+ *   - CST_ERR_INVALID_ARGUMENT, before the device is touched: every refusal of the plain call; jump_interval 0, not a multiple of 16 or
+ *     > 2^31 - 1; n_chunks_total > 2^32 - 1; a NULL d_chunk_offsets, table array or d_scratch; an unknown family.  n_streams == 0: CST_OK,
+ *     nothing is launched.
+ * cst_last_kernel_name(): {ans,range}_{encode,decode}_{gaussian,laplace,cauchy}_ragged_kernel<jump>. */
+size_t cst_persymbol_ragged_jump_scratch_bytes(size_t n_chunks_total);
+cst_status cst_ans_encode_gaussian_ragged_jump(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                               const int32_t *d_symbols, const double *d_means, const double *d_stds,
+                                               const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                               uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                               uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                               uint32_t *d_jump_pos, uint64_t *d_jump_state, int32_t *d_status,
+                                               void *stream);
+cst_status cst_ans_decode_gaussian_ragged_jump(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                               const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                               size_t words_capacity, const uint32_t *d_n_words, const double *d_means,
+                                               const double *d_stds, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                               size_t n_streams, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                               size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                               const uint64_t *d_jump_state, void *d_scratch, int32_t *d_status,
+                                               void *stream);
+cst_status cst_range_encode_gaussian_ragged_jump(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                 const int32_t *d_symbols, const double *d_means, const double *d_stds,
+                                                 const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                                 uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                 uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                 uint32_t *d_jump_pos, uint64_t *d_jump_lower, uint64_t *d_jump_range,
+                                                 int32_t *d_status, void *stream);
+cst_status cst_range_decode_gaussian_ragged_jump(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                 const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                 size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                 const double *d_means, const double *d_stds, int32_t *d_symbols,
+                                                 const uint64_t *d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                 const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                 const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
+                                                 const uint64_t *d_jump_range, void *d_scratch, int32_t *d_status,
+                                                 void *stream);
+cst_status cst_ans_encode_family_ragged_jump(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                             const int32_t *d_symbols, const double *d_a, const double *d_b,
+                                             const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                             uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                             uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                             uint32_t *d_jump_pos, uint64_t *d_jump_state, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_family_ragged_jump(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                             const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                             size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
+                                             const double *d_b, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                             size_t n_streams, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                             size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                             const uint64_t *d_jump_state, void *d_scratch, int32_t *d_status,
+                                             void *stream);
+cst_status cst_range_encode_family_ragged_jump(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                               const int32_t *d_symbols, const double *d_a, const double *d_b,
+                                               const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                               uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                               uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                               uint32_t *d_jump_pos, uint64_t *d_jump_lower, uint64_t *d_jump_range,
+                                               int32_t *d_status, void *stream);
+cst_status cst_range_decode_family_ragged_jump(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                               const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                               size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
+                                               const double *d_b, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                               size_t n_streams, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                               size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                               const uint64_t *d_jump_lower, const uint64_t *d_jump_range, void *d_scratch,
+                                               int32_t *d_status, void *stream);
 
 /* The range coder with ONE SHARED TABLE for streams of different lengths: cst_ans_{encode,decode}_ragged / cst_ans_count_until for the
  * reference's queue -- one RangeEncoder / RangeDecoder per document (src/stream/queue.rs), the symbols decoded in the order they were

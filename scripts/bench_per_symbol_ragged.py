@@ -6,6 +6,9 @@
       length (the groups' matrices are built beforehand and not timed);
   (c) the price of raggedness: the rectangular calls on a 16 384 x 4224 matrix (the same number of symbols) beside the ragged calls
       on that same matrix expressed with equal lengths.
+--jump-every N (a multiple of 16; default 0: not run): also (j) the same batch with a jump point every N symbols of every stream --
+`jump_every=N` of the encoder, and the decode of all chunks side by side -- timed beside the plain pair of (a) in the same run,
+alternating; recorded per alternation, with the size of the table against the words.  No condition on it.
 --coder ans|range and --family gaussian|laplace|cauchy choose the form (default: ans, gaussian); --skip-grouped leaves (b) out (it
 takes seconds per alternation and minutes to set up; its condition is then not judged).
 Device events on the launch stream, warmed up, in one process, the candidates alternating, medians of the alternations.  Every
@@ -24,6 +27,8 @@ ap.add_argument("--max-len", type=int, default=8192)
 ap.add_argument("--alternations", type=int, default=5)
 ap.add_argument("--coder", choices=["ans", "range"], default="ans")
 ap.add_argument("--family", choices=["gaussian", "laplace", "cauchy"], default="gaussian")
+ap.add_argument("--jump-every", type=int, default=0, help="also time the pair with a jump point every N symbols (a multiple of 16)")
+ap.add_argument("--skip-rectangular", action="store_true", help="leave (c), the rectangular matrix, out")
 ap.add_argument("--skip-grouped", action="store_true", help="leave (b), one rectangular call per distinct length, out")
 args = ap.parse_args()
 assert args.alternations >= 5 or args.streams < 16384, "the recorded figures are medians of at least five alternations"
@@ -139,22 +144,43 @@ faster = args.skip_grouped or (all(a < b for a, b in zip(t_ab["a_encode"], t_ab[
                                and all(a < b for a, b in zip(t_ab["a_decode"], t_ab["b_decode"])))
 del groups, group_enc, group_dec
 
+# ---- (j): jump points, beside the plain pair ----
+ok_j, t_j, jump_info = True, {}, None
+if args.jump_every:
+    enc_j = enc_ragged(sym, offsets, LO, HI, mu, sd, CFG, jump_every=args.jump_every)
+    dec_j, st_j = dec_ragged(enc_j, offsets, LO, HI, mu, sd)
+    torch.cuda.synchronize()
+    ok_j = (B.last_kernel() == f"{args.coder}_decode_{args.family}_ragged_kernel<jump>" and bool(torch.equal(dec_j, sym)) and int(st_j.abs().sum()) == 0
+            and int(enc_j.status.abs().sum()) == 0 and bool(torch.equal(enc_j.n_words, enc.n_words)))
+    t_j = alternate({"plain_encode": lambda: enc_ragged(sym, offsets, LO, HI, mu, sd, CFG),
+                     "jump_encode": lambda: enc_ragged(sym, offsets, LO, HI, mu, sd, CFG, jump_every=args.jump_every),
+                     "plain_decode": lambda: dec_ragged(enc, offsets, LO, HI, mu, sd, out=dec),
+                     "jump_decode": lambda: dec_ragged(enc_j, offsets, LO, HI, mu, sd, out=dec_j)}, args.alternations)
+    n_chunks = int(enc_j.jump.chunk_offsets[-1])
+    jump_info = {"every": args.jump_every, "chunks": n_chunks, "table_bytes": n_chunks * (12 if args.coder == "ans" else 20),
+                 "word_bytes": 4 * int(enc.n_words.sum()),
+                 "pair_lower_in_every_alternation": all(je + jd < pe + pd for pe, pd, je, jd in zip(t_j["plain_encode"], t_j["plain_decode"],
+                                                                                                    t_j["jump_encode"], t_j["jump_decode"]))}
+    del enc_j, dec_j
+
 # ---- (c): a rectangular matrix of the same size, both ways ----
-n_per = (args.min_len + args.max_len) // 2
-sym_r, mu_r, sd_r = draw(n, n_per)
-off_r = torch.arange(n + 1, dtype=torch.int64, device=dev) * n_per
-flat_r, mu_f, sd_f = sym_r.reshape(-1), mu_r.reshape(-1), sd_r.reshape(-1)
-enc_r = enc_rect(sym_r, LO, HI, mu_r, sd_r, CFG, **NO_JUMP)
-dec_r, st_r = dec_rect(enc_r, LO, HI, mu_r, sd_r)
-enc_e = enc_ragged(flat_r, off_r, LO, HI, mu_f, sd_f, CFG)
-dec_e, st_e = dec_ragged(enc_e, off_r, LO, HI, mu_f, sd_f)
-torch.cuda.synchronize()
-ok_c = bool(torch.equal(dec_r, sym_r)) and bool(torch.equal(dec_e, flat_r)) and int(st_r.abs().sum()) == 0 and int(st_e.abs().sum()) == 0 \
-    and bool(torch.equal(enc_r.n_words, enc_e.n_words))
-t_c = alternate({"rect_encode": lambda: enc_rect(sym_r, LO, HI, mu_r, sd_r, CFG, out=enc_r, **NO_JUMP),
-                 "ragged_encode": lambda: enc_ragged(flat_r, off_r, LO, HI, mu_f, sd_f, CFG),
-                 "rect_decode": lambda: dec_rect(enc_r, LO, HI, mu_r, sd_r, out=dec_r),
-                 "ragged_decode": lambda: dec_ragged(enc_e, off_r, LO, HI, mu_f, sd_f, out=dec_e)}, args.alternations)
+ok_c, t_c = True, {}
+if not args.skip_rectangular:
+    n_per = (args.min_len + args.max_len) // 2
+    sym_r, mu_r, sd_r = draw(n, n_per)
+    off_r = torch.arange(n + 1, dtype=torch.int64, device=dev) * n_per
+    flat_r, mu_f, sd_f = sym_r.reshape(-1), mu_r.reshape(-1), sd_r.reshape(-1)
+    enc_r = enc_rect(sym_r, LO, HI, mu_r, sd_r, CFG, **NO_JUMP)
+    dec_r, st_r = dec_rect(enc_r, LO, HI, mu_r, sd_r)
+    enc_e = enc_ragged(flat_r, off_r, LO, HI, mu_f, sd_f, CFG)
+    dec_e, st_e = dec_ragged(enc_e, off_r, LO, HI, mu_f, sd_f)
+    torch.cuda.synchronize()
+    ok_c = bool(torch.equal(dec_r, sym_r)) and bool(torch.equal(dec_e, flat_r)) and int(st_r.abs().sum()) == 0 and int(st_e.abs().sum()) == 0 \
+        and bool(torch.equal(enc_r.n_words, enc_e.n_words))
+    t_c = alternate({"rect_encode": lambda: enc_rect(sym_r, LO, HI, mu_r, sd_r, CFG, out=enc_r, **NO_JUMP),
+                     "ragged_encode": lambda: enc_ragged(flat_r, off_r, LO, HI, mu_f, sd_f, CFG),
+                     "rect_decode": lambda: dec_rect(enc_r, LO, HI, mu_r, sd_r, out=dec_r),
+                     "ragged_decode": lambda: dec_ragged(enc_e, off_r, LO, HI, mu_f, sd_f, out=dec_e)}, args.alternations)
 
 med = lambda xs: statistics.median(xs)
 m_ab = {k: med(v) for k, v in t_ab.items()}
@@ -170,9 +196,22 @@ if args.skip_grouped:
 else:
     print(f"  (b) one call per length:       encode {m_ab['b_encode']:9.3f} ms  decode {m_ab['b_decode']:9.3f} ms  round trip ok={ok_b}")
     print(f"      (a) faster than (b) in every alternation: {faster}")
-print(f"  (c) {n} x {n_per} rectangular:  encode {m_c['rect_encode']:9.3f} ms  decode {m_c['rect_decode']:9.3f} ms")
-print(f"      the same through the ragged calls: encode {m_c['ragged_encode']:9.3f} ms ({m_c['ragged_encode'] / m_c['rect_encode']:.2f}x)  "
-      f"decode {m_c['ragged_decode']:9.3f} ms ({m_c['ragged_decode'] / m_c['rect_decode']:.2f}x)  round trips ok={ok_c}")
+if args.jump_every:
+    m_j = {k: med(v) for k, v in t_j.items()}
+    spread = lambda k: f"{min(t_j[k]):.3f} - {max(t_j[k]):.3f}"
+    print(f"  (j) a jump point every {args.jump_every} symbols ({jump_info['chunks']} chunks, table {jump_info['table_bytes'] / 1e6:.2f} MB against "
+          f"{jump_info['word_bytes'] / 1e6:.1f} MB of words = {100 * jump_info['table_bytes'] / jump_info['word_bytes']:.2f} %), plain beside it:")
+    print(f"      plain: encode {m_j['plain_encode']:9.3f} ms ({spread('plain_encode')})  decode {m_j['plain_decode']:9.3f} ms ({spread('plain_decode')})")
+    print(f"      jump:  encode {m_j['jump_encode']:9.3f} ms ({spread('jump_encode')}, {m_j['jump_encode'] / m_j['plain_encode']:.3f}x)  "
+          f"decode {m_j['jump_decode']:9.3f} ms ({spread('jump_decode')}, {m_j['jump_decode'] / m_j['plain_decode']:.3f}x)  round trip ok={ok_j}")
+    print(f"      encode + decode lower with jump points in every alternation: {jump_info['pair_lower_in_every_alternation']}")
+if args.skip_rectangular:
+    print("  (c) rectangular matrix:        left out (--skip-rectangular)")
+else:
+    print(f"  (c) {n} x {n_per} rectangular:  encode {m_c['rect_encode']:9.3f} ms  decode {m_c['rect_decode']:9.3f} ms")
+    print(f"      the same through the ragged calls: encode {m_c['ragged_encode']:9.3f} ms ({m_c['ragged_encode'] / m_c['rect_encode']:.2f}x)  "
+          f"decode {m_c['ragged_decode']:9.3f} ms ({m_c['ragged_decode'] / m_c['rect_decode']:.2f}x)  round trips ok={ok_c}")
 print(json.dumps({"coder": args.coder, "family": args.family, "grouped": not args.skip_grouped, "streams": n, "symbols": total, "alternations": args.alternations, "ms": {**m_ab, **m_c}, "all_ms": {**t_ab, **t_c},
-                  "a_faster_than_b": faster, "round_trips_ok": ok_a and ok_b and ok_c}))
-sys.exit(0 if faster and ok_a and ok_b and ok_c else 1)
+                  "jump": jump_info, "jump_ms": {k: med(v) for k, v in t_j.items()}, "jump_all_ms": t_j,
+                  "a_faster_than_b": faster, "round_trips_ok": ok_a and ok_b and ok_c and ok_j}))
+sys.exit(0 if faster and ok_a and ok_b and ok_c and ok_j else 1)
