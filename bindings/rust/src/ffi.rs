@@ -2064,6 +2064,196 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    /// Categorical probability matrices for streams of DIFFERENT lengths (the fast quantisation of cst_*_categorical_batch: Categorical(perfect=False) /
+    /// Categorical(lazy=True)), plain and with jump points, both coders, both presets.  Stream s owns rows [d_sym_offsets[s], d_sym_offsets[s + 1])
+    /// of the flat matrix d_probs [n_total][n_symbols] (float: prob_bytes = 4, double: 8) and of the flat d_symbols [n_total].  Every stream's
+    /// words, word count and status are those of cst_{ans,range}_{encode,decode}_categorical_batch for that stream alone, bit for bit.
+    ///   - d_order, d_word_offsets / stride_words / words_capacity, the slabs and empty streams (no words, CST_STREAM_OK): as in
+    ///     cst_{ans,range}_{encode,decode}_gaussian_ragged.
+    ///   - n_total: the rows of d_probs and the elements of d_symbols.  Pass 1 of the encoders is sized by it (no read-back of d_sym_offsets), and
+    ///     the device bounds every row index by it: a stream that reaches beyond n_total reports CST_STREAM_INVALID_DATA and nothing is coded for
+    ///     it; one whose symbol range runs backwards or exceeds 2^32 - 1 reports CST_STREAM_CAPACITY.  The other streams are unaffected.
+    ///   - A bad row (see cst_ans_encode_categorical_batch), a symbol outside [0, n_symbols) and an empty interval yield
+    ///     CST_STREAM_IMPOSSIBLE_SYMBOL for their stream only.
+    ///   - *_jump: the plain call's arguments (the decoders' WITHOUT d_order), then jump_interval, d_chunk_offsets and the table -- argument order,
+    ///     table layout and semantics exactly those of cst_{ans,range}_{encode,decode}_gaussian_ragged_jump; the decoders' d_scratch holds
+    ///     cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) bytes.  jump_interval: a positive multiple of 16, at most 2^31 - 1.
+    ///   - Before the device is touched: a NULL pointer (d_order and d_word_offsets may be NULL, the latter with stride_words > 0), prob_bytes
+    ///     outside {4, 8}, an unsupported cfg, n_streams > 2^31 - 1, n_total > 64 (2^31 - 1) (encoders) and every refusal of the Gaussian jump
+    ///     calls return CST_ERR_INVALID_ARGUMENT; then n_symbols < 2 or n_symbols >= 2^precision - 1 returns CST_ERR_MODEL.  n_streams == 0:
+    ///     CST_OK, nothing is launched.
+    ///   - One route for every batch size: built for many streams; a few are coded correctly, but slowly.  Not here: the perfect quantisation,
+    ///     the symbol-major layout (a ragged batch has none), a count_until, intervals that are no multiple of 16.
+    /// cst_last_kernel_name(): {ans,range}_encode_categorical_ragged_two_pass, {ans,range}_decode_categorical_ragged_kernel, and the same names
+    /// followed by <jump>.
+    pub fn cst_ans_encode_categorical_ragged(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_categorical_ragged(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_encode_categorical_ragged(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_categorical_ragged(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_encode_categorical_ragged_jump(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32,
+        d_jump_state: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_categorical_ragged_jump(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_encode_categorical_ragged_jump(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32,
+        d_jump_lower: *mut u64,
+        d_jump_range: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_categorical_ragged_jump(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// ABI 5: jump points for the per-symbol Gaussian calls of the RANGE coder (RangeEncoder::pos / RangeDecoder::seek, src/stream/queue.rs:172-196,
     /// 900-926), as cst_ans_{encode,decode}_gaussian_batch_ckpt are for ANS: the fused encoder notes (words emitted including held-back ones,
     /// lower, range) in front of every chunk of ckpt_interval symbols (a multiple of 16 that divides n_per_stream; stream-major), the decoder

@@ -1925,6 +1925,237 @@ impl BatchedAnsCoder {
         Ok(status)
     }
 
+    /// `encode_symbols_reverse_categorical` for streams of different lengths (`cst_ans_encode_categorical_ragged`): stream `s` owns rows
+    /// `[sym_offsets[s], sym_offsets[s + 1])` of the flat matrix `probabilities` (`symbols.len()` rows of `n_symbols` entries) and of the
+    /// flat `symbols`, and writes into the slab `[word_offsets[s], word_offsets[s + 1])` of `words`.  `order`: a schedule as for the
+    /// ordered ragged calls, or `None`.  Every stream's words are those of `encode_symbols_reverse_categorical` for that stream alone.
+    ///
+    /// # Safety
+    /// The offsets are DEVICE memory and cannot be checked here: every slab must lie inside `words`.  Row indices ARE bounded on the
+    /// device by `symbols.len()`: a stream that reaches beyond reports `CST_STREAM_INVALID_DATA`.
+    pub unsafe fn encode_symbols_reverse_categorical_ragged<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>)> {
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_ans_encode_categorical_ragged(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status))
+    }
+
+    /// The decoder of `encode_symbols_reverse_categorical_ragged` (`cst_ans_decode_categorical_ragged`): stream `s` yields `sym_offsets[s + 1] - sym_offsets[s]` symbols at
+    /// `symbols[sym_offsets[s]..]`, decoded with rows `sym_offsets[s]..` of `probabilities`.
+    ///
+    /// # Safety
+    /// `sym_offsets` is DEVICE memory; the symbol ranges are bounded on the device by `symbols.len()`, the word slices by `words.len()`.
+    pub unsafe fn decode_symbols_categorical_ragged<F: Probability>(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        symbols: &mut DeviceBuffer<i32>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_ans_decode_categorical_ragged(
+                self.config,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok(status)
+    }
+
+    /// `encode_symbols_reverse_categorical_ragged` that also notes `AnsCoder::pos()` in front of every `jump_interval` symbols of every stream (`cst_ans_encode_categorical_ragged_jump`): the
+    /// table of the Gaussian `_with_jump_points` encoder -- chunk `j` of stream `s` is entry `chunk_offsets[s] + j` of the returned
+    /// `(pos, state)` arrays.  `jump_interval`: a positive multiple of 16.  The words are those of `encode_symbols_reverse_categorical_ragged`.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_reverse_categorical_ragged`; `chunk_offsets` must be the exclusive prefix sum of `ceil(length / jump_interval)`.
+    pub unsafe fn encode_symbols_reverse_categorical_ragged_with_jump_points<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>, DeviceBuffer<u32>, DeviceBuffer<u64>)> {
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut pos: DeviceBuffer<u32> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut state: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        check(unsafe {
+            ffi::cst_ans_encode_categorical_ragged_jump(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                pos.as_mut_ptr(),
+                state.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status, pos, state))
+    }
+
+    /// The decoder of `encode_symbols_reverse_categorical_ragged_with_jump_points` (`cst_ans_decode_categorical_ragged_jump`): every chunk of every stream as a coder of its own
+    /// (seek + at most `jump_interval` symbols).  One status per stream.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_categorical_ragged`.  The jump table is checked against the lengths and word counts on the device.
+    pub unsafe fn decode_symbols_categorical_ragged_from_jump_points<F: Probability>(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        symbols: &mut DeviceBuffer<i32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        pos: &DeviceBuffer<u32>,
+        state: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || pos.len() < n_chunks_total || state.len() < n_chunks_total || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) })?;
+        check(unsafe {
+            ffi::cst_ans_decode_categorical_ragged_jump(
+                self.config,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                n_chunks_total,
+                pos.as_ptr(),
+                state.as_ptr(),
+                scratch.as_mut_ptr() as *mut c_void,
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
+        Ok(status)
+    }
+
     /// `encode_symbols_reverse_family_ragged` that also notes `AnsCoder::pos()` in front of every `jump_interval` symbols of every stream (`cst_ans_encode_family_ragged_jump`): chunk `j` of
     /// stream `s` is entry `chunk_offsets[s] + j` of the returned `(pos, state)` arrays, `chunk_offsets[n_streams + 1]` the exclusive prefix
     /// sum of `ceil(length / jump_interval)` (device memory, `n_chunks_total` its last entry or an upper bound).  `jump_interval`: a
@@ -2915,6 +3146,122 @@ impl BatchedRangeEncoder {
         Ok((n_words, status, pos, lower, range))
     }
 
+    /// `encode_symbols_categorical` for streams of different lengths (`cst_range_encode_categorical_ragged`): stream `s` owns rows
+    /// `[sym_offsets[s], sym_offsets[s + 1])` of the flat matrix `probabilities` (`symbols.len()` rows of `n_symbols` entries) and of the
+    /// flat `symbols`, and writes into the slab `[word_offsets[s], word_offsets[s + 1])` of `words`.  `order`: a schedule as for the
+    /// ordered ragged calls, or `None`.  Every stream's words are those of `encode_symbols_categorical` for that stream alone.
+    ///
+    /// # Safety
+    /// The offsets are DEVICE memory and cannot be checked here: every slab must lie inside `words`.  Row indices ARE bounded on the
+    /// device by `symbols.len()`: a stream that reaches beyond reports `CST_STREAM_INVALID_DATA`.
+    pub unsafe fn encode_symbols_categorical_ragged<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>)> {
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_range_encode_categorical_ragged(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status))
+    }
+
+    /// `encode_symbols_categorical_ragged` that also notes `RangeEncoder::pos()` in front of every `jump_interval` symbols of every stream (`cst_range_encode_categorical_ragged_jump`): the
+    /// table of the Gaussian `_with_jump_points` encoder -- chunk `j` of stream `s` is entry `chunk_offsets[s] + j` of the returned
+    /// `(pos, lower, range)` arrays.  `jump_interval`: a positive multiple of 16.  The words are those of `encode_symbols_categorical_ragged`.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_categorical_ragged`; `chunk_offsets` must be the exclusive prefix sum of `ceil(length / jump_interval)`.
+    pub unsafe fn encode_symbols_categorical_ragged_with_jump_points<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>, DeviceBuffer<u32>, DeviceBuffer<u64>, DeviceBuffer<u64>)> {
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut pos: DeviceBuffer<u32> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut lower: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut range: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        check(unsafe {
+            ffi::cst_range_encode_categorical_ragged_jump(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                pos.as_mut_ptr(),
+                lower.as_mut_ptr(),
+                range.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status, pos, lower, range))
+    }
+
     /// `encode_symbols_family_ragged` that also notes `RangeEncoder::pos()` in front of every `jump_interval` symbols of every stream (`cst_range_encode_family_ragged_jump`): chunk `j` of
     /// stream `s` is entry `chunk_offsets[s] + j` of the returned `(pos, lower, range)` arrays, `chunk_offsets[n_streams + 1]` the exclusive prefix
     /// sum of `ceil(length / jump_interval)` (device memory, `n_chunks_total` its last entry or an upper bound).  `jump_interval`: a
@@ -3769,6 +4116,125 @@ impl BatchedRangeDecoder {
                 n_words.as_ptr(),
                 means.as_ptr(),
                 stds.as_ptr(),
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                n_chunks_total,
+                pos.as_ptr(),
+                lower.as_ptr(),
+                range.as_ptr(),
+                scratch.as_mut_ptr() as *mut c_void,
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
+        Ok(status)
+    }
+
+    /// The decoder of `encode_symbols_categorical_ragged` (`cst_range_decode_categorical_ragged`): stream `s` yields `sym_offsets[s + 1] - sym_offsets[s]` symbols at
+    /// `symbols[sym_offsets[s]..]`, decoded with rows `sym_offsets[s]..` of `probabilities`.
+    ///
+    /// # Safety
+    /// `sym_offsets` is DEVICE memory; the symbol ranges are bounded on the device by `symbols.len()`, the word slices by `words.len()`.
+    pub unsafe fn decode_symbols_categorical_ragged<F: Probability>(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        symbols: &mut DeviceBuffer<i32>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_range_decode_categorical_ragged(
+                self.config,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok(status)
+    }
+
+    /// The decoder of `encode_symbols_categorical_ragged_with_jump_points` (`cst_range_decode_categorical_ragged_jump`): every chunk of every stream as a coder of its own
+    /// (seek + at most `jump_interval` symbols).  One status per stream.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_categorical_ragged`.  The jump table is checked against the lengths and word counts on the device.
+    pub unsafe fn decode_symbols_categorical_ragged_from_jump_points<F: Probability>(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        symbols: &mut DeviceBuffer<i32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        pos: &DeviceBuffer<u32>,
+        lower: &DeviceBuffer<u64>,
+        range: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || pos.len() < n_chunks_total || lower.len() < n_chunks_total || range.len() < n_chunks_total || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) })?;
+        check(unsafe {
+            ffi::cst_range_decode_categorical_ragged_jump(
+                self.config,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
                 symbols.as_mut_ptr(),
                 sym_offsets.as_ptr(),
                 n_streams,

@@ -169,6 +169,18 @@ SIGNATURES = {
     "cst_ans_decode_categorical_batch": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _vp, _z, _z, _i32, _vp, _vp, _vp, _u32, _vp]),
     "cst_range_encode_categorical_batch": (_i32, [CoderConfig, _vp, _vp, _i32, _i32, _z, _z, _i32, _vp, _z, _vp, _vp, _vp, _u32, _vp]),
     "cst_range_decode_categorical_batch": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _vp, _z, _z, _i32, _vp, _vp, _u32, _vp]),
+    "cst_ans_encode_categorical_ragged": (_i32, [CoderConfig, _vp, _vp, _i32, _i32, _z, _vp, _z, _vp, _vp, _vp, _z, _vp, _vp, _vp]),
+    "cst_ans_decode_categorical_ragged": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _z, _vp, _vp, _z, _vp, _vp, _vp]),
+    "cst_range_encode_categorical_ragged": (_i32, [CoderConfig, _vp, _vp, _i32, _i32, _z, _vp, _z, _vp, _vp, _vp, _z, _vp, _vp, _vp]),
+    "cst_range_decode_categorical_ragged": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _z, _vp, _vp, _z, _vp, _vp, _vp]),
+    "cst_ans_encode_categorical_ragged_jump": (_i32, [CoderConfig, _vp, _vp, _i32, _i32, _z, _vp, _z, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp,
+                                                      _vp]),
+    "cst_ans_decode_categorical_ragged_jump": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _z, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp,
+                                                      _vp, _vp]),
+    "cst_range_encode_categorical_ragged_jump": (_i32, [CoderConfig, _vp, _vp, _i32, _i32, _z, _vp, _z, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp,
+                                                        _vp, _vp]),
+    "cst_range_decode_categorical_ragged_jump": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _z, _vp, _vp, _z, _z, _vp, _z, _vp, _vp,
+                                                        _vp, _vp, _vp, _vp]),
     "cst_categorical_fast_cdf_rows": (_i32, [_i32, _vp, _i32, _z, _i32, _vp, _vp, _vp]),
     "cst_categorical_fast_cdf_host": (_i32, [_i32, _vp, _i32, _z, _i32, _vp, _vp]),
     "cst_ans_encode_categorical_perfect_batch": (_i32, [CoderConfig, _vp, _vp, _i32, _i32, _z, _z, _i32, _vp, _z, _vp, _vp, _vp, _u32, _vp]),

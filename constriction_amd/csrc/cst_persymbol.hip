@@ -34,8 +34,6 @@ __global__ void cp_entries_kernel(const uint32_t* __restrict__ left, const uint3
     out[i] = make_entry(c, p);
 }
 
-constexpr int kEntryGroup = 8;     // entries requested together (8 x 16 bytes = one 128-byte line of a stream-major row)
-
 // one lane per stream over precomputed entries; ANS walks backwards, the range coder forwards
 template <int W, int S, int KIND>
 __global__ __launch_bounds__(kBlock) void encode_entries_kernel(const EntriesEncodeArgs a) {

@@ -5,9 +5,12 @@
 //   cst_persymbol_ragged.hip       streams of different lengths
 //   cst_persymbol_ragged_jump.hip  ... with jump points (both share their kernels through cst_persymbol_ragged.hpp)
 //   cst_persymbol_categorical.hip  Categorical models from probability matrices
+//   cst_persymbol_categorical_ragged.hip  ... for streams of different lengths, plain and with jump points (they share the row tile and
+//                                  pass 1 of the encoders through cst_persymbol_categorical.hpp)
 // EVERY KERNEL INSTANTIATION LIVES IN ONE FILE: nothing here is relocatable device code, so a second implicit instantiation would
 // compile and ship the kernel twice.  A kernel needed from another file is reached through a host launcher declared here and defined
-// next to the kernel.
+// next to the kernel.  (The exceptions are small and named where they are: categorical_entries_kernel, cst_persymbol_categorical.hpp,
+// and the two kernels around a jump table, cst_persymbol_ragged.hpp.)
 #pragma once
 #include <type_traits>
 
@@ -45,6 +48,9 @@ struct EntriesEncodeArgs {
     const uint32_t* pop_words; const uint64_t* pop_offsets; size_t pop_stride; uint32_t* n_pop;
     cst_chain_heads* heads;
 };
+
+// pass 2 of the two-pass encoders (encode_entries_kernel in cst_persymbol.hip, encode_entries_ragged_kernel)
+constexpr int kEntryGroup = 8;     // entries requested together (8 x 16 bytes = one 128-byte line of a stream-major row)
 
 // the fused encoders' tiles (encode_gaussian_fused_kernel in cst_persymbol_encode.hip, encode_gaussian_ragged_kernel)
 constexpr int kFuTile = 16;                               // symbols per tile

@@ -1,0 +1,550 @@
+// cst_persymbol_categorical_ragged.hip -- per-symbol Categorical models (the fast quantiser of cst_categorical.hpp) for streams of
+// DIFFERENT lengths, plain and with jump points (cst_persymbol.hpp has the map of the per-symbol files): stream s owns
+// rows [sym_offsets[s], sym_offsets[s + 1]) of a flat probability matrix [n_total][K] and of the flat symbols.
+//   categorical_entries_kernel        encoder pass 1, as it is (cst_persymbol_categorical.hpp): rows are rows, whichever stream owns them
+//   encode_entries_ragged_kernel      encoder pass 2: encode_entries_kernel's ANS and range branches with one lane per stream
+//   decode_categorical_ragged_kernel  decode_categorical_lane_kernel with a row index per lane
+// Their JUMP forms note / start from the jump table of cst_*_gaussian_ragged_jump; the kernels that turn a table into chunks and chunk
+// statuses into stream statuses are the model-independent ones of cst_persymbol_ragged.hpp.  A unit of its own: the instantiations
+// stay out of cst_persymbol_categorical.hip, the build's longest compile.
+#include "cst_persymbol_ragged.hpp"
+#include "cst_categorical.hpp"
+#include "cst_persymbol_categorical.hpp"
+
+namespace cst {
+
+// where a stream's symbols lie, judged before anything becomes an address: a range that runs backwards or is too long for one coder
+// (CST_STREAM_CAPACITY, as the other ragged calls say), or one that reaches beyond the n_total rows there are (CST_STREAM_INVALID_DATA).
+// Either way the stream has NO symbols for the kernel.
+struct CatRaggedSpan {
+    uint64_t lo; uint32_t len; bool too_long, beyond;
+    __device__ __forceinline__ CatRaggedSpan(uint64_t sym_lo, uint64_t sym_hi, uint64_t n_total) {
+        too_long = sym_hi < sym_lo || sym_hi - sym_lo > 0xffffffffull;
+        beyond = !too_long && sym_hi > sym_lo && sym_hi > n_total;
+        lo = sym_lo;
+        len = too_long || beyond ? 0u : (uint32_t)(sym_hi - sym_lo);
+    }
+    __device__ __forceinline__ int32_t status(int32_t coded) const {
+        return too_long ? (int32_t)CST_STREAM_CAPACITY : beyond ? (int32_t)CST_STREAM_INVALID_DATA : coded;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
+// encoder pass 2
+// ------------------------------------------------------------------------------------------------
+struct EntriesRaggedEncodeArgs {
+    const EncEntry* entries;         // [n_total], entry i from row i (pass 1)
+    uint64_t n_total;
+    const uint64_t* sym_offsets;     // [n_streams + 1]
+    size_t n_streams;
+    const uint32_t* order;           // null, or [n_streams]
+    int32_t precision;
+    uint32_t* words;
+    const uint64_t* word_offsets;    // [n_streams + 1], or null: s * stride_words
+    size_t stride_words;
+    uint32_t* n_words;
+    int32_t* status;
+};
+// (the table of GaussianRaggedEncodeJumpArgs; chunks are counted in symbols here, not in tiles)
+struct EntriesRaggedEncodeJumpArgs : EntriesRaggedEncodeArgs {
+    uint32_t jump_interval;
+    const uint64_t* jump_chunk_offsets;     // [n_streams + 1]
+    uint32_t* jump_pos;
+    uint64_t* jump_a;                       // ANS: the state; the range coder: lower
+    uint64_t* jump_b;                       // the range coder: range
+};
+
+// One lane per stream over the entries of pass 1, lane slot i on stream order[i] (null: i).  The wave walks position t of ALL its
+// streams together -- the range coder t = 0 .. mx - 1, ANS t = mx - 1 .. 0, mx the wave's longest stream -- and a lane takes a step
+// where t < its own length: t, the flush_chunks() countdown and the jump counters are wave-uniform, every stream is still coded first
+// to last (last to first) without a gap.  Entries come kEntryGroup at a time, one group ahead of their use, as in
+// encode_entries_kernel; the loads are unconditional, from entry 0 where the lane has nothing at t (a wave with a step to take has an
+// entry).
+// JUMP: chunk j of a stream is symbols [j I, j I + I): a queue notes pos() BEFORE t = j I is coded, a stack AFTER it (the symbols from
+// j I on are then encoded) -- what encode_gaussian_ragged_kernel<JUMP> notes.  Only where t < len: no chunk starts at a stream's end.
+template <int W, int S, int KIND, bool JUMP>
+__global__ __launch_bounds__(kBlock) void encode_entries_ragged_kernel(const std::conditional_t<JUMP, EntriesRaggedEncodeJumpArgs, EntriesRaggedEncodeArgs> a) {
+    static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & (kWave - 1);
+    uint32_t* ring = reinterpret_cast<uint32_t*>(smem) + (threadIdx.x >> 6) * kRingWords;
+    const size_t slot = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot - lane >= a.n_streams) return;
+    bool active;
+    const size_t s = persymbol_ragged_stream(a.order, slot, a.n_streams, active);
+    const CatRaggedSpan span(active ? a.sym_offsets[s] : 0, active ? a.sym_offsets[s + 1] : 0, a.n_total);
+    const uint32_t len = span.len;
+    const uint32_t mx = persymbol_wave_max(len);
+    const int P = a.precision;
+    const int G4 = 4 * groups_per_point(W, P);
+    const EncEntry* my = a.entries + span.lo;
+
+    const uint64_t slab_lo = !active ? 0 : (a.word_offsets ? a.word_offsets[s] : (uint64_t)s * a.stride_words);
+    // (offsets that run backwards give the stream a slab of NO words: it reports CST_STREAM_CAPACITY and writes nothing)
+    const uint64_t slab_hi = !active ? 0 : (a.word_offsets ? a.word_offsets[s + 1] : 0);
+    const uint64_t slab_n = !active ? 0 : (a.word_offsets ? (slab_hi >= slab_lo ? slab_hi - slab_lo : 0) : (uint64_t)a.stride_words);
+    std::conditional_t<KIND == kAns, EncLane<W, S>, RangeEncLane<W, S>> L;
+    L.init(a.words + slab_lo, (uint32_t)(slab_n > 0xffffffffull ? 0xffffffffull : slab_n), ring, lane);
+    uint32_t bad = 0;
+    int countdown = G4;
+    // JUMP: position t is symbol `jump_in` of chunk `jump_j` of every stream (wave-uniform counters: no division per symbol)
+    uint32_t jump_in = 0, jump_j = 0;
+    uint64_t jump_c0 = 0;
+    if constexpr (JUMP) {
+        if (KIND == kAns && mx > 0) { jump_in = (mx - 1u) % a.jump_interval; jump_j = (mx - 1u) / a.jump_interval; }
+        jump_c0 = active ? a.jump_chunk_offsets[s] : 0;
+    }
+
+    const auto load = [&](uint32_t t) { return a.entries == nullptr ? EncEntry{} : (t < len ? my[t] : a.entries[0]); };
+    const auto one = [&](const EncEntry e, uint32_t t) {
+        const bool mine = t < len;
+        if constexpr (JUMP && KIND == kRange) {
+            if (jump_in == 0 && mine) {
+                a.jump_pos[jump_c0 + jump_j] = L.out.wr + L.inv_n;
+                a.jump_a[jump_c0 + jump_j] = (uint64_t)L.lower;
+                a.jump_b[jump_c0 + jump_j] = (uint64_t)L.range;
+            }
+            if (++jump_in == a.jump_interval) { jump_in = 0; ++jump_j; }
+        }
+        if (mine) {
+            if (e.p == 0) bad = 1;
+            else if (!bad) {
+                if constexpr (KIND == kAns) L.template step<false>(e, P); else L.step(e.c, e.p, P);
+            }
+        }
+        if constexpr (JUMP && KIND == kAns) {
+            if (jump_in == 0 && mine) {
+                a.jump_pos[jump_c0 + jump_j] = L.out.wr;
+                a.jump_a[jump_c0 + jump_j] = (uint64_t)L.state;
+            }
+            // (selects, not `if (..) { .. --jump_j; } else --jump_in;`: the compiler merges those two decrements into one store through a
+            //  selected pointer, and both counters then live in scratch memory)
+            const bool first = jump_in == 0;
+            jump_j -= first ? 1u : 0u;
+            jump_in = first ? a.jump_interval - 1u : jump_in - 1u;
+        }
+        if (--countdown == 0) { countdown = G4; L.out.flush_chunks(); }
+    };
+
+    const uint32_t tail = mx % kEntryGroup;
+    EncEntry cur[kEntryGroup], nxt[kEntryGroup];
+    if constexpr (KIND == kAns) {
+        for (uint32_t t = mx; t-- > mx - tail;) one(load(t), t);
+        uint32_t g = mx - tail;                    // entries [g - kEntryGroup, g) are the next group
+        if (g > 0) {
+#pragma unroll
+            for (int j = 0; j < kEntryGroup; ++j) nxt[j] = load(g - 1u - (uint32_t)j);
+        }
+        while (g > 0) {
+#pragma unroll
+            for (int j = 0; j < kEntryGroup; ++j) cur[j] = nxt[j];
+            g -= kEntryGroup;
+            if (g > 0) {
+#pragma unroll
+                for (int j = 0; j < kEntryGroup; ++j) nxt[j] = load(g - 1u - (uint32_t)j);
+            }
+#pragma unroll
+            for (int j = 0; j < kEntryGroup; ++j) one(cur[j], g + (uint32_t)(kEntryGroup - 1 - j));
+        }
+    } else {
+        const uint32_t n_grouped = mx - tail;
+        uint32_t g = 0;                            // entries [g, g + kEntryGroup) are the next group
+        if (n_grouped > 0) {
+#pragma unroll
+            for (int j = 0; j < kEntryGroup; ++j) nxt[j] = load((uint32_t)j);
+        }
+        while (g < n_grouped) {
+#pragma unroll
+            for (int j = 0; j < kEntryGroup; ++j) cur[j] = nxt[j];
+            g += kEntryGroup;
+            if (g < n_grouped) {
+#pragma unroll
+                for (int j = 0; j < kEntryGroup; ++j) nxt[j] = load(g + (uint32_t)j);
+            }
+#pragma unroll
+            for (int j = 0; j < kEntryGroup; ++j) one(cur[j], g - (uint32_t)kEntryGroup + (uint32_t)j);
+        }
+        for (uint32_t t = n_grouped; t < mx; ++t) one(load(t), t);
+    }
+
+    uint32_t n_words = 0;
+    int32_t status;
+    if constexpr (KIND == kAns) status = L.finish(true, 1u, n_words);
+    else status = L.finish(1u, n_words);                // (no symbols: `range` is still all ones and nothing is sealed)
+    if (!active) return;
+    if (bad) status = CST_STREAM_IMPOSSIBLE_SYMBOL;
+    status = span.status(status);
+    a.status[s] = status;
+    a.n_words[s] = status == CST_STREAM_OK ? n_words : 0u;
+}
+
+// ------------------------------------------------------------------------------------------------
+// decoder
+// ------------------------------------------------------------------------------------------------
+struct CatRaggedDecodeArgs {
+    PerSymbolDecodeArgs p;           // words / offsets / stride_words / n_words / words_capacity, symbols (flat), n_symbols = K
+    const void* probs;               // [n_total][K]
+    uint64_t n_total;
+    const uint64_t* sym_offsets;     // [n_streams + 1]
+    const uint32_t* order;           // null, or [n_streams]
+};
+// JUMP form: every "stream" of the launch is entry c of the jump table, with its symbols given outright (GaussianRaggedChunkArgs)
+struct CatRaggedChunkArgs {
+    PerSymbolDecodeArgs p;
+    const void* probs;
+    uint64_t n_total;
+    const uint64_t* sym_lo;          // [n chunks]: first element
+    const uint32_t* len;             // [n chunks]: symbols, <= jump_interval
+};
+
+// behind the tile: the row that each of the wave's 64 lanes walks at this position
+constexpr size_t kCatRowTableBytes = (size_t)kWave * sizeof(uint64_t);
+template <class F> constexpr size_t kCatRaggedLdsBytes = kCatTileBytes<F> + kCatRowTableBytes;
+static_assert(kCatTileBytes<float> % 8 == 0 && kCatTileBytes<double> % 8 == 0, "the row table is read as 64-bit words");
+
+// cat_stage for rows that lie anywhere: row r of the wave is row rows[r] of the matrix -- always one that exists -- and is kept
+// where bit r of `live` is set.  The loads are unconditional (a conditional load is waited for at once); the 16-byte path's condition
+// is the same for every row.
+template <class F>
+__device__ __forceinline__ void cat_stage_rows(F* tile, const F* __restrict__ probs, const uint64_t* rows, unsigned long long live, size_t K,
+                                               size_t c0, int n_here, bool vec, int lane) {
+    if (vec) {
+        using V = typename CatVec<F>::type;
+        constexpr int kV = CatVec<F>::n, kLanesPerRow = kCatChunk / kV, kRowsPerLoad = kWave / kLanesPerRow;
+        const int col = (lane % kLanesPerRow) * kV, r0 = lane / kLanesPerRow;
+        const bool col_ok = col < n_here;
+        const F* src = probs + c0 + (size_t)(col_ok ? col : 0);
+#pragma unroll 8
+        for (int it = 0; it < kWave / kRowsPerLoad; ++it) {
+            const int r = it * kRowsPerLoad + r0;
+            const V v = *reinterpret_cast<const V*>(src + (size_t)rows[r] * K);
+            if (((live >> r) & 1ull) && col_ok) {
+#pragma unroll
+                for (int k = 0; k < kV; ++k) tile[r * kCatPitch + col + k] = v[k];
+            }
+        }
+    } else {
+        const bool col_ok = lane < n_here;
+        const F* src = probs + c0 + (size_t)(col_ok ? lane : 0);
+#pragma unroll 8
+        for (int r = 0; r < kWave; ++r) {
+            const F v = src[(size_t)rows[r] * K];
+            if (((live >> r) & 1ull) && col_ok) tile[r * kCatPitch + lane] = v;
+        }
+    }
+}
+
+// decode_categorical_lane_kernel for ragged rows: one LANE per stream (JUMP: per table entry), 64 per wave, one wave per workgroup.
+// At position t lane r walks row sym_lo_r + t: the lanes leave their row indices in a table behind the tile, and the staging loop takes
+// row r's from there.  The loop runs to the wave's longest lane; a lane past its own length stages a row that exists (row 0: a wave
+// with a symbol to decode has one), decodes and stores nothing, and goes on taking part in the wave-wide loads, fences and votes.
+template <int W, int S, int KIND, class F, bool JUMP>
+__global__ __launch_bounds__(kWave) void decode_categorical_ragged_kernel(const std::conditional_t<JUMP, CatRaggedChunkArgs, CatRaggedDecodeArgs> ra) {
+    static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    F* tile = reinterpret_cast<F*>(smem);
+    uint64_t* rows = reinterpret_cast<uint64_t*>(smem + kCatTileBytes<F>);
+    const PerSymbolDecodeArgs& a = ra.p;
+    const F* probs = reinterpret_cast<const F*>(ra.probs);
+    const int lane = threadIdx.x;
+    const size_t slot = (size_t)blockIdx.x * kWave + (size_t)lane;
+    if (slot - lane >= a.n_streams) return;
+    bool active;
+    const size_t s = ragged_lane_stream<JUMP>(ra, slot, a.n_streams, active);
+    const size_t se = active ? s : 0;                         // idle lanes look at stream 0's words and decode nothing
+    const CatRaggedSpan span(active ? ragged_lane_begin<JUMP>(ra, s) : 0, active ? ragged_lane_end<JUMP>(ra, s) : 0, ra.n_total);
+    const uint32_t len = span.len;
+    const uint32_t mx = persymbol_wave_max(len);
+    const size_t K = (size_t)a.n_symbols;
+    const int P = a.precision;
+    const uint32_t total = 1u << P;
+    const bool vec = cat_vec_ok(probs, K);
+    const F* my = tile + lane * kCatPitch;
+
+    DirectDecoder<W, S, KIND> D;
+    D.init(a, se, JUMP);                                      // (JUMP: AnsCoder::seek / RangeDecoder::seek have been done for it)
+    int32_t status = D.status;
+    for (uint32_t t = 0; t < mx; ++t) {
+        const bool here = t < len;
+        if (!__any(here && status == CST_STREAM_OK)) break;             // (what follows a failure is unspecified)
+        const unsigned long long live = __ballot(here);
+        wave_lds_fence();                                               // (the previous position's rows have been staged)
+        rows[lane] = here ? span.lo + (uint64_t)t : 0;
+        CatSum<F> sum;
+        for (size_t c0 = 0; c0 < K; c0 += kCatChunk) {
+            const int n_here = (int)(K - c0 < (size_t)kCatChunk ? K - c0 : (size_t)kCatChunk);
+            wave_lds_fence();
+            cat_stage_rows(tile, probs, rows, live, K, c0, n_here, vec, lane);
+            wave_lds_fence();
+#pragma unroll 8
+            for (int j = 0; j < n_here; ++j) sum.add(my[j]);
+        }
+        bool search = here && status == CST_STREAM_OK;
+        if (search && sum.bad()) { status = CST_STREAM_IMPOSSIBLE_SYMBOL; search = false; }
+        uint32_t q = 0;
+        if (search) {
+            q = D.quantile(P);
+            if (D.status != CST_STREAM_OK) { status = D.status; search = false; }
+        }
+        const F scale = cat_scale<F>(P, (uint32_t)K, search ? sum.cum : F(1));
+        // entries 0 .. K - 2 have a right boundary of their own; `prev` is the left boundary of the entry looked at
+        F cum = F(0);
+        uint32_t prev = 0, c = 0, right = total, sym = (uint32_t)K - 1u;
+        bool found = !search;
+        for (size_t c0 = 0; c0 < K - 1; c0 += kCatChunk) {
+            const int n_here = (int)(K - 1 - c0 < (size_t)kCatChunk ? K - 1 - c0 : (size_t)kCatChunk);
+            if (K > (size_t)kCatChunk) {
+                wave_lds_fence();
+                cat_stage_rows(tile, probs, rows, live, K, c0, (int)(K - c0 < (size_t)kCatChunk ? K - c0 : (size_t)kCatChunk), vec, lane);
+            }
+            wave_lds_fence();
+#pragma unroll 8
+            for (int j = 0; j < n_here; ++j) {
+                cum = cum + my[j];
+                const uint32_t r = cat_left<F>(cum, scale, (uint32_t)c0 + (uint32_t)j + 1u);
+                const bool hit = !found && r > q;
+                sym = hit ? (uint32_t)c0 + (uint32_t)j : sym;
+                c = hit ? prev : c;
+                right = hit ? r : right;
+                found = found || hit;
+                prev = r;
+            }
+            if (!__any(!found)) break;
+        }
+        if (!found) c = prev;                                           // the last symbol: everything up to 2^P
+        int32_t decoded = 0;
+        if (search) {
+            const uint32_t p = right - c;
+            if (p == 0 || right < c || right > total) status = CST_STREAM_IMPOSSIBLE_SYMBOL;     // an empty or wrapped interval
+            else { decoded = (int32_t)sym; D.advance(q, c, p, P); }
+        }
+        D.look_ahead();                                                 // (once per symbol, outside any divergent branch)
+        if (here) a.symbols[span.lo + (uint64_t)t] = decoded;
+    }
+    if (!active) return;
+    a.status[s] = span.status(status);
+    D.finish(a, s, false);
+}
+
+// ---- host side: one route whatever the batch ----
+static constexpr const char* kCatRaggedEncodeNames[2][2] = {{"ans_encode_categorical_ragged_two_pass", "range_encode_categorical_ragged_two_pass"},
+                                                            {"ans_encode_categorical_ragged_two_pass<jump>", "range_encode_categorical_ragged_two_pass<jump>"}};
+static constexpr const char* kCatRaggedDecodeNames[2][2] = {{"ans_decode_categorical_ragged_kernel", "range_decode_categorical_ragged_kernel"},
+                                                            {"ans_decode_categorical_ragged_kernel<jump>", "range_decode_categorical_ragged_kernel<jump>"}};
+
+// what all eight calls refuse before they touch the device
+static cst_status check_categorical_ragged_args(cst_coder_config cfg, const void* d_symbols, const void* d_probs, int32_t prob_bytes, int32_t n_symbols,
+                                                const void* d_sym_offsets, const void* d_words, const void* d_word_offsets, size_t stride_words,
+                                                const void* d_n_words, const void* d_status, size_t n_streams) {
+    if (!d_symbols || !d_probs || !d_sym_offsets || !d_words || !d_n_words || !d_status) return CST_ERR_INVALID_ARGUMENT;
+    if (prob_bytes != 4 && prob_bytes != 8) return CST_ERR_INVALID_ARGUMENT;
+    if (!config_supported(cfg)) return CST_ERR_INVALID_ARGUMENT;
+    if (!d_word_offsets && stride_words == 0) return CST_ERR_INVALID_ARGUMENT;
+    if (n_streams > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;          // (a launch has at most 2^31 - 1 blocks; an order names 32-bit indices)
+    // from_floating_point_probabilities_fast: room for a nonzero probability each plus one (check_categorical_args)
+    if (n_symbols < 2 || (uint64_t)n_symbols > ((uint64_t)1 << cfg.precision) - 2) return CST_ERR_MODEL;
+    return CST_OK;
+}
+
+template <int KIND, bool JUMP>
+static cst_status encode_categorical_ragged(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes, int32_t n_symbols,
+                                            size_t n_total, const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order,
+                                            uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words, uint32_t* d_n_words,
+                                            size_t jump_interval, const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos, uint64_t* d_jump_a,
+                                            uint64_t* d_jump_b, int32_t* d_status, hipStream_t hs) {
+    if constexpr (JUMP)
+        if (jump_interval_bad(jump_interval) || !d_chunk_offsets || !d_jump_pos || !d_jump_a || (KIND == kRange && !d_jump_b)) return CST_ERR_INVALID_ARGUMENT;
+    if (cst_status st = check_categorical_ragged_args(cfg, d_symbols, d_probs, prob_bytes, n_symbols, d_sym_offsets, d_words, d_word_offsets,
+                                                      stride_words, d_n_words, d_status, n_streams)) return st;
+    if ((n_total + kWave - 1) / kWave > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;      // (pass 1: a block per 64 rows)
+    if (n_streams == 0) return CST_OK;
+    std::conditional_t<JUMP, EntriesRaggedEncodeJumpArgs, EntriesRaggedEncodeArgs> a{};
+    a.n_total = n_total; a.sym_offsets = d_sym_offsets; a.n_streams = n_streams; a.order = d_order; a.precision = cfg.precision;
+    a.words = d_words; a.word_offsets = d_word_offsets; a.stride_words = stride_words; a.n_words = d_n_words; a.status = d_status;
+    if constexpr (JUMP) {
+        a.jump_interval = (uint32_t)jump_interval; a.jump_chunk_offsets = d_chunk_offsets; a.jump_pos = d_jump_pos; a.jump_a = d_jump_a;
+        a.jump_b = d_jump_b;
+    }
+    const char* name = kCatRaggedEncodeNames[JUMP][KIND == kRange];
+    EncEntry* entries = nullptr;
+    if (n_total > 0) {
+        // pass 1 over the flat matrix, sized by n_total: no read-back of sym_offsets
+        CST_HIP_TRY(scratch_alloc((void**)&entries, n_total * sizeof(EncEntry), hs));
+        const dim3 grid((unsigned)((n_total + kWave - 1) / kWave));
+        if (prob_bytes == 4)
+            hipLaunchKernelGGL(categorical_entries_kernel<float>, grid, dim3(kWave), kCatTileBytes<float>, hs, cfg.precision, (uint32_t)n_symbols,
+                               d_symbols, reinterpret_cast<const float*>(d_probs), n_total, entries);
+        else
+            hipLaunchKernelGGL(categorical_entries_kernel<double>, grid, dim3(kWave), kCatTileBytes<double>, hs, cfg.precision, (uint32_t)n_symbols,
+                               d_symbols, reinterpret_cast<const double*>(d_probs), n_total, entries);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_hip_error(e, "entry kernel"); (void)hipFreeAsync(entries, hs); return note_kernel(name, CST_ERR_HIP); }
+    }
+    a.entries = entries;
+    const size_t blocks = (n_streams + kBlock - 1) / kBlock;
+    const size_t lds = (size_t)(kBlock / kWave) * kRingWords * sizeof(uint32_t);
+    const cst_status st = dispatch_word_size(cfg, [&](auto W, auto S) {
+        return launch_with_lds(encode_entries_ragged_kernel<W, S, KIND, JUMP>, blocks, kBlock, lds, a, hs);
+    });
+    if (entries) {
+        const hipError_t e = hipFreeAsync(entries, hs);
+        if (e != hipSuccess && st == CST_OK) { set_hip_error(e, "hipFreeAsync(entries, hs)"); return note_kernel(name, CST_ERR_HIP); }
+    }
+    return note_kernel(name, st);
+}
+
+template <int KIND, bool JUMP, class Args>
+static cst_status launch_decode_categorical_ragged(cst_coder_config cfg, const Args& a, int32_t prob_bytes, hipStream_t hs) {
+    const size_t blocks = (a.p.n_streams + kWave - 1) / kWave;
+    if (blocks > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
+    return dispatch_word_size(cfg, [&](auto W, auto S) {
+        if (prob_bytes == 4) return launch_with_lds(decode_categorical_ragged_kernel<W, S, KIND, float, JUMP>, blocks, kWave, kCatRaggedLdsBytes<float>, a, hs);
+        return launch_with_lds(decode_categorical_ragged_kernel<W, S, KIND, double, JUMP>, blocks, kWave, kCatRaggedLdsBytes<double>, a, hs);
+    });
+}
+
+template <int KIND>
+static cst_status decode_categorical_ragged(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                            size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                            int32_t n_symbols, size_t n_total, int32_t* d_symbols, const uint64_t* d_sym_offsets, size_t n_streams,
+                                            const uint32_t* d_order, int32_t* d_status, hipStream_t hs) {
+    if (cst_status st = check_categorical_ragged_args(cfg, d_symbols, d_probs, prob_bytes, n_symbols, d_sym_offsets, d_words, d_word_offsets,
+                                                      stride_words, d_n_words, d_status, n_streams)) return st;
+    if (n_streams == 0) return CST_OK;
+    CatRaggedDecodeArgs a{};
+    a.p.words = d_words; a.p.offsets = d_word_offsets; a.p.stride_words = stride_words; a.p.n_words = d_n_words; a.p.words_capacity = words_capacity;
+    a.p.symbols = d_symbols; a.p.n_streams = n_streams; a.p.precision = cfg.precision; a.p.min_symbol = 0; a.p.n_symbols = n_symbols;
+    a.p.status = d_status;
+    a.probs = d_probs; a.n_total = n_total; a.sym_offsets = d_sym_offsets; a.order = d_order;
+    return note_kernel(kCatRaggedDecodeNames[0][KIND == kRange], launch_decode_categorical_ragged<KIND, false>(cfg, a, prob_bytes, hs));
+}
+
+// decode_ragged_jump (cst_persymbol_ragged_jump.hip) with the Categorical chunk decoder between the two table kernels
+// d_jump_a / d_jump_b: the state (ANS, d_jump_b unused), or lower / range (the range coder)
+template <int KIND>
+static cst_status decode_categorical_ragged_jump(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                 size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                                 int32_t n_symbols, size_t n_total, int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                                 size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                 const uint32_t* d_jump_pos, const uint64_t* d_jump_a, const uint64_t* d_jump_b, void* d_scratch,
+                                                 int32_t* d_status, hipStream_t hs) {
+    if (jump_interval_bad(jump_interval) || n_chunks_total > 0xffffffffull || !d_chunk_offsets || !d_jump_pos || !d_jump_a ||
+        (KIND == kRange && !d_jump_b) || !d_scratch) return CST_ERR_INVALID_ARGUMENT;
+    if (cst_status st = check_categorical_ragged_args(cfg, d_symbols, d_probs, prob_bytes, n_symbols, d_sym_offsets, d_words, d_word_offsets,
+                                                      stride_words, d_n_words, d_status, n_streams)) return st;
+    if (n_streams == 0) return CST_OK;
+    const uint32_t interval = (uint32_t)jump_interval;
+    // (slab form without a capacity: all the slabs, as the ragged table coders' jump decoders take it)
+    const uint64_t capacity = words_capacity ? words_capacity : (d_word_offsets ? 0 : (uint64_t)n_streams * stride_words);
+    const PerSymbolJumpScratch v(d_scratch, n_chunks_total);
+    const char* name = kCatRaggedDecodeNames[1][KIND == kRange];
+    if (n_chunks_total > 0) {
+        const unsigned grid = (unsigned)((n_chunks_total + 255) / 256);
+        dispatch_word_size(cfg, [&](auto W, auto S) {
+            hipLaunchKernelGGL((persymbol_jump_chunks_kernel<W, S, KIND>), dim3(grid), dim3(256), 0, hs, d_words, d_sym_offsets, d_word_offsets, stride_words,
+                               capacity, d_n_words, d_chunk_offsets, n_streams, n_chunks_total, interval, d_jump_pos, d_jump_a, d_jump_b, v);
+            return 0;
+        });
+        CST_HIP_TRY(hipGetLastError());
+        // (the slices handed on are absolute offsets that passed the check, or empty: `capacity` bounds them once more; the symbol
+        //  ranges lie inside ONE stream's symbols, and the chunk decoder bounds them by n_total)
+        CatRaggedChunkArgs a{};
+        a.p.words = d_words; a.p.offsets = v.word_off; a.p.stride_words = 0; a.p.n_words = v.n_words; a.p.words_capacity = capacity;
+        a.p.symbols = d_symbols; a.p.n_streams = n_chunks_total; a.p.precision = cfg.precision; a.p.min_symbol = 0; a.p.n_symbols = n_symbols;
+        a.p.status = v.status; a.p.state = v.state; a.p.rstate = v.rstate;
+        a.probs = d_probs; a.n_total = n_total; a.sym_lo = v.sym_lo; a.len = v.len;
+        const cst_status rc = launch_decode_categorical_ragged<KIND, true>(cfg, a, prob_bytes, hs);
+        if (rc != CST_OK) return note_kernel(name, rc);
+    }
+    hipLaunchKernelGGL(persymbol_jump_status_kernel<>, dim3((unsigned)((n_streams + 255) / 256)), dim3(256), 0, hs, v, d_sym_offsets, d_word_offsets,
+                       stride_words, capacity, d_chunk_offsets, d_jump_pos, d_n_words, n_streams, n_chunks_total, interval, d_status);
+    CST_HIP_TRY(hipGetLastError());
+    return note_kernel(name, CST_OK);
+}
+
+} // namespace cst
+
+using namespace cst;
+
+extern "C" {
+
+cst_status cst_ans_encode_categorical_ragged(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes, int32_t n_symbols,
+                                             size_t n_total, const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order,
+                                             uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words, uint32_t* d_n_words,
+                                             int32_t* d_status, void* stream) {
+    return encode_categorical_ragged<kAns, false>(cfg, d_symbols, d_probs, prob_bytes, n_symbols, n_total, d_sym_offsets, n_streams, d_order, d_words,
+                                                  d_word_offsets, stride_words, d_n_words, 0, nullptr, nullptr, nullptr, nullptr, d_status,
+                                                  (hipStream_t)stream);
+}
+
+cst_status cst_range_encode_categorical_ragged(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes,
+                                               int32_t n_symbols, size_t n_total, const uint64_t* d_sym_offsets, size_t n_streams,
+                                               const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                               uint32_t* d_n_words, int32_t* d_status, void* stream) {
+    return encode_categorical_ragged<kRange, false>(cfg, d_symbols, d_probs, prob_bytes, n_symbols, n_total, d_sym_offsets, n_streams, d_order, d_words,
+                                                    d_word_offsets, stride_words, d_n_words, 0, nullptr, nullptr, nullptr, nullptr, d_status,
+                                                    (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_categorical_ragged(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                             size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                             int32_t n_symbols, size_t n_total, int32_t* d_symbols, const uint64_t* d_sym_offsets, size_t n_streams,
+                                             const uint32_t* d_order, int32_t* d_status, void* stream) {
+    return decode_categorical_ragged<kAns>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes, n_symbols, n_total,
+                                           d_symbols, d_sym_offsets, n_streams, d_order, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_categorical_ragged(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                               size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                               int32_t n_symbols, size_t n_total, int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                               size_t n_streams, const uint32_t* d_order, int32_t* d_status, void* stream) {
+    return decode_categorical_ragged<kRange>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes, n_symbols,
+                                             n_total, d_symbols, d_sym_offsets, n_streams, d_order, d_status, (hipStream_t)stream);
+}
+
+// ---- jump points: the plain calls' arguments, then the interval and the table ----
+
+cst_status cst_ans_encode_categorical_ragged_jump(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes,
+                                                  int32_t n_symbols, size_t n_total, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                  const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                  uint32_t* d_n_words, size_t jump_interval, const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos,
+                                                  uint64_t* d_jump_state, int32_t* d_status, void* stream) {
+    return encode_categorical_ragged<kAns, true>(cfg, d_symbols, d_probs, prob_bytes, n_symbols, n_total, d_sym_offsets, n_streams, d_order, d_words,
+                                                 d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos, d_jump_state,
+                                                 nullptr, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_encode_categorical_ragged_jump(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes,
+                                                    int32_t n_symbols, size_t n_total, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                    const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                    uint32_t* d_n_words, size_t jump_interval, const uint64_t* d_chunk_offsets,
+                                                    uint32_t* d_jump_pos, uint64_t* d_jump_lower, uint64_t* d_jump_range, int32_t* d_status,
+                                                    void* stream) {
+    return encode_categorical_ragged<kRange, true>(cfg, d_symbols, d_probs, prob_bytes, n_symbols, n_total, d_sym_offsets, n_streams, d_order, d_words,
+                                                   d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos, d_jump_lower,
+                                                   d_jump_range, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_categorical_ragged_jump(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                  size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                                  int32_t n_symbols, size_t n_total, int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                                  size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                  const uint32_t* d_jump_pos, const uint64_t* d_jump_state, void* d_scratch, int32_t* d_status,
+                                                  void* stream) {
+    return decode_categorical_ragged_jump<kAns>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes, n_symbols,
+                                                n_total, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos,
+                                                d_jump_state, nullptr, d_scratch, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_categorical_ragged_jump(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                    size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                                    int32_t n_symbols, size_t n_total, int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                                    size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                    const uint32_t* d_jump_pos, const uint64_t* d_jump_lower, const uint64_t* d_jump_range,
+                                                    void* d_scratch, int32_t* d_status, void* stream) {
+    return decode_categorical_ragged_jump<kRange>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes, n_symbols,
+                                                  n_total, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos,
+                                                  d_jump_lower, d_jump_range, d_scratch, d_status, (hipStream_t)stream);
+}
+
+} // extern "C"

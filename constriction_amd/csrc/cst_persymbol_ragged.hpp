@@ -1,6 +1,7 @@
 // cst_persymbol_ragged.hpp -- the kernels of the per-symbol coders for streams of DIFFERENT lengths, shared by the two files that
 // instantiate them: cst_persymbol_ragged.hip (the plain forms, JUMP = false) and cst_persymbol_ragged_jump.hip (JUMP = true).  Every
-// instantiation still lives in ONE file (cst_persymbol.hpp): the template parameter decides which.
+// instantiation of these still lives in ONE file (cst_persymbol.hpp): the template parameter decides which.  At the end: the
+// model-independent kernels around a jump table, which cst_persymbol_categorical_ragged.hip launches too.
 #pragma once
 #include "cst_persymbol.hpp"
 
@@ -523,5 +524,107 @@ inline cst_status check_ragged_gaussian_args(cst_coder_config cfg, int32_t min_s
     if (support_too_large(cfg, min_symbol, max_symbol)) return CST_ERR_MODEL;      // (the support limit of the rectangular calls)
     return CST_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// jump points: the encoder's JUMP form notes the table; the decoder runs every table entry as a coder of its own.  What follows knows
+// nothing of the model: cst_persymbol_ragged_jump.hip and cst_persymbol_categorical_ragged.hip both launch it around their own chunk
+// decoder (templates, all of them: each unit's code object carries its copy, the host side folds them).
+// ------------------------------------------------------------------------------------------------
+
+// what the decoder keeps per table entry (d_scratch, cst_persymbol_ragged_jump_scratch_bytes): 80 bytes each
+struct PerSymbolJumpScratch {
+    uint64_t* sym_lo; uint64_t* word_off; uint64_t* state; cst_range_state* rstate;
+    uint32_t* len; uint32_t* n_words; uint32_t* owner; int32_t* status;
+    PerSymbolJumpScratch(void* d_scratch, size_t n) {
+        unsigned char* b = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(d_scratch) + 15) & ~(uintptr_t)15);
+        rstate = reinterpret_cast<cst_range_state*>(b);
+        sym_lo = reinterpret_cast<uint64_t*>(rstate + n); word_off = sym_lo + n; state = word_off + n;
+        len = reinterpret_cast<uint32_t*>(state + n); n_words = len + n; owner = n_words + n;
+        status = reinterpret_cast<int32_t*>(owner + n);
+    }
+};
+static_assert(sizeof(cst_range_state) == 40, "the scratch layout above");
+constexpr uint32_t kPjNoOwner = 0xffffffffu;
+
+// The chunks of a batch as coders of their own, one thread per table entry (rr_chunks_kernel's scheme, cst_range_ragged.hip): entry c
+// belongs to the stream s with chunk_offsets[s] <= c < chunk_offsets[s + 1], found by bisection -- the table is caller data, and
+// whatever it holds, every entry is written here and gets a symbol range inside ONE stream's symbols or none at all.  It decodes symbols
+// [j I, min(j I + I, len)) of its stream, j = c - chunk_offsets[s]; entries that belong to no stream (behind the last chunk:
+// n_chunks_total may be an upper bound) are empty.  The stream's slice of the words is checked HERE as the plain decoder checks it
+// (per-slab bound included) and handed on as an absolute offset, or as the empty slice.
+//   ANS:    the chunk's words are the first jump_pos[c] of its stream's (AnsCoder::seek, stack.rs:1107-1139) -- none where the jump
+//           point lies beyond the stream's words -- and its state a copy of jump_state[c].
+//   range:  RangeDecoder::seek (queue.rs:911-926) as gaussian_range_virtual_kernel does it: lower and range from the table, the point
+//           re-read at the jump point, which is clamped to the stream's words; the chunk reads on from there, never past n_words[s].
+template <int W, int S, int KIND>
+__global__ void persymbol_jump_chunks_kernel(const uint32_t* __restrict__ words, const uint64_t* __restrict__ sym_offsets,
+                                             const uint64_t* __restrict__ word_offsets, size_t stride_words, uint64_t words_capacity,
+                                             const uint32_t* __restrict__ n_words, const uint64_t* __restrict__ chunk_offsets, size_t n_streams,
+                                             size_t n_chunks_total, uint32_t interval, const uint32_t* __restrict__ jump_pos,
+                                             const uint64_t* __restrict__ jump_a, const uint64_t* __restrict__ jump_b, PerSymbolJumpScratch v) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_chunks_total) return;
+    size_t s = 0, hi = n_streams;          // the last stream with chunk_offsets[s] <= c
+    while (hi - s > 1) {
+        const size_t mid = s + (hi - s) / 2;
+        if (chunk_offsets[mid] <= c) s = mid; else hi = mid;
+    }
+    const uint64_t c0 = chunk_offsets[s], c1 = chunk_offsets[s + 1];
+    const uint64_t lo = sym_offsets[s], end = sym_offsets[s + 1];
+    const uint64_t start = (c - c0) * interval;
+    const bool mine = c >= c0 && c < c1 && end >= lo && end - lo <= 0xffffffffull && start < end - lo;
+    const WordSlice ws = mine ? word_slice(word_offsets, stride_words, n_words, s, words_capacity) : WordSlice{0, 0u, false};
+    const uint64_t left = mine ? end - lo - start : 0;
+    v.sym_lo[c] = mine ? lo + start : 0;
+    v.len[c] = (uint32_t)(left < interval ? left : interval);
+    v.word_off[c] = ws.off;
+    v.owner[c] = mine ? (uint32_t)s : kPjNoOwner;
+    const uint32_t jp = mine ? jump_pos[c] : 0u;
+    if constexpr (KIND == kAns) {
+        v.n_words[c] = jp <= ws.n ? jp : 0u;
+        v.state[c] = mine ? jump_a[c] : 0;
+    } else {
+        uint32_t pos = jp < ws.n ? jp : ws.n;
+        uint64_t pt = 0;
+        int num_read = 0;
+        const uint64_t mask = S == 64 ? ~0ull : ((1ull << (S % 64)) - 1ull);
+        while (pos < ws.n) {                                          // read_point, queue.rs:847-868
+            pt = ((pt << (W % 64)) | (uint64_t)words[ws.off + pos++]) & mask;
+            if (++num_read == S / W) break;
+        }
+        if (num_read < S / W && num_read != 0) pt = (pt << (S - num_read * W)) & mask;
+        cst_range_state r{};
+        r.lower = mine ? jump_a[c] & mask : 0; r.range = mine ? jump_b[c] & mask : mask; r.point = pt; r.position = pos;
+        v.rstate[c] = r;
+        v.n_words[c] = ws.n;
+    }
+}
+
+// a stream's status: the worst of its chunks'.  A table that does not describe the stream (chunks != ceil(len / I), entries beyond
+// n_chunks_total or given to another stream), a jump point beyond the stream's words, or words that leave the buffer, are caller data
+// gone wrong: CST_STREAM_INVALID_DATA.  (A stream too long for one coder: CST_STREAM_CAPACITY, as the plain decoder says.)
+template <int = 0>       // (a template only so that every unit that launches it may hold a copy: launched as ...<>)
+__global__ void persymbol_jump_status_kernel(PerSymbolJumpScratch v, const uint64_t* __restrict__ sym_offsets, const uint64_t* __restrict__ word_offsets,
+                                             size_t stride_words, uint64_t words_capacity, const uint64_t* __restrict__ chunk_offsets,
+                                             const uint32_t* __restrict__ jump_pos, const uint32_t* __restrict__ n_words, size_t n_streams,
+                                             size_t n_chunks_total, uint32_t interval, int32_t* __restrict__ status) {
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_streams) return;
+    const uint64_t lo = sym_offsets[s], end = sym_offsets[s + 1];
+    const uint64_t c0 = chunk_offsets[s], c1 = chunk_offsets[s + 1];
+    int32_t worst = CST_STREAM_OK;
+    if (word_slice(word_offsets, stride_words, n_words, s, words_capacity).bad) worst = CST_STREAM_INVALID_DATA;
+    else if (end < lo || end - lo > 0xffffffffull) worst = CST_STREAM_CAPACITY;
+    else if (c1 < c0 || c1 > n_chunks_total || c1 - c0 != (end - lo + interval - 1) / interval) worst = CST_STREAM_INVALID_DATA;
+    else
+        for (uint64_t c = c0; c < c1; ++c) {
+            worst = max(worst, v.status[c]);
+            if (v.owner[c] != (uint32_t)s || jump_pos[c] > n_words[s]) worst = CST_STREAM_INVALID_DATA;
+        }
+    status[s] = worst;
+}
+
+// what the jump calls refuse on top of the plain calls' refusals
+static bool jump_interval_bad(size_t jump_interval) { return jump_interval == 0 || jump_interval % kFuTile != 0 || jump_interval > 0x7fffffffull; }
 
 } // namespace cst

@@ -1044,6 +1044,73 @@ cst_status cst_range_decode_categorical_perfect_batch(cst_coder_config cfg, cons
                                                       cst_layout layout, cst_range_state *d_rstate, int32_t *d_status,
                                                       uint32_t flags, void *stream);
 
+/* Categorical probability matrices for streams of DIFFERENT lengths (the fast quantisation of cst_*_categorical_batch: Categorical(perfect=False) /
+ * Categorical(lazy=True)), plain and with jump points, both coders, both presets.  Stream s owns rows [d_sym_offsets[s], d_sym_offsets[s + 1])
+ * of the flat matrix d_probs [n_total][n_symbols] (float: prob_bytes = 4, double: 8) and of the flat d_symbols [n_total].  Every stream's
+ * words, word count and status are those of cst_{ans,range}_{encode,decode}_categorical_batch for that stream alone, bit for bit.
+ *   - d_order, d_word_offsets / stride_words / words_capacity, the slabs and empty streams (no words, CST_STREAM_OK): as in
+ *     cst_{ans,range}_{encode,decode}_gaussian_ragged.
+ *   - n_total: the rows of d_probs and the elements of d_symbols.  Pass 1 of the encoders is sized by it (no read-back of d_sym_offsets), and
+ *     the device bounds every row index by it: a stream that reaches beyond n_total reports CST_STREAM_INVALID_DATA and nothing is coded for
+ *     it; one whose symbol range runs backwards or exceeds 2^32 - 1 reports CST_STREAM_CAPACITY.  The other streams are unaffected.
+ *   - A bad row (see cst_ans_encode_categorical_batch), a symbol outside [0, n_symbols) and an empty interval yield
+ *     CST_STREAM_IMPOSSIBLE_SYMBOL for their stream only.
+ *   - *_jump: the plain call's arguments (the decoders' WITHOUT d_order), then jump_interval, d_chunk_offsets and the table -- argument order,
+ *     table layout and semantics exactly those of cst_{ans,range}_{encode,decode}_gaussian_ragged_jump; the decoders' d_scratch holds
+ *     cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) bytes.  jump_interval: a positive multiple of 16, at most 2^31 - 1.
+ *   - Before the device is touched: a NULL pointer (d_order and d_word_offsets may be NULL, the latter with stride_words > 0), prob_bytes
+ *     outside {4, 8}, an unsupported cfg, n_streams > 2^31 - 1, n_total > 64 (2^31 - 1) (encoders) and every refusal of the Gaussian jump
+ *     calls return CST_ERR_INVALID_ARGUMENT; then n_symbols < 2 or n_symbols >= 2^precision - 1 returns CST_ERR_MODEL.  n_streams == 0:
+ *     CST_OK, nothing is launched.
+ *   - One route for every batch size: built for many streams; a few are coded correctly, but slowly.  Not here: the perfect quantisation,
+ *     the symbol-major layout (a ragged batch has none), a count_until, intervals that are no multiple of 16.
+ * cst_last_kernel_name(): {ans,range}_encode_categorical_ragged_two_pass, {ans,range}_decode_categorical_ragged_kernel, and the same names
+ * followed by <jump>. */
+cst_status cst_ans_encode_categorical_ragged(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs, int32_t prob_bytes,
+                                             int32_t n_symbols, size_t n_total, const uint64_t *d_sym_offsets, size_t n_streams,
+                                             const uint32_t *d_order, uint32_t *d_words, const uint64_t *d_word_offsets,
+                                             size_t stride_words, uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_categorical_ragged(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                             size_t stride_words, size_t words_capacity, const uint32_t *d_n_words, const void *d_probs,
+                                             int32_t prob_bytes, int32_t n_symbols, size_t n_total, int32_t *d_symbols,
+                                             const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order, int32_t *d_status,
+                                             void *stream);
+cst_status cst_range_encode_categorical_ragged(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs, int32_t prob_bytes,
+                                               int32_t n_symbols, size_t n_total, const uint64_t *d_sym_offsets, size_t n_streams,
+                                               const uint32_t *d_order, uint32_t *d_words, const uint64_t *d_word_offsets,
+                                               size_t stride_words, uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_range_decode_categorical_ragged(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                               size_t stride_words, size_t words_capacity, const uint32_t *d_n_words, const void *d_probs,
+                                               int32_t prob_bytes, int32_t n_symbols, size_t n_total, int32_t *d_symbols,
+                                               const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order, int32_t *d_status,
+                                               void *stream);
+cst_status cst_ans_encode_categorical_ragged_jump(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs, int32_t prob_bytes,
+                                                  int32_t n_symbols, size_t n_total, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                  const uint32_t *d_order, uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                  size_t stride_words, uint32_t *d_n_words, size_t jump_interval,
+                                                  const uint64_t *d_chunk_offsets, uint32_t *d_jump_pos, uint64_t *d_jump_state,
+                                                  int32_t *d_status, void *stream);
+cst_status cst_ans_decode_categorical_ragged_jump(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                  size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                  const void *d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                  int32_t *d_symbols, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                  size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                  const uint32_t *d_jump_pos, const uint64_t *d_jump_state, void *d_scratch,
+                                                  int32_t *d_status, void *stream);
+cst_status cst_range_encode_categorical_ragged_jump(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs, int32_t prob_bytes,
+                                                    int32_t n_symbols, size_t n_total, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                    const uint32_t *d_order, uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                    size_t stride_words, uint32_t *d_n_words, size_t jump_interval,
+                                                    const uint64_t *d_chunk_offsets, uint32_t *d_jump_pos, uint64_t *d_jump_lower,
+                                                    uint64_t *d_jump_range, int32_t *d_status, void *stream);
+cst_status cst_range_decode_categorical_ragged_jump(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                    size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                    const void *d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                    int32_t *d_symbols, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                    size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                    const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
+                                                    const uint64_t *d_jump_range, void *d_scratch, int32_t *d_status, void *stream);
+
 /* ABI 5: jump points for the per-symbol Gaussian calls of the RANGE coder (RangeEncoder::pos / RangeDecoder::seek, src/stream/queue.rs:172-196,
  * 900-926), as cst_ans_{encode,decode}_gaussian_batch_ckpt are for ANS: the fused encoder notes (words emitted including held-back ones,
  * lower, range) in front of every chunk of ckpt_interval symbols (a multiple of 16 that divides n_per_stream; stream-major), the decoder

@@ -9,8 +9,10 @@
 --jump-every N (a multiple of 16; default 0: not run): also (j) the same batch with a jump point every N symbols of every stream --
 `jump_every=N` of the encoder, and the decode of all chunks side by side -- timed beside the plain pair of (a) in the same run,
 alternating; recorded per alternation, with the size of the table against the words.  No condition on it.
---coder ans|range and --family gaussian|laplace|cauchy choose the form (default: ans, gaussian); --skip-grouped leaves (b) out (it
-takes seconds per alternation and minutes to set up; its condition is then not judged).
+--coder ans|range and --family gaussian|laplace|cauchy|categorical choose the form (default: ans, gaussian); --skip-grouped leaves (b)
+out (it takes seconds per alternation and minutes to set up; its condition is then not judged).
+--family categorical --k K: every symbol has its own row of K float32 probabilities (exp(3 z), z normal: not normalised; symbols drawn
+from the rows) in place of (mean, std) -- symbols x K x 4 bytes for the ragged batch and as much again for (c), so K has to fit memory.
 Device events on the launch stream, warmed up, in one process, the candidates alternating, medians of the alternations.  Every
 stream is checked by the decode round trip.  The one condition: (a) is faster than (b) in every alternation (exit status 1 otherwise);
 (c) is a recorded ratio."""
@@ -26,7 +28,8 @@ ap.add_argument("--min-len", type=int, default=256)
 ap.add_argument("--max-len", type=int, default=8192)
 ap.add_argument("--alternations", type=int, default=5)
 ap.add_argument("--coder", choices=["ans", "range"], default="ans")
-ap.add_argument("--family", choices=["gaussian", "laplace", "cauchy"], default="gaussian")
+ap.add_argument("--family", choices=["gaussian", "laplace", "cauchy", "categorical"], default="gaussian")
+ap.add_argument("--k", type=int, default=16, help="--family categorical: entries of a probability row")
 ap.add_argument("--jump-every", type=int, default=0, help="also time the pair with a jump point every N symbols (a multiple of 16)")
 ap.add_argument("--skip-rectangular", action="store_true", help="leave (c), the rectangular matrix, out")
 ap.add_argument("--skip-grouped", action="store_true", help="leave (b), one rectangular call per distinct length, out")
@@ -39,10 +42,20 @@ dev = "cuda"
 enc_ragged, dec_ragged = getattr(B, f"{args.coder}_encode_{args.family}_ragged"), getattr(B, f"{args.coder}_decode_{args.family}_ragged")
 enc_rect, dec_rect = getattr(B, f"{args.coder}_encode_{args.family}"), getattr(B, f"{args.coder}_decode_{args.family}")
 NO_JUMP = {"jump_points": 0} if args.family == "gaussian" else {}      # (the family calls have no jump points to switch off)
+CATEGORICAL = args.family == "categorical"
+HEAD = () if CATEGORICAL else (LO, HI)                                  # what the calls take in front of the model's tensors
 
 
 def draw(*shape):
-    """mu uniform in 0.6 [lo, hi], sd log-uniform in 0.3 .. 40, symbols = clipped rounded draws from the family"""
+    """mu uniform in 0.6 [lo, hi], sd log-uniform in 0.3 .. 40, symbols = clipped rounded draws from the family; returns (symbols, the
+    model's tensors)"""
+    if CATEGORICAL:
+        probs = torch.randn(*shape, args.k, dtype=torch.float32, device=dev).mul_(3.0).exp_()      # (in place: the matrix is the memory)
+        sym = torch.empty(shape, dtype=torch.int32, device=dev)
+        flat_p, flat_s = probs.view(-1, args.k), sym.view(-1)
+        for i in range(0, flat_s.numel(), 1 << 22):           # (multinomial takes at most 2^24 rows a call)
+            flat_s[i: i + (1 << 22)] = torch.multinomial(flat_p[i: i + (1 << 22)], 1).view(-1).to(torch.int32)
+        return sym, (probs,)
     mu = (torch.rand(*shape, dtype=torch.float64, device=dev) * 2 - 1) * (0.6 * HI)
     sd = torch.exp(torch.log(torch.tensor(0.3, dtype=torch.float64, device=dev))
                    + torch.rand(*shape, dtype=torch.float64, device=dev) * torch.log(torch.tensor(40.0 / 0.3, dtype=torch.float64, device=dev)))
@@ -52,7 +65,7 @@ def draw(*shape):
         u = torch.rand(*shape, dtype=torch.float64, device=dev) - 0.5
         noise = -torch.sign(u) * torch.log1p(-2 * u.abs()) if args.family == "laplace" else torch.tan(torch.pi * u)
     sym = torch.clamp(torch.round(mu + sd * noise), LO, HI).to(torch.int32)
-    return sym, mu, sd
+    return sym, (mu, sd)
 
 
 def timed(fn):
@@ -81,10 +94,10 @@ lengths = torch.randint(args.min_len, args.max_len + 1, (n,), dtype=torch.int64,
 offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
 torch.cumsum(lengths, 0, out=offsets[1:])
 total = int(offsets[-1])
-sym, mu, sd = draw(total)
+sym, model = draw(total)
 
-enc = enc_ragged(sym, offsets, LO, HI, mu, sd, CFG)
-dec, st = dec_ragged(enc, offsets, LO, HI, mu, sd)
+enc = enc_ragged(sym, offsets, *HEAD, *model, CFG)
+dec, st = dec_ragged(enc, offsets, *HEAD, *model)
 torch.cuda.synchronize()
 ok_a = bool(torch.equal(dec, sym)) and int(enc.status.abs().sum()) == 0 and int(st.abs().sum()) == 0
 
@@ -92,7 +105,7 @@ ok_a = bool(torch.equal(dec, sym)) and int(enc.status.abs().sum()) == 0 and int(
 order = torch.argsort(lengths, stable=True)
 sorted_len = lengths[order].cpu().tolist() if not args.skip_grouped else []
 order_h, off_h = order.cpu().tolist(), offsets.cpu().tolist()
-groups = []          # (streams, symbols, means, stds) per distinct length
+groups = []          # (streams, symbols, the model's tensors) per distinct length
 i = 0 if not args.skip_grouped else n
 while i < n:
     j = i
@@ -101,20 +114,20 @@ while i < n:
     L = sorted_len[i]
     rows = order_h[i:j]
     idx = torch.cat([torch.arange(off_h[s], off_h[s] + L, device=dev) for s in rows])
-    groups.append((rows, sym[idx].reshape(len(rows), L), mu[idx].reshape(len(rows), L), sd[idx].reshape(len(rows), L)))
+    groups.append((rows, sym[idx].reshape(len(rows), L), tuple(m[idx].reshape(len(rows), L, *m.shape[1:]) for m in model)))
     i = j
 group_enc = [None] * len(groups)
 group_dec = [None] * len(groups)
 
 
 def b_encode():
-    for g, (_, s_, m_, d_) in enumerate(groups):
-        group_enc[g] = enc_rect(s_, LO, HI, m_, d_, CFG, **NO_JUMP)
+    for g, (_, s_, m_) in enumerate(groups):
+        group_enc[g] = enc_rect(s_, *HEAD, *m_, CFG, **NO_JUMP)
 
 
 def b_decode():
-    for g, (_, s_, m_, d_) in enumerate(groups):
-        group_dec[g] = dec_rect(group_enc[g], LO, HI, m_, d_)
+    for g, (_, s_, m_) in enumerate(groups):
+        group_dec[g] = dec_rect(group_enc[g], *HEAD, *m_)
 
 
 b_encode(); b_decode()
@@ -129,17 +142,17 @@ ok_b = ok_b and (args.skip_grouped or bool(torch.equal(n_words_b, enc.n_words)))
 
 # (a) once more with a schedule (streams of similar length side by side, the sort itself not timed): recorded, no condition on it
 by_length = B.ragged_order(lengths)
-enc_s = enc_ragged(sym, offsets, LO, HI, mu, sd, CFG, order=by_length)
-dec_s, st_s = dec_ragged(enc_s, offsets, LO, HI, mu, sd)
+enc_s = enc_ragged(sym, offsets, *HEAD, *model, CFG, order=by_length)
+dec_s, st_s = dec_ragged(enc_s, offsets, *HEAD, *model)
 torch.cuda.synchronize()
 ok_a = ok_a and bool(torch.equal(dec_s, sym)) and int(st_s.abs().sum()) == 0 and bool(torch.equal(enc_s.n_words, enc.n_words))
 
-t_ab = alternate({"a_encode": lambda: enc_ragged(sym, offsets, LO, HI, mu, sd, CFG),
+t_ab = alternate({"a_encode": lambda: enc_ragged(sym, offsets, *HEAD, *model, CFG),
                   "b_encode": b_encode,
-                  "a_sorted_encode": lambda: enc_ragged(sym, offsets, LO, HI, mu, sd, CFG, order=by_length),
-                  "a_decode": lambda: dec_ragged(enc, offsets, LO, HI, mu, sd, out=dec),
+                  "a_sorted_encode": lambda: enc_ragged(sym, offsets, *HEAD, *model, CFG, order=by_length),
+                  "a_decode": lambda: dec_ragged(enc, offsets, *HEAD, *model, out=dec),
                   "b_decode": b_decode,
-                  "a_sorted_decode": lambda: dec_ragged(enc_s, offsets, LO, HI, mu, sd, out=dec_s)}, args.alternations)
+                  "a_sorted_decode": lambda: dec_ragged(enc_s, offsets, *HEAD, *model, out=dec_s)}, args.alternations)
 faster = args.skip_grouped or (all(a < b for a, b in zip(t_ab["a_encode"], t_ab["b_encode"]))
                                and all(a < b for a, b in zip(t_ab["a_decode"], t_ab["b_decode"])))
 del groups, group_enc, group_dec
@@ -147,15 +160,15 @@ del groups, group_enc, group_dec
 # ---- (j): jump points, beside the plain pair ----
 ok_j, t_j, jump_info = True, {}, None
 if args.jump_every:
-    enc_j = enc_ragged(sym, offsets, LO, HI, mu, sd, CFG, jump_every=args.jump_every)
-    dec_j, st_j = dec_ragged(enc_j, offsets, LO, HI, mu, sd)
+    enc_j = enc_ragged(sym, offsets, *HEAD, *model, CFG, jump_every=args.jump_every)
+    dec_j, st_j = dec_ragged(enc_j, offsets, *HEAD, *model)
     torch.cuda.synchronize()
     ok_j = (B.last_kernel() == f"{args.coder}_decode_{args.family}_ragged_kernel<jump>" and bool(torch.equal(dec_j, sym)) and int(st_j.abs().sum()) == 0
             and int(enc_j.status.abs().sum()) == 0 and bool(torch.equal(enc_j.n_words, enc.n_words)))
-    t_j = alternate({"plain_encode": lambda: enc_ragged(sym, offsets, LO, HI, mu, sd, CFG),
-                     "jump_encode": lambda: enc_ragged(sym, offsets, LO, HI, mu, sd, CFG, jump_every=args.jump_every),
-                     "plain_decode": lambda: dec_ragged(enc, offsets, LO, HI, mu, sd, out=dec),
-                     "jump_decode": lambda: dec_ragged(enc_j, offsets, LO, HI, mu, sd, out=dec_j)}, args.alternations)
+    t_j = alternate({"plain_encode": lambda: enc_ragged(sym, offsets, *HEAD, *model, CFG),
+                     "jump_encode": lambda: enc_ragged(sym, offsets, *HEAD, *model, CFG, jump_every=args.jump_every),
+                     "plain_decode": lambda: dec_ragged(enc, offsets, *HEAD, *model, out=dec),
+                     "jump_decode": lambda: dec_ragged(enc_j, offsets, *HEAD, *model, out=dec_j)}, args.alternations)
     n_chunks = int(enc_j.jump.chunk_offsets[-1])
     jump_info = {"every": args.jump_every, "chunks": n_chunks, "table_bytes": n_chunks * (12 if args.coder == "ans" else 20),
                  "word_bytes": 4 * int(enc.n_words.sum()),
@@ -167,25 +180,26 @@ if args.jump_every:
 ok_c, t_c = True, {}
 if not args.skip_rectangular:
     n_per = (args.min_len + args.max_len) // 2
-    sym_r, mu_r, sd_r = draw(n, n_per)
+    del model
+    sym_r, model_r = draw(n, n_per)
     off_r = torch.arange(n + 1, dtype=torch.int64, device=dev) * n_per
-    flat_r, mu_f, sd_f = sym_r.reshape(-1), mu_r.reshape(-1), sd_r.reshape(-1)
-    enc_r = enc_rect(sym_r, LO, HI, mu_r, sd_r, CFG, **NO_JUMP)
-    dec_r, st_r = dec_rect(enc_r, LO, HI, mu_r, sd_r)
-    enc_e = enc_ragged(flat_r, off_r, LO, HI, mu_f, sd_f, CFG)
-    dec_e, st_e = dec_ragged(enc_e, off_r, LO, HI, mu_f, sd_f)
+    flat_r, model_f = sym_r.reshape(-1), tuple(m.reshape(n * n_per, *m.shape[2:]) for m in model_r)
+    enc_r = enc_rect(sym_r, *HEAD, *model_r, CFG, **NO_JUMP)
+    dec_r, st_r = dec_rect(enc_r, *HEAD, *model_r)
+    enc_e = enc_ragged(flat_r, off_r, *HEAD, *model_f, CFG)
+    dec_e, st_e = dec_ragged(enc_e, off_r, *HEAD, *model_f)
     torch.cuda.synchronize()
     ok_c = bool(torch.equal(dec_r, sym_r)) and bool(torch.equal(dec_e, flat_r)) and int(st_r.abs().sum()) == 0 and int(st_e.abs().sum()) == 0 \
         and bool(torch.equal(enc_r.n_words, enc_e.n_words))
-    t_c = alternate({"rect_encode": lambda: enc_rect(sym_r, LO, HI, mu_r, sd_r, CFG, out=enc_r, **NO_JUMP),
-                     "ragged_encode": lambda: enc_ragged(flat_r, off_r, LO, HI, mu_f, sd_f, CFG),
-                     "rect_decode": lambda: dec_rect(enc_r, LO, HI, mu_r, sd_r, out=dec_r),
-                     "ragged_decode": lambda: dec_ragged(enc_e, off_r, LO, HI, mu_f, sd_f, out=dec_e)}, args.alternations)
+    t_c = alternate({"rect_encode": lambda: enc_rect(sym_r, *HEAD, *model_r, CFG, out=enc_r, **NO_JUMP),
+                     "ragged_encode": lambda: enc_ragged(flat_r, off_r, *HEAD, *model_f, CFG),
+                     "rect_decode": lambda: dec_rect(enc_r, *HEAD, *model_r, out=dec_r),
+                     "ragged_decode": lambda: dec_ragged(enc_e, off_r, *HEAD, *model_f, out=dec_e)}, args.alternations)
 
 med = lambda xs: statistics.median(xs)
 m_ab = {k: med(v) for k, v in t_ab.items()}
 m_c = {k: med(v) for k, v in t_c.items()}
-print(f"{args.coder} x {args.family}: {n} streams of {args.min_len} .. {args.max_len} symbols ({total / 1e6:.1f} M symbols), (32,64,24), "
+print(f"{args.coder} x {args.family}{f' (K = {args.k}, float32)' if CATEGORICAL else ''}: {n} streams of {args.min_len} .. {args.max_len} symbols ({total / 1e6:.1f} M symbols), (32,64,24), "
       f"medians of {args.alternations}:")
 print(f"  (a) ragged calls:               encode {m_ab['a_encode']:9.3f} ms ({total / m_ab['a_encode'] / 1e6:.2f} Gsym/s)  "
       f"decode {m_ab['a_decode']:9.3f} ms ({total / m_ab['a_decode'] / 1e6:.2f} Gsym/s)  round trip ok={ok_a}")
@@ -211,7 +225,7 @@ else:
     print(f"  (c) {n} x {n_per} rectangular:  encode {m_c['rect_encode']:9.3f} ms  decode {m_c['rect_decode']:9.3f} ms")
     print(f"      the same through the ragged calls: encode {m_c['ragged_encode']:9.3f} ms ({m_c['ragged_encode'] / m_c['rect_encode']:.2f}x)  "
           f"decode {m_c['ragged_decode']:9.3f} ms ({m_c['ragged_decode'] / m_c['rect_decode']:.2f}x)  round trips ok={ok_c}")
-print(json.dumps({"coder": args.coder, "family": args.family, "grouped": not args.skip_grouped, "streams": n, "symbols": total, "alternations": args.alternations, "ms": {**m_ab, **m_c}, "all_ms": {**t_ab, **t_c},
+print(json.dumps({"coder": args.coder, "family": args.family, "k": args.k if CATEGORICAL else None, "grouped": not args.skip_grouped, "streams": n, "symbols": total, "alternations": args.alternations, "ms": {**m_ab, **m_c}, "all_ms": {**t_ab, **t_c},
                   "jump": jump_info, "jump_ms": {k: med(v) for k, v in t_j.items()}, "jump_all_ms": t_j,
                   "a_faster_than_b": faster, "round_trips_ok": ok_a and ok_b and ok_c and ok_j}))
 sys.exit(0 if faster and ok_a and ok_b and ok_c and ok_j else 1)
