@@ -5,7 +5,7 @@
 //   encode_entries_ragged_kernel      encoder pass 2: encode_entries_kernel's ANS and range branches with one lane per stream
 //   decode_categorical_ragged_kernel  decode_categorical_lane_kernel with a row index per lane
 // Their JUMP forms note / start from the jump table of cst_*_gaussian_ragged_jump; the kernels that turn a table into chunks and chunk
-// statuses into stream statuses are the model-independent ones of cst_persymbol_ragged.hpp.  A unit of its own: the instantiations
+// statuses into stream statuses, and the host routine around them, are the model-independent ones of cst_persymbol_ragged.hpp.  A unit of its own: the instantiations
 // stay out of cst_persymbol_categorical.hip, the build's longest compile.
 #include "cst_persymbol_ragged.hpp"
 #include "cst_categorical.hpp"
@@ -353,7 +353,7 @@ static cst_status encode_categorical_ragged(cst_coder_config cfg, const int32_t*
                                             size_t jump_interval, const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos, uint64_t* d_jump_a,
                                             uint64_t* d_jump_b, int32_t* d_status, hipStream_t hs) {
     if constexpr (JUMP)
-        if (jump_interval_bad(jump_interval) || !d_chunk_offsets || !d_jump_pos || !d_jump_a || (KIND == kRange && !d_jump_b)) return CST_ERR_INVALID_ARGUMENT;
+        if (jump_table_bad<KIND>(jump_interval, d_chunk_offsets, d_jump_pos, d_jump_a, d_jump_b)) return CST_ERR_INVALID_ARGUMENT;
     if (cst_status st = check_categorical_ragged_args(cfg, d_symbols, d_probs, prob_bytes, n_symbols, d_sym_offsets, d_words, d_word_offsets,
                                                       stride_words, d_n_words, d_status, n_streams)) return st;
     if ((n_total + kWave - 1) / kWave > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;      // (pass 1: a block per 64 rows)
@@ -419,8 +419,7 @@ static cst_status decode_categorical_ragged(cst_coder_config cfg, const uint32_t
     return note_kernel(kCatRaggedDecodeNames[0][KIND == kRange], launch_decode_categorical_ragged<KIND, false>(cfg, a, prob_bytes, hs));
 }
 
-// decode_ragged_jump (cst_persymbol_ragged_jump.hip) with the Categorical chunk decoder between the two table kernels
-// d_jump_a / d_jump_b: the state (ANS, d_jump_b unused), or lower / range (the range coder)
+// the Categorical chunk decoder between the two table kernels (decode_jump_chunks, cst_persymbol_ragged.hpp)
 template <int KIND>
 static cst_status decode_categorical_ragged_jump(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
                                                  size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
@@ -428,38 +427,19 @@ static cst_status decode_categorical_ragged_jump(cst_coder_config cfg, const uin
                                                  size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
                                                  const uint32_t* d_jump_pos, const uint64_t* d_jump_a, const uint64_t* d_jump_b, void* d_scratch,
                                                  int32_t* d_status, hipStream_t hs) {
-    if (jump_interval_bad(jump_interval) || n_chunks_total > 0xffffffffull || !d_chunk_offsets || !d_jump_pos || !d_jump_a ||
-        (KIND == kRange && !d_jump_b) || !d_scratch) return CST_ERR_INVALID_ARGUMENT;
-    if (cst_status st = check_categorical_ragged_args(cfg, d_symbols, d_probs, prob_bytes, n_symbols, d_sym_offsets, d_words, d_word_offsets,
-                                                      stride_words, d_n_words, d_status, n_streams)) return st;
-    if (n_streams == 0) return CST_OK;
-    const uint32_t interval = (uint32_t)jump_interval;
-    // (slab form without a capacity: all the slabs, as the ragged table coders' jump decoders take it)
-    const uint64_t capacity = words_capacity ? words_capacity : (d_word_offsets ? 0 : (uint64_t)n_streams * stride_words);
-    const PerSymbolJumpScratch v(d_scratch, n_chunks_total);
+    const cst_status plain = check_categorical_ragged_args(cfg, d_symbols, d_probs, prob_bytes, n_symbols, d_sym_offsets, d_words, d_word_offsets,
+                                                           stride_words, d_n_words, d_status, n_streams);
     const char* name = kCatRaggedDecodeNames[1][KIND == kRange];
-    if (n_chunks_total > 0) {
-        const unsigned grid = (unsigned)((n_chunks_total + 255) / 256);
-        dispatch_word_size(cfg, [&](auto W, auto S) {
-            hipLaunchKernelGGL((persymbol_jump_chunks_kernel<W, S, KIND>), dim3(grid), dim3(256), 0, hs, d_words, d_sym_offsets, d_word_offsets, stride_words,
-                               capacity, d_n_words, d_chunk_offsets, n_streams, n_chunks_total, interval, d_jump_pos, d_jump_a, d_jump_b, v);
-            return 0;
-        });
-        CST_HIP_TRY(hipGetLastError());
-        // (the slices handed on are absolute offsets that passed the check, or empty: `capacity` bounds them once more; the symbol
-        //  ranges lie inside ONE stream's symbols, and the chunk decoder bounds them by n_total)
+    return decode_jump_chunks<KIND>(cfg, plain, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_symbols, d_sym_offsets, n_streams,
+                                    jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_a, d_jump_b, d_scratch, d_status, name, hs,
+                                    [&](const PerSymbolDecodeArgs& p, const PerSymbolJumpScratch& v) {
+        // (the chunk decoder bounds the symbol ranges by n_total)
         CatRaggedChunkArgs a{};
-        a.p.words = d_words; a.p.offsets = v.word_off; a.p.stride_words = 0; a.p.n_words = v.n_words; a.p.words_capacity = capacity;
-        a.p.symbols = d_symbols; a.p.n_streams = n_chunks_total; a.p.precision = cfg.precision; a.p.min_symbol = 0; a.p.n_symbols = n_symbols;
-        a.p.status = v.status; a.p.state = v.state; a.p.rstate = v.rstate;
+        a.p = p; a.p.min_symbol = 0; a.p.n_symbols = n_symbols;
         a.probs = d_probs; a.n_total = n_total; a.sym_lo = v.sym_lo; a.len = v.len;
         const cst_status rc = launch_decode_categorical_ragged<KIND, true>(cfg, a, prob_bytes, hs);
-        if (rc != CST_OK) return note_kernel(name, rc);
-    }
-    hipLaunchKernelGGL(persymbol_jump_status_kernel<>, dim3((unsigned)((n_streams + 255) / 256)), dim3(256), 0, hs, v, d_sym_offsets, d_word_offsets,
-                       stride_words, capacity, d_chunk_offsets, d_jump_pos, d_n_words, n_streams, n_chunks_total, interval, d_status);
-    CST_HIP_TRY(hipGetLastError());
-    return note_kernel(name, CST_OK);
+        return rc == CST_OK ? rc : note_kernel(name, rc);
+    });
 }
 
 } // namespace cst

@@ -1,7 +1,8 @@
 // cst_persymbol_ragged.hpp -- the kernels of the per-symbol coders for streams of DIFFERENT lengths, shared by the two files that
 // instantiate them: cst_persymbol_ragged.hip (the plain forms, JUMP = false) and cst_persymbol_ragged_jump.hip (JUMP = true).  Every
 // instantiation of these still lives in ONE file (cst_persymbol.hpp): the template parameter decides which.  At the end: the
-// model-independent kernels around a jump table, which cst_persymbol_categorical_ragged.hip launches too.
+// model-independent kernels around a jump table and the host routine that launches them around a caller's chunk decoder
+// (decode_jump_chunks), for cst_persymbol_categorical_ragged.hip too.
 #pragma once
 #include "cst_persymbol.hpp"
 
@@ -527,8 +528,9 @@ inline cst_status check_ragged_gaussian_args(cst_coder_config cfg, int32_t min_s
 
 // ------------------------------------------------------------------------------------------------
 // jump points: the encoder's JUMP form notes the table; the decoder runs every table entry as a coder of its own.  What follows knows
-// nothing of the model: cst_persymbol_ragged_jump.hip and cst_persymbol_categorical_ragged.hip both launch it around their own chunk
-// decoder (templates, all of them: each unit's code object carries its copy, the host side folds them).
+// nothing of the model: cst_persymbol_ragged_jump.hip and cst_persymbol_categorical_ragged.hip both hand their own chunk decoder to
+// decode_jump_chunks, which launches it between the two kernels (templates, all of them: each unit's code object carries its copy,
+// the host side folds them).
 // ------------------------------------------------------------------------------------------------
 
 // what the decoder keeps per table entry (d_scratch, cst_persymbol_ragged_jump_scratch_bytes): 80 bytes each
@@ -624,7 +626,54 @@ __global__ void persymbol_jump_status_kernel(PerSymbolJumpScratch v, const uint6
     status[s] = worst;
 }
 
-// what the jump calls refuse on top of the plain calls' refusals
-static bool jump_interval_bad(size_t jump_interval) { return jump_interval == 0 || jump_interval % kFuTile != 0 || jump_interval > 0x7fffffffull; }
+// what the jump calls refuse on top of the plain calls' refusals: an interval that is no whole number of tiles, or a table that is not
+// all there (d_jump_a / d_jump_b: the state (ANS, d_jump_b unused), or lower / range (the range coder))
+template <int KIND>
+inline bool jump_table_bad(size_t jump_interval, const void* d_chunk_offsets, const void* d_jump_pos, const void* d_jump_a, const void* d_jump_b) {
+    return jump_interval == 0 || jump_interval % kFuTile != 0 || jump_interval > 0x7fffffffull || !d_chunk_offsets || !d_jump_pos || !d_jump_a ||
+           (KIND == kRange && !d_jump_b);
+}
+
+// The host side of a jump decode, whatever the model: the chunks kernel fills the scratch, `launch_chunks(p, v)` runs the caller's
+// chunk decoder over it -- p: the coder's arguments, one "stream" per table entry, to which the caller adds its model's fields and the
+// chunks' symbols (v.sym_lo, v.len); it returns the launch's status -- and the status kernel folds the chunks' statuses into d_status.
+// `plain`: what the caller's plain decode says of the arguments, looked at AFTER the table's own refusals, as the calls always did.
+template <int KIND, class LaunchChunks>
+cst_status decode_jump_chunks(cst_coder_config cfg, cst_status plain, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                              size_t words_capacity, const uint32_t* d_n_words, int32_t* d_symbols, const uint64_t* d_sym_offsets, size_t n_streams,
+                              size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint32_t* d_jump_pos,
+                              const uint64_t* d_jump_a, const uint64_t* d_jump_b, void* d_scratch, int32_t* d_status, const char* name,
+                              hipStream_t hs, LaunchChunks launch_chunks) {
+    if (jump_table_bad<KIND>(jump_interval, d_chunk_offsets, d_jump_pos, d_jump_a, d_jump_b) || n_chunks_total > 0xffffffffull || !d_scratch)
+        return CST_ERR_INVALID_ARGUMENT;
+    if (plain != CST_OK) return plain;
+    if (n_streams == 0) return CST_OK;
+    if (n_streams > ((size_t)0x7fffffff) * 256) return CST_ERR_INVALID_ARGUMENT;      // (the status kernel: a thread per stream)
+    const uint32_t interval = (uint32_t)jump_interval;
+    // (slab form without a capacity: all the slabs, as the ragged table coders' jump decoders take it)
+    const uint64_t capacity = words_capacity ? words_capacity : (d_word_offsets ? 0 : (uint64_t)n_streams * stride_words);
+    const PerSymbolJumpScratch v(d_scratch, n_chunks_total);
+    if (n_chunks_total > 0) {
+        const unsigned grid = (unsigned)((n_chunks_total + 255) / 256);
+        dispatch_word_size(cfg, [&](auto W, auto S) {
+            hipLaunchKernelGGL((persymbol_jump_chunks_kernel<W, S, KIND>), dim3(grid), dim3(256), 0, hs, d_words, d_sym_offsets, d_word_offsets, stride_words,
+                               capacity, d_n_words, d_chunk_offsets, n_streams, n_chunks_total, interval, d_jump_pos, d_jump_a, d_jump_b, v);
+            return 0;
+        });
+        CST_HIP_TRY(hipGetLastError());
+        // (the slices handed on are absolute offsets that passed the check, or empty: `capacity` bounds them once more; the symbol
+        //  ranges lie inside ONE stream's symbols)
+        PerSymbolDecodeArgs p{};
+        p.words = d_words; p.offsets = v.word_off; p.stride_words = 0; p.n_words = v.n_words; p.words_capacity = capacity;
+        p.symbols = d_symbols; p.n_streams = n_chunks_total; p.precision = cfg.precision;
+        p.status = v.status; p.state = v.state; p.rstate = v.rstate;
+        const cst_status rc = launch_chunks(p, v);
+        if (rc != CST_OK) return rc;
+    }
+    hipLaunchKernelGGL(persymbol_jump_status_kernel<>, dim3((unsigned)((n_streams + 255) / 256)), dim3(256), 0, hs, v, d_sym_offsets, d_word_offsets,
+                       stride_words, capacity, d_chunk_offsets, d_jump_pos, d_n_words, n_streams, n_chunks_total, interval, d_status);
+    CST_HIP_TRY(hipGetLastError());
+    return note_kernel(name, CST_OK);
+}
 
 } // namespace cst

@@ -12,7 +12,7 @@ static cst_status encode_ragged_jump(cst_coder_config cfg, int32_t min_symbol, i
                                      const uint64_t* d_word_offsets, size_t stride_words, uint32_t* d_n_words, size_t jump_interval,
                                      const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos, uint64_t* d_jump_a, uint64_t* d_jump_b,
                                      int32_t* d_status, hipStream_t hs) {
-    if (jump_interval_bad(jump_interval) || !d_chunk_offsets || !d_jump_pos || !d_jump_a || (KIND == kRange && !d_jump_b)) return CST_ERR_INVALID_ARGUMENT;
+    if (jump_table_bad<KIND>(jump_interval, d_chunk_offsets, d_jump_pos, d_jump_a, d_jump_b)) return CST_ERR_INVALID_ARGUMENT;
     if (cst_status st = check_ragged_gaussian_args(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, d_sym_offsets, d_words, d_word_offsets,
                                                    stride_words, d_n_words, d_status, d_order, n_streams)) return st;
     if (n_streams == 0) return CST_OK;
@@ -31,49 +31,28 @@ static cst_status encode_ragged_jump(cst_coder_config cfg, int32_t min_symbol, i
     }));
 }
 
-// d_jump_a / d_jump_b: the state (ANS, d_jump_b unused), or lower / range (the range coder)
+// (the table kernels around decode_gaussian_ragged_kernel<JUMP>: decode_jump_chunks, cst_persymbol_ragged.hpp)
 template <int KIND, class FAM>
 static cst_status decode_ragged_jump(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
                                      const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
                                      const double* d_a, const double* d_b, int32_t* d_symbols, const uint64_t* d_sym_offsets, size_t n_streams,
                                      size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint32_t* d_jump_pos,
                                      const uint64_t* d_jump_a, const uint64_t* d_jump_b, void* d_scratch, int32_t* d_status, hipStream_t hs) {
-    if (jump_interval_bad(jump_interval) || n_chunks_total > 0xffffffffull || !d_chunk_offsets || !d_jump_pos || !d_jump_a ||
-        (KIND == kRange && !d_jump_b) || !d_scratch) return CST_ERR_INVALID_ARGUMENT;
-    if (cst_status st = check_ragged_gaussian_args(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, d_sym_offsets, d_words, d_word_offsets,
-                                                   stride_words, d_n_words, d_status, nullptr, n_streams)) return st;
-    if (n_streams == 0) return CST_OK;
-    if (n_streams > ((size_t)0x7fffffff) * 256) return CST_ERR_INVALID_ARGUMENT;
-    const uint32_t interval = (uint32_t)jump_interval;
-    // (slab form without a capacity: all the slabs, as the ragged table coders' jump decoders take it)
-    const uint64_t capacity = words_capacity ? words_capacity : (d_word_offsets ? 0 : (uint64_t)n_streams * stride_words);
-    const PerSymbolJumpScratch v(d_scratch, n_chunks_total);
-    if (n_chunks_total > 0) {
-        const unsigned grid = (unsigned)((n_chunks_total + 255) / 256);
-        dispatch_word_size(cfg, [&](auto W, auto S) {
-            hipLaunchKernelGGL((persymbol_jump_chunks_kernel<W, S, KIND>), dim3(grid), dim3(256), 0, hs, d_words, d_sym_offsets, d_word_offsets, stride_words,
-                               capacity, d_n_words, d_chunk_offsets, n_streams, n_chunks_total, interval, d_jump_pos, d_jump_a, d_jump_b, v);
-            return 0;
-        });
-        CST_HIP_TRY(hipGetLastError());
-        // (the slices handed on are absolute offsets that passed the check, or empty: `capacity` bounds them once more)
+    const cst_status plain = check_ragged_gaussian_args(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, d_sym_offsets, d_words, d_word_offsets,
+                                                        stride_words, d_n_words, d_status, nullptr, n_streams);
+    return decode_jump_chunks<KIND>(cfg, plain, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_symbols, d_sym_offsets, n_streams,
+                                    jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_a, d_jump_b, d_scratch, d_status,
+                                    FamilyNames<FAM>::ragged_jump[KIND == kRange][1], hs,
+                                    [&](const PerSymbolDecodeArgs& p, const PerSymbolJumpScratch& v) {
         GaussianRaggedChunkArgs a{};
-        a.p.words = d_words; a.p.offsets = v.word_off; a.p.stride_words = 0; a.p.n_words = v.n_words; a.p.words_capacity = capacity;
-        a.p.symbols = d_symbols; a.p.n_streams = n_chunks_total; a.p.precision = cfg.precision;
-        a.p.min_symbol = min_symbol; a.p.n_symbols = (int32_t)((int64_t)max_symbol - min_symbol + 1);
-        a.p.means = d_a; a.p.stds = d_b; a.p.status = v.status; a.p.state = v.state; a.p.rstate = v.rstate;
+        a.p = p; a.p.min_symbol = min_symbol; a.p.n_symbols = (int32_t)((int64_t)max_symbol - min_symbol + 1); a.p.means = d_a; a.p.stds = d_b;
         a.sym_lo = v.sym_lo; a.len = v.len;
-        const size_t blocks = (n_chunks_total + kRgDecThreads - 1) / kRgDecThreads;
+        const size_t blocks = (p.n_streams + kRgDecThreads - 1) / kRgDecThreads;
         const size_t lds = FAM::kErfTab ? kRgDecLdsBytes : kRgDecLdsBytesNoTab;
-        const cst_status rc = dispatch_word_size(cfg, [&](auto W, auto S) {
+        return dispatch_word_size(cfg, [&](auto W, auto S) {
             return launch_with_lds(decode_gaussian_ragged_kernel<W, S, KIND, FAM, true>, blocks, kRgDecThreads, lds, a, hs);
         });
-        if (rc != CST_OK) return rc;
-    }
-    hipLaunchKernelGGL(persymbol_jump_status_kernel<>, dim3((unsigned)((n_streams + 255) / 256)), dim3(256), 0, hs, v, d_sym_offsets, d_word_offsets,
-                       stride_words, capacity, d_chunk_offsets, d_jump_pos, d_n_words, n_streams, n_chunks_total, interval, d_status);
-    CST_HIP_TRY(hipGetLastError());
-    return note_kernel(FamilyNames<FAM>::ragged_jump[KIND == kRange][1], CST_OK);
+    });
 }
 
 } // namespace cst
