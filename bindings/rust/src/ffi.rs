@@ -1326,6 +1326,7 @@ extern "C" {
     ///   CST_SUB_ORDER=0          range sub-lane decoder: chunks side by side      CST_LANE_GEO=big|small   per-symbol lane decoder geometry
     ///   CST_FUSED_MIN_STREAMS=n  from how many streams the fused per-symbol encoder runs         CST_CATEGORICAL_ROUTE=fused|rows   per-symbol Categorical decoders: the route
     ///   CST_AUTO_JUMP=0          cst_jump_points_auto* answer 0                  CST_RAGGED_GROUP=8|16|32   ragged encoder: symbols per memory point
+    ///   CST_PERFECT_RAGGED_BUDGET=n   ragged Categorical(perfect=True) decoders: 32-bit words of tabulated rows per step (default 16777216 = 64 MiB)
     /// (CST_RCCL_LIB=<path>, read at the first collective call, names the RCCL library to open.)
     /// cst_debug_reload_knobs re-reads them: for tests that drive several paths inside one process; not thread-safe against
     /// concurrent coder calls.
@@ -2082,7 +2083,8 @@ extern "C" {
     ///     outside {4, 8}, an unsupported cfg, n_streams > 2^31 - 1, n_total > 64 (2^31 - 1) (encoders) and every refusal of the Gaussian jump
     ///     calls return CST_ERR_INVALID_ARGUMENT; then n_symbols < 2 or n_symbols >= 2^precision - 1 returns CST_ERR_MODEL.  n_streams == 0:
     ///     CST_OK, nothing is launched.
-    ///   - One route for every batch size: built for many streams; a few are coded correctly, but slowly.  Not here: the perfect quantisation,
+    ///   - One route for every batch size: built for many streams; a few are coded correctly, but slowly.  Not here: the perfect quantisation (the
+    ///     cst_*_categorical_perfect_ragged calls below),
     ///     the symbol-major layout (a ragged batch has none), a count_until, intervals that are no multiple of 16.
     /// cst_last_kernel_name(): {ans,range}_encode_categorical_ragged_two_pass, {ans,range}_decode_categorical_ragged_kernel, and the same names
     /// followed by <jump>.
@@ -2230,6 +2232,194 @@ extern "C" {
     ) -> CstStatus;
 
     pub fn cst_range_decode_categorical_ragged_jump(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// ... and with the perfect quantisation: Categorical(perfect=True), the reference's default, for streams of DIFFERENT lengths, plain and with
+    /// jump points (ABI 5).  The argument lists are those of cst_*_categorical_ragged[_jump] with ONE exception: the two plain
+    /// decoders take max_len directly after n_total.  Stream s owns rows [d_sym_offsets[s], d_sym_offsets[s + 1]) of d_probs [n_total][n_symbols]
+    /// and of the flat d_symbols; its words, word count and status are those of cst_{ans,range}_{encode,decode}_categorical_perfect_batch for
+    /// that stream alone, bit for bit.  d_order, the slabs, empty streams, the refusals against n_total (CST_STREAM_CAPACITY /
+    /// CST_STREAM_INVALID_DATA), the jump table, its layout and d_scratch (cst_persymbol_ragged_jump_scratch_bytes) are exactly those of
+    /// cst_*_categorical_ragged[_jump].
+    ///   - max_len (plain decoders): an upper bound of the longest stream.  The decoders tabulate the rows of a piece of positions of a group of
+    ///     streams, then look the symbols up, piece after piece up to max_len, without reading d_sym_offsets back.  A stream longer than max_len
+    ///     reports CST_STREAM_CAPACITY and decodes nothing.  The jump decoders need none: a chunk has at most jump_interval symbols.
+    ///   - The rows of one step stay within 64 MiB (CST_PERFECT_RAGGED_BUDGET, a debug switch, gives the budget in 32-bit words).
+    ///   - A bad or non-converged row (codes 1 and 2 of cst_categorical_perfect_cdf_rows) and a symbol outside [0, n_symbols) yield
+    ///     CST_STREAM_IMPOSSIBLE_SYMBOL for their stream only.
+    ///   - Before the device is touched: the refusals of cst_*_categorical_ragged[_jump], with the model limits of the perfect quantisation --
+    ///     n_symbols < 2, n_symbols > CST_CATEGORICAL_PERFECT_MAX_K or n_symbols > 2^precision return CST_ERR_MODEL -- and, encoders,
+    ///     n_total > 2^31 - 1 returns CST_ERR_INVALID_ARGUMENT (one quantiser workgroup per row).  n_streams == 0: CST_OK, nothing is launched.
+    /// cst_last_kernel_name(): {ans,range}_encode_categorical_perfect_ragged_two_pass, {ans,range}_decode_categorical_perfect_ragged_by_rows, and the
+    /// same names followed by <jump>.
+    pub fn cst_ans_encode_categorical_perfect_ragged(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_categorical_perfect_ragged(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        max_len: usize,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_encode_categorical_perfect_ragged(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_categorical_perfect_ragged(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        max_len: usize,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_encode_categorical_perfect_ragged_jump(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32,
+        d_jump_state: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_categorical_perfect_ragged_jump(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_encode_categorical_perfect_ragged_jump(
+        cfg: CstCoderConfig,
+        d_symbols: *const i32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32,
+        d_jump_lower: *mut u64,
+        d_jump_range: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_categorical_perfect_ragged_jump(
         cfg: CstCoderConfig,
         d_words: *const u32,
         d_word_offsets: *const u64,

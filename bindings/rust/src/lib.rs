@@ -1977,6 +1977,55 @@ impl BatchedAnsCoder {
         Ok((n_words, status))
     }
 
+    /// `encode_symbols_reverse_categorical_ragged` under `Categorical(perfect=True)`, the reference's default (`cst_ans_encode_categorical_perfect_ragged`): the same arguments, every row quantised by the
+    /// device quantiser (`2 <= n_symbols <= 1024`), every stream's words those of the `_categorical_perfect` call for that stream alone.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_reverse_categorical_ragged`.
+    pub unsafe fn encode_symbols_reverse_categorical_perfect_ragged<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>)> {
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_ans_encode_categorical_perfect_ragged(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status))
+    }
+
     /// The decoder of `encode_symbols_reverse_categorical_ragged` (`cst_ans_decode_categorical_ragged`): stream `s` yields `sym_offsets[s + 1] - sym_offsets[s]` symbols at
     /// `symbols[sym_offsets[s]..]`, decoded with rows `sym_offsets[s]..` of `probabilities`.
     ///
@@ -2019,6 +2068,62 @@ impl BatchedAnsCoder {
                 F::BYTES,
                 n_symbols as i32,
                 n_total,
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok(status)
+    }
+
+    /// `decode_symbols_categorical_ragged` under `Categorical(perfect=True)`, the reference's default (`cst_ans_decode_categorical_perfect_ragged`): the same arguments, every row quantised by the
+    /// device quantiser (`2 <= n_symbols <= 1024`), every stream's words those of the `_categorical_perfect` call for that stream alone.  `max_len`: an upper bound of the longest stream -- the rows are tabulated a piece of positions at a
+    /// time up to it, and a longer stream reports `CST_STREAM_CAPACITY`.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_categorical_ragged`.
+    pub unsafe fn decode_symbols_categorical_perfect_ragged<F: Probability>(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        max_len: usize,
+        order: Option<&DeviceBuffer<u32>>,
+        symbols: &mut DeviceBuffer<i32>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_ans_decode_categorical_perfect_ragged(
+                self.config,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                max_len,
                 symbols.as_mut_ptr(),
                 sym_offsets.as_ptr(),
                 n_streams,
@@ -2092,6 +2197,67 @@ impl BatchedAnsCoder {
         Ok((n_words, status, pos, state))
     }
 
+    /// `encode_symbols_reverse_categorical_ragged_with_jump_points` under `Categorical(perfect=True)`, the reference's default (`cst_ans_encode_categorical_perfect_ragged_jump`): the same arguments, every row quantised by the
+    /// device quantiser (`2 <= n_symbols <= 1024`), every stream's words those of the `_categorical_perfect` call for that stream alone.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_reverse_categorical_ragged_with_jump_points`.
+    pub unsafe fn encode_symbols_reverse_categorical_perfect_ragged_with_jump_points<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>, DeviceBuffer<u32>, DeviceBuffer<u64>)> {
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut pos: DeviceBuffer<u32> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut state: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        check(unsafe {
+            ffi::cst_ans_encode_categorical_perfect_ragged_jump(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                pos.as_mut_ptr(),
+                state.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status, pos, state))
+    }
+
     /// The decoder of `encode_symbols_reverse_categorical_ragged_with_jump_points` (`cst_ans_decode_categorical_ragged_jump`): every chunk of every stream as a coder of its own
     /// (seek + at most `jump_interval` symbols).  One status per stream.
     ///
@@ -2129,6 +2295,70 @@ impl BatchedAnsCoder {
         let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) })?;
         check(unsafe {
             ffi::cst_ans_decode_categorical_ragged_jump(
+                self.config,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                n_chunks_total,
+                pos.as_ptr(),
+                state.as_ptr(),
+                scratch.as_mut_ptr() as *mut c_void,
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
+        Ok(status)
+    }
+
+    /// `decode_symbols_categorical_ragged_from_jump_points` under `Categorical(perfect=True)`, the reference's default (`cst_ans_decode_categorical_perfect_ragged_jump`): the same arguments, every row quantised by the
+    /// device quantiser (`2 <= n_symbols <= 1024`), every stream's words those of the `_categorical_perfect` call for that stream alone.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_categorical_ragged_from_jump_points`.
+    pub unsafe fn decode_symbols_categorical_perfect_ragged_from_jump_points<F: Probability>(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        symbols: &mut DeviceBuffer<i32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        pos: &DeviceBuffer<u32>,
+        state: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || pos.len() < n_chunks_total || state.len() < n_chunks_total || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) })?;
+        check(unsafe {
+            ffi::cst_ans_decode_categorical_perfect_ragged_jump(
                 self.config,
                 words.as_ptr(),
                 word_offsets.as_ptr(),
@@ -3198,6 +3428,55 @@ impl BatchedRangeEncoder {
         Ok((n_words, status))
     }
 
+    /// `encode_symbols_categorical_ragged` under `Categorical(perfect=True)`, the reference's default (`cst_range_encode_categorical_perfect_ragged`): the same arguments, every row quantised by the
+    /// device quantiser (`2 <= n_symbols <= 1024`), every stream's words those of the `_categorical_perfect` call for that stream alone.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_categorical_ragged`.
+    pub unsafe fn encode_symbols_categorical_perfect_ragged<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>)> {
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_range_encode_categorical_perfect_ragged(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status))
+    }
+
     /// `encode_symbols_categorical_ragged` that also notes `RangeEncoder::pos()` in front of every `jump_interval` symbols of every stream (`cst_range_encode_categorical_ragged_jump`): the
     /// table of the Gaussian `_with_jump_points` encoder -- chunk `j` of stream `s` is entry `chunk_offsets[s] + j` of the returned
     /// `(pos, lower, range)` arrays.  `jump_interval`: a positive multiple of 16.  The words are those of `encode_symbols_categorical_ragged`.
@@ -3237,6 +3516,69 @@ impl BatchedRangeEncoder {
         let mut range: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
         check(unsafe {
             ffi::cst_range_encode_categorical_ragged_jump(
+                self.config,
+                symbols.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                words.as_mut_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                n_words.as_mut_ptr(),
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                pos.as_mut_ptr(),
+                lower.as_mut_ptr(),
+                range.as_mut_ptr(),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok((n_words, status, pos, lower, range))
+    }
+
+    /// `encode_symbols_categorical_ragged_with_jump_points` under `Categorical(perfect=True)`, the reference's default (`cst_range_encode_categorical_perfect_ragged_jump`): the same arguments, every row quantised by the
+    /// device quantiser (`2 <= n_symbols <= 1024`), every stream's words those of the `_categorical_perfect` call for that stream alone.
+    ///
+    /// # Safety
+    /// As for `encode_symbols_categorical_ragged_with_jump_points`.
+    pub unsafe fn encode_symbols_categorical_perfect_ragged_with_jump_points<F: Probability>(
+        &self,
+        symbols: &DeviceBuffer<i32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        order: Option<&DeviceBuffer<u32>>,
+        word_offsets: &DeviceBuffer<u64>,
+        words: &mut DeviceBuffer<u32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>, DeviceBuffer<u32>, DeviceBuffer<u64>, DeviceBuffer<u64>)> {
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut pos: DeviceBuffer<u32> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut lower: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        let mut range: DeviceBuffer<u64> = DeviceBuffer::new(n_chunks_total.max(1))?;
+        check(unsafe {
+            ffi::cst_range_encode_categorical_perfect_ragged_jump(
                 self.config,
                 symbols.as_ptr(),
                 probabilities.as_ptr() as *const c_void,
@@ -4187,6 +4529,62 @@ impl BatchedRangeDecoder {
         Ok(status)
     }
 
+    /// `decode_symbols_categorical_ragged` under `Categorical(perfect=True)`, the reference's default (`cst_range_decode_categorical_perfect_ragged`): the same arguments, every row quantised by the
+    /// device quantiser (`2 <= n_symbols <= 1024`), every stream's words those of the `_categorical_perfect` call for that stream alone.  `max_len`: an upper bound of the longest stream -- the rows are tabulated a piece of positions at a
+    /// time up to it, and a longer stream reports `CST_STREAM_CAPACITY`.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_categorical_ragged`.
+    pub unsafe fn decode_symbols_categorical_perfect_ragged<F: Probability>(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        max_len: usize,
+        order: Option<&DeviceBuffer<u32>>,
+        symbols: &mut DeviceBuffer<i32>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        if order.map_or(false, |o| o.len() != n_streams) {
+            return Err(Error::InvalidArgument);
+        }
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_range_decode_categorical_perfect_ragged(
+                self.config,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                max_len,
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                order.map_or(core::ptr::null(), |o| o.as_ptr()),
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        Ok(status)
+    }
+
     /// The decoder of `encode_symbols_categorical_ragged_with_jump_points` (`cst_range_decode_categorical_ragged_jump`): every chunk of every stream as a coder of its own
     /// (seek + at most `jump_interval` symbols).  One status per stream.
     ///
@@ -4225,6 +4623,72 @@ impl BatchedRangeDecoder {
         let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) })?;
         check(unsafe {
             ffi::cst_range_decode_categorical_ragged_jump(
+                self.config,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                probabilities.as_ptr() as *const c_void,
+                F::BYTES,
+                n_symbols as i32,
+                n_total,
+                symbols.as_mut_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                jump_interval,
+                chunk_offsets.as_ptr(),
+                n_chunks_total,
+                pos.as_ptr(),
+                lower.as_ptr(),
+                range.as_ptr(),
+                scratch.as_mut_ptr() as *mut c_void,
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
+        Ok(status)
+    }
+
+    /// `decode_symbols_categorical_ragged_from_jump_points` under `Categorical(perfect=True)`, the reference's default (`cst_range_decode_categorical_perfect_ragged_jump`): the same arguments, every row quantised by the
+    /// device quantiser (`2 <= n_symbols <= 1024`), every stream's words those of the `_categorical_perfect` call for that stream alone.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_categorical_ragged_from_jump_points`.
+    pub unsafe fn decode_symbols_categorical_perfect_ragged_from_jump_points<F: Probability>(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        symbols: &mut DeviceBuffer<i32>,
+        jump_interval: usize,
+        chunk_offsets: &DeviceBuffer<u64>,
+        pos: &DeviceBuffer<u32>,
+        lower: &DeviceBuffer<u64>,
+        range: &DeviceBuffer<u64>,
+        n_chunks_total: usize,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_total = symbols.len();
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        if chunk_offsets.len() != sym_offsets.len() || pos.len() < n_chunks_total || lower.len() < n_chunks_total || range.len() < n_chunks_total || jump_interval == 0 || jump_interval % 16 != 0 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) })?;
+        check(unsafe {
+            ffi::cst_range_decode_categorical_perfect_ragged_jump(
                 self.config,
                 words.as_ptr(),
                 word_offsets.as_ptr(),

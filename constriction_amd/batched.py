@@ -1404,11 +1404,12 @@ def _decode_persymbol_ragged(fn_name, coder, encoded: RaggedBatch, sym_offsets, 
                                 (_ptr(_never_null(a)), _ptr(_never_null(b))))
 
 
-def _decode_ragged_slabs(fn_name, coder, encoded: RaggedBatch, jump, sym_offsets, n_streams, total, out, order, head, model):
+def _decode_ragged_slabs(fn_name, coder, encoded: RaggedBatch, jump, sym_offsets, n_streams, total, out, order, head, model, plain_extra=None):
     """the schedule, the output, the route (whole streams, or the chunks of a jump table side by side) and the call of every ragged
     per-symbol decoder, once its arguments are judged: `head` is what the entry point takes between cfg and d_words (the family's
     (lo, hi)), `model` what it takes between d_n_words and d_symbols (the family's (a, b), or the Categorical's (probabilities,
-    prob_bytes, K, n_total)); `total`: the symbols of all streams"""
+    prob_bytes, K, n_total)); `total`: the symbols of all streams.  `plain_extra`: a callable, asked only on the whole-stream route, for
+    what the plain entry point takes behind `model` and the jump form does not (Categorical(perfect=True): max_len)"""
     if encoded.n_words.numel() != n_streams:
         raise ValueError("sym_offsets does not match the number of streams of the batch")
     take_jump = jump is not None and (order is None or (isinstance(order, str) and order == "auto"))
@@ -1438,8 +1439,9 @@ def _decode_ragged_slabs(fn_name, coder, encoded: RaggedBatch, jump, sym_offsets
                                               _ptr(target), _ptr(sym_offsets), n_streams, jump.interval, _ptr(jump.chunk_offsets), n_chunks,
                                               *(_ptr(t) for t in arrays), _ptr(scratch), _ptr(status), _stream_ptr()), fn_name + "_jump")
         return out, status
+    extra = plain_extra() if plain_extra is not None else ()
     N.check(getattr(N.lib(), fn_name)(_cfg(*encoded.config), *head, _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
-                                      encoded.words.numel(), _ptr(encoded.n_words), *model, _ptr(target),
+                                      encoded.words.numel(), _ptr(encoded.n_words), *model, *extra, _ptr(target),
                                       _ptr(sym_offsets), n_streams, _ptr(order) if order is not None else None, _ptr(status), _stream_ptr()),
             fn_name)
     return out, status
@@ -1722,21 +1724,22 @@ def range_decode_categorical(encoded, probabilities, layout="stream_major", offs
 
 # ---------------------------------------------------------------------------------------------------------------------
 # ... for streams of DIFFERENT lengths: the ragged calls' indexing (flat symbols + sym_offsets) on a flat matrix of rows,
-# `probabilities` [symbols.numel(), K], plain and with jump points (Categorical(perfect=False) / Categorical(lazy=True) only)
+# `probabilities` [symbols.numel(), K], plain and with jump points (Categorical(perfect=False) / Categorical(lazy=True); perfect=True: the
+# *_categorical_perfect_ragged names behind them)
 # ---------------------------------------------------------------------------------------------------------------------
 
-def _categorical_ragged_args(sym_offsets, n_rows, probabilities, precision):
+def _categorical_ragged_args(sym_offsets, n_rows, probabilities, precision, perfect=False):
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
     n_streams = sym_offsets.numel() - 1
     if sym_offsets.dim() != 1 or n_streams < 0:
         raise ValueError("sym_offsets must be 1-d and hold n_streams + 1 entries")
     if not isinstance(probabilities, torch.Tensor) or probabilities.dim() != 2:
         raise ValueError("probabilities must be 2-d: one row of K entries per symbol")
-    probs, nbytes, k = _categorical_args(None if n_rows is None else (n_rows,), probabilities, precision)
+    probs, nbytes, k = _categorical_args(None if n_rows is None else (n_rows,), probabilities, precision, perfect)
     return sym_offsets, n_streams, probs, nbytes, k
 
 
-def _encode_categorical_ragged(fn_name, coder, symbols, sym_offsets, probabilities, config, order, jump_every) -> RaggedBatch:
+def _encode_categorical_ragged(fn_name, coder, symbols, sym_offsets, probabilities, config, order, jump_every, perfect=False) -> RaggedBatch:
     """the body of {ans,range}_encode_categorical_ragged: _encode_persymbol_ragged with a matrix of rows in place of (lo, hi, a, b).
     jump_every="auto" keeps the RAGGED_JUMP_EVERY rule of the other families -- a jump point every 256 symbols where the streams average
     more than 256.  That rule was measured for the Gaussian, Laplace and Cauchy forms.  For the Categorical it was
@@ -1746,17 +1749,19 @@ def _encode_categorical_ragged(fn_name, coder, symbols, sym_offsets, probabiliti
     symbols = _require_cuda(symbols, torch.int32, "symbols")
     if symbols.dim() != 1:
         raise ValueError("symbols must be flat")
-    sym_offsets, n_streams, probs, nbytes, k = _categorical_ragged_args(sym_offsets, symbols.numel(), probabilities, config[2])
+    sym_offsets, n_streams, probs, nbytes, k = _categorical_ragged_args(sym_offsets, symbols.numel(), probabilities, config[2], perfect)
     model = (_ptr(_never_null(symbols)), _ptr(_never_null(probs)), nbytes, k, symbols.numel())
     return _encode_ragged_slabs(fn_name, coder, symbols, sym_offsets, n_streams, config, order, jump_every, model)
 
 
-def _decode_categorical_ragged(fn_name, coder, encoded: RaggedBatch, sym_offsets, probabilities, out, order):
+def _decode_categorical_ragged(fn_name, coder, encoded: RaggedBatch, sym_offsets, probabilities, out, order, perfect=False):
     jump = _ragged_jump_of(encoded, coder)
-    sym_offsets, n_streams, probs, nbytes, k = _categorical_ragged_args(sym_offsets, None, probabilities, encoded.config[2])
+    sym_offsets, n_streams, probs, nbytes, k = _categorical_ragged_args(sym_offsets, None, probabilities, encoded.config[2], perfect)
     n_total = int(probs.shape[0])
+    # perfect=True, whole streams: the host loops over pieces of positions up to the longest stream -- the one value read back
+    longest = (lambda: (max(int((sym_offsets[1:] - sym_offsets[:-1]).max().item()), 0),)) if perfect else None
     return _decode_ragged_slabs(fn_name, coder, encoded, jump, sym_offsets, n_streams, n_total, out, order, (),
-                                (_ptr(_never_null(probs)), nbytes, k, n_total))
+                                (_ptr(_never_null(probs)), nbytes, k, n_total), longest)
 
 
 def ans_encode_categorical_ragged(symbols, sym_offsets, probabilities, config=(32, 64, 24), order="auto", *, jump_every=0) -> RaggedBatch:
@@ -1788,6 +1793,40 @@ def range_decode_categorical_ragged(encoded: RaggedBatch, sym_offsets, probabili
     """RangeDecoder(words of stream s).decode(Categorical(lazy=True), probabilities[lo:hi]) for every stream of a RaggedBatch that a
     range encoder wrote.  Returns (symbols flat, status per stream); see ans_decode_categorical_ragged."""
     return _decode_categorical_ragged("cst_range_decode_categorical_ragged", "range", encoded, sym_offsets, probabilities, out, order)
+
+
+# ... and with the perfect quantisation, Categorical(perfect=True), the reference's default: new names, the signatures of the four above
+
+def ans_encode_categorical_perfect_ragged(symbols, sym_offsets, probabilities, config=(32, 64, 24), order="auto", *, jump_every=0) -> RaggedBatch:
+    """ans_encode_categorical_ragged with Categorical(perfect=True): every row is quantised by one wave of the device quantiser
+    (cst_ans_encode_categorical_perfect_ragged, 2 <= K <= min(1024, 2**precision)), in f64 whatever the dtype of `probabilities`
+    (float32 is widened, as the reference does).  Every stream's words are those of ans_encode_categorical(..., perfect=True) for that
+    stream alone.  Slabs, `.order`, `jump_every` (0, a positive multiple of 16, or "auto": the RAGGED_JUMP_EVERY rule) and `.jump` are
+    those of ans_encode_categorical_ragged; DESIGN.md 4.23 has what was measured."""
+    return _encode_categorical_ragged("cst_ans_encode_categorical_perfect_ragged", "ans", symbols, sym_offsets, probabilities, config, order,
+                                      jump_every, True)
+
+
+def ans_decode_categorical_perfect_ragged(encoded: RaggedBatch, sym_offsets, probabilities, out: Optional[torch.Tensor] = None, order="auto"):
+    """AnsCoder(words of stream s).decode(Categorical(perfect=True), probabilities[lo:hi]) for every stream of a RaggedBatch.  Returns
+    (symbols flat, status per stream).  The rows are tabulated on the device, a piece of positions of a group of streams at a time,
+    and looked up.  A batch with jump points decodes its chunks side by side when `order` is None or "auto", and reads nothing back;
+    whole streams (no jump points, or a schedule handed in) read back one value, the longest stream's length."""
+    return _decode_categorical_ragged("cst_ans_decode_categorical_perfect_ragged", "ans", encoded, sym_offsets, probabilities, out, order, True)
+
+
+def range_encode_categorical_perfect_ragged(symbols, sym_offsets, probabilities, config=(32, 64, 24), order="auto", *, jump_every=0) -> RaggedBatch:
+    """ans_encode_categorical_perfect_ragged for the queue: every stream's words are those of range_encode_categorical(...,
+    perfect=True) for that stream alone; the batch says `.coder == "range"` and carries a RangeRaggedJump."""
+    return _encode_categorical_ragged("cst_range_encode_categorical_perfect_ragged", "range", symbols, sym_offsets, probabilities, config, order,
+                                      jump_every, True)
+
+
+def range_decode_categorical_perfect_ragged(encoded: RaggedBatch, sym_offsets, probabilities, out: Optional[torch.Tensor] = None, order="auto"):
+    """RangeDecoder(words of stream s).decode(Categorical(perfect=True), probabilities[lo:hi]) for every stream of a RaggedBatch that
+    a range encoder wrote.  Returns (symbols flat, status per stream); see ans_decode_categorical_perfect_ragged."""
+    return _decode_categorical_ragged("cst_range_decode_categorical_perfect_ragged", "range", encoded, sym_offsets, probabilities, out, order,
+                                      True)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

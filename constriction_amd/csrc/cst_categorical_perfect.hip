@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 #include "cst_categorical_perfect.hpp"
@@ -70,8 +71,10 @@ __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
     return v;
 }
 
-template <class F, int CAP>
-__global__ __launch_bounds__(kWave) void categorical_perfect_kernel(const CatPerfectArgs a) {
+// RAGGED: the addressing of CatPerfectRaggedArgs (cst_categorical_perfect.hpp) -- `s` is then a unit of the group, and its wave leaves
+// at once where the unit has no position t.  A template parameter, so the rectangular kernels stay the code they were.
+template <class F, int CAP, bool RAGGED = false>
+__global__ __launch_bounds__(kWave) void categorical_perfect_kernel(const std::conditional_t<RAGGED, CatPerfectRaggedArgs, CatPerfectArgs> a) {
     static_assert(CAP % kWave == 0, "a lane holds CAP / 64 slots");
     constexpr int kPer = CAP / kWave;
     __shared__ PerfectSlots<CAP> sl;
@@ -79,7 +82,21 @@ __global__ __launch_bounds__(kWave) void categorical_perfect_kernel(const CatPer
     const uint32_t K = a.K;                                              // <= CAP (the launcher's choice)
     const size_t o = blockIdx.x;
     const size_t s = o / a.count, t = a.t0 + (o - s * a.count);
-    const size_t in_row = a.layout == CST_LAYOUT_SYMBOL_MAJOR ? t * a.n_streams + s : s * a.N + t;
+    size_t in_row;
+    if constexpr (RAGGED) {
+        const size_t slot = a.u0 + s;                                    // (< n_all: the launcher's group)
+        uint64_t lo = 0, hi = 0;
+        if (a.sym_lo) { lo = a.sym_lo[slot]; hi = lo + (uint64_t)a.len[slot]; }
+        else {
+            const size_t stream = a.order ? (size_t)a.order[slot] : slot;
+            if (stream < a.n_all) { lo = a.sym_offsets[stream]; hi = a.sym_offsets[stream + 1]; }
+        }
+        const CatRaggedSpan span(lo, hi, a.n_total);
+        if ((uint64_t)t >= (uint64_t)span.len || (uint64_t)span.len > a.max_len) return;      // (the same for the whole wave)
+        in_row = (size_t)span.lo + t;                                    // (< n_total: the span lies inside the matrix)
+    } else {
+        in_row = a.layout == CST_LAYOUT_SYMBOL_MAJOR ? t * a.n_streams + s : s * a.N + t;
+    }
     const F* src = reinterpret_cast<const F*>(a.probs) + in_row * (size_t)K;
     const uint32_t total = 1u << a.P;
     const double inf = std::numeric_limits<double>::infinity();
@@ -241,6 +258,26 @@ cst_status launch_categorical_perfect(const CatPerfectArgs& a, hipStream_t hs) {
     if (blocks > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
     if (a.prob_bytes == 4) launch_perfect<float>(a, (unsigned)blocks, hs);
     else launch_perfect<double>(a, (unsigned)blocks, hs);
+    CST_HIP_TRY(hipGetLastError());
+    return CST_OK;
+}
+
+template <class F>
+static void launch_perfect_ragged(const CatPerfectRaggedArgs& a, unsigned blocks, hipStream_t hs) {
+    if (a.K <= 64u) hipLaunchKernelGGL((categorical_perfect_kernel<F, 64, true>), dim3(blocks), dim3(kWave), 0, hs, a);
+    else if (a.K <= 256u) hipLaunchKernelGGL((categorical_perfect_kernel<F, 256, true>), dim3(blocks), dim3(kWave), 0, hs, a);
+    else hipLaunchKernelGGL((categorical_perfect_kernel<F, kCatPerfectMaxK, true>), dim3(blocks), dim3(kWave), 0, hs, a);
+}
+
+// a.n_streams units from slot a.u0 on, a.count positions each: a block per output row, as above
+cst_status launch_categorical_perfect_ragged(const CatPerfectRaggedArgs& a, hipStream_t hs) {
+    if (a.K < 2u || a.K > (uint32_t)kCatPerfectMaxK || !a.rows || a.pitch < (size_t)a.K + 1) return CST_ERR_MODEL;
+    if (a.u0 > a.n_all || a.n_streams > a.n_all - a.u0) return CST_ERR_INVALID_ARGUMENT;   // (the group lies inside the slots)
+    if (a.count != 0 && a.n_streams > 0x7fffffffull / a.count) return CST_ERR_INVALID_ARGUMENT;
+    const size_t blocks = a.n_streams * a.count;
+    if (blocks == 0) return CST_OK;
+    if (a.prob_bytes == 4) launch_perfect_ragged<float>(a, (unsigned)blocks, hs);
+    else launch_perfect_ragged<double>(a, (unsigned)blocks, hs);
     CST_HIP_TRY(hipGetLastError());
     return CST_OK;
 }

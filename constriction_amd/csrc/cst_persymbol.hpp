@@ -6,7 +6,8 @@
 //   cst_persymbol_ragged_jump.hip  ... with jump points (both share their kernels through cst_persymbol_ragged.hpp)
 //   cst_persymbol_categorical.hip  Categorical models from probability matrices
 //   cst_persymbol_categorical_ragged.hip  ... for streams of different lengths, plain and with jump points (they share the row tile and
-//                                  pass 1 of the encoders through cst_persymbol_categorical.hpp)
+//                                  pass 1 of the encoders through cst_persymbol_categorical.hpp), under both quantisers: the ragged
+//                                  Categorical(perfect=True) decoder over rows that cst_categorical_perfect.hip tabulates lives here too
 // EVERY KERNEL INSTANTIATION LIVES IN ONE FILE: nothing here is relocatable device code, so a second implicit instantiation would
 // compile and ship the kernel twice.  A kernel needed from another file is reached through a host launcher declared here and defined
 // next to the kernel.  (The exceptions are small and named where they are: categorical_entries_kernel, cst_persymbol_categorical.hpp,

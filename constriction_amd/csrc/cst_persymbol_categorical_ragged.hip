@@ -1,33 +1,24 @@
-// cst_persymbol_categorical_ragged.hip -- per-symbol Categorical models (the fast quantiser of cst_categorical.hpp) for streams of
-// DIFFERENT lengths, plain and with jump points (cst_persymbol.hpp has the map of the per-symbol files; DESIGN.md 4.21): stream s owns
+// cst_persymbol_categorical_ragged.hip -- per-symbol Categorical models (the fast quantiser of cst_categorical.hpp; the perfect one of
+// cst_categorical_perfect.hip at the end of the list) for streams of
+// DIFFERENT lengths, plain and with jump points (cst_persymbol.hpp has the map of the per-symbol files; DESIGN.md 4.21, 4.23): stream s owns
 // rows [sym_offsets[s], sym_offsets[s + 1]) of a flat probability matrix [n_total][K] and of the flat symbols.
 //   categorical_entries_kernel        encoder pass 1, as it is (cst_persymbol_categorical.hpp): rows are rows, whichever stream owns them
 //   encode_entries_ragged_kernel      encoder pass 2: encode_entries_kernel's ANS and range branches with one lane per stream
 //   decode_categorical_ragged_kernel  decode_categorical_lane_kernel with a row index per lane
+//   decode_rows_piece_ragged_kernel   Categorical(perfect=True), DESIGN.md 4.23: decode_rows_piece_wave_kernel for units of different lengths, over
+//                                     rows that categorical_perfect_kernel tabulates in its ragged mode; the encoders of that model are
+//                                     host glue (the quantiser in entry mode for pass 1, then encode_entries_ragged_kernel)
 // Their JUMP forms note / start from the jump table of cst_*_gaussian_ragged_jump; the kernels that turn a table into chunks and chunk
 // statuses into stream statuses, and the host routine around them, are the model-independent ones of cst_persymbol_ragged.hpp.  A unit of its own: the instantiations
 // stay out of cst_persymbol_categorical.hip, the build's longest compile.
 #include "cst_persymbol_ragged.hpp"
 #include "cst_categorical.hpp"
 #include "cst_persymbol_categorical.hpp"
+#include "cst_categorical_perfect.hpp"
 
 namespace cst {
 
-// where a stream's symbols lie, judged before anything becomes an address: a range that runs backwards or is too long for one coder
-// (CST_STREAM_CAPACITY, as the other ragged calls say), or one that reaches beyond the n_total rows there are (CST_STREAM_INVALID_DATA).
-// Either way the stream has NO symbols for the kernel.
-struct CatRaggedSpan {
-    uint64_t lo; uint32_t len; bool too_long, beyond;
-    __device__ __forceinline__ CatRaggedSpan(uint64_t sym_lo, uint64_t sym_hi, uint64_t n_total) {
-        too_long = sym_hi < sym_lo || sym_hi - sym_lo > 0xffffffffull;
-        beyond = !too_long && sym_hi > sym_lo && sym_hi > n_total;
-        lo = sym_lo;
-        len = too_long || beyond ? 0u : (uint32_t)(sym_hi - sym_lo);
-    }
-    __device__ __forceinline__ int32_t status(int32_t coded) const {
-        return too_long ? (int32_t)CST_STREAM_CAPACITY : beyond ? (int32_t)CST_STREAM_INVALID_DATA : coded;
-    }
-};
+// (CatRaggedSpan, where a stream's symbols lie: cst_categorical_perfect.hpp, for the quantiser's ragged mode too)
 
 // ------------------------------------------------------------------------------------------------
 // encoder pass 2
@@ -326,27 +317,122 @@ __global__ __launch_bounds__(kWave) void decode_categorical_ragged_kernel(const 
     D.finish(a, s, false);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Categorical(perfect=True), decoder: rows in pieces.  The quantiser needs a WAVE per row, so the rows are tabulated
+// first -- categorical_perfect_kernel in its ragged mode, K + 1 words each -- and then looked up; a UNIT is a stream (plain) or an entry
+// of the jump table (JUMP), and the host codes groups of consecutive unit slots in pieces of positions so that the rows of one step fit
+// a budget (decode_perfect_ragged_units below).
+// ------------------------------------------------------------------------------------------------
+struct CatPerfectPieceCommon {
+    PerSymbolDecodeArgs p;           // as CatRaggedDecodeArgs / CatRaggedChunkArgs; n_streams: ALL unit slots
+    const uint32_t* rows;            // [units of the group][count][K + 1]
+    uint64_t n_total;
+    size_t u0, n_units;              // the group: slots [u0, u0 + n_units)
+    uint64_t t0, count;              // the piece: positions [t0, t0 + count) of every unit
+    uint64_t max_len;                // a longer unit is refused (CST_STREAM_CAPACITY)
+    DecodeResume* resume;            // [n_units]: the group's decoders between two pieces
+};
+struct CatPerfectPieceArgs : CatPerfectPieceCommon {
+    const uint64_t* sym_offsets;     // [n_streams + 1]
+    const uint32_t* order;           // null, or [n_streams]
+};
+struct CatPerfectPieceChunkArgs : CatPerfectPieceCommon {
+    const uint64_t* sym_lo;          // [n chunks]
+    const uint32_t* len;
+};
+
+// decode_rows_piece_wave_kernel (cst_persymbol.hip) for units of different lengths: one WAVE per unit, the same search over the
+// tabulated rows, symbols to symbols[lo_u + t].  A unit is initialised in the piece with t0 = 0 (JUMP: from the raw state of its jump
+// point), parked in `resume` after every piece that does not hold its last position, and FINISHED -- status written -- in the piece that
+// does; an empty or refused unit finishes in the first piece.  In the pieces after its last one its wave returns at once.  Everything a
+// wave does is uniform over its lanes (the coder's state is), so the ballots and shuffles of the search have every lane.
+template <int W, int S, int KIND, bool JUMP>
+__global__ __launch_bounds__(kBlock) void decode_rows_piece_ragged_kernel(const std::conditional_t<JUMP, CatPerfectPieceChunkArgs, CatPerfectPieceArgs> ra) {
+    static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
+    const PerSymbolDecodeArgs& a = ra.p;
+    const int lane = threadIdx.x & (kWave - 1);
+    const size_t u = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (u >= ra.n_units) return;
+    bool active;
+    const size_t s = ragged_lane_stream<JUMP>(ra, ra.u0 + u, a.n_streams, active);
+    if (!active) return;                                                // (a slot whose order entry names no stream)
+    const CatRaggedSpan span(ragged_lane_begin<JUMP>(ra, s), ragged_lane_end<JUMP>(ra, s), ra.n_total);
+    const bool over = (uint64_t)span.len > ra.max_len;
+    const uint64_t len = over ? 0 : (uint64_t)span.len;
+    if (ra.t0 != 0 && ra.t0 >= len) return;                             // finished in an earlier piece
+    const uint64_t end = len < ra.t0 + ra.count ? len : ra.t0 + ra.count;
+    const bool finishes = end == len;
+    const int P = a.precision;
+    const uint32_t n = (uint32_t)a.n_symbols;
+
+    DirectDecoder<W, S, KIND> D;
+    int32_t status;
+    if (ra.t0 == 0) { D.init(a, s, JUMP); status = D.status; }
+    else { const DecodeResume r = ra.resume[u]; D.resume(a, s, r); status = r.status; }
+    for (uint64_t t = ra.t0; t < end && status == CST_STREAM_OK; ++t) {
+        const uint32_t* row = ra.rows + ((uint64_t)u * ra.count + (t - ra.t0)) * ((uint64_t)n + 1);
+        const uint32_t q = D.quantile(P);
+        if (D.status != CST_STREAM_OK) { status = D.status; break; }
+        uint32_t base = 0, left_over = n;             // invariant: row[base] <= q
+        while (left_over > 63) {
+            const uint32_t stride = (left_over + 63) / 64;
+            const uint32_t off = (uint32_t)lane * stride;
+            const bool valid = off < left_over;
+            const uint32_t val = valid ? row[base + off] : 0u;
+            const unsigned long long m = __ballot(valid && val <= q);
+            const uint32_t k = max((uint32_t)__popcll(m), 1u);
+            const uint32_t adv = (k - 1) * stride;
+            base += adv;
+            left_over = min(stride, left_over - adv);
+        }
+        const uint32_t val = ((uint32_t)lane <= left_over) ? row[base + lane] : 0u;
+        const unsigned long long m = __ballot((uint32_t)lane < left_over && val <= q);
+        const uint32_t k = (uint32_t)__popcll(m);
+        const uint32_t c = __shfl(val, (int)(k > 0 ? k - 1 : 0), 64), nxt = __shfl(val, (int)min(k, 63u), 64);
+        const uint32_t p = nxt - c;
+        // (a bad or non-converged row starts with 0xffffffff: k == 0 or c > q)
+        if (p == 0 || k == 0 || c > q || (uint64_t)c + p > ((uint64_t)1 << P)) { status = CST_STREAM_IMPOSSIBLE_SYMBOL; break; }
+        if (lane == 0) a.symbols[span.lo + t] = (int32_t)(base + k - 1);
+        D.advance(q, c, p, P);
+        D.look_ahead();
+    }
+    if (lane != 0) return;
+    if (finishes) { a.status[s] = over ? (int32_t)CST_STREAM_CAPACITY : span.status(status); D.finish(a, s, false); }
+    else { DecodeResume r{}; D.park(r); r.status = status; ra.resume[u] = r; }
+}
+
 // ---- host side: one route whatever the batch ----
 static constexpr const char* kCatRaggedEncodeNames[2][2] = {{"ans_encode_categorical_ragged_two_pass", "range_encode_categorical_ragged_two_pass"},
                                                             {"ans_encode_categorical_ragged_two_pass<jump>", "range_encode_categorical_ragged_two_pass<jump>"}};
 static constexpr const char* kCatRaggedDecodeNames[2][2] = {{"ans_decode_categorical_ragged_kernel", "range_decode_categorical_ragged_kernel"},
                                                             {"ans_decode_categorical_ragged_kernel<jump>", "range_decode_categorical_ragged_kernel<jump>"}};
 
-// what all eight calls refuse before they touch the device
+static constexpr const char* kCatPerfectRaggedEncodeNames[2][2] = {
+    {"ans_encode_categorical_perfect_ragged_two_pass", "range_encode_categorical_perfect_ragged_two_pass"},
+    {"ans_encode_categorical_perfect_ragged_two_pass<jump>", "range_encode_categorical_perfect_ragged_two_pass<jump>"}};
+static constexpr const char* kCatPerfectRaggedDecodeNames[2][2] = {
+    {"ans_decode_categorical_perfect_ragged_by_rows", "range_decode_categorical_perfect_ragged_by_rows"},
+    {"ans_decode_categorical_perfect_ragged_by_rows<jump>", "range_decode_categorical_perfect_ragged_by_rows<jump>"}};
+
+// what all sixteen calls refuse before they touch the device (`perfect`: the limits of check_categorical_args, cst_persymbol_categorical.hip)
 static cst_status check_categorical_ragged_args(cst_coder_config cfg, const void* d_symbols, const void* d_probs, int32_t prob_bytes, int32_t n_symbols,
                                                 const void* d_sym_offsets, const void* d_words, const void* d_word_offsets, size_t stride_words,
-                                                const void* d_n_words, const void* d_status, size_t n_streams) {
+                                                const void* d_n_words, const void* d_status, size_t n_streams, bool perfect = false) {
     if (!d_symbols || !d_probs || !d_sym_offsets || !d_words || !d_n_words || !d_status) return CST_ERR_INVALID_ARGUMENT;
     if (prob_bytes != 4 && prob_bytes != 8) return CST_ERR_INVALID_ARGUMENT;
     if (!config_supported(cfg)) return CST_ERR_INVALID_ARGUMENT;
     if (!d_word_offsets && stride_words == 0) return CST_ERR_INVALID_ARGUMENT;
     if (n_streams > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;          // (a launch has at most 2^31 - 1 blocks; an order names 32-bit indices)
-    // from_floating_point_probabilities_fast: room for a nonzero probability each plus one (check_categorical_args)
-    if (n_symbols < 2 || (uint64_t)n_symbols > ((uint64_t)1 << cfg.precision) - 2) return CST_ERR_MODEL;
+    // from_floating_point_probabilities_fast: room for a nonzero probability each plus one; perfectly_quantized_probabilities: a unit of
+    // weight for each, and the quantiser's slots (check_categorical_args)
+    const uint64_t total = (uint64_t)1 << cfg.precision;
+    const uint64_t limit = !perfect ? total - 2 : total < (uint64_t)kCatPerfectMaxK ? total : (uint64_t)kCatPerfectMaxK;
+    if (n_symbols < 2 || (uint64_t)n_symbols > limit) return CST_ERR_MODEL;
     return CST_OK;
 }
 
-template <int KIND, bool JUMP>
+// PERFECT: pass 1 is the device quantiser in entry mode over the flat matrix (one workgroup per row); pass 2 is the same kernel
+template <int KIND, bool JUMP, bool PERFECT = false>
 static cst_status encode_categorical_ragged(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes, int32_t n_symbols,
                                             size_t n_total, const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order,
                                             uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words, uint32_t* d_n_words,
@@ -355,8 +441,9 @@ static cst_status encode_categorical_ragged(cst_coder_config cfg, const int32_t*
     if constexpr (JUMP)
         if (jump_table_bad<KIND>(jump_interval, d_chunk_offsets, d_jump_pos, d_jump_a, d_jump_b)) return CST_ERR_INVALID_ARGUMENT;
     if (cst_status st = check_categorical_ragged_args(cfg, d_symbols, d_probs, prob_bytes, n_symbols, d_sym_offsets, d_words, d_word_offsets,
-                                                      stride_words, d_n_words, d_status, n_streams)) return st;
-    if ((n_total + kWave - 1) / kWave > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;      // (pass 1: a block per 64 rows)
+                                                      stride_words, d_n_words, d_status, n_streams, PERFECT)) return st;
+    // (pass 1: a block per 64 rows; PERFECT: a block per row)
+    if (PERFECT ? n_total > 0x7fffffffull : (n_total + kWave - 1) / kWave > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
     if (n_streams == 0) return CST_OK;
     std::conditional_t<JUMP, EntriesRaggedEncodeJumpArgs, EntriesRaggedEncodeArgs> a{};
     a.n_total = n_total; a.sym_offsets = d_sym_offsets; a.n_streams = n_streams; a.order = d_order; a.precision = cfg.precision;
@@ -365,13 +452,20 @@ static cst_status encode_categorical_ragged(cst_coder_config cfg, const int32_t*
         a.jump_interval = (uint32_t)jump_interval; a.jump_chunk_offsets = d_chunk_offsets; a.jump_pos = d_jump_pos; a.jump_a = d_jump_a;
         a.jump_b = d_jump_b;
     }
-    const char* name = kCatRaggedEncodeNames[JUMP][KIND == kRange];
+    const char* name = (PERFECT ? kCatPerfectRaggedEncodeNames : kCatRaggedEncodeNames)[JUMP][KIND == kRange];
     EncEntry* entries = nullptr;
     if (n_total > 0) {
         // pass 1 over the flat matrix, sized by n_total: no read-back of sym_offsets
         CST_HIP_TRY(scratch_alloc((void**)&entries, n_total * sizeof(EncEntry), hs));
         const dim3 grid((unsigned)((n_total + kWave - 1) / kWave));
-        if (prob_bytes == 4)
+        if constexpr (PERFECT) {
+            CatPerfectArgs r{};
+            r.probs = d_probs; r.prob_bytes = prob_bytes; r.K = (uint32_t)n_symbols; r.P = cfg.precision; r.layout = CST_LAYOUT_STREAM_MAJOR;
+            r.n_streams = 1; r.N = n_total; r.t0 = 0; r.count = n_total;
+            r.symbols = d_symbols; r.entries = entries;
+            const cst_status rc = launch_categorical_perfect(r, hs);     // (it has read its launch error)
+            if (rc != CST_OK) { (void)hipFreeAsync(entries, hs); return note_kernel(name, rc); }
+        } else if (prob_bytes == 4)
             hipLaunchKernelGGL(categorical_entries_kernel<float>, grid, dim3(kWave), kCatTileBytes<float>, hs, cfg.precision, (uint32_t)n_symbols,
                                d_symbols, reinterpret_cast<const float*>(d_probs), n_total, entries);
         else
@@ -438,6 +532,95 @@ static cst_status decode_categorical_ragged_jump(cst_coder_config cfg, const uin
         a.p = p; a.p.min_symbol = 0; a.p.n_symbols = n_symbols;
         a.probs = d_probs; a.n_total = n_total; a.sym_lo = v.sym_lo; a.len = v.len;
         const cst_status rc = launch_decode_categorical_ragged<KIND, true>(cfg, a, prob_bytes, hs);
+        return rc == CST_OK ? rc : note_kernel(name, rc);
+    });
+}
+
+// ---- Categorical(perfect=True): rows in pieces, for groups of units ----
+// The rows of one step -- `units` consecutive unit slots times `piece` positions, K + 1 words each -- stay within the budget (64 MiB of
+// rows, CST_PERFECT_RAGGED_BUDGET words): units = clamp(budget / (K + 1), 1, n_units), piece = clamp(budget / (units (K + 1)), 1, bound),
+// `bound` the longest unit there may be.  For every group, for every piece: tabulate, then decode; the decoders of a group are parked in
+// `resume` between its pieces.  Without the groups a table of many chunks at large K would not fit: one position of ALL units is
+// n_units (K + 1) words.  `pa`: everything but the group, the piece, the rows and the resume scratch.
+template <int KIND, bool JUMP, class PieceArgs>
+static cst_status decode_perfect_ragged_units(cst_coder_config cfg, PieceArgs pa, const void* d_probs, int32_t prob_bytes, uint64_t bound, hipStream_t hs) {
+    const size_t n_units = pa.p.n_streams, pitch = (size_t)pa.p.n_symbols + 1;
+    const size_t budget = knobs().perfect_ragged_budget;
+    size_t units = budget / pitch;
+    units = units < 1 ? 1 : units > n_units ? n_units : units;
+    const uint64_t last = bound ? bound : 1;                            // (no symbols at all: one piece initialises and finishes the decoders)
+    uint64_t piece = budget / (units * pitch);
+    piece = piece < 1 ? 1 : piece > last ? last : piece;
+    uint32_t* rows = nullptr;
+    DecodeResume* resume = nullptr;
+    CST_HIP_TRY(scratch_alloc((void**)&rows, units * (size_t)piece * pitch * sizeof(uint32_t), hs));
+    hipError_t err = scratch_alloc((void**)&resume, units * sizeof(DecodeResume), hs);
+    cst_status rc = CST_OK;
+    CatPerfectRaggedArgs r{};
+    r.probs = d_probs; r.prob_bytes = prob_bytes; r.K = (uint32_t)pa.p.n_symbols; r.P = cfg.precision; r.rows = rows; r.pitch = pitch;
+    r.n_total = pa.n_total; r.n_all = n_units; r.max_len = pa.max_len;
+    if constexpr (JUMP) { r.sym_lo = pa.sym_lo; r.len = pa.len; }
+    else { r.sym_offsets = pa.sym_offsets; r.order = pa.order; }
+    pa.rows = rows; pa.resume = resume;
+    for (size_t u0 = 0; u0 < n_units && err == hipSuccess && rc == CST_OK; u0 += units) {
+        const size_t n_here = n_units - u0 < units ? n_units - u0 : units;
+        for (uint64_t t0 = 0; t0 < last && err == hipSuccess && rc == CST_OK; t0 += piece) {
+            const uint64_t count = last - t0 < piece ? last - t0 : piece;
+            r.u0 = u0; r.n_streams = n_here; r.t0 = (size_t)t0; r.count = (size_t)count;
+            rc = launch_categorical_perfect_ragged(r, hs);
+            if (rc != CST_OK) break;
+            pa.u0 = u0; pa.n_units = n_here; pa.t0 = t0; pa.count = count;
+            const dim3 grid((unsigned)((n_here * kWave + kBlock - 1) / kBlock));
+            dispatch_word_size(cfg, [&](auto W, auto S) {
+                hipLaunchKernelGGL((decode_rows_piece_ragged_kernel<W, S, KIND, JUMP>), grid, dim3(kBlock), 0, hs, pa);
+                return 0;
+            });
+            err = hipGetLastError();
+        }
+    }
+    if (resume) (void)hipFreeAsync(resume, hs);
+    (void)hipFreeAsync(rows, hs);
+    CST_HIP_TRY(err);
+    return rc;
+}
+
+template <int KIND>
+static cst_status decode_categorical_perfect_ragged(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                    size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                                    int32_t n_symbols, size_t n_total, size_t max_len, int32_t* d_symbols,
+                                                    const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order, int32_t* d_status,
+                                                    hipStream_t hs) {
+    if (cst_status st = check_categorical_ragged_args(cfg, d_symbols, d_probs, prob_bytes, n_symbols, d_sym_offsets, d_words, d_word_offsets,
+                                                      stride_words, d_n_words, d_status, n_streams, true)) return st;
+    if (n_streams == 0) return CST_OK;
+    CatPerfectPieceArgs a{};
+    a.p.words = d_words; a.p.offsets = d_word_offsets; a.p.stride_words = stride_words; a.p.n_words = d_n_words; a.p.words_capacity = words_capacity;
+    a.p.symbols = d_symbols; a.p.n_streams = n_streams; a.p.precision = cfg.precision; a.p.min_symbol = 0; a.p.n_symbols = n_symbols;
+    a.p.status = d_status;
+    a.n_total = n_total; a.sym_offsets = d_sym_offsets; a.order = d_order;
+    a.max_len = max_len > 0xffffffffull ? 0xffffffffull : (uint64_t)max_len;          // (a coder has at most 2^32 - 1 symbols)
+    return note_kernel(kCatPerfectRaggedDecodeNames[0][KIND == kRange], decode_perfect_ragged_units<KIND, false>(cfg, a, d_probs, prob_bytes, a.max_len, hs));
+}
+
+// the piece decoder over the table's entries, between the two table kernels (decode_jump_chunks): an entry has at most jump_interval symbols
+template <int KIND>
+static cst_status decode_categorical_perfect_ragged_jump(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                         size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const void* d_probs,
+                                                         int32_t prob_bytes, int32_t n_symbols, size_t n_total, int32_t* d_symbols,
+                                                         const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                         const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint32_t* d_jump_pos,
+                                                         const uint64_t* d_jump_a, const uint64_t* d_jump_b, void* d_scratch, int32_t* d_status,
+                                                         hipStream_t hs) {
+    const cst_status plain = check_categorical_ragged_args(cfg, d_symbols, d_probs, prob_bytes, n_symbols, d_sym_offsets, d_words, d_word_offsets,
+                                                           stride_words, d_n_words, d_status, n_streams, true);
+    const char* name = kCatPerfectRaggedDecodeNames[1][KIND == kRange];
+    return decode_jump_chunks<KIND>(cfg, plain, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_symbols, d_sym_offsets, n_streams,
+                                    jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_a, d_jump_b, d_scratch, d_status, name, hs,
+                                    [&](const PerSymbolDecodeArgs& p, const PerSymbolJumpScratch& v) {
+        CatPerfectPieceChunkArgs a{};
+        a.p = p; a.p.min_symbol = 0; a.p.n_symbols = n_symbols;
+        a.n_total = n_total; a.sym_lo = v.sym_lo; a.len = v.len; a.max_len = (uint64_t)jump_interval;
+        const cst_status rc = decode_perfect_ragged_units<KIND, true>(cfg, a, d_probs, prob_bytes, (uint64_t)jump_interval, hs);
         return rc == CST_OK ? rc : note_kernel(name, rc);
     });
 }
@@ -525,6 +708,93 @@ cst_status cst_range_decode_categorical_ragged_jump(cst_coder_config cfg, const 
     return decode_categorical_ragged_jump<kRange>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes, n_symbols,
                                                   n_total, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos,
                                                   d_jump_lower, d_jump_range, d_scratch, d_status, (hipStream_t)stream);
+}
+
+// ---- Categorical(perfect=True): the same argument lists; the plain decoders take max_len after n_total ----
+
+cst_status cst_ans_encode_categorical_perfect_ragged(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes,
+                                                     int32_t n_symbols, size_t n_total, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                     const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                     uint32_t* d_n_words, int32_t* d_status, void* stream) {
+    return encode_categorical_ragged<kAns, false, true>(cfg, d_symbols, d_probs, prob_bytes, n_symbols, n_total, d_sym_offsets, n_streams, d_order,
+                                                        d_words, d_word_offsets, stride_words, d_n_words, 0, nullptr, nullptr, nullptr, nullptr,
+                                                        d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_encode_categorical_perfect_ragged(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes,
+                                                       int32_t n_symbols, size_t n_total, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                       const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                       size_t stride_words, uint32_t* d_n_words, int32_t* d_status, void* stream) {
+    return encode_categorical_ragged<kRange, false, true>(cfg, d_symbols, d_probs, prob_bytes, n_symbols, n_total, d_sym_offsets, n_streams, d_order,
+                                                          d_words, d_word_offsets, stride_words, d_n_words, 0, nullptr, nullptr, nullptr, nullptr,
+                                                          d_status, (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_categorical_perfect_ragged(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                     size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const void* d_probs,
+                                                     int32_t prob_bytes, int32_t n_symbols, size_t n_total, size_t max_len, int32_t* d_symbols,
+                                                     const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order, int32_t* d_status,
+                                                     void* stream) {
+    return decode_categorical_perfect_ragged<kAns>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes,
+                                                   n_symbols, n_total, max_len, d_symbols, d_sym_offsets, n_streams, d_order, d_status,
+                                                   (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_categorical_perfect_ragged(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                       size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const void* d_probs,
+                                                       int32_t prob_bytes, int32_t n_symbols, size_t n_total, size_t max_len, int32_t* d_symbols,
+                                                       const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order,
+                                                       int32_t* d_status, void* stream) {
+    return decode_categorical_perfect_ragged<kRange>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes,
+                                                     n_symbols, n_total, max_len, d_symbols, d_sym_offsets, n_streams, d_order, d_status,
+                                                     (hipStream_t)stream);
+}
+
+cst_status cst_ans_encode_categorical_perfect_ragged_jump(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes,
+                                                          int32_t n_symbols, size_t n_total, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                          const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                          size_t stride_words, uint32_t* d_n_words, size_t jump_interval,
+                                                          const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos, uint64_t* d_jump_state,
+                                                          int32_t* d_status, void* stream) {
+    return encode_categorical_ragged<kAns, true, true>(cfg, d_symbols, d_probs, prob_bytes, n_symbols, n_total, d_sym_offsets, n_streams, d_order,
+                                                       d_words, d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos,
+                                                       d_jump_state, nullptr, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_encode_categorical_perfect_ragged_jump(cst_coder_config cfg, const int32_t* d_symbols, const void* d_probs, int32_t prob_bytes,
+                                                            int32_t n_symbols, size_t n_total, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                            const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                            size_t stride_words, uint32_t* d_n_words, size_t jump_interval,
+                                                            const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos, uint64_t* d_jump_lower,
+                                                            uint64_t* d_jump_range, int32_t* d_status, void* stream) {
+    return encode_categorical_ragged<kRange, true, true>(cfg, d_symbols, d_probs, prob_bytes, n_symbols, n_total, d_sym_offsets, n_streams, d_order,
+                                                         d_words, d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos,
+                                                         d_jump_lower, d_jump_range, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_categorical_perfect_ragged_jump(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                          size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                          const void* d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                          int32_t* d_symbols, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                          size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                          const uint32_t* d_jump_pos, const uint64_t* d_jump_state, void* d_scratch,
+                                                          int32_t* d_status, void* stream) {
+    return decode_categorical_perfect_ragged_jump<kAns>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes,
+                                                        n_symbols, n_total, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets,
+                                                        n_chunks_total, d_jump_pos, d_jump_state, nullptr, d_scratch, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_categorical_perfect_ragged_jump(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                            size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                            const void* d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                            int32_t* d_symbols, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                            size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                            const uint32_t* d_jump_pos, const uint64_t* d_jump_lower,
+                                                            const uint64_t* d_jump_range, void* d_scratch, int32_t* d_status, void* stream) {
+    return decode_categorical_perfect_ragged_jump<kRange>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes,
+                                                          n_symbols, n_total, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets,
+                                                          n_chunks_total, d_jump_pos, d_jump_lower, d_jump_range, d_scratch, d_status,
+                                                          (hipStream_t)stream);
 }
 
 } // extern "C"

@@ -712,6 +712,7 @@ size_t cst_jump_points_auto_gaussian(cst_coder_config cfg, int32_t coder, size_t
  *   CST_SUB_ORDER=0          range sub-lane decoder: chunks side by side      CST_LANE_GEO=big|small   per-symbol lane decoder geometry
  *   CST_FUSED_MIN_STREAMS=n  from how many streams the fused per-symbol encoder runs         CST_CATEGORICAL_ROUTE=fused|rows   per-symbol Categorical decoders: the route
  *   CST_AUTO_JUMP=0          cst_jump_points_auto* answer 0                  CST_RAGGED_GROUP=8|16|32   ragged encoder: symbols per memory point
+ *   CST_PERFECT_RAGGED_BUDGET=n   ragged Categorical(perfect=True) decoders: 32-bit words of tabulated rows per step (default 16777216 = 64 MiB)
  * (CST_RCCL_LIB=<path>, read at the first collective call, names the RCCL library to open.)
  * cst_debug_reload_knobs re-reads them: for tests that drive several paths inside one process; not thread-safe against
  * concurrent coder calls. */
@@ -1062,7 +1063,8 @@ cst_status cst_range_decode_categorical_perfect_batch(cst_coder_config cfg, cons
  *     outside {4, 8}, an unsupported cfg, n_streams > 2^31 - 1, n_total > 64 (2^31 - 1) (encoders) and every refusal of the Gaussian jump
  *     calls return CST_ERR_INVALID_ARGUMENT; then n_symbols < 2 or n_symbols >= 2^precision - 1 returns CST_ERR_MODEL.  n_streams == 0:
  *     CST_OK, nothing is launched.
- *   - One route for every batch size: built for many streams; a few are coded correctly, but slowly.  Not here: the perfect quantisation,
+ *   - One route for every batch size: built for many streams; a few are coded correctly, but slowly.  Not here: the perfect quantisation (the
+ *     cst_*_categorical_perfect_ragged calls below),
  *     the symbol-major layout (a ragged batch has none), a count_until, intervals that are no multiple of 16.
  * cst_last_kernel_name(): {ans,range}_encode_categorical_ragged_two_pass, {ans,range}_decode_categorical_ragged_kernel, and the same names
  * followed by <jump>. */
@@ -1110,6 +1112,70 @@ cst_status cst_range_decode_categorical_ragged_jump(cst_coder_config cfg, const 
                                                     size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
                                                     const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
                                                     const uint64_t *d_jump_range, void *d_scratch, int32_t *d_status, void *stream);
+
+/* ... and with the perfect quantisation: Categorical(perfect=True), the reference's default, for streams of DIFFERENT lengths, plain and with
+ * jump points (ABI 5).  The argument lists are those of cst_*_categorical_ragged[_jump] with ONE exception: the two plain
+ * decoders take max_len directly after n_total.  Stream s owns rows [d_sym_offsets[s], d_sym_offsets[s + 1]) of d_probs [n_total][n_symbols]
+ * and of the flat d_symbols; its words, word count and status are those of cst_{ans,range}_{encode,decode}_categorical_perfect_batch for
+ * that stream alone, bit for bit.  d_order, the slabs, empty streams, the refusals against n_total (CST_STREAM_CAPACITY /
+ * CST_STREAM_INVALID_DATA), the jump table, its layout and d_scratch (cst_persymbol_ragged_jump_scratch_bytes) are exactly those of
+ * cst_*_categorical_ragged[_jump].
+ *   - max_len (plain decoders): an upper bound of the longest stream.  The decoders tabulate the rows of a piece of positions of a group of
+ *     streams, then look the symbols up, piece after piece up to max_len, without reading d_sym_offsets back.  A stream longer than max_len
+ *     reports CST_STREAM_CAPACITY and decodes nothing.  The jump decoders need none: a chunk has at most jump_interval symbols.
+ *   - The rows of one step stay within 64 MiB (CST_PERFECT_RAGGED_BUDGET, a debug switch, gives the budget in 32-bit words).
+ *   - A bad or non-converged row (codes 1 and 2 of cst_categorical_perfect_cdf_rows) and a symbol outside [0, n_symbols) yield
+ *     CST_STREAM_IMPOSSIBLE_SYMBOL for their stream only.
+ *   - Before the device is touched: the refusals of cst_*_categorical_ragged[_jump], with the model limits of the perfect quantisation --
+ *     n_symbols < 2, n_symbols > CST_CATEGORICAL_PERFECT_MAX_K or n_symbols > 2^precision return CST_ERR_MODEL -- and, encoders,
+ *     n_total > 2^31 - 1 returns CST_ERR_INVALID_ARGUMENT (one quantiser workgroup per row).  n_streams == 0: CST_OK, nothing is launched.
+ * cst_last_kernel_name(): {ans,range}_encode_categorical_perfect_ragged_two_pass, {ans,range}_decode_categorical_perfect_ragged_by_rows, and the
+ * same names followed by <jump>. */
+cst_status cst_ans_encode_categorical_perfect_ragged(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs, int32_t prob_bytes,
+                                                     int32_t n_symbols, size_t n_total, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                     const uint32_t *d_order, uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                     size_t stride_words, uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_categorical_perfect_ragged(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                     size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                     const void *d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                     size_t max_len, int32_t *d_symbols, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                     const uint32_t *d_order, int32_t *d_status, void *stream);
+cst_status cst_range_encode_categorical_perfect_ragged(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs, int32_t prob_bytes,
+                                                       int32_t n_symbols, size_t n_total, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                       const uint32_t *d_order, uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                       size_t stride_words, uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_range_decode_categorical_perfect_ragged(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                       size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                       const void *d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                       size_t max_len, int32_t *d_symbols, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                       const uint32_t *d_order, int32_t *d_status, void *stream);
+cst_status cst_ans_encode_categorical_perfect_ragged_jump(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs,
+                                                          int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                          const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                                          uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                          uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                          uint32_t *d_jump_pos, uint64_t *d_jump_state, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_categorical_perfect_ragged_jump(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                          size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                          const void *d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                          int32_t *d_symbols, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                          size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                          const uint32_t *d_jump_pos, const uint64_t *d_jump_state, void *d_scratch,
+                                                          int32_t *d_status, void *stream);
+cst_status cst_range_encode_categorical_perfect_ragged_jump(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs,
+                                                            int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                            const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                                            uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                            uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                            uint32_t *d_jump_pos, uint64_t *d_jump_lower, uint64_t *d_jump_range,
+                                                            int32_t *d_status, void *stream);
+cst_status cst_range_decode_categorical_perfect_ragged_jump(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                            size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                            const void *d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                            int32_t *d_symbols, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                            size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                            const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
+                                                            const uint64_t *d_jump_range, void *d_scratch, int32_t *d_status, void *stream);
 
 /* ABI 5: jump points for the per-symbol Gaussian calls of the RANGE coder (RangeEncoder::pos / RangeDecoder::seek, src/stream/queue.rs:172-196,
  * 900-926), as cst_ans_{encode,decode}_gaussian_batch_ckpt are for ANS: the fused encoder notes (words emitted including held-back ones,

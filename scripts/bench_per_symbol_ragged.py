@@ -13,10 +13,13 @@ alternating; recorded per alternation, with the size of the table against the wo
 out (it takes seconds per alternation and minutes to set up; its condition is then not judged).
 --family categorical --k K: every symbol has its own row of K float32 probabilities (exp(3 z), z normal: not normalised; symbols drawn
 from the rows) in place of (mean, std) -- symbols x K x 4 bytes for the ragged batch and as much again for (c), so K has to fit memory.
+--perfect (with --family categorical): Categorical(perfect=True) -- the *_categorical_perfect_ragged calls beside *_categorical(...,
+perfect=True).  A wave quantises ONE row (millions of rows a second, not billions): take a batch of minutes, not hours, with --streams,
+--min-len and --max-len.
 Device events on the launch stream, warmed up, in one process, the candidates alternating, medians of the alternations.  Every
 stream is checked by the decode round trip.  The one condition: (a) is faster than (b) in every alternation (exit status 1 otherwise);
 (c) is a recorded ratio."""
-import argparse, json, statistics, sys
+import argparse, functools, json, statistics, sys
 from pathlib import Path
 import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
@@ -30,17 +33,23 @@ ap.add_argument("--alternations", type=int, default=5)
 ap.add_argument("--coder", choices=["ans", "range"], default="ans")
 ap.add_argument("--family", choices=["gaussian", "laplace", "cauchy", "categorical"], default="gaussian")
 ap.add_argument("--k", type=int, default=16, help="--family categorical: entries of a probability row")
+ap.add_argument("--perfect", action="store_true", help="--family categorical: Categorical(perfect=True), quantised by the device quantiser")
 ap.add_argument("--jump-every", type=int, default=0, help="also time the pair with a jump point every N symbols (a multiple of 16)")
 ap.add_argument("--skip-rectangular", action="store_true", help="leave (c), the rectangular matrix, out")
 ap.add_argument("--skip-grouped", action="store_true", help="leave (b), one rectangular call per distinct length, out")
 args = ap.parse_args()
 assert args.alternations >= 5 or args.streams < 16384, "the recorded figures are medians of at least five alternations"
+assert not args.perfect or args.family == "categorical", "--perfect goes with --family categorical"
 
 CFG, LO, HI = (32, 64, 24), -100, 100
 torch.manual_seed(1)
 dev = "cuda"
-enc_ragged, dec_ragged = getattr(B, f"{args.coder}_encode_{args.family}_ragged"), getattr(B, f"{args.coder}_decode_{args.family}_ragged")
+FORM = args.family + ("_perfect" if args.perfect else "")
+enc_ragged, dec_ragged = getattr(B, f"{args.coder}_encode_{FORM}_ragged"), getattr(B, f"{args.coder}_decode_{FORM}_ragged")
 enc_rect, dec_rect = getattr(B, f"{args.coder}_encode_{args.family}"), getattr(B, f"{args.coder}_decode_{args.family}")
+if args.perfect:
+    enc_rect, dec_rect = functools.partial(enc_rect, perfect=True), functools.partial(dec_rect, perfect=True)
+JUMP_KERNEL = f"{args.coder}_decode_categorical_perfect_ragged_by_rows<jump>" if args.perfect else f"{args.coder}_decode_{args.family}_ragged_kernel<jump>"
 NO_JUMP = {"jump_points": 0} if args.family == "gaussian" else {}      # (the family calls have no jump points to switch off)
 CATEGORICAL = args.family == "categorical"
 HEAD = () if CATEGORICAL else (LO, HI)                                  # what the calls take in front of the model's tensors
@@ -163,7 +172,7 @@ if args.jump_every:
     enc_j = enc_ragged(sym, offsets, *HEAD, *model, CFG, jump_every=args.jump_every)
     dec_j, st_j = dec_ragged(enc_j, offsets, *HEAD, *model)
     torch.cuda.synchronize()
-    ok_j = (B.last_kernel() == f"{args.coder}_decode_{args.family}_ragged_kernel<jump>" and bool(torch.equal(dec_j, sym)) and int(st_j.abs().sum()) == 0
+    ok_j = (B.last_kernel() == JUMP_KERNEL and bool(torch.equal(dec_j, sym)) and int(st_j.abs().sum()) == 0
             and int(enc_j.status.abs().sum()) == 0 and bool(torch.equal(enc_j.n_words, enc.n_words)))
     t_j = alternate({"plain_encode": lambda: enc_ragged(sym, offsets, *HEAD, *model, CFG),
                      "jump_encode": lambda: enc_ragged(sym, offsets, *HEAD, *model, CFG, jump_every=args.jump_every),
@@ -199,7 +208,7 @@ if not args.skip_rectangular:
 med = lambda xs: statistics.median(xs)
 m_ab = {k: med(v) for k, v in t_ab.items()}
 m_c = {k: med(v) for k, v in t_c.items()}
-print(f"{args.coder} x {args.family}{f' (K = {args.k}, float32)' if CATEGORICAL else ''}: {n} streams of {args.min_len} .. {args.max_len} symbols ({total / 1e6:.1f} M symbols), (32,64,24), "
+print(f"{args.coder} x {FORM}{f' (K = {args.k}, float32)' if CATEGORICAL else ''}: {n} streams of {args.min_len} .. {args.max_len} symbols ({total / 1e6:.1f} M symbols), (32,64,24), "
       f"medians of {args.alternations}:")
 print(f"  (a) ragged calls:               encode {m_ab['a_encode']:9.3f} ms ({total / m_ab['a_encode'] / 1e6:.2f} Gsym/s)  "
       f"decode {m_ab['a_decode']:9.3f} ms ({total / m_ab['a_decode'] / 1e6:.2f} Gsym/s)  round trip ok={ok_a}")
@@ -225,7 +234,7 @@ else:
     print(f"  (c) {n} x {n_per} rectangular:  encode {m_c['rect_encode']:9.3f} ms  decode {m_c['rect_decode']:9.3f} ms")
     print(f"      the same through the ragged calls: encode {m_c['ragged_encode']:9.3f} ms ({m_c['ragged_encode'] / m_c['rect_encode']:.2f}x)  "
           f"decode {m_c['ragged_decode']:9.3f} ms ({m_c['ragged_decode'] / m_c['rect_decode']:.2f}x)  round trips ok={ok_c}")
-print(json.dumps({"coder": args.coder, "family": args.family, "k": args.k if CATEGORICAL else None, "grouped": not args.skip_grouped, "streams": n, "symbols": total, "alternations": args.alternations, "ms": {**m_ab, **m_c}, "all_ms": {**t_ab, **t_c},
+print(json.dumps({"coder": args.coder, "family": args.family, "perfect": args.perfect, "k": args.k if CATEGORICAL else None, "grouped": not args.skip_grouped, "streams": n, "symbols": total, "alternations": args.alternations, "ms": {**m_ab, **m_c}, "all_ms": {**t_ab, **t_c},
                   "jump": jump_info, "jump_ms": {k: med(v) for k, v in t_j.items()}, "jump_all_ms": t_j,
                   "a_faster_than_b": faster, "round_trips_ok": ok_a and ok_b and ok_c and ok_j}))
 sys.exit(0 if faster and ok_a and ok_b and ok_c and ok_j else 1)
