@@ -1083,6 +1083,102 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    /// Random access into a ragged batch -- what the reference's `Seek` is FOR (src/stream/stack.rs:1107-1139, queue.rs:900-926): decode
+    /// selected documents, or ranges of documents, and nothing else.  cst_ans_decode_ragged_select / cst_range_decode_ragged_select take the
+    /// batch exactly as cst_{ans,range}_decode_ragged[_jump] take it (words, d_word_offsets or stride_words, words_capacity, d_n_words,
+    /// d_sym_offsets, and optionally a jump table) and a list of n_queries queries:
+    ///     query q = symbols [d_query_first[q], d_query_first[q] + d_query_count[q]) of document d_query_stream[q]
+    ///     (d_query_stream uint32 [n_queries]; d_query_first / d_query_count uint64 [n_queries], or BOTH NULL: whole documents)
+    /// in any order, repeats and overlaps allowed, count 0 allowed.  The output is a ragged array of its own: query q owns
+    /// d_symbols_out[d_out_offsets[q] .. d_out_offsets[q + 1]) (d_out_offsets uint64 [n_queries + 1], the exclusive prefix sum of the counts)
+    /// and receives exactly the symbols a full decode puts at d_sym_offsets[stream] + first ...; d_status holds one entry per QUERY.
+    ///   - With a jump table (jump_interval a positive multiple of 8, d_chunk_offsets / n_chunks_total / d_jump_pos / d_jump_state or
+    ///     d_jump_lower + d_jump_range as the jump decoders take them) a query is cut into PIECES, one per chunk it touches:
+    ///     ceil((first % jump_interval + count) / jump_interval) for count > 0, none for count 0.  The first piece starts at jump point
+    ///     first / jump_interval, decodes and DISCARDS first % jump_interval symbols, then stores up to the chunk's or the query's end; the
+    ///     others are whole chunks or a chunk's head.  Every piece is one lane and at most jump_interval dependent steps.
+    ///   - Without a table (jump_interval 0 and every table pointer NULL; n_chunks_total is ignored) a query is ONE piece that starts where
+    ///     its document starts and discards `first` symbols: correct, and as slow as its `first` is deep -- this is what jump points are for.
+    ///   - d_piece_offsets: uint64 [n_queries + 1], the exclusive prefix sum of the piece counts (the d_chunk_offsets convention);
+    ///     n_pieces_total: its last entry or any upper bound of it.  d_scratch: cst_ragged_select_scratch_bytes(n_pieces_total) /
+    ///     cst_range_ragged_select_scratch_bytes(n_pieces_total) bytes.
+    ///   - Everything above is caller data and checked on the device.  A query reports CST_STREAM_INVALID_DATA and writes NOTHING if
+    ///     its stream is >= n_streams; first + count lies beyond the document (judged without forming the sum: no 64-bit wrap); its slice of
+    ///     d_out_offsets is not `count` long or its slice of d_piece_offsets not its piece count (or beyond n_pieces_total); its stream's
+    ///     words leave the buffer (the check of cst_{ans,range}_decode_ragged); its stream's slice of the table is not
+    ///     ceil(length / jump_interval) entries inside n_chunks_total; or a table entry it touches has a d_jump_pos above the stream's
+    ///     d_n_words.  (A document longer than 2^32 - 1 symbols: CST_STREAM_CAPACITY, as in the plain decoders.)  The other queries still
+    ///     decode.  Otherwise a query's status is the worst of its pieces', as a stream's is in the jump decoders; piece offsets that do not
+    ///     ascend may leave a query with a piece the device gave to another one: CST_STREAM_INVALID_DATA for that query.  Nothing is written
+    ///     outside the output slices of valid queries, nothing is read outside words_capacity.
+    ///   - CST_ERR_INVALID_ARGUMENT, before the device is touched: every refusal of cst_ans_decode_ragged / cst_range_decode_ragged; a
+    ///     jump_interval that is neither 0 nor a multiple of 8, or above 2^31 - 1; a table given in part (an interval without all of its
+    ///     arrays, arrays without an interval); n_chunks_total or n_pieces_total > 2^32 - 1; exactly one of d_query_first / d_query_count
+    ///     NULL; with n_queries > 0 a NULL d_query_stream, d_piece_offsets, d_out_offsets, d_scratch or d_status.  n_queries == 0: CST_OK,
+    ///     nothing is launched.
+    /// cst_last_kernel_name: "ans_decode_ragged_kernel<select>" / "range_decode_ragged_kernel<select>".  Shared-table models only: the
+    /// per-symbol ragged coders index their parameters by symbol position and have no select form yet.
+    pub fn cst_ragged_select_scratch_bytes(n_pieces_total: usize) -> usize;
+
+    pub fn cst_range_ragged_select_scratch_bytes(n_pieces_total: usize) -> usize;
+
+    pub fn cst_ans_decode_ragged_select(
+        model: *const CstModel,
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_ragged_select(
+        model: *const CstModel,
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// Checkpointed streams -- the reference's Pos / Seek jump tables (src/stream/stack.rs:1107-1139; test :1456-1548) for the
     /// batched coder.  The encoder notes, in front of every chunk of `ckpt_interval` symbols, what `AnsCoder::pos()` returns
     /// there: d_ckpt_pos[s][j] = words in the bulk, d_ckpt_state[s][j] = coder state once symbols [j * interval, n) are

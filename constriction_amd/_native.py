@@ -122,6 +122,12 @@ SIGNATURES = {
     "cst_ragged_jump_scratch_bytes": (_z, [_z]),
     "cst_ans_encode_ragged_jump": (_i32, [_vp, CoderConfig, _vp, _vp, _z, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
     "cst_ans_decode_ragged_jump": (_i32, [_vp, CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_ragged_select_scratch_bytes": (_z, [_z]),
+    "cst_range_ragged_select_scratch_bytes": (_z, [_z]),
+    "cst_ans_decode_ragged_select": (_i32, [_vp, CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp, _z, _vp, _z,
+                                            _vp, _vp, _vp, _vp, _vp]),
+    "cst_range_decode_ragged_select": (_i32, [_vp, CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp, _vp, _z, _vp,
+                                              _z, _vp, _vp, _vp, _vp, _vp]),
     "cst_compact_scratch_bytes": (_z, [_z]),
     "cst_compact_words": (_i32, [_vp, _z, _vp, _z, _vp, _vp, _z, _vp, _vp]),
     "cst_words_reverse": (_i32, [_vp, _vp, _z, _vp, _z, _vp, _vp, _z, _vp]),

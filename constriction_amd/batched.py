@@ -889,6 +889,111 @@ def range_decode_ragged(encoded: RaggedBatch, model: Model, sym_offsets: torch.T
     return _to_symbols(model, out), status
 
 
+# ... and random access: selected documents, or ranges of documents, of a ragged batch (what the reference's `Seek` is for)
+
+def _select_piece_counts(first: torch.Tensor, count: torch.Tensor, interval: int) -> torch.Tensor:
+    """Pieces of the queries (first, count) of a select call (int64 tensors on any device): one per chunk of `interval` symbols a query
+    touches -- ceil((first % interval + count) / interval), none for count 0; without a table (interval 0) one piece per query that
+    asks for anything."""
+    if interval == 0:
+        return (count > 0).to(torch.int64)
+    return torch.where(count > 0, (first % interval + count + (interval - 1)) // interval, torch.zeros_like(count))
+
+
+def _decode_ragged_select(coder, jump_type, encoded, model, sym_offsets, streams, first, count, out):
+    """the body of ans_decode_ragged_select and range_decode_ragged_select"""
+    _require_coder(encoded, coder)
+    sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
+    n_streams = sym_offsets.numel() - 1
+    if sym_offsets.dim() != 1 or encoded.n_words.numel() != n_streams:
+        raise ValueError("sym_offsets does not match the number of streams of the batch")
+    jump = encoded.jump
+    if jump is not None and not isinstance(jump, jump_type):
+        raise ValueError("the batch carries the jump points of another coder")
+    dev = encoded.words.device
+    streams = torch.as_tensor(streams, device=dev)
+    if streams.dtype.is_floating_point or streams.dtype.is_complex or streams.dtype == torch.bool or streams.dim() != 1:
+        raise TypeError("streams: a flat integer tensor or sequence of document indices")
+    streams = streams.to(torch.int64)
+    n_queries = streams.numel()
+    whole = first is None and count is None
+
+    def as_i64(x, name):
+        x = torch.as_tensor(x, device=dev)
+        if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool or x.shape != streams.shape:
+            raise TypeError(f"{name}: one integer per query")
+        return x.to(torch.int64).contiguous()
+
+    # everything below is device arithmetic on caller data the kernels judge again: a query the device will refuse (a stream that is
+    # none, a range beyond its document) only has to get SOME slice here -- never one larger than a document
+    lengths = sym_offsets[1:] - sym_offsets[:-1]
+    known = (streams >= 0) & (streams < n_streams)
+    doc = torch.where(known, lengths[streams.clamp(0, max(n_streams - 1, 0))], torch.zeros_like(streams)) if n_streams > 0 else torch.zeros_like(streams)
+    query_stream = torch.where(known, streams, torch.full_like(streams, 0xffffffff)).to(torch.int32)
+    if not whole:
+        first = as_i64(first, "first") if first is not None else torch.zeros_like(streams)
+        count = as_i64(count, "count") if count is not None else (doc - first).clamp(min=0)
+    sizes = doc if whole else torch.minimum(count.clamp(min=0), doc)
+    interval = int(jump.interval) if jump is not None and jump.chunk_offsets.numel() == n_streams + 1 else 0
+    pieces = _select_piece_counts(torch.zeros_like(sizes) if whole else first, sizes, interval)
+    out_offsets = torch.zeros(n_queries + 1, dtype=torch.int64, device=dev)
+    piece_offsets = torch.zeros(n_queries + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(sizes, 0, out=out_offsets[1:])
+    torch.cumsum(pieces, 0, out=piece_offsets[1:])
+    total = int(out_offsets[-1].item()) if n_queries > 0 else 0         # (the only read-back, as ans_decode_ragged reads sym_offsets[-1])
+    # a query of `count` symbols has at most count // I + 2 pieces: an upper bound of the pieces, without a second read-back
+    n_pieces = (total // interval + 2 * n_queries) if interval else n_queries
+    if out is None:
+        out = torch.empty(total, dtype=torch.int32, device=dev)
+    else:
+        out = _require_cuda(out, torch.int32, "out")
+        if out.dim() != 1 or out.numel() < total:
+            raise ValueError("out must be flat and hold every query's symbols")
+    status = torch.empty(n_queries, dtype=torch.int32, device=dev)
+    if n_queries == 0:
+        return out[:0], out_offsets, status
+    L = N.lib()
+    head = (model._h, _cfg(*encoded.config), _ptr(encoded.words), _ptr(encoded.word_offsets), 0, encoded.words.numel(), _ptr(encoded.n_words),
+            _ptr(sym_offsets), n_streams)
+    tail = (_ptr(query_stream), None if whole else _ptr(first), None if whole else _ptr(count), n_queries, _ptr(piece_offsets), n_pieces,
+            _ptr(out), _ptr(out_offsets))
+    if coder == "ans":
+        table = (interval, _ptr(jump.chunk_offsets), min(int(jump.pos.numel()), int(jump.state.numel())), _ptr(jump.pos),
+                 _ptr(jump.state)) if interval else (0, None, 0, None, None)
+        scratch = _ckpt_scratch("ragged_select", dev, L.cst_ragged_select_scratch_bytes(n_pieces))
+        N.check(L.cst_ans_decode_ragged_select(*head, *table, *tail, _ptr(scratch), _ptr(status), _stream_ptr()), "cst_ans_decode_ragged_select")
+    else:
+        table = (interval, _ptr(jump.chunk_offsets), min(int(jump.pos.numel()), int(jump.lower.numel()), int(jump.range.numel())), _ptr(jump.pos),
+                 _ptr(jump.lower), _ptr(jump.range)) if interval else (0, None, 0, None, None, None)
+        scratch = _ckpt_scratch("range_ragged_select", dev, L.cst_range_ragged_select_scratch_bytes(n_pieces))
+        N.check(L.cst_range_decode_ragged_select(*head, *table, *tail, _ptr(scratch), _ptr(status), _stream_ptr()), "cst_range_decode_ragged_select")
+    return _to_symbols(model, out[:total]), out_offsets, status
+
+
+def ans_decode_ragged_select(encoded: RaggedBatch, model: Model, sym_offsets: torch.Tensor, streams, first=None, count=None,
+                             out: Optional[torch.Tensor] = None):
+    """Random access into a ragged ANS batch: query q decodes symbols [first[q], first[q] + count[q]) of document streams[q], and
+    nothing else is decoded.  `streams`: an integer tensor or sequence, in any order, repeats and overlaps allowed; `first` / `count`:
+    one integer per query (None: from the document's start / to its end; both None: whole documents).  Returns (symbols flat int32,
+    out_offsets int64 [n_queries + 1], status int32 [n_queries]): query q owns symbols[out_offsets[q]:out_offsets[q + 1]], exactly what
+    ans_decode_ragged puts at sym_offsets[streams[q]] + first[q] ...
+    With jump points (`encoded.jump`, see ans_encode_ragged) every query starts at the jump point in front of `first`, decodes and
+    discards first % interval symbols, and every chunk it touches runs on a lane of its own: at most `interval` dependent steps.
+    WITHOUT them a query starts where its document starts and discards `first` symbols -- correct, and as slow as `first` is deep: that
+    is what jump points are for.  A query the device refuses (no such document, a range beyond its document, a table or counts that do
+    not fit) reports INVALID_DATA (3) and writes nothing; the others decode.  (Sized on the device: the output total is the only
+    read-back.)"""
+    return _decode_ragged_select("ans", RaggedJump, encoded, model, sym_offsets, streams, first, count, out)
+
+
+def range_decode_ragged_select(encoded: RaggedBatch, model: Model, sym_offsets: torch.Tensor, streams, first=None, count=None,
+                               out: Optional[torch.Tensor] = None):
+    """ans_decode_ragged_select for a range batch (range_encode_ragged / range_encode_ragged_jump): the same queries, the same three
+    results.  A piece seeks to its (pos, lower, range) entry and reads forward; without jump points it starts at word 0 of its document
+    and discards `first` symbols."""
+    return _decode_ragged_select("range", RangeRaggedJump, encoded, model, sym_offsets, streams, first, count, out)
+
+
 def range_decode_until(encoded: RaggedBatch, model: Model, eof_symbol: int, max_symbols: Optional[int] = None):
     """Streams whose length is not stored: every stream is decoded until `eof_symbol`, which a queue writes LAST.  Two launches --
     count, prefix sum, decode -- as ans_decode_until.  Returns (symbols flat, sym_offsets [n + 1], status); the terminator is the last

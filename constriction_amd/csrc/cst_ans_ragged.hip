@@ -23,6 +23,7 @@
 // Words go through the per-lane LDS rings of the other kernels.
 // Every stream's words are those of cst_ans_encode_batch for that stream alone (stack.rs:835-849, 891-895; 1070-1100).
 #include "cst_ans_kernels.hpp"
+#include "cst_ragged_select.hpp"
 
 namespace cst {
 
@@ -265,6 +266,18 @@ struct RaggedDecoder {
         L.in.prime();
         wave_lds_fence();
     }
+    // a piece of a query (SELECT: the lane's `s` is a piece index): its stream's words in front of its jump point -- the slice the
+    // piece builder checked, bounded once more as start() bounds a stream's --, the coder state of its table entry (AnsCoder::seek) or,
+    // for a piece that starts where its document starts, read_initial_state
+    __device__ __forceinline__ void start_piece(const RaggedArgs& a, const RaggedSelectLanes& v, uint32_t* ring) {
+        ws = active ? word_slice(v.word_off, 0, v.n_words, s, a.words_capacity) : WordSlice{0, 0u, false};
+        L.init(a.words_in + ws.off, ws.n, ring, lane);
+        const uint32_t e = (active && !ws.bad) ? v.entry[s] : kSelectNoEntry;
+        if (e != kSelectNoEntry) L.state = (typename StateT<S>::type)v.jump_a[e];
+        else L.read_initial_state();
+        L.in.prime();
+        wave_lds_fence();
+    }
     __device__ __forceinline__ void land() { ring_land_all(L.in, dump); }
     __device__ __forceinline__ void request() { ring_request<kRaggedDecAhead>(L.in); }
     __device__ __forceinline__ uint32_t step(const RaggedArgs& a) {
@@ -272,35 +285,63 @@ struct RaggedDecoder {
     }
 };
 
-template <int W, int S, bool STAGED, bool FAST>
-__global__ __launch_bounds__(kBlock) void ans_decode_ragged_kernel(const RaggedArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// the decoder: SELECT = false is ans_decode_ragged_kernel (a lane per stream, or per chunk of a batch with jump points);
+// SELECT = true the form with a lane per PIECE of a query (cst_ragged_select.hpp): a lane decodes `skip` symbols it does not store,
+// then its piece's symbols into its own row of the output.  The skipped symbols go through the same groups of eight -- land, request, eight
+// steps: one memory point per group --, only their stores are left out; a wave runs as long as its longest skip + length.
+template <int W, int S, bool STAGED, bool FAST, bool SELECT>
+__device__ __forceinline__ void ans_decode_ragged_body(const RaggedArgs& a, const RaggedSelectLanes& v, unsigned char* smem) {
     static_assert(2 * kRaggedGroup <= kRaggedDecAhead - 4, "a group may consume kRaggedGroup words before the chunks requested at its start land");
     RaggedDecoder<W, S, STAGED, FAST> D;
     D.stage(a, smem);
     if (!D.wave_has_streams(a)) return;
-    D.start(a, reinterpret_cast<uint32_t*>(smem) + (threadIdx.x >> 6) * (kRaggedDecSlots * kWave));
+    uint32_t* ring = reinterpret_cast<uint32_t*>(smem) + (threadIdx.x >> 6) * (kRaggedDecSlots * kWave);
+    if constexpr (SELECT) D.start_piece(a, v, ring);
+    else D.start(a, ring);
     D.dump = reinterpret_cast<uint32_t*>(smem + kRaggedDecRingBytes - kRaggedDumpBytes) + (threadIdx.x >> 6) * (4 * kWave) + D.lane;
-    const uint64_t sym_lo = D.active ? a.sym_offsets[D.s] : 0, sym_hi = D.active ? a.sym_offsets[D.s + 1] : 0;
+    uint64_t sym_lo = 0, sym_hi = 0;
+    [[maybe_unused]] uint32_t skip = 0;
+    if constexpr (SELECT) {
+        if (D.active) { sym_lo = v.out_lo[D.s]; skip = v.skip[D.s]; sym_hi = sym_lo + skip + v.len[D.s]; }
+    } else {
+        sym_lo = D.active ? a.sym_offsets[D.s] : 0; sym_hi = D.active ? a.sym_offsets[D.s + 1] : 0;
+    }
     const bool too_long = sym_hi - sym_lo > 0xffffffffull || sym_hi < sym_lo;
     const uint32_t len = too_long ? 0u : (uint32_t)(sym_hi - sym_lo);
+    // (SELECT: `len` counts the symbols the lane DECODES, the first `skip` of which it does not store: skip + the piece's length, at
+    //  most 2^32 - 1 by the piece builder's bound; decoded symbol k >= skip is row[k - skip])
     int32_t* row = a.symbols_out + sym_lo;
     const uint32_t mx = wave_max_u32(len);
     int32_t o[kRaggedGroup];
 #pragma unroll
     for (int j = 0; j < kRaggedGroup; ++j) o[j] = 0;
-    // symbols k0 - 8 .. k0 - 1 (decoded by the previous group) -> HBM: two 16-byte pieces, or one by one at the end of a row
+    // symbols k0 - 8 .. k0 - 1 (decoded by the previous group) -> HBM: two 16-byte pieces, or one by one at the end of a row.
+    // SELECT: a group wholly in front of `skip` stores nothing; the pieces are 16-byte stores at 4-byte boundaries, so a group wholly
+    // behind it keeps them wherever in a group the first stored symbol fell; the group that holds that symbol goes one by one
     auto store_group = [&](uint32_t k0) {
         if (k0 < kRaggedGroup || k0 - kRaggedGroup >= len) return;
         const uint32_t b = k0 - kRaggedGroup;
-        if (k0 <= len) {
-            rv4i_unaligned* d = reinterpret_cast<rv4i_unaligned*>(row + b);
-            d[0].v = rv4i{o[0], o[1], o[2], o[3]};
-            d[1].v = rv4i{o[4], o[5], o[6], o[7]};
-        } else {
+        if constexpr (SELECT) {
+            if (k0 <= skip) return;
+            if (b >= skip && k0 <= len) {
+                rv4i_unaligned* d = reinterpret_cast<rv4i_unaligned*>(row + (b - skip));
+                d[0].v = rv4i{o[0], o[1], o[2], o[3]};
+                d[1].v = rv4i{o[4], o[5], o[6], o[7]};
+            } else {
 #pragma unroll
-            for (int j = 0; j < kRaggedGroup; ++j)
-                if (b + (uint32_t)j < len) row[b + (uint32_t)j] = o[j];
+                for (int j = 0; j < kRaggedGroup; ++j)
+                    if (b + (uint32_t)j >= skip && b + (uint32_t)j < len) row[b + (uint32_t)j - skip] = o[j];
+            }
+        } else {
+            if (k0 <= len) {
+                rv4i_unaligned* d = reinterpret_cast<rv4i_unaligned*>(row + b);
+                d[0].v = rv4i{o[0], o[1], o[2], o[3]};
+                d[1].v = rv4i{o[4], o[5], o[6], o[7]};
+            } else {
+#pragma unroll
+                for (int j = 0; j < kRaggedGroup; ++j)
+                    if (b + (uint32_t)j < len) row[b + (uint32_t)j] = o[j];
+            }
         }
     };
     for (uint32_t k0 = 0; k0 < mx; k0 += kRaggedGroup) {
@@ -314,6 +355,18 @@ __global__ __launch_bounds__(kBlock) void ans_decode_ragged_kernel(const RaggedA
     store_group((mx + kRaggedGroup - 1) / kRaggedGroup * kRaggedGroup);
     if (!D.active) return;
     a.status[D.s] = D.ws.bad ? (int32_t)CST_STREAM_INVALID_DATA : (too_long ? (int32_t)CST_STREAM_CAPACITY : D.L.status);
+}
+
+template <int W, int S, bool STAGED, bool FAST>
+__global__ __launch_bounds__(kBlock) void ans_decode_ragged_kernel(const RaggedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ans_decode_ragged_body<W, S, STAGED, FAST, false>(a, RaggedSelectLanes{}, smem);
+}
+
+template <int W, int S, bool STAGED, bool FAST>
+__global__ __launch_bounds__(kBlock) void ans_decode_ragged_select_kernel(const RaggedArgs a, const RaggedSelectLanes v) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ans_decode_ragged_body<W, S, STAGED, FAST, true>(a, v, smem);
 }
 
 // The reference's index stores no lengths: a document ends where its terminator symbol is decoded (tests/issue52.rs:63-80).
@@ -545,6 +598,22 @@ cst_status ans_decode_ragged_jump(const cst_model* model, cst_coder_config cfg, 
                        n_chunks_total, interval, d_status);
     CST_HIP_TRY(hipGetLastError());
     return CST_OK;
+}
+
+// ---- random access: selected documents and ranges (cst_ragged_select.hpp) ----
+static cst_status decode_ragged_select_lanes(const cst_model* model, cst_coder_config cfg, const RaggedArgs& a, const RaggedSelectLanes& v, hipStream_t hs) {
+    CST_RAGGED_DISPATCH(ans_decode_ragged_select_kernel, kRaggedDecRingBytes, ragged_decode_table_bytes(model), v);
+}
+
+cst_status ans_decode_ragged_select(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const RaggedSelect& b,
+                                    const uint64_t* d_jump_state, int32_t* d_symbols, void* d_scratch, int32_t* d_status, hipStream_t hs) {
+    const RaggedSelectPieces v(d_scratch, b.n_pieces_total);
+    return ragged_select_run<true>(b, v, d_status, hs, [&]() {
+        // (the slices handed on are absolute offsets that passed the check, or empty: `words_capacity` bounds them once more)
+        RaggedArgs a = ragged_decode_args(model, d_words, nullptr, 0, b.words_capacity, nullptr, b.n_pieces_total, v.status, nullptr);
+        a.symbols_out = d_symbols;
+        return decode_ragged_select_lanes(model, cfg, a, select_lanes(v, nullptr, d_jump_state, nullptr), hs);
+    });
 }
 #undef CST_RAGGED_DISPATCH
 

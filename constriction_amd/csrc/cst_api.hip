@@ -534,6 +534,80 @@ cst_status cst_range_decode_ragged_jump(const cst_model* model, cst_coder_config
                                                                                      d_jump_lower, d_jump_range, d_scratch, d_status, (hipStream_t)stream));
 }
 
+// ---- random access into ragged batches: selected documents and ranges (cst_ragged_select.hpp) ----
+size_t cst_ragged_select_scratch_bytes(size_t n_pieces_total) { return ragged_select_scratch_bytes(n_pieces_total); }
+size_t cst_range_ragged_select_scratch_bytes(size_t n_pieces_total) { return ragged_select_scratch_bytes(n_pieces_total); }
+
+// what the two select calls refuse alike, whatever the numbers of streams and queries; `table` = how many of the table's pointers are given
+static bool ragged_select_args_ok(size_t jump_interval, int table, int table_pointers, size_t n_chunks_total, const void* d_query_first,
+                                  const void* d_query_count, size_t n_pieces_total) {
+    if (jump_interval != 0 && !ragged_jump_interval_ok(jump_interval)) return false;
+    // a table is an interval and ALL its arrays, or nothing at all
+    if (table != 0 && table != table_pointers) return false;
+    if ((jump_interval != 0) != (table != 0)) return false;
+    if ((table != 0 && n_chunks_total > 0xffffffffull) || n_pieces_total > 0xffffffffull) return false;
+    return (d_query_first == nullptr) == (d_query_count == nullptr);
+}
+
+static RaggedSelect ragged_select_batch(const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                        const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets,
+                                        size_t n_chunks_total, const uint32_t* d_jump_pos, const uint32_t* d_query_stream,
+                                        const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                        const uint64_t* d_piece_offsets, size_t n_pieces_total, const uint64_t* d_out_offsets) {
+    RaggedSelect b{};
+    b.sym_offsets = d_sym_offsets; b.word_offsets = d_word_offsets; b.stride_words = stride_words; b.n_words = d_n_words; b.n_streams = n_streams;
+    // (slab form without a capacity: the slabs themselves bound every slice, as in the jump decoders)
+    b.words_capacity = words_capacity ? words_capacity : (d_word_offsets ? 0 : n_streams * stride_words);
+    b.interval = (uint32_t)jump_interval; b.chunk_offsets = d_chunk_offsets; b.n_chunks_total = n_chunks_total; b.jump_pos = d_jump_pos;
+    b.query_stream = d_query_stream; b.query_first = d_query_first; b.query_count = d_query_count; b.n_queries = n_queries;
+    b.piece_offsets = d_piece_offsets; b.n_pieces_total = n_pieces_total; b.out_offsets = d_out_offsets;
+    return b;
+}
+
+cst_status cst_ans_decode_ragged_select(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                        size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const uint64_t* d_sym_offsets,
+                                        size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                        const uint32_t* d_jump_pos, const uint64_t* d_jump_state, const uint32_t* d_query_stream,
+                                        const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                        const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                        const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    if (!model || !config_supported(cfg) || cfg.precision != model->precision || model->per_stream) return CST_ERR_INVALID_ARGUMENT;
+    const int table = (d_chunk_offsets != nullptr) + (d_jump_pos != nullptr) + (d_jump_state != nullptr);
+    if (!ragged_select_args_ok(jump_interval, table, 3, n_chunks_total, d_query_first, d_query_count, n_pieces_total)) return CST_ERR_INVALID_ARGUMENT;
+    if (n_streams > 0 && (!d_sym_offsets || !d_n_words)) return CST_ERR_INVALID_ARGUMENT;
+    if (n_queries > 0 && (!d_query_stream || !d_piece_offsets || !d_out_offsets || !d_scratch || !d_status)) return CST_ERR_INVALID_ARGUMENT;
+    if (n_queries == 0) return CST_OK;
+    if (n_queries > ((size_t)0x7fffffff) * 256) return CST_ERR_INVALID_ARGUMENT;
+    if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    const RaggedSelect b = ragged_select_batch(d_word_offsets, stride_words, words_capacity, d_n_words, d_sym_offsets, n_streams, jump_interval,
+                                               d_chunk_offsets, n_chunks_total, d_jump_pos, d_query_stream, d_query_first, d_query_count, n_queries,
+                                               d_piece_offsets, n_pieces_total, d_out_offsets);
+    return note_kernel("ans_decode_ragged_kernel<select>", ans_decode_ragged_select(model, cfg, d_words, b, d_jump_state, d_symbols_out, d_scratch, d_status,
+                                                                                     (hipStream_t)stream));
+}
+
+cst_status cst_range_decode_ragged_select(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                          size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const uint64_t* d_sym_offsets,
+                                          size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                          const uint32_t* d_jump_pos, const uint64_t* d_jump_lower, const uint64_t* d_jump_range,
+                                          const uint32_t* d_query_stream, const uint64_t* d_query_first, const uint64_t* d_query_count,
+                                          size_t n_queries, const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                          const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, nullptr, n_streams)) return CST_ERR_INVALID_ARGUMENT;
+    const int table = (d_chunk_offsets != nullptr) + (d_jump_pos != nullptr) + (d_jump_lower != nullptr) + (d_jump_range != nullptr);
+    if (!ragged_select_args_ok(jump_interval, table, 4, n_chunks_total, d_query_first, d_query_count, n_pieces_total)) return CST_ERR_INVALID_ARGUMENT;
+    if (!d_sym_offsets || !d_n_words) return CST_ERR_INVALID_ARGUMENT;
+    if (n_queries > 0 && (!d_query_stream || !d_piece_offsets || !d_out_offsets || !d_scratch || !d_status)) return CST_ERR_INVALID_ARGUMENT;
+    if (n_queries == 0) return CST_OK;
+    if (n_queries > ((size_t)0x7fffffff) * 256) return CST_ERR_INVALID_ARGUMENT;
+    if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    const RaggedSelect b = ragged_select_batch(d_word_offsets, stride_words, words_capacity, d_n_words, d_sym_offsets, n_streams, jump_interval,
+                                               d_chunk_offsets, n_chunks_total, d_jump_pos, d_query_stream, d_query_first, d_query_count, n_queries,
+                                               d_piece_offsets, n_pieces_total, d_out_offsets);
+    return note_kernel("range_decode_ragged_kernel<select>", range_decode_ragged_select(model, cfg, d_words, b, d_jump_lower, d_jump_range, d_symbols_out,
+                                                                                         d_scratch, d_status, (hipStream_t)stream));
+}
+
 cst_status cst_words_reverse(const uint32_t* d_words_in, const uint64_t* d_offsets_in, size_t stride_in, const uint32_t* d_n_words,
                              size_t n_streams, uint32_t* d_words_out, const uint64_t* d_offsets_out, size_t stride_out, void* stream) {
     if (n_streams == 0) return CST_OK;

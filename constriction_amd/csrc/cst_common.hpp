@@ -242,6 +242,37 @@ cst_status range_decode_ragged_jump(const cst_model* model, cst_coder_config cfg
                                     size_t n_chunks_total, const uint32_t* d_jump_pos, const uint64_t* d_jump_lower,
                                     const uint64_t* d_jump_range, void* d_scratch, int32_t* d_status, hipStream_t hs);
 
+// random access into a ragged batch (cst_ragged_select.hpp; kernels in cst_ans_ragged.hip / cst_range_ragged.hip): selected documents
+// and ranges of documents, arguments checked by the C entry points in cst_api.hip
+// the batch as cst_{ans,range}_decode_ragged[_jump] take it, and the queries
+struct RaggedSelect {
+    const uint64_t* sym_offsets;     // [n_streams + 1]
+    const uint64_t* word_offsets;    // [n_streams] or null (slabs `stride_words` apart)
+    size_t stride_words;
+    uint64_t words_capacity;
+    const uint32_t* n_words;         // [n_streams]
+    size_t n_streams;
+    uint32_t interval;               // 0: no table
+    const uint64_t* chunk_offsets;   // [n_streams + 1]
+    size_t n_chunks_total;
+    const uint32_t* jump_pos;
+    const uint32_t* query_stream;    // [n_queries]
+    const uint64_t* query_first;     // [n_queries], or null with query_count: whole documents
+    const uint64_t* query_count;
+    size_t n_queries;
+    const uint64_t* piece_offsets;   // [n_queries + 1]
+    size_t n_pieces_total;
+    const uint64_t* out_offsets;     // [n_queries + 1]
+};
+
+constexpr size_t kRaggedSelectPieceBytes = 40;         // scratch per piece (RaggedSelectPieces, cst_ragged_select.hpp)
+inline size_t ragged_select_scratch_bytes(size_t n_pieces_total) { return kRaggedSelectPieceBytes * n_pieces_total + 128; }
+cst_status ans_decode_ragged_select(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const RaggedSelect& b,
+                                    const uint64_t* d_jump_state, int32_t* d_symbols, void* d_scratch, int32_t* d_status, hipStream_t hs);
+cst_status range_decode_ragged_select(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const RaggedSelect& b,
+                                      const uint64_t* d_jump_lower, const uint64_t* d_jump_range, int32_t* d_symbols, void* d_scratch,
+                                      int32_t* d_status, hipStream_t hs);
+
 // trimmed-packed-row coder launches (cst_ans_pt.hip); return CST_ERR_INVALID_ARGUMENT if the shape is not theirs
 bool pt_usable(const cst_model* model, cst_coder_config cfg, cst_layout layout, size_t n_per_stream);
 cst_status ans_encode_pt(const cst_model* model, cst_coder_config cfg, const int32_t* d_symbols, size_t n_streams,

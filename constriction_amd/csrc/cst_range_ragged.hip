@@ -19,8 +19,10 @@
 // 458-523, 847-868, 968-1033).
 // Jump points (RangeEncoder::pos / RangeDecoder::seek, queue.rs:172-196, 900-926) are a form of their own of the two coding kernels
 // (JUMP, a compile-time parameter of the shared bodies: the plain kernels keep their registers, LDS, occupancy and timings): see
-// RangeRaggedJump and RangeRaggedChunks below.
+// RangeRaggedJump and RangeRaggedChunks below.  Random access -- selected documents and ranges of documents -- is a third form of the
+// decoder's body (its MODE: kRrPlain, kRrJump, kRrSelect), around it the kernels of cst_ragged_select.hpp.
 #include "cst_range_kernels.hpp"
+#include "cst_ragged_select.hpp"
 
 namespace cst {
 
@@ -268,21 +270,41 @@ struct RangeRaggedDecoder {
         L.in.prime();
         wave_lds_fence();
     }
+    // a piece of a query (SELECT: the lane's `s` is a piece index): seek to its table entry -- or to the start of its document, which is
+    // jump point (0, 0, all ones) -- on its STREAM's slice of the words, the one the piece builder checked, bounded once more here
+    __device__ __forceinline__ void start_piece(const RangeRaggedArgs& a, const RaggedSelectLanes& v, uint32_t* ring) {
+        using st_t = typename StateT<S>::type;
+        ws = active ? word_slice(v.word_off, 0, v.n_words, s, a.words_capacity) : WordSlice{0, 0u, false};
+        const uint32_t e = (active && !ws.bad) ? v.entry[s] : kSelectNoEntry;
+        const bool at = e != kSelectNoEntry;
+        L.init_at(a.words_in + ws.off, ws.n, at ? v.jump_pos[e] : 0u, at ? (st_t)v.jump_a[e] : (st_t)0, at ? (st_t)v.jump_b[e] : (st_t)~(st_t)0, ring, lane);
+        L.in.prime();
+        wave_lds_fence();
+    }
     __device__ __forceinline__ uint32_t step(const RangeRaggedArgs& a) {
         return L.template step<kDecBucket>(lut, cdf, bucket, a.precision - a.bucket_bits, a.n_symbols, a.precision);
     }
 };
 
-// the decoder: JUMP = false is range_decode_ragged_kernel (a lane per stream), JUMP = true the form with a lane per chunk of `v`
-template <int W, int S, bool STAGED, bool JUMP>
-__device__ __forceinline__ void rr_decode(const RangeRaggedArgs& a, const RangeRaggedChunks& v, unsigned char* smem) {
+// the decoder: MODE kRrPlain is range_decode_ragged_kernel (a lane per stream), kRrJump the form with a lane per chunk of `v`, kRrSelect
+// the form with a lane per PIECE of a query (`q`, cst_ragged_select.hpp): a lane decodes `skip` symbols it does not store, then its
+// piece's symbols into its own row of the output.  The skipped symbols go through the same groups of eight (advance_window, eight steps: one
+// memory point per group), only their stores are left out; a wave runs as long as its longest skip + length.
+constexpr int kRrPlain = 0, kRrJump = 1, kRrSelect = 2;
+template <int W, int S, bool STAGED, int MODE>
+__device__ __forceinline__ void rr_decode(const RangeRaggedArgs& a, const RangeRaggedChunks& v, const RaggedSelectLanes& q, unsigned char* smem) {
     constexpr int G = kRrGroup;
+    constexpr bool SELECT = MODE == kRrSelect;
     RangeRaggedDecoder<W, S, STAGED> D;
     D.stage(a, smem);
     if (!D.wave_has_streams(a)) return;
     uint32_t* ring = reinterpret_cast<uint32_t*>(smem) + (threadIdx.x >> 6) * (kRrDecSlots * kWave);
     uint64_t sym_lo = 0, sym_hi = 0;
-    if constexpr (JUMP) {
+    [[maybe_unused]] uint32_t skip = 0;
+    if constexpr (SELECT) {
+        D.start_piece(a, q, ring);
+        if (D.active) { sym_lo = q.out_lo[D.s]; skip = q.skip[D.s]; sym_hi = sym_lo + skip + q.len[D.s]; }
+    } else if constexpr (MODE == kRrJump) {
         D.start_at(a, v, ring);
         if (D.active) { sym_lo = v.sym_lo[D.s]; sym_hi = sym_lo + v.len[D.s]; }
     } else {
@@ -291,23 +313,40 @@ __device__ __forceinline__ void rr_decode(const RangeRaggedArgs& a, const RangeR
     }
     const bool too_long = sym_hi - sym_lo > 0xffffffffull || sym_hi < sym_lo;
     const uint32_t len = too_long ? 0u : (uint32_t)(sym_hi - sym_lo);
+    // (SELECT: `len` counts the symbols the lane DECODES, the first `skip` of which it does not store: skip + the piece's length, at
+    //  most 2^32 - 1 by the piece builder's bound; decoded symbol k >= skip is row[k - skip])
     int32_t* row = a.symbols_out + sym_lo;
     const uint32_t mx = rr_wave_max_u32(len);
     int32_t o[G];
 #pragma unroll
     for (int j = 0; j < G; ++j) o[j] = 0;
-    // symbols k0 - 8 .. k0 - 1 (decoded by the previous group) -> HBM: two 16-byte pieces, or one by one at the end of a row
+    // symbols k0 - 8 .. k0 - 1 (decoded by the previous group) -> HBM: two 16-byte pieces, or one by one at the end of a row.
+    // SELECT: a group wholly in front of `skip` stores nothing; the pieces are 16-byte stores at 4-byte boundaries, so a group wholly
+    // behind it keeps them wherever in a group the first stored symbol fell; the group that holds that symbol goes one by one
     auto store_group = [&](uint32_t k0) {
         if (k0 < (uint32_t)G || k0 - G >= len) return;
         const uint32_t b = k0 - G;
-        if (k0 <= len) {
-            rr_v4i_unaligned* d = reinterpret_cast<rr_v4i_unaligned*>(row + b);
-            d[0].v = rr_v4i{o[0], o[1], o[2], o[3]};
-            d[1].v = rr_v4i{o[4], o[5], o[6], o[7]};
-        } else {
+        if constexpr (SELECT) {
+            if (k0 <= skip) return;
+            if (b >= skip && k0 <= len) {
+                rr_v4i_unaligned* d = reinterpret_cast<rr_v4i_unaligned*>(row + (b - skip));
+                d[0].v = rr_v4i{o[0], o[1], o[2], o[3]};
+                d[1].v = rr_v4i{o[4], o[5], o[6], o[7]};
+            } else {
 #pragma unroll
-            for (int j = 0; j < G; ++j)
-                if (b + (uint32_t)j < len) row[b + (uint32_t)j] = o[j];
+                for (int j = 0; j < G; ++j)
+                    if (b + (uint32_t)j >= skip && b + (uint32_t)j < len) row[b + (uint32_t)j - skip] = o[j];
+            }
+        } else {
+            if (k0 <= len) {
+                rr_v4i_unaligned* d = reinterpret_cast<rr_v4i_unaligned*>(row + b);
+                d[0].v = rr_v4i{o[0], o[1], o[2], o[3]};
+                d[1].v = rr_v4i{o[4], o[5], o[6], o[7]};
+            } else {
+#pragma unroll
+                for (int j = 0; j < G; ++j)
+                    if (b + (uint32_t)j < len) row[b + (uint32_t)j] = o[j];
+            }
         }
     };
     for (uint32_t k0 = 0; k0 < mx; k0 += G) {
@@ -325,13 +364,19 @@ __device__ __forceinline__ void rr_decode(const RangeRaggedArgs& a, const RangeR
 template <int W, int S, bool STAGED>
 __global__ __launch_bounds__(kBlock) void range_decode_ragged_kernel(const RangeRaggedArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    rr_decode<W, S, STAGED, false>(a, RangeRaggedChunks{}, smem);
+    rr_decode<W, S, STAGED, kRrPlain>(a, RangeRaggedChunks{}, RaggedSelectLanes{}, smem);
 }
 
 template <int W, int S, bool STAGED>
 __global__ __launch_bounds__(kBlock) void range_decode_ragged_jump_kernel(const RangeRaggedArgs a, const RangeRaggedChunks v) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    rr_decode<W, S, STAGED, true>(a, v, smem);
+    rr_decode<W, S, STAGED, kRrJump>(a, v, RaggedSelectLanes{}, smem);
+}
+
+template <int W, int S, bool STAGED>
+__global__ __launch_bounds__(kBlock) void range_decode_ragged_select_kernel(const RangeRaggedArgs a, const RaggedSelectLanes q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rr_decode<W, S, STAGED, kRrSelect>(a, RangeRaggedChunks{}, q, smem);
 }
 
 // The reference's index stores no lengths: a document ends where its terminator is decoded, and a queue writes it LAST.  First pass of
@@ -554,6 +599,23 @@ cst_status range_decode_ragged_jump(const cst_model* model, cst_coder_config cfg
                        (uint64_t)words_capacity, d_chunk_offsets, d_jump_pos, d_n_words, n_streams, n_chunks_total, interval, d_status);
     CST_HIP_TRY(hipGetLastError());
     return CST_OK;
+}
+
+// ---- random access: selected documents and ranges (cst_ragged_select.hpp) ----
+static cst_status rr_decode_select_lanes(const cst_model* model, cst_coder_config cfg, const RangeRaggedArgs& a, const RaggedSelectLanes& q, hipStream_t hs) {
+    CST_RANGE_RAGGED_DISPATCH(range_decode_ragged_select_kernel, kRrDecRingBytes, rr_decode_table_bytes(model), q);
+}
+
+cst_status range_decode_ragged_select(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const RaggedSelect& b,
+                                      const uint64_t* d_jump_lower, const uint64_t* d_jump_range, int32_t* d_symbols, void* d_scratch,
+                                      int32_t* d_status, hipStream_t hs) {
+    const RaggedSelectPieces v(d_scratch, b.n_pieces_total);
+    return ragged_select_run<false>(b, v, d_status, hs, [&]() {
+        // (the slices handed on are absolute offsets that passed the check, or empty: `words_capacity` bounds them once more)
+        RangeRaggedArgs a = rr_decode_args(model, d_words, nullptr, 0, b.words_capacity, nullptr, b.n_pieces_total, v.status, nullptr);
+        a.symbols_out = d_symbols;
+        return rr_decode_select_lanes(model, cfg, a, select_lanes(v, b.jump_pos, d_jump_lower, d_jump_range), hs);
+    });
 }
 #undef CST_RANGE_RAGGED_DISPATCH
 

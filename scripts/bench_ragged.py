@@ -5,7 +5,10 @@ model at P = 24 through `batched.ans_{encode,decode}_ragged` (one launch each), 
 `--coder range`: the same workloads through `batched.range_{encode,decode}_ragged` (one RangeEncoder / RangeDecoder per document), with
 `ans_encode_ragged(..., jump_every=0)` / `ans_decode_ragged` on the same documents in the same run beside them.
 `--coder range --jump-every N`: also `range_encode_ragged_jump(..., jump_every=N)` and the decode of its chunks side by side, beside the
-plain pair on the same documents in the same run; every figure is measured twice (the second run shows the spread)."""
+plain pair on the same documents in the same run; every figure is measured twice (the second run shows the spread).
+`--select N [--coder range] --jump-every I`: random access on the first batch (20 .. 2000 symbols, shuffled) with a jump point every I
+symbols (default 256) -- N documents drawn at random through `batched.{ans,range}_decode_ragged_select` beside the full decode of the
+batch followed by a device gather of those documents, and N ranges of 64 symbols at random depths with the table and without."""
 import argparse, sys, time
 from pathlib import Path
 import numpy as np, torch
@@ -17,6 +20,7 @@ from constriction_amd.stream import model as M, stack
 args = argparse.ArgumentParser(description=__doc__)
 args.add_argument("--coder", choices=("ans", "range"), default="ans")
 args.add_argument("--jump-every", type=int, default=0, help="range coder: also time the pair with a jump point every N symbols")
+args.add_argument("--select", type=int, default=0, metavar="N", help="time random access to N documents / N ranges of 64 symbols, then stop")
 opts = args.parse_args()
 coder, jump_every = opts.coder, opts.jump_every
 best = lambda fn: min(bench.event_ms(fn, 5) for _ in range(3))      # best of three event timings of five calls
@@ -27,6 +31,57 @@ single = M.Categorical(probs, perfect=False)
 from oracle import oracle as O      # (the table only: test infrastructure is not timed)
 cdf = O.categorical_fast_cdf(probs, P)
 model = B.Model.from_cdf(cdf, 0, P)
+
+
+def bench_select(n_queries, every):
+    """(a) N whole documents through the select call, (b) what a caller had before it: the full decode of the batch and a device gather
+    of those documents, (c) N ranges of 64 symbols at random depths, (d) the same ranges on the batch encoded without jump points"""
+    lengths = np.exp(rng.uniform(np.log(20), np.log(2000), n_docs)).astype(np.int64)
+    offsets = np.zeros(n_docs + 1, dtype=np.int64); np.cumsum(lengths, out=offsets[1:])
+    flat = torch.from_numpy(rng.choice(n_sym, size=int(offsets[-1]), p=probs).astype(np.int32)).cuda()
+    off_d = torch.from_numpy(offsets).cuda()
+    if coder == "range":
+        with_table, without = B.range_encode_ragged_jump(flat, off_d, model, jump_every=every), B.range_encode_ragged(flat, off_d, model)
+        decode, select = B.range_decode_ragged, B.range_decode_ragged_select
+    else:
+        with_table, without = B.ans_encode_ragged(flat, off_d, model, jump_every=every), B.ans_encode_ragged(flat, off_d, model, jump_every=0)
+        decode, select = B.ans_decode_ragged, B.ans_decode_ragged_select
+    picks = rng.choice(n_docs, size=n_queries, replace=False)
+    streams = torch.from_numpy(picks).cuda()
+    # the gather a caller writes: the flat positions of the picked documents' symbols
+    sizes = off_d[streams + 1] - off_d[streams]
+    starts = torch.zeros(n_queries + 1, dtype=torch.int64, device="cuda"); torch.cumsum(sizes, 0, out=starts[1:])
+    index = torch.arange(int(starts[-1]), device="cuda") + torch.repeat_interleave(off_d[streams] - starts[:-1], sizes)
+    want = flat[index]
+    whole = torch.empty_like(flat)
+
+    def full_then_gather():
+        decode(with_table, model, off_d, out=whole)
+        return whole[index]
+
+    first_h = np.array([rng.integers(0, max(int(lengths[s]) - 64, 0) + 1) for s in picks], dtype=np.int64)
+    count_h = np.minimum(64, lengths[picks] - first_h)
+    first, count = torch.from_numpy(first_h).cuda(), torch.from_numpy(count_h).cuda()
+    want_ranges = torch.cat([flat[offsets[s] + f: offsets[s] + f + c] for s, f, c in zip(picks, first_h, count_h)])
+    got_a, _, st_a = select(with_table, model, off_d, streams)
+    name = B.last_kernel()
+    got_c, _, st_c = select(with_table, model, off_d, streams, first, count)
+    got_d, _, st_d = select(without, model, off_d, streams, first, count)
+    ok = (name.endswith("<select>") and bool(torch.equal(got_a, want)) and bool(torch.equal(full_then_gather(), want)) and bool(torch.equal(got_c, want_ranges))
+          and bool(torch.equal(got_d, want_ranges)) and int(st_a.abs().sum() + st_c.abs().sum() + st_d.abs().sum()) == 0)
+    a = best(lambda: select(with_table, model, off_d, streams, out=got_a))
+    b = best(full_then_gather)
+    c = best(lambda: select(with_table, model, off_d, streams, first, count, out=got_c))
+    d = best(lambda: select(without, model, off_d, streams, first, count, out=got_d))
+    print(f"{coder}: {n_docs} documents of 20 .. 2000 symbols ({int(offsets[-1]) / 1e6:.1f} M symbols), jump point every {every}; {n_queries} queries "
+          f"({int(starts[-1])} symbols as whole documents, {int(count_h.sum())} as ranges of 64, mean depth {first_h.mean():.0f}):  "
+          f"(a) select, whole documents {a:.3f} ms  (b) full decode + gather {b:.3f} ms  (c) select, ranges {c:.3f} ms  "
+          f"(d) the ranges without jump points {d:.3f} ms  |  a / b {a / b:.2f}x  d / c {d / c:.1f}x  ok={ok}", flush=True)
+
+
+if opts.select:
+    bench_select(opts.select, jump_every or 256)
+    sys.exit(0)
 for label, lengths in (("20 .. 2000 symbols, shuffled", np.exp(rng.uniform(np.log(20), np.log(2000), n_docs)).astype(np.int64)),
                        ("the same, sorted by length", None), ("200 symbols each", np.full(n_docs, 200, dtype=np.int64))):
     if lengths is None:
