@@ -947,6 +947,159 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    /// Random access into a ragged per-symbol batch: cst_{ans,range}_decode_ragged_select (below, where queries, pieces, d_out_offsets,
+    /// d_piece_offsets and the per-query statuses are described) for the eight decoders above.  The arguments are the model's (cfg, the
+    /// family, min_symbol, max_symbol), then the words block, d_means / d_stds (d_a / d_b) -- the batch's FULL arrays, laid out exactly as
+    /// the plain decode call takes them -- d_sym_offsets and n_streams, then the table block and the query block of
+    /// cst_{ans,range}_decode_ragged_select with the same conventions: jump_interval 0 and every table pointer NULL is no table; both of
+    /// d_query_first / d_query_count NULL is whole documents; n_queries == 0 returns CST_OK and launches nothing.
+    ///   - A piece reads its parameters from the element of its jump point on: element d_sym_offsets[s] + (first / jump_interval + j) *
+    ///     jump_interval for piece j of a query, d_sym_offsets[s] without a table.  The symbols in front of `first` are decoded with their
+    ///     own parameters and dropped.  ONLY the parameters of elements [that first element, d_sym_offsets[s] + first + count) of a query can
+    ///     influence any result or status: everything else in d_means / d_stds may hold anything (NaN included).
+    ///   - Statuses, one per QUERY: CST_STREAM_INVALID_DATA (nothing is written) for every query cst_{ans,range}_decode_ragged_select refuse.
+    ///     A query whose decoded range, the dropped symbols included, meets an invalid model or an impossible quantile reports
+    ///     CST_STREAM_IMPOSSIBLE_SYMBOL and may leave anything inside its own output slice, nothing outside it; the other queries are
+    ///     unaffected.
+    ///   - d_scratch: cst_persymbol_ragged_select_scratch_bytes(n_pieces_total) bytes (a piece's record also holds where its parameters
+    ///     start and its coder's state at the jump point).
+    ///   - CST_ERR_INVALID_ARGUMENT / CST_ERR_MODEL, before the device is touched: every refusal of the plain decode call (d_symbols_out in
+    ///     the place of d_symbols; d_order does not exist here), a support too large for the precision included; with a table, every refusal
+    ///     of the _jump decoders (jump_interval not a multiple of 16 or > 2^31 - 1, a NULL d_chunk_offsets or table array, n_chunks_total >
+    ///     2^32 - 1); table arrays without an interval; n_pieces_total > 2^32 - 1; exactly one of d_query_first / d_query_count NULL; with
+    ///     n_queries > 0 a NULL d_query_stream, d_piece_offsets, d_out_offsets or d_scratch; an unknown family.
+    /// cst_last_kernel_name(): {ans,range}_decode_{gaussian,laplace,cauchy}_ragged_kernel<select>.  (The Categorical ragged decoders have no
+    /// select form.)
+    pub fn cst_persymbol_ragged_select_scratch_bytes(n_pieces_total: usize) -> usize;
+
+    pub fn cst_ans_decode_gaussian_ragged_select(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_means: *const f64,
+        d_stds: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_gaussian_ragged_select(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_means: *const f64,
+        d_stds: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_family_ragged_select(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const f64,
+        d_b: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_family_ragged_select(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const f64,
+        d_b: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// The range coder with ONE SHARED TABLE for streams of different lengths: cst_ans_{encode,decode}_ragged / cst_ans_count_until for the
     /// reference's queue -- one RangeEncoder / RangeDecoder per document (src/stream/queue.rs), the symbols decoded in the order they were
     /// encoded, so that a terminator is simply written last.  Symbols, slabs, d_word_offsets / stride_words / words_capacity / d_n_words
@@ -1116,8 +1269,9 @@ extern "C" {
     ///     arrays, arrays without an interval); n_chunks_total or n_pieces_total > 2^32 - 1; exactly one of d_query_first / d_query_count
     ///     NULL; with n_queries > 0 a NULL d_query_stream, d_piece_offsets, d_out_offsets, d_scratch or d_status.  n_queries == 0: CST_OK,
     ///     nothing is launched.
-    /// cst_last_kernel_name: "ans_decode_ragged_kernel<select>" / "range_decode_ragged_kernel<select>".  Shared-table models only: the
-    /// per-symbol ragged coders index their parameters by symbol position and have no select form yet.
+    /// cst_last_kernel_name: "ans_decode_ragged_kernel<select>" / "range_decode_ragged_kernel<select>".  Shared-table models; the
+    /// per-symbol ragged coders (Gaussian, Laplace, Cauchy) have cst_{ans,range}_decode_{gaussian,family}_ragged_select, where a piece also
+    /// carries the position its parameters start at.
     pub fn cst_ragged_select_scratch_bytes(n_pieces_total: usize) -> usize;
 
     pub fn cst_range_ragged_select_scratch_bytes(n_pieces_total: usize) -> usize;

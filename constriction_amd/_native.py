@@ -156,6 +156,15 @@ SIGNATURES = {
     "cst_ans_decode_family_ragged_jump": (_i32, [CoderConfig, _i32, _i32, _i32, _vp, _vp, _z, _z, _vp, _vp, _vp, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
     "cst_range_encode_family_ragged_jump": (_i32, [CoderConfig, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _z, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cst_range_decode_family_ragged_jump": (_i32, [CoderConfig, _i32, _i32, _i32, _vp, _vp, _z, _z, _vp, _vp, _vp, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cst_persymbol_ragged_select_scratch_bytes": (_z, [_z]),
+    "cst_ans_decode_gaussian_ragged_select": (_i32, [CoderConfig, _i32, _i32, _vp, _vp, _z, _z, _vp, _vp, _vp, _vp, _z, _z, _vp,
+                                                      _z, _vp, _vp, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_range_decode_gaussian_ragged_select": (_i32, [CoderConfig, _i32, _i32, _vp, _vp, _z, _z, _vp, _vp, _vp, _vp, _z, _z, _vp,
+                                                        _z, _vp, _vp, _vp, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_ans_decode_family_ragged_select": (_i32, [CoderConfig, _i32, _i32, _i32, _vp, _vp, _z, _z, _vp, _vp, _vp, _vp, _z, _z,
+                                                    _vp, _z, _vp, _vp, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_range_decode_family_ragged_select": (_i32, [CoderConfig, _i32, _i32, _i32, _vp, _vp, _z, _z, _vp, _vp, _vp, _vp, _z, _z, _vp,
+                                                      _z, _vp, _vp, _vp, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
     "cst_range_encode_ragged": (_i32, [_vp, CoderConfig, _vp, _vp, _z, _vp, _vp, _vp, _z, _vp, _vp, _vp]),
     "cst_range_decode_ragged": (_i32, [_vp, CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _vp, _z, _vp, _vp, _vp]),
     "cst_range_count_until": (_i32, [_vp, CoderConfig, _vp, _vp, _z, _z, _vp, _z, _vp, _i32, _z, _vp, _vp, _vp]),

@@ -900,16 +900,21 @@ def _select_piece_counts(first: torch.Tensor, count: torch.Tensor, interval: int
     return torch.where(count > 0, (first % interval + count + (interval - 1)) // interval, torch.zeros_like(count))
 
 
-def _decode_ragged_select(coder, jump_type, encoded, model, sym_offsets, streams, first, count, out):
-    """the body of ans_decode_ragged_select and range_decode_ragged_select"""
-    _require_coder(encoded, coder)
+class _SelectQueries:
+    """what _select_queries prepares for a select call: the queries as the entry points take them, and the output"""
+    __slots__ = ("sym_offsets", "n_streams", "n_queries", "whole", "query_stream", "first", "count", "interval", "out_offsets", "piece_offsets",
+                 "total", "n_pieces", "out", "status")
+
+
+def _select_queries(encoded, jump, sym_offsets, streams, first, count, out) -> _SelectQueries:
+    """The query preparation of every select call (shared-table and per-symbol models alike), once the batch's coder and the type of its
+    jump table are judged: the queries as tensors, their sizes and pieces, the two prefix sums, the single read-back (the output
+    total), an upper bound of the pieces, the output and the statuses.  `jump`: the batch's table or None."""
+    r = _SelectQueries()
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
     n_streams = sym_offsets.numel() - 1
     if sym_offsets.dim() != 1 or encoded.n_words.numel() != n_streams:
         raise ValueError("sym_offsets does not match the number of streams of the batch")
-    jump = encoded.jump
-    if jump is not None and not isinstance(jump, jump_type):
-        raise ValueError("the batch carries the jump points of another coder")
     dev = encoded.words.device
     streams = torch.as_tensor(streams, device=dev)
     if streams.dtype.is_floating_point or streams.dtype.is_complex or streams.dtype == torch.bool or streams.dim() != 1:
@@ -949,14 +954,34 @@ def _decode_ragged_select(coder, jump_type, encoded, model, sym_offsets, streams
         out = _require_cuda(out, torch.int32, "out")
         if out.dim() != 1 or out.numel() < total:
             raise ValueError("out must be flat and hold every query's symbols")
-    status = torch.empty(n_queries, dtype=torch.int32, device=dev)
-    if n_queries == 0:
+    r.sym_offsets, r.n_streams, r.n_queries, r.whole, r.query_stream, r.first, r.count = sym_offsets, n_streams, n_queries, whole, query_stream, first, count
+    r.interval, r.out_offsets, r.piece_offsets, r.total, r.n_pieces, r.out = interval, out_offsets, piece_offsets, total, n_pieces, out
+    r.status = torch.empty(n_queries, dtype=torch.int32, device=dev)
+    return r
+
+
+def _select_tail(r: _SelectQueries):
+    """the query block and the output of a select entry point, up to d_out_offsets"""
+    return (_ptr(r.query_stream), None if r.whole else _ptr(r.first), None if r.whole else _ptr(r.count), r.n_queries, _ptr(r.piece_offsets),
+            r.n_pieces, _ptr(r.out), _ptr(r.out_offsets))
+
+
+def _decode_ragged_select(coder, jump_type, encoded, model, sym_offsets, streams, first, count, out):
+    """the body of ans_decode_ragged_select and range_decode_ragged_select"""
+    _require_coder(encoded, coder)
+    jump = encoded.jump
+    if jump is not None and not isinstance(jump, jump_type):
+        raise ValueError("the batch carries the jump points of another coder")
+    r = _select_queries(encoded, jump, sym_offsets, streams, first, count, out)
+    sym_offsets, n_streams, interval, n_pieces, out, out_offsets, status, total = (r.sym_offsets, r.n_streams, r.interval, r.n_pieces, r.out,
+                                                                                   r.out_offsets, r.status, r.total)
+    dev = encoded.words.device
+    if r.n_queries == 0:
         return out[:0], out_offsets, status
     L = N.lib()
     head = (model._h, _cfg(*encoded.config), _ptr(encoded.words), _ptr(encoded.word_offsets), 0, encoded.words.numel(), _ptr(encoded.n_words),
             _ptr(sym_offsets), n_streams)
-    tail = (_ptr(query_stream), None if whole else _ptr(first), None if whole else _ptr(count), n_queries, _ptr(piece_offsets), n_pieces,
-            _ptr(out), _ptr(out_offsets))
+    tail = _select_tail(r)
     if coder == "ans":
         table = (interval, _ptr(jump.chunk_offsets), min(int(jump.pos.numel()), int(jump.state.numel())), _ptr(jump.pos),
                  _ptr(jump.state)) if interval else (0, None, 0, None, None)
@@ -1688,6 +1713,73 @@ ans_encode_laplace_ragged, ans_encode_cauchy_ragged = (_named_family(ans_encode_
 ans_decode_laplace_ragged, ans_decode_cauchy_ragged = (_named_family(ans_decode_family_ragged, f) for f in ("laplace", "cauchy"))
 range_encode_laplace_ragged, range_encode_cauchy_ragged = (_named_family(range_encode_family_ragged, f) for f in ("laplace", "cauchy"))
 range_decode_laplace_ragged, range_decode_cauchy_ragged = (_named_family(range_decode_family_ragged, f) for f in ("laplace", "cauchy"))
+
+
+# ... and random access into them: selected streams, or ranges of streams (ans_decode_ragged_select for models that differ per symbol)
+
+def _decode_persymbol_ragged_select(fn_name, coder, encoded: RaggedBatch, sym_offsets, lo, hi, a, b, streams, first, count, out, family=()):
+    """the body of every {ans,range}_decode_{gaussian,family}_ragged_select: the queries of _select_queries on the arguments of
+    _decode_persymbol_ragged"""
+    jump = _ragged_jump_of(encoded, coder)
+    sym_offsets, _, a, b = _gaussian_ragged_args(sym_offsets, None, a, b)
+    r = _select_queries(encoded, jump, sym_offsets, streams, first, count, out)
+    if r.n_queries == 0:
+        return r.out[:0], r.out_offsets, r.status
+    L = N.lib()
+    if r.interval:
+        arrays = (jump.pos, jump.state) if coder == "ans" else (jump.pos, jump.lower, jump.range)
+        table = (r.interval, _ptr(jump.chunk_offsets), min(int(t.numel()) for t in arrays), *(_ptr(t) for t in arrays))
+    else:
+        table = (0, None, 0, None, None) if coder == "ans" else (0, None, 0, None, None, None)
+    # (r.out stands in where it is empty: the entry points refuse NULL and write nothing)
+    head = (*_select_tail(r)[:6], _ptr(_never_null(r.out)), _ptr(r.out_offsets))
+    scratch = _ckpt_scratch("persymbol_ragged_select", encoded.words.device, L.cst_persymbol_ragged_select_scratch_bytes(r.n_pieces))
+    N.check(getattr(L, fn_name)(_cfg(*encoded.config), *family, int(lo), int(hi), _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
+                                encoded.words.numel(), _ptr(encoded.n_words), _ptr(_never_null(a)), _ptr(_never_null(b)), _ptr(r.sym_offsets),
+                                r.n_streams, *table, *head, _ptr(scratch), _ptr(r.status), _stream_ptr()), fn_name)
+    return r.out[:r.total], r.out_offsets, r.status
+
+
+def ans_decode_gaussian_ragged_select(encoded: RaggedBatch, sym_offsets, min_symbol, max_symbol, means, stds, streams, first=None, count=None,
+                                      out: Optional[torch.Tensor] = None):
+    """Random access into a batch of ans_encode_gaussian_ragged: query q decodes symbols [first[q], first[q] + count[q]) of stream
+    streams[q], and nothing else is decoded.  `means` / `stds`: the batch's full arrays, exactly as ans_decode_gaussian_ragged takes
+    them; `streams`, `first`, `count` and the three results (symbols flat int32, out_offsets int64 [n_queries + 1], status int32
+    [n_queries]) as in ans_decode_ragged_select.  With jump points (`jump_every` of the encoder) a query starts at the jump point in
+    front of `first`, decodes and discards first % interval symbols with THEIR parameters, and every chunk it touches runs on a lane of
+    its own; without them it starts where its stream starts.  Only the parameters from that starting point to the query's end can
+    influence anything: the rest of `means` / `stds` may hold anything.  A query that meets an invalid model or an impossible quantile,
+    in its discarded part too, reports IMPOSSIBLE_SYMBOL (1); a refused one INVALID_DATA (3) and writes nothing.  The same holds for
+    all eight {ans,range}_decode_{gaussian,laplace,cauchy,family}_ragged_select."""
+    return _decode_persymbol_ragged_select("cst_ans_decode_gaussian_ragged_select", "ans", encoded, sym_offsets, min_symbol, max_symbol, means, stds,
+                                           streams, first, count, out)
+
+
+def range_decode_gaussian_ragged_select(encoded: RaggedBatch, sym_offsets, min_symbol, max_symbol, means, stds, streams, first=None, count=None,
+                                        out: Optional[torch.Tensor] = None):
+    """ans_decode_gaussian_ragged_select for a batch of range_encode_gaussian_ragged: a piece seeks to its (pos, lower, range) entry
+    and reads forward."""
+    return _decode_persymbol_ragged_select("cst_range_decode_gaussian_ragged_select", "range", encoded, sym_offsets, min_symbol, max_symbol, means,
+                                           stds, streams, first, count, out)
+
+
+def ans_decode_family_ragged_select(family, encoded: RaggedBatch, sym_offsets, lo, hi, a, b, streams, first=None, count=None,
+                                    out: Optional[torch.Tensor] = None):
+    """ans_decode_gaussian_ragged_select over Family(lo, hi) with a[s], b[s] (see ans_decode_family_ragged)."""
+    return _decode_persymbol_ragged_select("cst_ans_decode_family_ragged_select", "ans", encoded, sym_offsets, lo, hi, a, b, streams, first, count, out,
+                                           (_family_id(family),))
+
+
+def range_decode_family_ragged_select(family, encoded: RaggedBatch, sym_offsets, lo, hi, a, b, streams, first=None, count=None,
+                                      out: Optional[torch.Tensor] = None):
+    """range_decode_gaussian_ragged_select over Family(lo, hi) with a[s], b[s] (see range_decode_family_ragged)."""
+    return _decode_persymbol_ragged_select("cst_range_decode_family_ragged_select", "range", encoded, sym_offsets, lo, hi, a, b, streams, first, count,
+                                           out, (_family_id(family),))
+
+
+ans_decode_laplace_ragged_select, ans_decode_cauchy_ragged_select = (_named_family(ans_decode_family_ragged_select, f) for f in ("laplace", "cauchy"))
+range_decode_laplace_ragged_select, range_decode_cauchy_ragged_select = (_named_family(range_decode_family_ragged_select, f)
+                                                                         for f in ("laplace", "cauchy"))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -340,6 +340,7 @@ template <class FAM> struct FamilyNames;
                                                      {"range_encode_" word "_ragged_kernel", "range_decode_" word "_ragged_kernel"}};     \
         static constexpr const char* ragged_jump[2][2] = {{"ans_encode_" word "_ragged_kernel<jump>", "ans_decode_" word "_ragged_kernel<jump>"},      \
                                                           {"range_encode_" word "_ragged_kernel<jump>", "range_decode_" word "_ragged_kernel<jump>"}}; \
+        static constexpr const char* ragged_select[2] = {"ans_decode_" word "_ragged_kernel<select>", "range_decode_" word "_ragged_kernel<select>"}; \
     }
 CST_FAMILY_NAMES(GaussianFamily, "gaussian");
 CST_FAMILY_NAMES(LaplaceFamily, "laplace");

@@ -1,5 +1,6 @@
 // cst_persymbol_ragged.hpp -- the kernels of the per-symbol coders for streams of DIFFERENT lengths, shared by the two files that
-// instantiate them: cst_persymbol_ragged.hip (the plain forms, JUMP = false) and cst_persymbol_ragged_jump.hip (JUMP = true).  Every
+// instantiate them: cst_persymbol_ragged.hip (the plain forms), cst_persymbol_ragged_jump.hip (the JUMP forms) and
+// cst_persymbol_ragged_select.hip (the decoder's SELECT form).  Every
 // instantiation of these still lives in ONE file (cst_persymbol.hpp): the template parameter decides which.  At the end: the
 // model-independent kernels around a jump table and the host routine that launches them around a caller's chunk decoder
 // (decode_jump_chunks), for cst_persymbol_categorical_ragged.hip too.
@@ -263,18 +264,45 @@ struct GaussianRaggedChunkArgs {
     const uint32_t* len;             // [n chunks]: symbols, <= jump_interval
 };
 
-// which stream (plain) or table entry (JUMP) a lane slot decodes, and where its symbols begin and end: the plain form's expressions are
-// the ones the kernel held before it had a JUMP form
-template <bool JUMP, class Args>
+// SELECT form (cst_persymbol_ragged_select.hip): every "stream" of the launch is a PIECE of a query (cst_ragged_select.hpp's
+// cut).  The two roles of the other forms' one number come apart: a piece reads its parameters from element par_lo on -- the element of its
+// jump point, or of its document's start without a table -- for skip + len symbols, and stores decoded symbol t >= skip at
+// p.symbols[out_lo + (t - skip)].  `raw`: the pieces start from the raw state of a jump point (p.state / p.rstate per piece), else from
+// all of their stream's words as the plain form does.
+struct GaussianRaggedSelectArgs {
+    PerSymbolDecodeArgs p;
+    const uint64_t* par_lo;          // [n pieces]: first element of means / stds
+    const uint64_t* out_lo;          // [n pieces]: first symbol stored, in p.symbols
+    const uint32_t* skip;            // [n pieces]: symbols decoded and dropped
+    const uint32_t* len;             // [n pieces]: symbols stored (skip + len <= 2^32 - 1)
+    bool raw;
+};
+
+// the forms of decode_gaussian_ragged_kernel
+constexpr int kRgPlain = 0, kRgJump = 1, kRgSelect = 2;
+template <int MODE>
+using GaussianRaggedDecodeArgsOf =
+    std::conditional_t<MODE == kRgSelect, GaussianRaggedSelectArgs, std::conditional_t<MODE == kRgJump, GaussianRaggedChunkArgs, GaussianRaggedDecodeArgs>>;
+
+// which stream (plain), table entry (JUMP) or piece (SELECT) a lane slot decodes, where its parameters begin and end, and how its coder
+// starts: the plain form's expressions are the ones the kernel held before it had other forms
+template <int MODE, class Args>
 __device__ __forceinline__ size_t ragged_lane_stream(const Args& ra, size_t slot, size_t n_streams, bool& active) {
-    if constexpr (JUMP) { active = slot < n_streams; return slot; }
+    if constexpr (MODE != kRgPlain) { active = slot < n_streams; return slot; }
     else return persymbol_ragged_stream(ra.order, slot, n_streams, active);
 }
-template <bool JUMP, class Args> __device__ __forceinline__ uint64_t ragged_lane_begin(const Args& ra, size_t s) {
-    if constexpr (JUMP) return ra.sym_lo[s]; else return ra.sym_offsets[s];
+template <int MODE, class Args> __device__ __forceinline__ uint64_t ragged_lane_begin(const Args& ra, size_t s) {
+    if constexpr (MODE == kRgSelect) return ra.par_lo[s];
+    else if constexpr (MODE == kRgJump) return ra.sym_lo[s];
+    else return ra.sym_offsets[s];
 }
-template <bool JUMP, class Args> __device__ __forceinline__ uint64_t ragged_lane_end(const Args& ra, size_t s) {
-    if constexpr (JUMP) return ra.sym_lo[s] + (uint64_t)ra.len[s]; else return ra.sym_offsets[s + 1];
+template <int MODE, class Args> __device__ __forceinline__ uint64_t ragged_lane_end(const Args& ra, size_t s) {
+    if constexpr (MODE == kRgSelect) return ra.par_lo[s] + (uint64_t)ra.skip[s] + (uint64_t)ra.len[s];
+    else if constexpr (MODE == kRgJump) return ra.sym_lo[s] + (uint64_t)ra.len[s];
+    else return ra.sym_offsets[s + 1];
+}
+template <int MODE, class Args> __device__ __forceinline__ bool ragged_lane_raw(const Args& ra) {
+    if constexpr (MODE == kRgSelect) return ra.raw; else return MODE == kRgJump;
 }
 
 typedef struct __attribute__((packed, aligned(4))) { v4i v; } v4i_at4;      // a 16-byte access at a 4-byte boundary
@@ -314,12 +342,39 @@ static __device__ __noinline__ void store_symbol_tile_ragged(int32_t* sym, uint3
     }
 }
 
+// ... for the SELECT form: row r stores its decoded symbols [skip, n) at out + (t - skip), and nothing outside [out, out + n - skip).  A
+// piece of four that lies wholly inside [skip, n) keeps the 16-byte store; the piece that holds the first stored symbol or the row's end
+// goes word by word (a piece may hold both: a range of one or two symbols); a piece in front of `skip` or behind `n` stores nothing.
+static __device__ __noinline__ void store_symbol_tile_select(int32_t* sym, uint32_t out_lo, uint32_t out_hi, uint32_t skip, uint32_t len, uint64_t t0,
+                                                             int lane, const int32_t* tile) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int r = (lane >> 2) + 16 * k;
+        const uint64_t out = ((uint64_t)(uint32_t)__shfl((int)out_hi, r) << 32) | (uint64_t)(uint32_t)__shfl((int)out_lo, r);
+        const uint64_t n = (uint64_t)(uint32_t)__shfl((int)len, r), sk = (uint64_t)(uint32_t)__shfl((int)skip, r);
+        const uint64_t tp = t0 + 4u * (uint32_t)(lane & 3);
+        if (tp >= n || tp + 4 <= sk) continue;
+        const int32_t* src = tile + r * 20 + 4 * (lane & 3);
+        if (tp >= sk && tp + 4 <= n) {
+            const int4 v = *reinterpret_cast<const int4*>(src);
+            v4i t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
+            reinterpret_cast<v4i_at4*>(sym + out + (tp - sk))->v = t;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (tp + (uint64_t)i >= sk && tp + (uint64_t)i < n) sym[out + (tp + (uint64_t)i - sk)] = src[i];
+        }
+    }
+}
+
 // decode_gaussian_lane_kernel<W, S, KIND> for ragged rows: one lane per stream, parameters one tile ahead in the item mapping
 // that puts consecutive lanes on consecutive addresses, the word window, FAM::left3 and the bracket search as they are.  The
 // loop runs to the wave's longest stream; a lane past its own length decodes and stores nothing but goes on taking part in the
 // wave-wide loads and fences.
-template <int W, int S, int KIND, class FAM = GaussianFamily, bool JUMP = false>
-__global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(const std::conditional_t<JUMP, GaussianRaggedChunkArgs, GaussianRaggedDecodeArgs> ra) {
+// MODE: kRgPlain, kRgJump (a lane per table entry) or kRgSelect (a lane per piece of a query: `len` below is skip + len of the piece,
+// `sym_lo` where its PARAMETERS begin; the symbols in front of `skip` run through the same loop and only their stores are left out).
+template <int W, int S, int KIND, class FAM = GaussianFamily, int MODE = kRgPlain>
+__global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(const GaussianRaggedDecodeArgsOf<MODE> ra) {
     static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
     using G = LaneGeo<true>;
     constexpr int kParTile = G::kParTile, kWordWindow = G::kWordWindow, kOutSyms = G::kOutSyms, kOutStride = G::kOutStride;
@@ -340,12 +395,18 @@ __global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(c
     const size_t slot = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (slot - lane >= a.n_streams) return;
     bool active;
-    const size_t s = ragged_lane_stream<JUMP>(ra, slot, a.n_streams, active);
+    const size_t s = ragged_lane_stream<MODE>(ra, slot, a.n_streams, active);
     const size_t se = active ? s : 0;                         // idle lanes look at stream 0's words and decode nothing
-    const uint64_t sym_lo = active ? ragged_lane_begin<JUMP>(ra, s) : 0, sym_hi = active ? ragged_lane_end<JUMP>(ra, s) : 0;
+    const uint64_t sym_lo = active ? ragged_lane_begin<MODE>(ra, s) : 0, sym_hi = active ? ragged_lane_end<MODE>(ra, s) : 0;
     const bool too_long = sym_hi - sym_lo > 0xffffffffull || sym_hi < sym_lo;      // (never a chunk: at most jump_interval symbols)
     const uint32_t len = too_long ? 0u : (uint32_t)(sym_hi - sym_lo);
     const uint32_t off_lo = (uint32_t)sym_lo, off_hi = (uint32_t)(sym_lo >> 32);
+    // SELECT: where the lane's symbols go, and how many of the decoded ones stay out
+    uint32_t out_lo = 0, out_hi = 0, skip = 0;
+    if constexpr (MODE == kRgSelect) {
+        const uint64_t o = active ? ra.out_lo[s] : 0;
+        out_lo = (uint32_t)o; out_hi = (uint32_t)(o >> 32); skip = active ? ra.skip[s] : 0u;
+    }
     const uint64_t mx = persymbol_wave_max(len);
     const int P = a.precision;
     const uint32_t n = (uint32_t)a.n_symbols;
@@ -355,7 +416,7 @@ __global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(c
     const bool two_step_guess = (double)n * 64.0 > free_weight;      // the leak moves the guess by more than 1/64 quantile
 
     DirectDecoder<W, S, KIND> D;
-    D.init(a, se, JUMP);                                      // (JUMP: AnsCoder::seek / RangeDecoder::seek have been done for it)
+    D.init(a, se, ragged_lane_raw<MODE>(ra));                 // (JUMP: AnsCoder::seek / RangeDecoder::seek have been done for it)
     int32_t status = D.status;
 
     // ---- parameter tiles: item w = it * 64 + lane of a tile is (stream j = w / 8, symbol tl = w % 8): eight consecutive lanes
@@ -500,14 +561,16 @@ __global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(c
             tile[lane * kOutStride + (int)(t % kOutSyms)] = sym;
             if (t % kOutSyms == kOutSyms - 1) {
                 wave_lds_fence();
-                store_symbol_tile_ragged(a.symbols, off_lo, off_hi, len, t - (kOutSyms - 1), lane, tile);
+                if constexpr (MODE == kRgSelect) store_symbol_tile_select(a.symbols, out_lo, out_hi, skip, len, t - (kOutSyms - 1), lane, tile);
+                else store_symbol_tile_ragged(a.symbols, off_lo, off_hi, len, t - (kOutSyms - 1), lane, tile);
                 wave_lds_fence();
             }
         }
     }
     if (mx % kOutSyms != 0) {
         wave_lds_fence();
-        store_symbol_tile_ragged(a.symbols, off_lo, off_hi, len, mx - mx % kOutSyms, lane, tile);
+        if constexpr (MODE == kRgSelect) store_symbol_tile_select(a.symbols, out_lo, out_hi, skip, len, mx - mx % kOutSyms, lane, tile);
+        else store_symbol_tile_ragged(a.symbols, off_lo, off_hi, len, mx - mx % kOutSyms, lane, tile);
     }
     if (!active) return;
     a.status[s] = too_long ? (int32_t)CST_STREAM_CAPACITY : status;

@@ -50,7 +50,7 @@ static cst_status decode_ragged_jump(cst_coder_config cfg, int32_t min_symbol, i
         const size_t blocks = (p.n_streams + kRgDecThreads - 1) / kRgDecThreads;
         const size_t lds = FAM::kErfTab ? kRgDecLdsBytes : kRgDecLdsBytesNoTab;
         return dispatch_word_size(cfg, [&](auto W, auto S) {
-            return launch_with_lds(decode_gaussian_ragged_kernel<W, S, KIND, FAM, true>, blocks, kRgDecThreads, lds, a, hs);
+            return launch_with_lds(decode_gaussian_ragged_kernel<W, S, KIND, FAM, kRgJump>, blocks, kRgDecThreads, lds, a, hs);
         });
     });
 }

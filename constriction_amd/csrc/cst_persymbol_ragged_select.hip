@@ -1,0 +1,222 @@
+// cst_persymbol_ragged_select.hip -- random access into the ragged per-symbol batches of cst_persymbol_ragged.hip: the
+// SELECT form of decode_gaussian_ragged_kernel, one lane per PIECE of a query (cst_ragged_select.hpp's cut), between that header's
+// queries and status kernels and a piece builder of its own, and the four entry points.  A piece of a per-symbol batch needs what a
+// piece of a shared-table batch does not: the element its PARAMETERS start at (the jump point's, not the first stored symbol's), and
+// the coder's raw state there, prepared as persymbol_jump_chunks_kernel prepares a chunk's.  A unit of its own: twelve more
+// instantiations of the decoding kernel belong on no other unit's compile time.
+#include "cst_persymbol_ragged.hpp"
+#include "cst_ragged_select.hpp"
+
+namespace cst {
+
+// the scratch of a call: one record per piece (structure of arrays), 92 bytes; cst_persymbol_ragged_select_scratch_bytes rounds up
+constexpr size_t kPsSelectPieceBytes = 96;
+struct PerSymbolSelectPieces {
+    cst_range_state* rstate;                          // the range coder at the jump point (with a table)
+    uint64_t *par_lo, *out_lo, *word_off, *state;     // first parameter element; first stored symbol; the stream's words; ANS: the state
+    uint32_t *skip, *len, *n_words, *owner;           // as RaggedSelectPieces
+    int32_t* status;                                  // written by the decoding kernel
+    PerSymbolSelectPieces(void* d_scratch, size_t n) {
+        unsigned char* b = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(d_scratch) + 15) & ~(uintptr_t)15);
+        rstate = reinterpret_cast<cst_range_state*>(b);
+        par_lo = reinterpret_cast<uint64_t*>(rstate + n); out_lo = par_lo + n; word_off = out_lo + n; state = word_off + n;
+        skip = reinterpret_cast<uint32_t*>(state + n); len = skip + n; n_words = len + n; owner = n_words + n;
+        status = reinterpret_cast<int32_t*>(owner + n);
+    }
+    // what ragged_select_status_kernel reads of a piece: its owner and its status
+    RaggedSelectPieces folded() const {
+        RaggedSelectPieces r(nullptr, 0);
+        r.owner = owner; r.status = status;
+        return r;
+    }
+};
+static_assert(sizeof(cst_range_state) + 4 * 8 + 5 * 4 <= kPsSelectPieceBytes, "a piece record");
+
+// ragged_select_pieces_kernel for the per-symbol decoders: the same cut, and per piece also where its parameters start and the coder's
+// raw state at its jump point --
+//   ANS:    the first min(jump_pos[entry], n_words[s]) words of the stream and jump_a[entry] (AnsCoder::seek);
+//   range:  lower / range from the table, the point re-read at the jump point clamped to the stream's words (RangeDecoder::seek), all
+//           of the stream's words to read on in: persymbol_jump_chunks_kernel's lines.
+// Without a table a piece is all of its stream's words from the document's first element; its coder starts as the plain decoder's.
+template <int W, int S, int KIND>
+__global__ void persymbol_select_pieces_kernel(const RaggedSelect b, const uint32_t* __restrict__ words, const uint64_t* __restrict__ jump_a,
+                                               const uint64_t* __restrict__ jump_b, const int32_t* __restrict__ query_status,
+                                               PerSymbolSelectPieces v) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= b.n_pieces_total) return;
+    size_t q = 0, hi = b.n_queries;          // the last query with piece_offsets[q] <= p
+    while (hi - q > 1) {
+        const size_t mid = q + (hi - q) / 2;
+        if (b.piece_offsets[mid] <= p) q = mid; else hi = mid;
+    }
+    const uint64_t p0 = b.piece_offsets[q], p1 = b.piece_offsets[q + 1];
+    bool mine = query_status[q] == CST_STREAM_OK && p >= p0 && p < p1;
+    uint64_t par_lo = 0, out_lo = 0, state = 0;
+    WordSlice ws{0, 0u, false};
+    uint32_t skip = 0, len = 0, n_words = 0;
+    cst_range_state r{};
+    if (mine) {
+        const SelectQuery sq = select_query(b, q);         // (passed once already: status OK, p1 - p0 == n_pieces)
+        const uint64_t j = p - p0;
+        ws = word_slice(b.word_offsets, b.stride_words, b.n_words, sq.s, b.words_capacity);
+        mine = sq.status == CST_STREAM_OK && j < sq.n_pieces && !ws.bad;
+        if (!mine) ws = WordSlice{0, 0u, false};
+        else if (b.interval == 0) {
+            skip = (uint32_t)sq.first; len = (uint32_t)sq.count;        // (first + count <= the document's length <= 2^32 - 1)
+            par_lo = b.sym_offsets[sq.s]; out_lo = b.out_offsets[q]; n_words = ws.n;
+        } else {
+            const uint64_t chunk = sq.first / b.interval + j;
+            const uint64_t start = j == 0 ? sq.first : chunk * b.interval;
+            const uint64_t stop = min((chunk + 1) * (uint64_t)b.interval, sq.first + sq.count);
+            skip = j == 0 ? (uint32_t)(sq.first % b.interval) : 0u;
+            len = (uint32_t)(stop - start);
+            par_lo = b.sym_offsets[sq.s] + chunk * b.interval;
+            out_lo = b.out_offsets[q] + (start - sq.first);
+            const uint64_t entry = b.chunk_offsets[sq.s] + chunk;         // (< n_chunks_total: the queries kernel has looked)
+            const uint32_t jp = b.jump_pos[entry];
+            if constexpr (KIND == kAns) {
+                n_words = min(jp, ws.n);
+                state = jump_a[entry];
+            } else {
+                uint32_t pos = min(jp, ws.n);
+                uint64_t pt = 0;
+                int num_read = 0;
+                const uint64_t mask = S == 64 ? ~0ull : ((1ull << (S % 64)) - 1ull);
+                while (pos < ws.n) {                                      // read_point, queue.rs:847-868
+                    pt = ((pt << (W % 64)) | (uint64_t)words[ws.off + pos++]) & mask;
+                    if (++num_read == S / W) break;
+                }
+                if (num_read < S / W && num_read != 0) pt = (pt << (S - num_read * W)) & mask;
+                r.lower = jump_a[entry] & mask; r.range = jump_b[entry] & mask; r.point = pt; r.position = pos;
+                n_words = ws.n;
+            }
+        }
+    }
+    v.par_lo[p] = par_lo; v.out_lo[p] = out_lo; v.word_off[p] = ws.off; v.state[p] = state; v.rstate[p] = r;
+    v.skip[p] = skip; v.len[p] = len; v.n_words[p] = n_words;
+    v.owner[p] = mine ? (uint32_t)q : kSelectNoEntry;
+}
+
+template <int KIND, class FAM>
+static cst_status decode_ragged_select(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                       const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                       const double* d_a, const double* d_b, const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                       const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint32_t* d_jump_pos, const uint64_t* d_jump_a,
+                                       const uint64_t* d_jump_b, const uint32_t* d_query_stream, const uint64_t* d_query_first,
+                                       const uint64_t* d_query_count, size_t n_queries, const uint64_t* d_piece_offsets, size_t n_pieces_total,
+                                       int32_t* d_symbols_out, const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, hipStream_t hs) {
+    // a table is an interval and ALL its arrays (jump_table_bad: the jump decoders' rule, whole tiles of 16 included), or nothing at all
+    const bool table = jump_interval != 0 || d_chunk_offsets || d_jump_pos || d_jump_a || d_jump_b;
+    if (table && (jump_table_bad<KIND>(jump_interval, d_chunk_offsets, d_jump_pos, d_jump_a, d_jump_b) || n_chunks_total > 0xffffffffull))
+        return CST_ERR_INVALID_ARGUMENT;
+    if (n_pieces_total > 0xffffffffull || (d_query_first == nullptr) != (d_query_count == nullptr)) return CST_ERR_INVALID_ARGUMENT;
+    if (cst_status st = check_ragged_gaussian_args(cfg, min_symbol, max_symbol, d_symbols_out, d_a, d_b, d_sym_offsets, d_words, d_word_offsets,
+                                                   stride_words, d_n_words, d_status, nullptr, n_streams)) return st;
+    if (n_queries > 0 && (!d_query_stream || !d_piece_offsets || !d_out_offsets || !d_scratch)) return CST_ERR_INVALID_ARGUMENT;
+    if (n_queries == 0) return CST_OK;
+    if (n_queries > ((size_t)0x7fffffff) * 256) return CST_ERR_INVALID_ARGUMENT;
+    RaggedSelect b{};
+    b.sym_offsets = d_sym_offsets; b.word_offsets = d_word_offsets; b.stride_words = stride_words; b.n_words = d_n_words; b.n_streams = n_streams;
+    // (slab form without a capacity: the slabs themselves bound every slice, as in the jump decoders)
+    b.words_capacity = words_capacity ? words_capacity : (d_word_offsets ? 0 : (uint64_t)n_streams * stride_words);
+    b.interval = (uint32_t)jump_interval; b.chunk_offsets = d_chunk_offsets; b.n_chunks_total = n_chunks_total; b.jump_pos = d_jump_pos;
+    b.query_stream = d_query_stream; b.query_first = d_query_first; b.query_count = d_query_count; b.n_queries = n_queries;
+    b.piece_offsets = d_piece_offsets; b.n_pieces_total = n_pieces_total; b.out_offsets = d_out_offsets;
+    const PerSymbolSelectPieces v(d_scratch, n_pieces_total);
+    const unsigned q_grid = (unsigned)((n_queries + 255) / 256);
+    hipLaunchKernelGGL(ragged_select_queries_kernel<0>, dim3(q_grid), dim3(256), 0, hs, b, d_status);
+    CST_HIP_TRY(hipGetLastError());
+    if (n_pieces_total > 0) {
+        const unsigned p_grid = (unsigned)((n_pieces_total + 255) / 256);
+        dispatch_word_size(cfg, [&](auto W, auto S) {
+            hipLaunchKernelGGL((persymbol_select_pieces_kernel<W, S, KIND>), dim3(p_grid), dim3(256), 0, hs, b, d_words, d_jump_a, d_jump_b, d_status, v);
+            return 0;
+        });
+        CST_HIP_TRY(hipGetLastError());
+        // (the slices handed on are absolute offsets that passed the check, or empty: the capacity bounds them once more)
+        GaussianRaggedSelectArgs a{};
+        a.p.words = d_words; a.p.offsets = v.word_off; a.p.stride_words = 0; a.p.n_words = v.n_words; a.p.words_capacity = b.words_capacity;
+        a.p.symbols = d_symbols_out; a.p.n_streams = n_pieces_total; a.p.precision = cfg.precision;
+        a.p.min_symbol = min_symbol; a.p.n_symbols = (int32_t)((int64_t)max_symbol - min_symbol + 1); a.p.means = d_a; a.p.stds = d_b;
+        a.p.status = v.status; a.p.state = v.state; a.p.rstate = v.rstate;
+        a.par_lo = v.par_lo; a.out_lo = v.out_lo; a.skip = v.skip; a.len = v.len; a.raw = jump_interval != 0;
+        const size_t blocks = (n_pieces_total + kRgDecThreads - 1) / kRgDecThreads;
+        const size_t lds = FAM::kErfTab ? kRgDecLdsBytes : kRgDecLdsBytesNoTab;
+        const cst_status rc = dispatch_word_size(cfg, [&](auto W, auto S) {
+            return launch_with_lds(decode_gaussian_ragged_kernel<W, S, KIND, FAM, kRgSelect>, blocks, kRgDecThreads, lds, a, hs);
+        });
+        if (rc != CST_OK) return rc;
+    }
+    hipLaunchKernelGGL(ragged_select_status_kernel<0>, dim3(q_grid), dim3(256), 0, hs, b, v.folded(), d_status);
+    CST_HIP_TRY(hipGetLastError());
+    return note_kernel(FamilyNames<FAM>::ragged_select[KIND == kRange], CST_OK);
+}
+
+} // namespace cst
+
+using namespace cst;
+
+extern "C" {
+
+size_t cst_persymbol_ragged_select_scratch_bytes(size_t n_pieces_total) { return kPsSelectPieceBytes * n_pieces_total + 128; }
+
+cst_status cst_ans_decode_gaussian_ragged_select(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                 const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                 const double* d_means, const double* d_stds, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                 size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                 const uint32_t* d_jump_pos, const uint64_t* d_jump_state, const uint32_t* d_query_stream,
+                                                 const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                                 const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                                 const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    return decode_ragged_select<kAns, GaussianFamily>(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                                                      d_means, d_stds, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+                                                      d_jump_pos, d_jump_state, nullptr, d_query_stream, d_query_first, d_query_count, n_queries,
+                                                      d_piece_offsets, n_pieces_total, d_symbols_out, d_out_offsets, d_scratch, d_status,
+                                                      (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_gaussian_ragged_select(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                   const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity,
+                                                   const uint32_t* d_n_words, const double* d_means, const double* d_stds,
+                                                   const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                   const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint32_t* d_jump_pos,
+                                                   const uint64_t* d_jump_lower, const uint64_t* d_jump_range, const uint32_t* d_query_stream,
+                                                   const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                                   const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                                   const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    return decode_ragged_select<kRange, GaussianFamily>(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                                                        d_means, d_stds, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+                                                        d_jump_pos, d_jump_lower, d_jump_range, d_query_stream, d_query_first, d_query_count,
+                                                        n_queries, d_piece_offsets, n_pieces_total, d_symbols_out, d_out_offsets, d_scratch,
+                                                        d_status, (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_family_ragged_select(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                               const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                               const double* d_a, const double* d_b, const uint64_t* d_sym_offsets, size_t n_streams,
+                                               size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                               const uint32_t* d_jump_pos, const uint64_t* d_jump_state, const uint32_t* d_query_stream,
+                                               const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                               const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                               const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    return CST_FAMILY_CALL(decode_ragged_select, kAns, cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                             d_a, d_b, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_state, nullptr,
+                             d_query_stream, d_query_first, d_query_count, n_queries, d_piece_offsets, n_pieces_total, d_symbols_out, d_out_offsets,
+                             d_scratch, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_family_ragged_select(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                                 const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity,
+                                                 const uint32_t* d_n_words, const double* d_a, const double* d_b, const uint64_t* d_sym_offsets,
+                                                 size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                 const uint32_t* d_jump_pos, const uint64_t* d_jump_lower, const uint64_t* d_jump_range,
+                                                 const uint32_t* d_query_stream, const uint64_t* d_query_first, const uint64_t* d_query_count,
+                                                 size_t n_queries, const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                                 const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    return CST_FAMILY_CALL(decode_ragged_select, kRange, cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                             d_a, d_b, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_lower,
+                             d_jump_range, d_query_stream, d_query_first, d_query_count, n_queries, d_piece_offsets, n_pieces_total, d_symbols_out,
+                             d_out_offsets, d_scratch, d_status, (hipStream_t)stream);
+}
+
+} // extern "C"

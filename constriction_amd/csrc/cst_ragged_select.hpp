@@ -9,7 +9,8 @@
 //   2. ragged_select_pieces_kernel    one thread per piece: its query by bisection in d_piece_offsets (rr_chunks_kernel's scheme), then
 //                                     table entry, skip, length, output position and its stream's checked slice of the words -> scratch;
 //   3. ragged_select_status_kernel    one thread per query: the worst of its pieces' statuses.
-// The kernels are templates so that each of the two translation units carries its own copy (no relocatable device code).
+// The kernels are templates so that each translation unit that launches them carries its own copy (no relocatable device code):
+// cst_ans_ragged.hip, cst_range_ragged.hip, and cst_persymbol_ragged_select.hip, whose pieces carry more (its own piece builder).
 #pragma once
 #include "cst_common.hpp"
 

@@ -524,6 +524,75 @@ cst_status cst_range_decode_family_ragged_jump(cst_coder_config cfg, int32_t fam
                                                const uint64_t *d_jump_lower, const uint64_t *d_jump_range, void *d_scratch,
                                                int32_t *d_status, void *stream);
 
+/* Random access into a ragged per-symbol batch: cst_{ans,range}_decode_ragged_select (below, where queries, pieces, d_out_offsets,
+ * d_piece_offsets and the per-query statuses are described) for the eight decoders above.  The arguments are the model's (cfg, the
+ * family, min_symbol, max_symbol), then the words block, d_means / d_stds (d_a / d_b) -- the batch's FULL arrays, laid out exactly as
+ * the plain decode call takes them -- d_sym_offsets and n_streams, then the table block and the query block of
+ * cst_{ans,range}_decode_ragged_select with the same conventions: jump_interval 0 and every table pointer NULL is no table; both of
+ * d_query_first / d_query_count NULL is whole documents; n_queries == 0 returns CST_OK and launches nothing.
+ *   - A piece reads its parameters from the element of its jump point on: element d_sym_offsets[s] + (first / jump_interval + j) *
+ *     jump_interval for piece j of a query, d_sym_offsets[s] without a table.  The symbols in front of `first` are decoded with their
+ *     own parameters and dropped.  ONLY the parameters of elements [that first element, d_sym_offsets[s] + first + count) of a query can
+ *     influence any result or status: everything else in d_means / d_stds may hold anything (NaN included).
+ *   - Statuses, one per QUERY: CST_STREAM_INVALID_DATA (nothing is written) for every query cst_{ans,range}_decode_ragged_select refuse.
+ *     A query whose decoded range, the dropped symbols included, meets an invalid model or an impossible quantile reports
+ *     CST_STREAM_IMPOSSIBLE_SYMBOL and may leave anything inside its own output slice, nothing outside it; the other queries are
+ *     unaffected.
+ *   - d_scratch: cst_persymbol_ragged_select_scratch_bytes(n_pieces_total) bytes (a piece's record also holds where its parameters
+ *     start and its coder's state at the jump point).
+ *   - CST_ERR_INVALID_ARGUMENT / CST_ERR_MODEL, before the device is touched: every refusal of the plain decode call (d_symbols_out in
+ *     the place of d_symbols; d_order does not exist here), a support too large for the precision included; with a table, every refusal
+ *     of the _jump decoders (jump_interval not a multiple of 16 or > 2^31 - 1, a NULL d_chunk_offsets or table array, n_chunks_total >
+ *     2^32 - 1); table arrays without an interval; n_pieces_total > 2^32 - 1; exactly one of d_query_first / d_query_count NULL; with
+ *     n_queries > 0 a NULL d_query_stream, d_piece_offsets, d_out_offsets or d_scratch; an unknown family.
+ * cst_last_kernel_name(): {ans,range}_decode_{gaussian,laplace,cauchy}_ragged_kernel<select>.  (The Categorical ragged decoders have no
+ * select form.) */
+size_t cst_persymbol_ragged_select_scratch_bytes(size_t n_pieces_total);
+cst_status cst_ans_decode_gaussian_ragged_select(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                 const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                 size_t words_capacity, const uint32_t *d_n_words, const double *d_means,
+                                                 const double *d_stds, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                 size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                 const uint32_t *d_jump_pos, const uint64_t *d_jump_state,
+                                                 const uint32_t *d_query_stream, const uint64_t *d_query_first,
+                                                 const uint64_t *d_query_count, size_t n_queries,
+                                                 const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
+                                                 const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status,
+                                                 void *stream);
+cst_status cst_range_decode_gaussian_ragged_select(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                   const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                   size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                   const double *d_means, const double *d_stds, const uint64_t *d_sym_offsets,
+                                                   size_t n_streams, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                   size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                                   const uint64_t *d_jump_lower, const uint64_t *d_jump_range,
+                                                   const uint32_t *d_query_stream, const uint64_t *d_query_first,
+                                                   const uint64_t *d_query_count, size_t n_queries,
+                                                   const uint64_t *d_piece_offsets, size_t n_pieces_total,
+                                                   int32_t *d_symbols_out, const uint64_t *d_out_offsets, void *d_scratch,
+                                                   int32_t *d_status, void *stream);
+cst_status cst_ans_decode_family_ragged_select(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                               const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                               size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
+                                               const double *d_b, const uint64_t *d_sym_offsets, size_t n_streams,
+                                               size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                               const uint32_t *d_jump_pos, const uint64_t *d_jump_state,
+                                               const uint32_t *d_query_stream, const uint64_t *d_query_first,
+                                               const uint64_t *d_query_count, size_t n_queries,
+                                               const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
+                                               const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status, void *stream);
+cst_status cst_range_decode_family_ragged_select(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                                 const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                 size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
+                                                 const double *d_b, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                 size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                 const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
+                                                 const uint64_t *d_jump_range, const uint32_t *d_query_stream,
+                                                 const uint64_t *d_query_first, const uint64_t *d_query_count, size_t n_queries,
+                                                 const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
+                                                 const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status,
+                                                 void *stream);
+
 /* The range coder with ONE SHARED TABLE for streams of different lengths: cst_ans_{encode,decode}_ragged / cst_ans_count_until for the
  * reference's queue -- one RangeEncoder / RangeDecoder per document (src/stream/queue.rs), the symbols decoded in the order they were
  * encoded, so that a terminator is simply written last.  Symbols, slabs, d_word_offsets / stride_words / words_capacity / d_n_words
@@ -626,8 +695,9 @@ cst_status cst_range_decode_ragged_jump(const cst_model *model, cst_coder_config
  *     arrays, arrays without an interval); n_chunks_total or n_pieces_total > 2^32 - 1; exactly one of d_query_first / d_query_count
  *     NULL; with n_queries > 0 a NULL d_query_stream, d_piece_offsets, d_out_offsets, d_scratch or d_status.  n_queries == 0: CST_OK,
  *     nothing is launched.
- * cst_last_kernel_name: "ans_decode_ragged_kernel<select>" / "range_decode_ragged_kernel<select>".  Shared-table models only: the
- * per-symbol ragged coders index their parameters by symbol position and have no select form yet. */
+ * cst_last_kernel_name: "ans_decode_ragged_kernel<select>" / "range_decode_ragged_kernel<select>".  Shared-table models; the
+ * per-symbol ragged coders (Gaussian, Laplace, Cauchy) have cst_{ans,range}_decode_{gaussian,family}_ragged_select, where a piece also
+ * carries the position its parameters start at. */
 size_t cst_ragged_select_scratch_bytes(size_t n_pieces_total);
 size_t cst_range_ragged_select_scratch_bytes(size_t n_pieces_total);
 cst_status cst_ans_decode_ragged_select(const cst_model *model, cst_coder_config cfg, const uint32_t *d_words,

@@ -9,6 +9,13 @@
 --jump-every N (a multiple of 16; default 0: not run): also (j) the same batch with a jump point every N symbols of every stream --
 `jump_every=N` of the encoder, and the decode of all chunks side by side -- timed beside the plain pair of (a) in the same run,
 alternating; recorded per alternation, with the size of the table against the words.  No condition on it.
+--select N (default 0: not run; not with --family categorical): also (s) random access through
+batched.{coder}_decode_{family}_ragged_select on the batch of (a) -- with --jump-every's table where that is given -- timed in the same
+run, alternating: N whole streams drawn at random through the select call; the full decode (whole streams, and through the jump table)
+followed by a device gather of the same streams (the gather's index is built beforehand and not timed), which is all a caller had
+before; N ranges of 64 symbols at random depths with the table and without it; and ALL streams in order through the select call beside
+the jump decode of the same batch (what the SELECT form's second index and store predicate cost: call against call, the select call's
+four launches, prefix sums and read-back included).  Recorded, no condition on it beyond the symbols being right.
 --coder ans|range and --family gaussian|laplace|cauchy|categorical choose the form (default: ans, gaussian); --skip-grouped leaves (b)
 out (it takes seconds per alternation and minutes to set up; its condition is then not judged).
 --family categorical --k K: every symbol has its own row of K float32 probabilities (exp(3 z), z normal: not normalised; symbols drawn
@@ -35,11 +42,13 @@ ap.add_argument("--family", choices=["gaussian", "laplace", "cauchy", "categoric
 ap.add_argument("--k", type=int, default=16, help="--family categorical: entries of a probability row")
 ap.add_argument("--perfect", action="store_true", help="--family categorical: Categorical(perfect=True), quantised by the device quantiser")
 ap.add_argument("--jump-every", type=int, default=0, help="also time the pair with a jump point every N symbols (a multiple of 16)")
+ap.add_argument("--select", type=int, default=0, help="also time random access: N whole streams, and N ranges of 64 symbols")
 ap.add_argument("--skip-rectangular", action="store_true", help="leave (c), the rectangular matrix, out")
 ap.add_argument("--skip-grouped", action="store_true", help="leave (b), one rectangular call per distinct length, out")
 args = ap.parse_args()
 assert args.alternations >= 5 or args.streams < 16384, "the recorded figures are medians of at least five alternations"
 assert not args.perfect or args.family == "categorical", "--perfect goes with --family categorical"
+assert not args.select or args.family != "categorical", "--select: the Categorical ragged decoders have no select form"
 
 CFG, LO, HI = (32, 64, 24), -100, 100
 torch.manual_seed(1)
@@ -183,6 +192,52 @@ if args.jump_every:
                  "word_bytes": 4 * int(enc.n_words.sum()),
                  "pair_lower_in_every_alternation": all(je + jd < pe + pd for pe, pd, je, jd in zip(t_j["plain_encode"], t_j["plain_decode"],
                                                                                                     t_j["jump_encode"], t_j["jump_decode"]))}
+
+# ---- (s): random access, beside the full decode and a gather ----
+ok_s, t_s, select_info = True, {}, None
+if args.select:
+    sel_ragged = getattr(B, f"{args.coder}_decode_{args.family}_ragged_select")
+    enc_t = enc_j if args.jump_every else enc                   # the batch with its table, where one was asked for
+    enc_0 = enc                                                 # ... and the same words without one
+    q_streams = torch.randint(0, n, (args.select,), dtype=torch.int64, device=dev)
+    q_len = lengths[q_streams]
+    q_count = torch.clamp(q_len, max=64)
+    q_first = (torch.rand(args.select, dtype=torch.float64, device=dev) * (q_len - q_count + 1).to(torch.float64)).to(torch.int64)
+    q_first = torch.minimum(q_first, q_len - q_count)
+
+    def gather_index(first, count):
+        """the elements of `sym` that the queries (q_streams, first, count) ask for, in their order"""
+        ends = torch.cumsum(count, 0)
+        starts = ends - count
+        k = torch.arange(int(ends[-1]), dtype=torch.int64, device=dev)
+        q = torch.searchsorted(ends, k, right=True)
+        return offsets[q_streams[q]] + first[q] + (k - starts[q])
+
+    idx_whole, idx_range = gather_index(torch.zeros_like(q_len), q_len), gather_index(q_first, q_count)
+    want_whole, want_range = sym[idx_whole], sym[idx_range]
+    every_stream = torch.arange(n, dtype=torch.int64, device=dev)
+    out_all = torch.empty_like(sym)
+    checks = [(sel_ragged(enc_t, offsets, *HEAD, *model, q_streams), want_whole),
+              (sel_ragged(enc_t, offsets, *HEAD, *model, q_streams, q_first, q_count), want_range),
+              (sel_ragged(enc_0, offsets, *HEAD, *model, q_streams, q_first, q_count), want_range),
+              (sel_ragged(enc_t, offsets, *HEAD, *model, every_stream, out=out_all), sym)]
+    torch.cuda.synchronize()
+    ok_s = B.last_kernel() == f"{args.coder}_decode_{args.family}_ragged_kernel<select>" and \
+        all(bool(torch.equal(got, want)) and int(status.abs().sum()) == 0 for (got, _, status), want in checks)
+    del checks
+    candidates = {"select_whole": lambda: sel_ragged(enc_t, offsets, *HEAD, *model, q_streams),
+                  "full_plain_gather": lambda: dec_ragged(enc_0, offsets, *HEAD, *model, out=dec)[0][idx_whole],
+                  "select_ranges": lambda: sel_ragged(enc_t, offsets, *HEAD, *model, q_streams, q_first, q_count),
+                  "select_ranges_no_table": lambda: sel_ragged(enc_0, offsets, *HEAD, *model, q_streams, q_first, q_count),
+                  "select_all": lambda: sel_ragged(enc_t, offsets, *HEAD, *model, every_stream, out=out_all)}
+    if args.jump_every:
+        candidates["full_jump_gather"] = lambda: dec_ragged(enc_t, offsets, *HEAD, *model, out=dec_j)[0][idx_whole]
+        candidates["full_jump"] = lambda: dec_ragged(enc_t, offsets, *HEAD, *model, out=dec_j)
+    t_s = alternate(candidates, args.alternations)
+    select_info = {"queries": args.select, "whole_symbols": int(idx_whole.numel()), "range_symbols": int(idx_range.numel()),
+                   "table_every": args.jump_every}
+    del out_all, idx_whole, idx_range, want_whole, want_range
+if args.jump_every:
     del enc_j, dec_j
 
 # ---- (c): a rectangular matrix of the same size, both ways ----
@@ -228,6 +283,18 @@ if args.jump_every:
     print(f"      jump:  encode {m_j['jump_encode']:9.3f} ms ({spread('jump_encode')}, {m_j['jump_encode'] / m_j['plain_encode']:.3f}x)  "
           f"decode {m_j['jump_decode']:9.3f} ms ({spread('jump_decode')}, {m_j['jump_decode'] / m_j['plain_decode']:.3f}x)  round trip ok={ok_j}")
     print(f"      encode + decode lower with jump points in every alternation: {jump_info['pair_lower_in_every_alternation']}")
+if args.select:
+    m_s = {k: med(v) for k, v in t_s.items()}
+    table = f"a jump point every {args.jump_every} symbols" if args.jump_every else "NO table"
+    print(f"  (s) random access, {args.select} queries, {table}:")
+    print(f"      {args.select} whole streams ({select_info['whole_symbols'] / 1e6:.2f} M symbols) through the select call: {m_s['select_whole']:9.3f} ms")
+    print(f"      full decode + gather of the same streams: whole streams {m_s['full_plain_gather']:9.3f} ms"
+          + (f", through the jump table {m_s['full_jump_gather']:9.3f} ms" if args.jump_every else ""))
+    print(f"      {args.select} ranges of 64 symbols at random depths: {m_s['select_ranges']:9.3f} ms with the table, "
+          f"{m_s['select_ranges_no_table']:9.3f} ms without ({m_s['select_ranges'] / m_s['select_ranges_no_table']:.3f}x)")
+    print(f"      all {n} streams in order through the select call: {m_s['select_all']:9.3f} ms"
+          + (f" against {m_s['full_jump']:9.3f} ms of the jump decode ({m_s['select_all'] / m_s['full_jump']:.2f}x)" if args.jump_every else "")
+          + f"  symbols ok={ok_s}")
 if args.skip_rectangular:
     print("  (c) rectangular matrix:        left out (--skip-rectangular)")
 else:
@@ -236,5 +303,6 @@ else:
           f"decode {m_c['ragged_decode']:9.3f} ms ({m_c['ragged_decode'] / m_c['rect_decode']:.2f}x)  round trips ok={ok_c}")
 print(json.dumps({"coder": args.coder, "family": args.family, "perfect": args.perfect, "k": args.k if CATEGORICAL else None, "grouped": not args.skip_grouped, "streams": n, "symbols": total, "alternations": args.alternations, "ms": {**m_ab, **m_c}, "all_ms": {**t_ab, **t_c},
                   "jump": jump_info, "jump_ms": {k: med(v) for k, v in t_j.items()}, "jump_all_ms": t_j,
-                  "a_faster_than_b": faster, "round_trips_ok": ok_a and ok_b and ok_c and ok_j}))
-sys.exit(0 if faster and ok_a and ok_b and ok_c and ok_j else 1)
+                  "select": select_info, "select_ms": {k: med(v) for k, v in t_s.items()}, "select_all_ms": t_s,
+                  "a_faster_than_b": faster, "round_trips_ok": ok_a and ok_b and ok_c and ok_j and ok_s}))
+sys.exit(0 if faster and ok_a and ok_b and ok_c and ok_j and ok_s else 1)
