@@ -968,8 +968,8 @@ extern "C" {
     ///     of the _jump decoders (jump_interval not a multiple of 16 or > 2^31 - 1, a NULL d_chunk_offsets or table array, n_chunks_total >
     ///     2^32 - 1); table arrays without an interval; n_pieces_total > 2^32 - 1; exactly one of d_query_first / d_query_count NULL; with
     ///     n_queries > 0 a NULL d_query_stream, d_piece_offsets, d_out_offsets or d_scratch; an unknown family.
-    /// cst_last_kernel_name(): {ans,range}_decode_{gaussian,laplace,cauchy}_ragged_kernel<select>.  (The Categorical ragged decoders have no
-    /// select form.)
+    /// cst_last_kernel_name(): {ans,range}_decode_{gaussian,laplace,cauchy}_ragged_kernel<select>.  (The Categorical ragged decoders:
+    /// cst_{ans,range}_decode_categorical[_perfect]_ragged_select, with those calls.)
     pub fn cst_persymbol_ragged_select_scratch_bytes(n_pieces_total: usize) -> usize;
 
     pub fn cst_ans_decode_gaussian_ragged_select(
@@ -2689,6 +2689,160 @@ extern "C" {
         d_jump_pos: *const u32,
         d_jump_lower: *const u64,
         d_jump_range: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// Random access into a ragged per-symbol Categorical batch, both quantisers: cst_{ans,range}_decode_gaussian_ragged_select (above) with
+    /// "parameters" read as "rows".  The arguments follow those calls block by block: cfg (no min_symbol / max_symbol); the words block; the
+    /// model arguments of cst_*_decode_categorical_ragged -- d_probs, prob_bytes, n_symbols, n_total: the batch's FULL [n_total][K] matrix,
+    /// laid out as the plain decode call takes it; the perfect pair only: max_piece_len; d_sym_offsets, n_streams; the table block (all
+    /// zero / NULL: no table); the query block and the tail, unchanged.
+    ///   - Piece j of a query reads rows from row d_sym_offsets[s] + (first / jump_interval + j) * jump_interval on (d_sym_offsets[s] without
+    ///     a table), decodes and drops its first symbols with THEIR rows and stores the rest at its place in the ragged output.  ONLY rows
+    ///     [that first row, d_sym_offsets[s] + first + count) of a query can influence any result or status: everything else in d_probs may
+    ///     hold anything (NaN included).
+    ///   - max_piece_len (the perfect pair): an upper bound of (symbols dropped + symbols stored) over all pieces -- with a table at most
+    ///     jump_interval (larger values are clamped to it), without one max(first + count) -- the role max_len has in
+    ///     cst_*_decode_categorical_perfect_ragged: the host loop runs without a read-back.  A piece longer than max_piece_len makes its
+    ///     query report CST_STREAM_CAPACITY and write nothing.  The rows are tabulated for groups of pieces within the 64 MiB of the plain
+    ///     perfect decoders (CST_PERFECT_RAGGED_BUDGET).
+    ///   - Statuses, one per QUERY.  Refused before decoding, nothing written: CST_STREAM_INVALID_DATA for every query
+    ///     cst_{ans,range}_decode_ragged_select refuse, and for a query whose stream's rows reach beyond n_total.  Failing while decoding: a
+    ///     query that meets a bad row or an impossible quantile, in its dropped part too, reports CST_STREAM_IMPOSSIBLE_SYMBOL and may leave
+    ///     anything inside its own output slice, nothing outside it.  The other queries are unaffected either way.
+    ///   - d_scratch: cst_persymbol_ragged_select_scratch_bytes(n_pieces_total) bytes, for all four.
+    ///   - CST_ERR_INVALID_ARGUMENT, then CST_ERR_MODEL, before the device is touched: every refusal of the plain Categorical ragged decode
+    ///     call of the same quantiser (d_symbols_out in the place of d_symbols; prob_bytes outside {4, 8}; its limits of K); with a table,
+    ///     every refusal of the _jump decoders; table arrays without an interval; n_pieces_total > 2^32 - 1; exactly one of d_query_first /
+    ///     d_query_count NULL; with n_queries > 0 a NULL d_query_stream, d_piece_offsets, d_out_offsets or d_scratch.  n_queries == 0
+    ///     returns CST_OK and launches nothing.
+    /// cst_last_kernel_name(): {ans,range}_decode_categorical_ragged_kernel<select>,
+    /// {ans,range}_decode_categorical_perfect_ragged_by_rows<select>.
+    pub fn cst_ans_decode_categorical_ragged_select(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_categorical_ragged_select(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_categorical_perfect_ragged_select(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        max_piece_len: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_categorical_perfect_ragged_select(
+        cfg: CstCoderConfig,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_probs: *const c_void,
+        prob_bytes: i32,
+        n_symbols: i32,
+        n_total: usize,
+        max_piece_len: usize,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
         d_scratch: *mut c_void,
         d_status: *mut i32,
         stream: *mut c_void,

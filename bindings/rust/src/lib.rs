@@ -2792,6 +2792,183 @@ impl BatchedAnsCoder {
         Ok(status)
     }
 
+    /// Random access into a ragged per-symbol Categorical batch (`cst_ans_decode_categorical_ragged_select`): the queries, piece offsets and
+    /// results of [`BatchedAnsCoder::seek_and_decode_ragged`] on the batches of `encode_symbols_reverse_categorical[_perfect]_ragged[_with_jump_points]`, with
+    /// `jump_points = Some((interval, chunk_offsets, pos, state, n_chunks_total))` (`interval` a multiple of 16).  `probabilities` is the batch's FULL
+    /// `[n_total][n_symbols]` matrix, as the plain decoder takes it: a piece reads rows from the row of its jump point on (from its stream's
+    /// first row without jump points), decodes the symbols in front of `first` with their own rows and drops them.  Only the rows from
+    /// there to the query's end can influence a result or a status.  One status per QUERY.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_categorical_ragged`.  Queries, piece offsets and the jump table are checked on the device; `symbols` must
+    /// hold `out_offsets[n_queries]` symbols, `probabilities` `n_total * n_symbols` entries.
+    pub unsafe fn seek_and_decode_categorical_ragged<F: Probability>(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_total: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        jump_points: Option<(usize, &DeviceBuffer<u64>, &DeviceBuffer<u32>, &DeviceBuffer<u64>, usize)>,
+        query_stream: &DeviceBuffer<u32>,
+        query_range: Option<(&DeviceBuffer<u64>, &DeviceBuffer<u64>)>,
+        piece_offsets: &DeviceBuffer<u64>,
+        n_pieces_total: usize,
+        symbols: &mut DeviceBuffer<i32>,
+        out_offsets: &DeviceBuffer<u64>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        unsafe { self.seek_and_decode_categorical_ragged_with(None, words, word_offsets, n_words, probabilities, n_symbols, n_total, sym_offsets, jump_points, query_stream, query_range, piece_offsets, n_pieces_total, symbols, out_offsets, stream) }
+    }
+
+    /// `seek_and_decode_categorical_ragged` under `Categorical(perfect=True)` (`cst_ans_decode_categorical_perfect_ragged_select`,
+    /// `2 <= n_symbols <= 1024`): only the rows the pieces walk are quantised.  `max_piece_len`: an upper bound of the symbols a piece
+    /// decodes, dropped ones included -- with jump points at most `interval`, without them the largest `first + count`; a longer piece
+    /// makes its query report `Capacity`.
+    ///
+    /// # Safety
+    /// As for `seek_and_decode_categorical_ragged`.
+    pub unsafe fn seek_and_decode_categorical_perfect_ragged<F: Probability>(
+        &self,
+        max_piece_len: usize,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_total: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        jump_points: Option<(usize, &DeviceBuffer<u64>, &DeviceBuffer<u32>, &DeviceBuffer<u64>, usize)>,
+        query_stream: &DeviceBuffer<u32>,
+        query_range: Option<(&DeviceBuffer<u64>, &DeviceBuffer<u64>)>,
+        piece_offsets: &DeviceBuffer<u64>,
+        n_pieces_total: usize,
+        symbols: &mut DeviceBuffer<i32>,
+        out_offsets: &DeviceBuffer<u64>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        unsafe { self.seek_and_decode_categorical_ragged_with(Some(max_piece_len), words, word_offsets, n_words, probabilities, n_symbols, n_total, sym_offsets, jump_points, query_stream, query_range, piece_offsets, n_pieces_total, symbols, out_offsets, stream) }
+    }
+
+    /// the body of the two above; `max_piece_len`: `Some` for the perfect quantiser
+    unsafe fn seek_and_decode_categorical_ragged_with<F: Probability>(
+        &self,
+        max_piece_len: Option<usize>,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_total: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        jump_points: Option<(usize, &DeviceBuffer<u64>, &DeviceBuffer<u32>, &DeviceBuffer<u64>, usize)>,
+        query_stream: &DeviceBuffer<u32>,
+        query_range: Option<(&DeviceBuffer<u64>, &DeviceBuffer<u64>)>,
+        piece_offsets: &DeviceBuffer<u64>,
+        n_pieces_total: usize,
+        symbols: &mut DeviceBuffer<i32>,
+        out_offsets: &DeviceBuffer<u64>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let n_queries = query_stream.len();
+        if piece_offsets.len() != n_queries + 1 || out_offsets.len() != n_queries + 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if let Some((first, count)) = query_range {
+            if first.len() != n_queries || count.len() != n_queries {
+                return Err(Error::InvalidArgument);
+            }
+        }
+        let (jump_interval, n_chunks_total) = jump_points.map_or((0, 0), |j| (j.0, j.4));
+        if let Some((_, chunk_offsets, pos, state, _)) = jump_points {
+            if chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 16 != 0 || pos.len() < n_chunks_total || state.len() < n_chunks_total {
+                return Err(Error::InvalidArgument);
+            }
+        }
+        let chunk_offsets_ = jump_points.map(|j| j.1);
+        let pos_ = jump_points.map(|j| j.2);
+        let state_ = jump_points.map(|j| j.3);
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_queries)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_select_scratch_bytes(n_pieces_total) })?;
+        check(unsafe {
+            match max_piece_len {
+                None => ffi::cst_ans_decode_categorical_ragged_select(
+                    self.config,
+                    words.as_ptr(),
+                    word_offsets.as_ptr(),
+                    0,
+                    words.len(),
+                    n_words.as_ptr(),
+                    probabilities.as_ptr() as *const c_void,
+                    F::BYTES,
+                    n_symbols as i32,
+                    n_total,
+                    sym_offsets.as_ptr(),
+                    n_streams,
+                    jump_interval,
+                    chunk_offsets_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    n_chunks_total,
+                    pos_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    state_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    query_stream.as_ptr(),
+                    query_range.map_or(core::ptr::null(), |r| r.0.as_ptr()),
+                    query_range.map_or(core::ptr::null(), |r| r.1.as_ptr()),
+                    n_queries,
+                    piece_offsets.as_ptr(),
+                    n_pieces_total,
+                    symbols.as_mut_ptr(),
+                    out_offsets.as_ptr(),
+                    scratch.as_mut_ptr() as *mut c_void,
+                    status.as_mut_ptr(),
+                    stream.as_raw(),
+                ),
+                Some(max_piece_len) => ffi::cst_ans_decode_categorical_perfect_ragged_select(
+                    self.config,
+                    words.as_ptr(),
+                    word_offsets.as_ptr(),
+                    0,
+                    words.len(),
+                    n_words.as_ptr(),
+                    probabilities.as_ptr() as *const c_void,
+                    F::BYTES,
+                    n_symbols as i32,
+                    n_total,
+                    max_piece_len,
+                    sym_offsets.as_ptr(),
+                    n_streams,
+                    jump_interval,
+                    chunk_offsets_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    n_chunks_total,
+                    pos_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    state_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    query_stream.as_ptr(),
+                    query_range.map_or(core::ptr::null(), |r| r.0.as_ptr()),
+                    query_range.map_or(core::ptr::null(), |r| r.1.as_ptr()),
+                    n_queries,
+                    piece_offsets.as_ptr(),
+                    n_pieces_total,
+                    symbols.as_mut_ptr(),
+                    out_offsets.as_ptr(),
+                    scratch.as_mut_ptr() as *mut c_void,
+                    status.as_mut_ptr(),
+                    stream.as_raw(),
+                ),
+            }
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
+        Ok(status)
+    }
+
     /// `seek_and_decode_gaussian_ragged` over `family` (`cst_ans_decode_family_ragged_select`): `a` / `b` are the batch's full location and scale arrays.
     ///
     /// # Safety
@@ -4685,6 +4862,186 @@ impl BatchedRangeDecoder {
                 status.as_mut_ptr(),
                 stream.as_raw(),
             )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
+        Ok(status)
+    }
+
+    /// Random access into a ragged per-symbol Categorical batch (`cst_range_decode_categorical_ragged_select`): the queries, piece offsets and
+    /// results of [`BatchedAnsCoder::seek_and_decode_ragged`] on the batches of `encode_symbols_categorical[_perfect]_ragged[_with_jump_points]`, with
+    /// `jump_points = Some((interval, chunk_offsets, pos, lower, range, n_chunks_total))` (`interval` a multiple of 16).  `probabilities` is the batch's FULL
+    /// `[n_total][n_symbols]` matrix, as the plain decoder takes it: a piece reads rows from the row of its jump point on (from its stream's
+    /// first row without jump points), decodes the symbols in front of `first` with their own rows and drops them.  Only the rows from
+    /// there to the query's end can influence a result or a status.  One status per QUERY.
+    ///
+    /// # Safety
+    /// As for `decode_symbols_categorical_ragged`.  Queries, piece offsets and the jump table are checked on the device; `symbols` must
+    /// hold `out_offsets[n_queries]` symbols, `probabilities` `n_total * n_symbols` entries.
+    pub unsafe fn seek_and_decode_categorical_ragged<F: Probability>(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_total: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        jump_points: Option<(usize, &DeviceBuffer<u64>, &DeviceBuffer<u32>, &DeviceBuffer<u64>, &DeviceBuffer<u64>, usize)>,
+        query_stream: &DeviceBuffer<u32>,
+        query_range: Option<(&DeviceBuffer<u64>, &DeviceBuffer<u64>)>,
+        piece_offsets: &DeviceBuffer<u64>,
+        n_pieces_total: usize,
+        symbols: &mut DeviceBuffer<i32>,
+        out_offsets: &DeviceBuffer<u64>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        unsafe { self.seek_and_decode_categorical_ragged_with(None, words, word_offsets, n_words, probabilities, n_symbols, n_total, sym_offsets, jump_points, query_stream, query_range, piece_offsets, n_pieces_total, symbols, out_offsets, stream) }
+    }
+
+    /// `seek_and_decode_categorical_ragged` under `Categorical(perfect=True)` (`cst_range_decode_categorical_perfect_ragged_select`,
+    /// `2 <= n_symbols <= 1024`): only the rows the pieces walk are quantised.  `max_piece_len`: an upper bound of the symbols a piece
+    /// decodes, dropped ones included -- with jump points at most `interval`, without them the largest `first + count`; a longer piece
+    /// makes its query report `Capacity`.
+    ///
+    /// # Safety
+    /// As for `seek_and_decode_categorical_ragged`.
+    pub unsafe fn seek_and_decode_categorical_perfect_ragged<F: Probability>(
+        &self,
+        max_piece_len: usize,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_total: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        jump_points: Option<(usize, &DeviceBuffer<u64>, &DeviceBuffer<u32>, &DeviceBuffer<u64>, &DeviceBuffer<u64>, usize)>,
+        query_stream: &DeviceBuffer<u32>,
+        query_range: Option<(&DeviceBuffer<u64>, &DeviceBuffer<u64>)>,
+        piece_offsets: &DeviceBuffer<u64>,
+        n_pieces_total: usize,
+        symbols: &mut DeviceBuffer<i32>,
+        out_offsets: &DeviceBuffer<u64>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        unsafe { self.seek_and_decode_categorical_ragged_with(Some(max_piece_len), words, word_offsets, n_words, probabilities, n_symbols, n_total, sym_offsets, jump_points, query_stream, query_range, piece_offsets, n_pieces_total, symbols, out_offsets, stream) }
+    }
+
+    /// the body of the two above; `max_piece_len`: `Some` for the perfect quantiser
+    unsafe fn seek_and_decode_categorical_ragged_with<F: Probability>(
+        &self,
+        max_piece_len: Option<usize>,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        probabilities: &DeviceBuffer<F>,
+        n_symbols: usize,
+        n_total: usize,
+        sym_offsets: &DeviceBuffer<u64>,
+        jump_points: Option<(usize, &DeviceBuffer<u64>, &DeviceBuffer<u32>, &DeviceBuffer<u64>, &DeviceBuffer<u64>, usize)>,
+        query_stream: &DeviceBuffer<u32>,
+        query_range: Option<(&DeviceBuffer<u64>, &DeviceBuffer<u64>)>,
+        piece_offsets: &DeviceBuffer<u64>,
+        n_pieces_total: usize,
+        symbols: &mut DeviceBuffer<i32>,
+        out_offsets: &DeviceBuffer<u64>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let entries = n_total.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+        if probabilities.len() < entries || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let n_queries = query_stream.len();
+        if piece_offsets.len() != n_queries + 1 || out_offsets.len() != n_queries + 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if let Some((first, count)) = query_range {
+            if first.len() != n_queries || count.len() != n_queries {
+                return Err(Error::InvalidArgument);
+            }
+        }
+        let (jump_interval, n_chunks_total) = jump_points.map_or((0, 0), |j| (j.0, j.5));
+        if let Some((_, chunk_offsets, pos, lower, range, _)) = jump_points {
+            if chunk_offsets.len() != sym_offsets.len() || jump_interval == 0 || jump_interval % 16 != 0 || pos.len() < n_chunks_total || lower.len() < n_chunks_total || range.len() < n_chunks_total {
+                return Err(Error::InvalidArgument);
+            }
+        }
+        let chunk_offsets_ = jump_points.map(|j| j.1);
+        let pos_ = jump_points.map(|j| j.2);
+        let lower_ = jump_points.map(|j| j.3);
+        let range_ = jump_points.map(|j| j.4);
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_queries)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_select_scratch_bytes(n_pieces_total) })?;
+        check(unsafe {
+            match max_piece_len {
+                None => ffi::cst_range_decode_categorical_ragged_select(
+                    self.config,
+                    words.as_ptr(),
+                    word_offsets.as_ptr(),
+                    0,
+                    words.len(),
+                    n_words.as_ptr(),
+                    probabilities.as_ptr() as *const c_void,
+                    F::BYTES,
+                    n_symbols as i32,
+                    n_total,
+                    sym_offsets.as_ptr(),
+                    n_streams,
+                    jump_interval,
+                    chunk_offsets_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    n_chunks_total,
+                    pos_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    lower_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    range_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    query_stream.as_ptr(),
+                    query_range.map_or(core::ptr::null(), |r| r.0.as_ptr()),
+                    query_range.map_or(core::ptr::null(), |r| r.1.as_ptr()),
+                    n_queries,
+                    piece_offsets.as_ptr(),
+                    n_pieces_total,
+                    symbols.as_mut_ptr(),
+                    out_offsets.as_ptr(),
+                    scratch.as_mut_ptr() as *mut c_void,
+                    status.as_mut_ptr(),
+                    stream.as_raw(),
+                ),
+                Some(max_piece_len) => ffi::cst_range_decode_categorical_perfect_ragged_select(
+                    self.config,
+                    words.as_ptr(),
+                    word_offsets.as_ptr(),
+                    0,
+                    words.len(),
+                    n_words.as_ptr(),
+                    probabilities.as_ptr() as *const c_void,
+                    F::BYTES,
+                    n_symbols as i32,
+                    n_total,
+                    max_piece_len,
+                    sym_offsets.as_ptr(),
+                    n_streams,
+                    jump_interval,
+                    chunk_offsets_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    n_chunks_total,
+                    pos_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    lower_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    range_.map_or(core::ptr::null(), |b| b.as_ptr()),
+                    query_stream.as_ptr(),
+                    query_range.map_or(core::ptr::null(), |r| r.0.as_ptr()),
+                    query_range.map_or(core::ptr::null(), |r| r.1.as_ptr()),
+                    n_queries,
+                    piece_offsets.as_ptr(),
+                    n_pieces_total,
+                    symbols.as_mut_ptr(),
+                    out_offsets.as_ptr(),
+                    scratch.as_mut_ptr() as *mut c_void,
+                    status.as_mut_ptr(),
+                    stream.as_raw(),
+                ),
+            }
         })?;
         stream.synchronize()?; // (the scratch buffer is dropped on return)
         Ok(status)

@@ -209,6 +209,16 @@ SIGNATURES = {
                                                                 _vp, _vp, _vp, _vp]),
     "cst_range_decode_categorical_perfect_ragged_jump": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _z, _vp, _vp, _z, _z, _vp, _z,
                                                                 _vp, _vp, _vp, _vp, _vp, _vp]),
+    # random access into the Categorical ragged batches: the Gaussian select lists with the plain decoders' model arguments (the
+    # perfect pair: max_piece_len after n_total)
+    "cst_ans_decode_categorical_ragged_select": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _z, _vp, _z, _z, _vp, _z, _vp, _vp,
+                                                        _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_range_decode_categorical_ragged_select": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _z, _vp, _z, _z, _vp, _z, _vp, _vp,
+                                                          _vp, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_ans_decode_categorical_perfect_ragged_select": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _z, _z, _vp, _z, _z, _vp, _z,
+                                                                _vp, _vp, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_range_decode_categorical_perfect_ragged_select": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _z, _z, _vp, _z, _z, _vp,
+                                                                  _z, _vp, _vp, _vp, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
     "cst_categorical_fast_cdf_rows": (_i32, [_i32, _vp, _i32, _z, _i32, _vp, _vp, _vp]),
     "cst_categorical_fast_cdf_host": (_i32, [_i32, _vp, _i32, _z, _i32, _vp, _vp]),
     "cst_ans_encode_categorical_perfect_batch": (_i32, [CoderConfig, _vp, _vp, _i32, _i32, _z, _z, _i32, _vp, _z, _vp, _vp, _vp, _u32, _vp]),

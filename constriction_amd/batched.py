@@ -903,13 +903,15 @@ def _select_piece_counts(first: torch.Tensor, count: torch.Tensor, interval: int
 class _SelectQueries:
     """what _select_queries prepares for a select call: the queries as the entry points take them, and the output"""
     __slots__ = ("sym_offsets", "n_streams", "n_queries", "whole", "query_stream", "first", "count", "interval", "out_offsets", "piece_offsets",
-                 "total", "n_pieces", "out", "status")
+                 "total", "n_pieces", "out", "status", "max_piece")
 
 
-def _select_queries(encoded, jump, sym_offsets, streams, first, count, out) -> _SelectQueries:
+def _select_queries(encoded, jump, sym_offsets, streams, first, count, out, piece_bound=False) -> _SelectQueries:
     """The query preparation of every select call (shared-table and per-symbol models alike), once the batch's coder and the type of its
     jump table are judged: the queries as tensors, their sizes and pieces, the two prefix sums, the single read-back (the output
-    total), an upper bound of the pieces, the output and the statuses.  `jump`: the batch's table or None."""
+    total), an upper bound of the pieces, the output and the statuses.  `jump`: the batch's table or None.  `piece_bound`: also
+    `max_piece`, an upper bound of the symbols any piece decodes, dropped ones included -- the interval, or without a table the largest
+    first + count of the queries the device can accept, which travels with the output total in the same read-back."""
     r = _SelectQueries()
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
     n_streams = sym_offsets.numel() - 1
@@ -945,7 +947,13 @@ def _select_queries(encoded, jump, sym_offsets, streams, first, count, out) -> _
     piece_offsets = torch.zeros(n_queries + 1, dtype=torch.int64, device=dev)
     torch.cumsum(sizes, 0, out=out_offsets[1:])
     torch.cumsum(pieces, 0, out=piece_offsets[1:])
-    total = int(out_offsets[-1].item()) if n_queries > 0 else 0         # (the only read-back, as ans_decode_ragged reads sym_offsets[-1])
+    max_piece = interval
+    if piece_bound and not interval and n_queries > 0:
+        ends = doc if whole else torch.where((first >= 0) & (first <= doc) & (count >= 0) & (count <= doc - first), first + count,
+                                             torch.zeros_like(doc))
+        total, max_piece = (int(x) for x in torch.stack((out_offsets[-1], ends.max())).tolist())
+    else:
+        total = int(out_offsets[-1].item()) if n_queries > 0 else 0     # (the only read-back, as ans_decode_ragged reads sym_offsets[-1])
     # a query of `count` symbols has at most count // I + 2 pieces: an upper bound of the pieces, without a second read-back
     n_pieces = (total // interval + 2 * n_queries) if interval else n_queries
     if out is None:
@@ -957,6 +965,7 @@ def _select_queries(encoded, jump, sym_offsets, streams, first, count, out) -> _
     r.sym_offsets, r.n_streams, r.n_queries, r.whole, r.query_stream, r.first, r.count = sym_offsets, n_streams, n_queries, whole, query_stream, first, count
     r.interval, r.out_offsets, r.piece_offsets, r.total, r.n_pieces, r.out = interval, out_offsets, piece_offsets, total, n_pieces, out
     r.status = torch.empty(n_queries, dtype=torch.int32, device=dev)
+    r.max_piece = max_piece
     return r
 
 
@@ -1723,6 +1732,12 @@ def _decode_persymbol_ragged_select(fn_name, coder, encoded: RaggedBatch, sym_of
     jump = _ragged_jump_of(encoded, coder)
     sym_offsets, _, a, b = _gaussian_ragged_args(sym_offsets, None, a, b)
     r = _select_queries(encoded, jump, sym_offsets, streams, first, count, out)
+    return _persymbol_select_call(fn_name, coder, encoded, jump, r, (*family, int(lo), int(hi)), (_ptr(_never_null(a)), _ptr(_never_null(b))))
+
+
+def _persymbol_select_call(fn_name, coder, encoded: RaggedBatch, jump, r: _SelectQueries, front, model):
+    """a per-symbol select entry point on prepared queries: cfg, `front` (what the model puts in front of the words), the words block,
+    `model` (its arrays), the streams, the table, the queries, the scratch"""
     if r.n_queries == 0:
         return r.out[:0], r.out_offsets, r.status
     L = N.lib()
@@ -1734,9 +1749,9 @@ def _decode_persymbol_ragged_select(fn_name, coder, encoded: RaggedBatch, sym_of
     # (r.out stands in where it is empty: the entry points refuse NULL and write nothing)
     head = (*_select_tail(r)[:6], _ptr(_never_null(r.out)), _ptr(r.out_offsets))
     scratch = _ckpt_scratch("persymbol_ragged_select", encoded.words.device, L.cst_persymbol_ragged_select_scratch_bytes(r.n_pieces))
-    N.check(getattr(L, fn_name)(_cfg(*encoded.config), *family, int(lo), int(hi), _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
-                                encoded.words.numel(), _ptr(encoded.n_words), _ptr(_never_null(a)), _ptr(_never_null(b)), _ptr(r.sym_offsets),
-                                r.n_streams, *table, *head, _ptr(scratch), _ptr(r.status), _stream_ptr()), fn_name)
+    N.check(getattr(L, fn_name)(_cfg(*encoded.config), *front, _ptr(encoded.words), _ptr(encoded.word_offsets), 0, encoded.words.numel(),
+                                _ptr(encoded.n_words), *model, _ptr(r.sym_offsets), r.n_streams, *table, *head, _ptr(scratch), _ptr(r.status),
+                                _stream_ptr()), fn_name)
     return r.out[:r.total], r.out_offsets, r.status
 
 
@@ -2024,6 +2039,58 @@ def range_decode_categorical_perfect_ragged(encoded: RaggedBatch, sym_offsets, p
     a range encoder wrote.  Returns (symbols flat, status per stream); see ans_decode_categorical_perfect_ragged."""
     return _decode_categorical_ragged("cst_range_decode_categorical_perfect_ragged", "range", encoded, sym_offsets, probabilities, out, order,
                                       True)
+
+
+# ... and random access into the eight batches above: ans_decode_gaussian_ragged_select with a matrix of rows in place of the parameters
+
+def _decode_categorical_ragged_select(fn_name, coder, encoded: RaggedBatch, sym_offsets, probabilities, streams, first, count, out, perfect=False):
+    """the body of {ans,range}_decode_categorical[_perfect]_ragged_select: the queries of _select_queries on the arguments of
+    _decode_categorical_ragged.  perfect: the call also takes the longest piece, which the queries' single read-back brings along."""
+    jump = _ragged_jump_of(encoded, coder)
+    sym_offsets, _, probs, nbytes, k = _categorical_ragged_args(sym_offsets, None, probabilities, encoded.config[2], perfect)
+    r = _select_queries(encoded, jump, sym_offsets, streams, first, count, out, piece_bound=perfect)
+    n_total = int(probs.shape[0])
+    model = (_ptr(_never_null(probs)), nbytes, k, n_total) + ((int(r.max_piece),) if perfect else ())
+    return _persymbol_select_call(fn_name, coder, encoded, jump, r, (), model)
+
+
+def ans_decode_categorical_ragged_select(encoded: RaggedBatch, sym_offsets, probabilities, streams, first=None, count=None,
+                                         out: Optional[torch.Tensor] = None):
+    """Random access into a batch of ans_encode_categorical_ragged: query q decodes symbols [first[q], first[q] + count[q]) of stream
+    streams[q], and nothing else is decoded.  `probabilities`: the batch's full [n_total, K] matrix, exactly as
+    ans_decode_categorical_ragged takes it; `streams`, `first`, `count` and the three results (symbols flat int32, out_offsets int64
+    [n_queries + 1], status int32 [n_queries]) as in ans_decode_ragged_select.  With jump points (`jump_every` of the encoder) a query
+    starts at the jump point in front of `first`, decodes and discards first % interval symbols with THEIR rows, and every chunk it
+    touches runs on a lane of its own; without them it starts where its stream starts.  Only the rows from that starting point to the
+    query's end can influence anything: the rest of `probabilities` may hold anything.  A query that meets a bad row or an impossible
+    quantile, in its discarded part too, reports IMPOSSIBLE_SYMBOL (1); a refused one -- also one whose stream's rows reach beyond the
+    matrix -- INVALID_DATA (3) and writes nothing.  The same holds for all four
+    {ans,range}_decode_categorical[_perfect]_ragged_select."""
+    return _decode_categorical_ragged_select("cst_ans_decode_categorical_ragged_select", "ans", encoded, sym_offsets, probabilities, streams, first,
+                                             count, out)
+
+
+def range_decode_categorical_ragged_select(encoded: RaggedBatch, sym_offsets, probabilities, streams, first=None, count=None,
+                                           out: Optional[torch.Tensor] = None):
+    """ans_decode_categorical_ragged_select for a batch of range_encode_categorical_ragged: a piece seeks to its (pos, lower, range)
+    entry and reads forward."""
+    return _decode_categorical_ragged_select("cst_range_decode_categorical_ragged_select", "range", encoded, sym_offsets, probabilities, streams,
+                                             first, count, out)
+
+
+def ans_decode_categorical_perfect_ragged_select(encoded: RaggedBatch, sym_offsets, probabilities, streams, first=None, count=None,
+                                                 out: Optional[torch.Tensor] = None):
+    """ans_decode_categorical_ragged_select for a batch of ans_encode_categorical_perfect_ragged: only the rows the queries' pieces walk
+    are quantised, a wave each, within the row budget of ans_decode_categorical_perfect_ragged -- a selection costs what its rows cost."""
+    return _decode_categorical_ragged_select("cst_ans_decode_categorical_perfect_ragged_select", "ans", encoded, sym_offsets, probabilities,
+                                             streams, first, count, out, True)
+
+
+def range_decode_categorical_perfect_ragged_select(encoded: RaggedBatch, sym_offsets, probabilities, streams, first=None, count=None,
+                                                   out: Optional[torch.Tensor] = None):
+    """ans_decode_categorical_perfect_ragged_select for a batch of range_encode_categorical_perfect_ragged."""
+    return _decode_categorical_ragged_select("cst_range_decode_categorical_perfect_ragged_select", "range", encoded, sym_offsets, probabilities,
+                                             streams, first, count, out, True)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -11,7 +11,9 @@
 // Their JUMP forms note / start from the jump table of cst_*_gaussian_ragged_jump; the kernels that turn a table into chunks and chunk
 // statuses into stream statuses, and the host routine around them, are the model-independent ones of cst_persymbol_ragged.hpp.  A unit of its own: the instantiations
 // stay out of cst_persymbol_categorical.hip, the build's longest compile.
-#include "cst_persymbol_ragged.hpp"
+// Their SELECT forms decode pieces of queries, a lane (the perfect quantiser: a unit) per piece of
+// cst_persymbol_ragged_select.hpp's records, between the query and status kernels of cst_ragged_select.hpp.
+#include "cst_persymbol_ragged_select.hpp"
 #include "cst_categorical.hpp"
 #include "cst_persymbol_categorical.hpp"
 #include "cst_categorical_perfect.hpp"
@@ -187,6 +189,20 @@ struct CatRaggedChunkArgs {
     const uint64_t* sym_lo;          // [n chunks]: first element
     const uint32_t* len;             // [n chunks]: symbols, <= jump_interval
 };
+// SELECT form: every "stream" of the launch is a PIECE of a query, GaussianRaggedSelectArgs with rows for parameters --
+// a piece walks rows par_lo + t, t in [0, skip + len), and stores decoded symbol t >= skip at p.symbols[out_lo + (t - skip)]
+struct CatRaggedSelectArgs {
+    PerSymbolDecodeArgs p;
+    const void* probs;
+    uint64_t n_total;
+    const uint64_t* par_lo;          // [n pieces]: first row
+    const uint64_t* out_lo;          // [n pieces]: first symbol stored, in p.symbols
+    const uint32_t* skip;            // [n pieces]: symbols decoded and dropped
+    const uint32_t* len;             // [n pieces]: symbols stored (skip + len <= 2^32 - 1)
+    bool raw;                        // the pieces start from the raw state of a jump point (the call has a table)
+};
+template <int MODE>
+using CatRaggedDecodeArgsOf = std::conditional_t<MODE == kRgSelect, CatRaggedSelectArgs, std::conditional_t<MODE == kRgJump, CatRaggedChunkArgs, CatRaggedDecodeArgs>>;
 
 // behind the tile: the row that each of the wave's 64 lanes walks at this position
 constexpr size_t kCatRowTableBytes = (size_t)kWave * sizeof(uint64_t);
@@ -229,8 +245,10 @@ __device__ __forceinline__ void cat_stage_rows(F* tile, const F* __restrict__ pr
 // At position t lane r walks row sym_lo_r + t: the lanes leave their row indices in a table behind the tile, and the staging loop takes
 // row r's from there.  The loop runs to the wave's longest lane; a lane past its own length stages a row that exists (row 0: a wave
 // with a symbol to decode has one), decodes and stores nothing, and goes on taking part in the wave-wide loads, fences and votes.
-template <int W, int S, int KIND, class F, bool JUMP>
-__global__ __launch_bounds__(kWave) void decode_categorical_ragged_kernel(const std::conditional_t<JUMP, CatRaggedChunkArgs, CatRaggedDecodeArgs> ra) {
+// MODE: kRgPlain, kRgJump (a lane per table entry) or kRgSelect (a lane per piece of a query: the span below is then rows
+// [par_lo, par_lo + skip + len), and the symbols in front of `skip` run through the same loop with only their stores left out).
+template <int W, int S, int KIND, class F, int MODE>
+__global__ __launch_bounds__(kWave) void decode_categorical_ragged_kernel(const CatRaggedDecodeArgsOf<MODE> ra) {
     static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     F* tile = reinterpret_cast<F*>(smem);
@@ -241,11 +259,15 @@ __global__ __launch_bounds__(kWave) void decode_categorical_ragged_kernel(const 
     const size_t slot = (size_t)blockIdx.x * kWave + (size_t)lane;
     if (slot - lane >= a.n_streams) return;
     bool active;
-    const size_t s = ragged_lane_stream<JUMP>(ra, slot, a.n_streams, active);
+    const size_t s = ragged_lane_stream<MODE>(ra, slot, a.n_streams, active);
     const size_t se = active ? s : 0;                         // idle lanes look at stream 0's words and decode nothing
-    const CatRaggedSpan span(active ? ragged_lane_begin<JUMP>(ra, s) : 0, active ? ragged_lane_end<JUMP>(ra, s) : 0, ra.n_total);
+    const CatRaggedSpan span(active ? ragged_lane_begin<MODE>(ra, s) : 0, active ? ragged_lane_end<MODE>(ra, s) : 0, ra.n_total);
     const uint32_t len = span.len;
     const uint32_t mx = persymbol_wave_max(len);
+    // SELECT: where the lane's symbols go, and how many of the decoded ones stay out
+    uint64_t out_lo = 0;
+    uint32_t skip = 0;
+    if constexpr (MODE == kRgSelect) { out_lo = active ? ra.out_lo[s] : 0; skip = active ? ra.skip[s] : 0u; }
     const size_t K = (size_t)a.n_symbols;
     const int P = a.precision;
     const uint32_t total = 1u << P;
@@ -253,7 +275,7 @@ __global__ __launch_bounds__(kWave) void decode_categorical_ragged_kernel(const 
     const F* my = tile + lane * kCatPitch;
 
     DirectDecoder<W, S, KIND> D;
-    D.init(a, se, JUMP);                                      // (JUMP: AnsCoder::seek / RangeDecoder::seek have been done for it)
+    D.init(a, se, ragged_lane_raw<MODE>(ra));                 // (JUMP: AnsCoder::seek / RangeDecoder::seek have been done for it)
     int32_t status = D.status;
     for (uint32_t t = 0; t < mx; ++t) {
         const bool here = t < len;
@@ -310,7 +332,8 @@ __global__ __launch_bounds__(kWave) void decode_categorical_ragged_kernel(const 
             else { decoded = (int32_t)sym; D.advance(q, c, p, P); }
         }
         D.look_ahead();                                                 // (once per symbol, outside any divergent branch)
-        if (here) a.symbols[span.lo + (uint64_t)t] = decoded;
+        if constexpr (MODE == kRgSelect) { if (here && t >= skip) a.symbols[out_lo + (uint64_t)(t - skip)] = decoded; }
+        else if (here) a.symbols[span.lo + (uint64_t)t] = decoded;
     }
     if (!active) return;
     a.status[s] = span.status(status);
@@ -340,23 +363,38 @@ struct CatPerfectPieceChunkArgs : CatPerfectPieceCommon {
     const uint64_t* sym_lo;          // [n chunks]
     const uint32_t* len;
 };
+// SELECT: a unit is a piece of a query (CatRaggedSelectArgs' fields); `span` is skip + len per piece, what the quantiser's ragged mode
+// takes for a unit's length beside par_lo
+struct CatPerfectPieceSelectArgs : CatPerfectPieceCommon {
+    const uint64_t* par_lo;
+    const uint64_t* out_lo;
+    const uint32_t* skip;
+    const uint32_t* len;
+    const uint32_t* span;
+    bool raw;
+};
+template <int MODE>
+using CatPerfectPieceArgsOf =
+    std::conditional_t<MODE == kRgSelect, CatPerfectPieceSelectArgs, std::conditional_t<MODE == kRgJump, CatPerfectPieceChunkArgs, CatPerfectPieceArgs>>;
 
 // decode_rows_piece_wave_kernel (cst_persymbol.hip) for units of different lengths: one WAVE per unit, the same search over the
 // tabulated rows, symbols to symbols[lo_u + t].  A unit is initialised in the piece with t0 = 0 (JUMP: from the raw state of its jump
 // point), parked in `resume` after every piece that does not hold its last position, and FINISHED -- status written -- in the piece that
 // does; an empty or refused unit finishes in the first piece.  In the pieces after its last one its wave returns at once.  Everything a
 // wave does is uniform over its lanes (the coder's state is), so the ballots and shuffles of the search have every lane.
-template <int W, int S, int KIND, bool JUMP>
-__global__ __launch_bounds__(kBlock) void decode_rows_piece_ragged_kernel(const std::conditional_t<JUMP, CatPerfectPieceChunkArgs, CatPerfectPieceArgs> ra) {
+// MODE == kRgSelect: a unit is a piece of a query, positions [0, skip + len) over rows from par_lo on; position t >= skip goes to
+// symbols[out_lo + (t - skip)], the positions in front of it are decoded and dropped; the status goes to the piece's slot.
+template <int W, int S, int KIND, int MODE>
+__global__ __launch_bounds__(kBlock) void decode_rows_piece_ragged_kernel(const CatPerfectPieceArgsOf<MODE> ra) {
     static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
     const PerSymbolDecodeArgs& a = ra.p;
     const int lane = threadIdx.x & (kWave - 1);
     const size_t u = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (u >= ra.n_units) return;
     bool active;
-    const size_t s = ragged_lane_stream<JUMP>(ra, ra.u0 + u, a.n_streams, active);
+    const size_t s = ragged_lane_stream<MODE>(ra, ra.u0 + u, a.n_streams, active);
     if (!active) return;                                                // (a slot whose order entry names no stream)
-    const CatRaggedSpan span(ragged_lane_begin<JUMP>(ra, s), ragged_lane_end<JUMP>(ra, s), ra.n_total);
+    const CatRaggedSpan span(ragged_lane_begin<MODE>(ra, s), ragged_lane_end<MODE>(ra, s), ra.n_total);
     const bool over = (uint64_t)span.len > ra.max_len;
     const uint64_t len = over ? 0 : (uint64_t)span.len;
     if (ra.t0 != 0 && ra.t0 >= len) return;                             // finished in an earlier piece
@@ -364,10 +402,12 @@ __global__ __launch_bounds__(kBlock) void decode_rows_piece_ragged_kernel(const 
     const bool finishes = end == len;
     const int P = a.precision;
     const uint32_t n = (uint32_t)a.n_symbols;
+    uint64_t out_lo = 0, skip = 0;
+    if constexpr (MODE == kRgSelect) { out_lo = ra.out_lo[s]; skip = (uint64_t)ra.skip[s]; }
 
     DirectDecoder<W, S, KIND> D;
     int32_t status;
-    if (ra.t0 == 0) { D.init(a, s, JUMP); status = D.status; }
+    if (ra.t0 == 0) { D.init(a, s, ragged_lane_raw<MODE>(ra)); status = D.status; }
     else { const DecodeResume r = ra.resume[u]; D.resume(a, s, r); status = r.status; }
     for (uint64_t t = ra.t0; t < end && status == CST_STREAM_OK; ++t) {
         const uint32_t* row = ra.rows + ((uint64_t)u * ra.count + (t - ra.t0)) * ((uint64_t)n + 1);
@@ -392,7 +432,8 @@ __global__ __launch_bounds__(kBlock) void decode_rows_piece_ragged_kernel(const 
         const uint32_t p = nxt - c;
         // (a bad or non-converged row starts with 0xffffffff: k == 0 or c > q)
         if (p == 0 || k == 0 || c > q || (uint64_t)c + p > ((uint64_t)1 << P)) { status = CST_STREAM_IMPOSSIBLE_SYMBOL; break; }
-        if (lane == 0) a.symbols[span.lo + t] = (int32_t)(base + k - 1);
+        if constexpr (MODE == kRgSelect) { if (lane == 0 && t >= skip) a.symbols[out_lo + (t - skip)] = (int32_t)(base + k - 1); }
+        else if (lane == 0) a.symbols[span.lo + t] = (int32_t)(base + k - 1);
         D.advance(q, c, p, P);
         D.look_ahead();
     }
@@ -487,13 +528,13 @@ static cst_status encode_categorical_ragged(cst_coder_config cfg, const int32_t*
     return note_kernel(name, st);
 }
 
-template <int KIND, bool JUMP, class Args>
+template <int KIND, int MODE, class Args>
 static cst_status launch_decode_categorical_ragged(cst_coder_config cfg, const Args& a, int32_t prob_bytes, hipStream_t hs) {
     const size_t blocks = (a.p.n_streams + kWave - 1) / kWave;
     if (blocks > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
     return dispatch_word_size(cfg, [&](auto W, auto S) {
-        if (prob_bytes == 4) return launch_with_lds(decode_categorical_ragged_kernel<W, S, KIND, float, JUMP>, blocks, kWave, kCatRaggedLdsBytes<float>, a, hs);
-        return launch_with_lds(decode_categorical_ragged_kernel<W, S, KIND, double, JUMP>, blocks, kWave, kCatRaggedLdsBytes<double>, a, hs);
+        if (prob_bytes == 4) return launch_with_lds(decode_categorical_ragged_kernel<W, S, KIND, float, MODE>, blocks, kWave, kCatRaggedLdsBytes<float>, a, hs);
+        return launch_with_lds(decode_categorical_ragged_kernel<W, S, KIND, double, MODE>, blocks, kWave, kCatRaggedLdsBytes<double>, a, hs);
     });
 }
 
@@ -510,7 +551,7 @@ static cst_status decode_categorical_ragged(cst_coder_config cfg, const uint32_t
     a.p.symbols = d_symbols; a.p.n_streams = n_streams; a.p.precision = cfg.precision; a.p.min_symbol = 0; a.p.n_symbols = n_symbols;
     a.p.status = d_status;
     a.probs = d_probs; a.n_total = n_total; a.sym_offsets = d_sym_offsets; a.order = d_order;
-    return note_kernel(kCatRaggedDecodeNames[0][KIND == kRange], launch_decode_categorical_ragged<KIND, false>(cfg, a, prob_bytes, hs));
+    return note_kernel(kCatRaggedDecodeNames[0][KIND == kRange], launch_decode_categorical_ragged<KIND, kRgPlain>(cfg, a, prob_bytes, hs));
 }
 
 // the Categorical chunk decoder between the two table kernels (decode_jump_chunks, cst_persymbol_ragged.hpp)
@@ -531,7 +572,7 @@ static cst_status decode_categorical_ragged_jump(cst_coder_config cfg, const uin
         CatRaggedChunkArgs a{};
         a.p = p; a.p.min_symbol = 0; a.p.n_symbols = n_symbols;
         a.probs = d_probs; a.n_total = n_total; a.sym_lo = v.sym_lo; a.len = v.len;
-        const cst_status rc = launch_decode_categorical_ragged<KIND, true>(cfg, a, prob_bytes, hs);
+        const cst_status rc = launch_decode_categorical_ragged<KIND, kRgJump>(cfg, a, prob_bytes, hs);
         return rc == CST_OK ? rc : note_kernel(name, rc);
     });
 }
@@ -542,7 +583,7 @@ static cst_status decode_categorical_ragged_jump(cst_coder_config cfg, const uin
 // `bound` the longest unit there may be.  For every group, for every piece: tabulate, then decode; the decoders of a group are parked in
 // `resume` between its pieces.  Without the groups a table of many chunks at large K would not fit: one position of ALL units is
 // n_units (K + 1) words.  `pa`: everything but the group, the piece, the rows and the resume scratch.
-template <int KIND, bool JUMP, class PieceArgs>
+template <int KIND, int MODE, class PieceArgs>
 static cst_status decode_perfect_ragged_units(cst_coder_config cfg, PieceArgs pa, const void* d_probs, int32_t prob_bytes, uint64_t bound, hipStream_t hs) {
     const size_t n_units = pa.p.n_streams, pitch = (size_t)pa.p.n_symbols + 1;
     const size_t budget = knobs().perfect_ragged_budget;
@@ -559,7 +600,8 @@ static cst_status decode_perfect_ragged_units(cst_coder_config cfg, PieceArgs pa
     CatPerfectRaggedArgs r{};
     r.probs = d_probs; r.prob_bytes = prob_bytes; r.K = (uint32_t)pa.p.n_symbols; r.P = cfg.precision; r.rows = rows; r.pitch = pitch;
     r.n_total = pa.n_total; r.n_all = n_units; r.max_len = pa.max_len;
-    if constexpr (JUMP) { r.sym_lo = pa.sym_lo; r.len = pa.len; }
+    if constexpr (MODE == kRgSelect) { r.sym_lo = pa.par_lo; r.len = pa.span; }
+    else if constexpr (MODE == kRgJump) { r.sym_lo = pa.sym_lo; r.len = pa.len; }
     else { r.sym_offsets = pa.sym_offsets; r.order = pa.order; }
     pa.rows = rows; pa.resume = resume;
     for (size_t u0 = 0; u0 < n_units && err == hipSuccess && rc == CST_OK; u0 += units) {
@@ -572,7 +614,7 @@ static cst_status decode_perfect_ragged_units(cst_coder_config cfg, PieceArgs pa
             pa.u0 = u0; pa.n_units = n_here; pa.t0 = t0; pa.count = count;
             const dim3 grid((unsigned)((n_here * kWave + kBlock - 1) / kBlock));
             dispatch_word_size(cfg, [&](auto W, auto S) {
-                hipLaunchKernelGGL((decode_rows_piece_ragged_kernel<W, S, KIND, JUMP>), grid, dim3(kBlock), 0, hs, pa);
+                hipLaunchKernelGGL((decode_rows_piece_ragged_kernel<W, S, KIND, MODE>), grid, dim3(kBlock), 0, hs, pa);
                 return 0;
             });
             err = hipGetLastError();
@@ -599,7 +641,7 @@ static cst_status decode_categorical_perfect_ragged(cst_coder_config cfg, const 
     a.p.status = d_status;
     a.n_total = n_total; a.sym_offsets = d_sym_offsets; a.order = d_order;
     a.max_len = max_len > 0xffffffffull ? 0xffffffffull : (uint64_t)max_len;          // (a coder has at most 2^32 - 1 symbols)
-    return note_kernel(kCatPerfectRaggedDecodeNames[0][KIND == kRange], decode_perfect_ragged_units<KIND, false>(cfg, a, d_probs, prob_bytes, a.max_len, hs));
+    return note_kernel(kCatPerfectRaggedDecodeNames[0][KIND == kRange], decode_perfect_ragged_units<KIND, kRgPlain>(cfg, a, d_probs, prob_bytes, a.max_len, hs));
 }
 
 // the piece decoder over the table's entries, between the two table kernels (decode_jump_chunks): an entry has at most jump_interval symbols
@@ -620,9 +662,116 @@ static cst_status decode_categorical_perfect_ragged_jump(cst_coder_config cfg, c
         CatPerfectPieceChunkArgs a{};
         a.p = p; a.p.min_symbol = 0; a.p.n_symbols = n_symbols;
         a.n_total = n_total; a.sym_lo = v.sym_lo; a.len = v.len; a.max_len = (uint64_t)jump_interval;
-        const cst_status rc = decode_perfect_ragged_units<KIND, true>(cfg, a, d_probs, prob_bytes, (uint64_t)jump_interval, hs);
+        const cst_status rc = decode_perfect_ragged_units<KIND, kRgJump>(cfg, a, d_probs, prob_bytes, (uint64_t)jump_interval, hs);
         return rc == CST_OK ? rc : note_kernel(name, rc);
     });
+}
+
+// ---- random access: the SELECT forms of the two decoders between the kernels of cst_ragged_select.hpp ----
+static constexpr const char* kCatRaggedSelectNames[2][2] = {
+    {"ans_decode_categorical_ragged_kernel<select>", "range_decode_categorical_ragged_kernel<select>"},
+    {"ans_decode_categorical_perfect_ragged_by_rows<select>", "range_decode_categorical_perfect_ragged_by_rows<select>"}};
+
+// What the Categorical calls refuse of a query that ragged_select_queries_kernel has accepted, as a WHOLE and before it gets a piece:
+//   - a stream whose rows reach beyond the n_total rows there are: CatRaggedSpan over the stream, as the plain decoders judge it (a
+//     piece's own span, inside the decoders, then always lies inside the matrix);
+//   - the perfect quantiser: a piece longer than max_len, CST_STREAM_CAPACITY.  The longest piece of a query is its first: without a
+//     table first + count, with one first % I + count, or I where the query goes on into the next chunk.
+__global__ void cat_select_queries_kernel(const RaggedSelect b, uint64_t n_total, uint64_t max_len, int32_t* __restrict__ status) {
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= b.n_queries || status[q] != CST_STREAM_OK) return;
+    const SelectQuery r = select_query(b, q);                             // (passed once already)
+    if (r.status != CST_STREAM_OK) return;
+    int32_t st = CatRaggedSpan(b.sym_offsets[r.s], b.sym_offsets[r.s + 1], n_total).status(CST_STREAM_OK);
+    const uint64_t longest = r.count == 0 ? 0                             // (an empty query has no piece)
+                             : b.interval == 0 ? r.first + r.count : min(r.first % b.interval + r.count, (uint64_t)b.interval);
+    if (st == CST_STREAM_OK && longest > max_len) st = CST_STREAM_CAPACITY;
+    status[q] = st;
+}
+
+// the perfect quantiser's ragged mode takes a unit's rows as (first row, length): a piece's length there is skip + len
+__global__ void cat_select_spans_kernel(const uint32_t* __restrict__ skip, const uint32_t* __restrict__ len, size_t n_pieces,
+                                        uint32_t* __restrict__ span) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n_pieces) span[p] = skip[p] + len[p];                         // (<= 2^32 - 1: inside one document)
+}
+// (the spans lie behind the piece records, in the four bytes per piece that cst_persymbol_ragged_select_scratch_bytes rounds up by)
+static_assert(sizeof(cst_range_state) + 4 * 8 + 6 * 4 <= kPsSelectPieceBytes, "a piece record and its span");
+
+// decode_ragged_select (cst_persymbol_ragged_select.hip) with rows for parameters.  PERFECT: the pieces are the units of
+// decode_perfect_ragged_units, none longer than max_piece_len (with a table: than the interval).
+template <int KIND, bool PERFECT>
+static cst_status decode_categorical_ragged_select(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                   size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                                   int32_t n_symbols, size_t n_total, size_t max_piece_len, const uint64_t* d_sym_offsets,
+                                                   size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                   const uint32_t* d_jump_pos, const uint64_t* d_jump_a, const uint64_t* d_jump_b,
+                                                   const uint32_t* d_query_stream, const uint64_t* d_query_first, const uint64_t* d_query_count,
+                                                   size_t n_queries, const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                                   const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, hipStream_t hs) {
+    // a table is an interval and ALL its arrays (jump_table_bad: the jump decoders' rule), or nothing at all
+    const bool table = jump_interval != 0 || d_chunk_offsets || d_jump_pos || d_jump_a || d_jump_b;
+    if (table && (jump_table_bad<KIND>(jump_interval, d_chunk_offsets, d_jump_pos, d_jump_a, d_jump_b) || n_chunks_total > 0xffffffffull))
+        return CST_ERR_INVALID_ARGUMENT;
+    if (n_pieces_total > 0xffffffffull || (d_query_first == nullptr) != (d_query_count == nullptr)) return CST_ERR_INVALID_ARGUMENT;
+    // (every CST_ERR_INVALID_ARGUMENT in front of the plain call's CST_ERR_MODEL)
+    const cst_status plain = check_categorical_ragged_args(cfg, d_symbols_out, d_probs, prob_bytes, n_symbols, d_sym_offsets, d_words, d_word_offsets,
+                                                           stride_words, d_n_words, d_status, n_streams, PERFECT);
+    if (plain == CST_ERR_INVALID_ARGUMENT) return plain;
+    if (n_queries > 0 && (!d_query_stream || !d_piece_offsets || !d_out_offsets || !d_scratch)) return CST_ERR_INVALID_ARGUMENT;
+    if (n_queries > ((size_t)0x7fffffff) * 256) return CST_ERR_INVALID_ARGUMENT;
+    if (plain != CST_OK) return plain;
+    if (n_queries == 0) return CST_OK;
+    const char* name = kCatRaggedSelectNames[PERFECT][KIND == kRange];
+    RaggedSelect b{};
+    b.sym_offsets = d_sym_offsets; b.word_offsets = d_word_offsets; b.stride_words = stride_words; b.n_words = d_n_words; b.n_streams = n_streams;
+    // (slab form without a capacity: the slabs themselves bound every slice, as in the jump decoders)
+    b.words_capacity = words_capacity ? words_capacity : (d_word_offsets ? 0 : (uint64_t)n_streams * stride_words);
+    b.interval = (uint32_t)jump_interval; b.chunk_offsets = d_chunk_offsets; b.n_chunks_total = n_chunks_total; b.jump_pos = d_jump_pos;
+    b.query_stream = d_query_stream; b.query_first = d_query_first; b.query_count = d_query_count; b.n_queries = n_queries;
+    b.piece_offsets = d_piece_offsets; b.n_pieces_total = n_pieces_total; b.out_offsets = d_out_offsets;
+    const PerSymbolSelectPieces v(d_scratch, n_pieces_total);
+    const unsigned q_grid = (unsigned)((n_queries + 255) / 256);
+    hipLaunchKernelGGL(ragged_select_queries_kernel<0>, dim3(q_grid), dim3(256), 0, hs, b, d_status);
+    CST_HIP_TRY(hipGetLastError());
+    // (a coder has at most 2^32 - 1 symbols; with a table no piece is longer than the interval)
+    uint64_t max_len = !PERFECT || max_piece_len > 0xffffffffull ? 0xffffffffull : (uint64_t)max_piece_len;
+    if (PERFECT && jump_interval != 0 && max_len > (uint64_t)jump_interval) max_len = (uint64_t)jump_interval;
+    hipLaunchKernelGGL(cat_select_queries_kernel, dim3(q_grid), dim3(256), 0, hs, b, (uint64_t)n_total, max_len, d_status);
+    CST_HIP_TRY(hipGetLastError());
+    if (n_pieces_total > 0) {
+        const unsigned p_grid = (unsigned)((n_pieces_total + 255) / 256);
+        dispatch_word_size(cfg, [&](auto W, auto S) {
+            hipLaunchKernelGGL((persymbol_select_pieces_kernel<W, S, KIND>), dim3(p_grid), dim3(256), 0, hs, b, d_words, d_jump_a, d_jump_b, d_status, v);
+            return 0;
+        });
+        CST_HIP_TRY(hipGetLastError());
+        // (the slices handed on are absolute offsets that passed the check, or empty: the capacity bounds them once more)
+        PerSymbolDecodeArgs p{};
+        p.words = d_words; p.offsets = v.word_off; p.stride_words = 0; p.n_words = v.n_words; p.words_capacity = b.words_capacity;
+        p.symbols = d_symbols_out; p.n_streams = n_pieces_total; p.precision = cfg.precision; p.min_symbol = 0; p.n_symbols = n_symbols;
+        p.status = v.status; p.state = v.state; p.rstate = v.rstate;
+        cst_status rc;
+        if constexpr (PERFECT) {
+            uint32_t* span = reinterpret_cast<uint32_t*>(v.status + n_pieces_total);
+            hipLaunchKernelGGL(cat_select_spans_kernel, dim3(p_grid), dim3(256), 0, hs, v.skip, v.len, n_pieces_total, span);
+            CST_HIP_TRY(hipGetLastError());
+            CatPerfectPieceSelectArgs a{};
+            a.p = p; a.n_total = n_total; a.par_lo = v.par_lo; a.out_lo = v.out_lo; a.skip = v.skip; a.len = v.len; a.span = span;
+            a.raw = jump_interval != 0;
+            a.max_len = max_len;
+            rc = decode_perfect_ragged_units<KIND, kRgSelect>(cfg, a, d_probs, prob_bytes, a.max_len, hs);
+        } else {
+            CatRaggedSelectArgs a{};
+            a.p = p; a.probs = d_probs; a.n_total = n_total; a.par_lo = v.par_lo; a.out_lo = v.out_lo; a.skip = v.skip; a.len = v.len;
+            a.raw = jump_interval != 0;
+            rc = launch_decode_categorical_ragged<KIND, kRgSelect>(cfg, a, prob_bytes, hs);
+        }
+        if (rc != CST_OK) return note_kernel(name, rc);
+    }
+    hipLaunchKernelGGL(ragged_select_status_kernel<0>, dim3(q_grid), dim3(256), 0, hs, b, v.folded(), d_status);
+    CST_HIP_TRY(hipGetLastError());
+    return note_kernel(name, CST_OK);
 }
 
 } // namespace cst
@@ -795,6 +944,73 @@ cst_status cst_range_decode_categorical_perfect_ragged_jump(cst_coder_config cfg
                                                           n_symbols, n_total, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets,
                                                           n_chunks_total, d_jump_pos, d_jump_lower, d_jump_range, d_scratch, d_status,
                                                           (hipStream_t)stream);
+}
+
+// ---- random access: the words, the plain decode's model arguments (the perfect pair: max_piece_len after n_total), the streams, the
+// table (all zero / NULL: none), the queries ----
+
+cst_status cst_ans_decode_categorical_ragged_select(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                    size_t words_capacity, const uint32_t* d_n_words, const void* d_probs, int32_t prob_bytes,
+                                                    int32_t n_symbols, size_t n_total, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                    size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                    const uint32_t* d_jump_pos, const uint64_t* d_jump_state, const uint32_t* d_query_stream,
+                                                    const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                                    const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                                    const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    return decode_categorical_ragged_select<kAns, false>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes,
+                                                         n_symbols, n_total, 0, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+                                                         d_jump_pos, d_jump_state, nullptr, d_query_stream, d_query_first, d_query_count, n_queries,
+                                                         d_piece_offsets, n_pieces_total, d_symbols_out, d_out_offsets, d_scratch, d_status,
+                                                         (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_categorical_ragged_select(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                      size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const void* d_probs,
+                                                      int32_t prob_bytes, int32_t n_symbols, size_t n_total, const uint64_t* d_sym_offsets,
+                                                      size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                      const uint32_t* d_jump_pos, const uint64_t* d_jump_lower, const uint64_t* d_jump_range,
+                                                      const uint32_t* d_query_stream, const uint64_t* d_query_first, const uint64_t* d_query_count,
+                                                      size_t n_queries, const uint64_t* d_piece_offsets, size_t n_pieces_total,
+                                                      int32_t* d_symbols_out, const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status,
+                                                      void* stream) {
+    return decode_categorical_ragged_select<kRange, false>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes,
+                                                           n_symbols, n_total, 0, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets,
+                                                           n_chunks_total, d_jump_pos, d_jump_lower, d_jump_range, d_query_stream, d_query_first,
+                                                           d_query_count, n_queries, d_piece_offsets, n_pieces_total, d_symbols_out, d_out_offsets,
+                                                           d_scratch, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_categorical_perfect_ragged_select(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                            size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                            const void* d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                            size_t max_piece_len, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                            size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                            const uint32_t* d_jump_pos, const uint64_t* d_jump_state, const uint32_t* d_query_stream,
+                                                            const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                                            const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                                            const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    return decode_categorical_ragged_select<kAns, true>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes,
+                                                        n_symbols, n_total, max_piece_len, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets,
+                                                        n_chunks_total, d_jump_pos, d_jump_state, nullptr, d_query_stream, d_query_first, d_query_count,
+                                                        n_queries, d_piece_offsets, n_pieces_total, d_symbols_out, d_out_offsets, d_scratch, d_status,
+                                                        (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_categorical_perfect_ragged_select(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                              size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                              const void* d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                              size_t max_piece_len, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                              size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                              const uint32_t* d_jump_pos, const uint64_t* d_jump_lower, const uint64_t* d_jump_range,
+                                                              const uint32_t* d_query_stream, const uint64_t* d_query_first,
+                                                              const uint64_t* d_query_count, size_t n_queries, const uint64_t* d_piece_offsets,
+                                                              size_t n_pieces_total, int32_t* d_symbols_out, const uint64_t* d_out_offsets,
+                                                              void* d_scratch, int32_t* d_status, void* stream) {
+    return decode_categorical_ragged_select<kRange, true>(cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_probs, prob_bytes,
+                                                          n_symbols, n_total, max_piece_len, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets,
+                                                          n_chunks_total, d_jump_pos, d_jump_lower, d_jump_range, d_query_stream, d_query_first,
+                                                          d_query_count, n_queries, d_piece_offsets, n_pieces_total, d_symbols_out, d_out_offsets,
+                                                          d_scratch, d_status, (hipStream_t)stream);
 }
 
 } // extern "C"

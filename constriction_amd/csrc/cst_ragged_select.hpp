@@ -10,7 +10,8 @@
 //                                     table entry, skip, length, output position and its stream's checked slice of the words -> scratch;
 //   3. ragged_select_status_kernel    one thread per query: the worst of its pieces' statuses.
 // The kernels are templates so that each translation unit that launches them carries its own copy (no relocatable device code):
-// cst_ans_ragged.hip, cst_range_ragged.hip, and cst_persymbol_ragged_select.hip, whose pieces carry more (its own piece builder).
+// cst_ans_ragged.hip, cst_range_ragged.hip, and cst_persymbol_ragged_select.hip and cst_persymbol_categorical_ragged.hip, whose pieces
+// carry more (their own piece builder, cst_persymbol_ragged_select.hpp).
 #pragma once
 #include "cst_common.hpp"
 

@@ -545,8 +545,8 @@ cst_status cst_range_decode_family_ragged_jump(cst_coder_config cfg, int32_t fam
  *     of the _jump decoders (jump_interval not a multiple of 16 or > 2^31 - 1, a NULL d_chunk_offsets or table array, n_chunks_total >
  *     2^32 - 1); table arrays without an interval; n_pieces_total > 2^32 - 1; exactly one of d_query_first / d_query_count NULL; with
  *     n_queries > 0 a NULL d_query_stream, d_piece_offsets, d_out_offsets or d_scratch; an unknown family.
- * cst_last_kernel_name(): {ans,range}_decode_{gaussian,laplace,cauchy}_ragged_kernel<select>.  (The Categorical ragged decoders have no
- * select form.) */
+ * cst_last_kernel_name(): {ans,range}_decode_{gaussian,laplace,cauchy}_ragged_kernel<select>.  (The Categorical ragged decoders:
+ * cst_{ans,range}_decode_categorical[_perfect]_ragged_select, with those calls.) */
 size_t cst_persymbol_ragged_select_scratch_bytes(size_t n_pieces_total);
 cst_status cst_ans_decode_gaussian_ragged_select(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                                  const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
@@ -1301,6 +1301,75 @@ cst_status cst_range_decode_categorical_perfect_ragged_jump(cst_coder_config cfg
                                                             size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
                                                             const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
                                                             const uint64_t *d_jump_range, void *d_scratch, int32_t *d_status, void *stream);
+
+/* Random access into a ragged per-symbol Categorical batch, both quantisers: cst_{ans,range}_decode_gaussian_ragged_select (above) with
+ * "parameters" read as "rows".  The arguments follow those calls block by block: cfg (no min_symbol / max_symbol); the words block; the
+ * model arguments of cst_*_decode_categorical_ragged -- d_probs, prob_bytes, n_symbols, n_total: the batch's FULL [n_total][K] matrix,
+ * laid out as the plain decode call takes it; the perfect pair only: max_piece_len; d_sym_offsets, n_streams; the table block (all
+ * zero / NULL: no table); the query block and the tail, unchanged.
+ *   - Piece j of a query reads rows from row d_sym_offsets[s] + (first / jump_interval + j) * jump_interval on (d_sym_offsets[s] without
+ *     a table), decodes and drops its first symbols with THEIR rows and stores the rest at its place in the ragged output.  ONLY rows
+ *     [that first row, d_sym_offsets[s] + first + count) of a query can influence any result or status: everything else in d_probs may
+ *     hold anything (NaN included).
+ *   - max_piece_len (the perfect pair): an upper bound of (symbols dropped + symbols stored) over all pieces -- with a table at most
+ *     jump_interval (larger values are clamped to it), without one max(first + count) -- the role max_len has in
+ *     cst_*_decode_categorical_perfect_ragged: the host loop runs without a read-back.  A piece longer than max_piece_len makes its
+ *     query report CST_STREAM_CAPACITY and write nothing.  The rows are tabulated for groups of pieces within the 64 MiB of the plain
+ *     perfect decoders (CST_PERFECT_RAGGED_BUDGET).
+ *   - Statuses, one per QUERY.  Refused before decoding, nothing written: CST_STREAM_INVALID_DATA for every query
+ *     cst_{ans,range}_decode_ragged_select refuse, and for a query whose stream's rows reach beyond n_total.  Failing while decoding: a
+ *     query that meets a bad row or an impossible quantile, in its dropped part too, reports CST_STREAM_IMPOSSIBLE_SYMBOL and may leave
+ *     anything inside its own output slice, nothing outside it.  The other queries are unaffected either way.
+ *   - d_scratch: cst_persymbol_ragged_select_scratch_bytes(n_pieces_total) bytes, for all four.
+ *   - CST_ERR_INVALID_ARGUMENT, then CST_ERR_MODEL, before the device is touched: every refusal of the plain Categorical ragged decode
+ *     call of the same quantiser (d_symbols_out in the place of d_symbols; prob_bytes outside {4, 8}; its limits of K); with a table,
+ *     every refusal of the _jump decoders; table arrays without an interval; n_pieces_total > 2^32 - 1; exactly one of d_query_first /
+ *     d_query_count NULL; with n_queries > 0 a NULL d_query_stream, d_piece_offsets, d_out_offsets or d_scratch.  n_queries == 0
+ *     returns CST_OK and launches nothing.
+ * cst_last_kernel_name(): {ans,range}_decode_categorical_ragged_kernel<select>,
+ * {ans,range}_decode_categorical_perfect_ragged_by_rows<select>. */
+cst_status cst_ans_decode_categorical_ragged_select(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                    size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                    const void *d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                    const uint64_t *d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                    const uint64_t *d_chunk_offsets, size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                                    const uint64_t *d_jump_state, const uint32_t *d_query_stream,
+                                                    const uint64_t *d_query_first, const uint64_t *d_query_count, size_t n_queries,
+                                                    const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
+                                                    const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status, void *stream);
+cst_status cst_range_decode_categorical_ragged_select(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                      size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                      const void *d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                      const uint64_t *d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                      const uint64_t *d_chunk_offsets, size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                                      const uint64_t *d_jump_lower, const uint64_t *d_jump_range,
+                                                      const uint32_t *d_query_stream, const uint64_t *d_query_first,
+                                                      const uint64_t *d_query_count, size_t n_queries, const uint64_t *d_piece_offsets,
+                                                      size_t n_pieces_total, int32_t *d_symbols_out, const uint64_t *d_out_offsets,
+                                                      void *d_scratch, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_categorical_perfect_ragged_select(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                            size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                            const void *d_probs, int32_t prob_bytes, int32_t n_symbols, size_t n_total,
+                                                            size_t max_piece_len, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                            size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                            const uint32_t *d_jump_pos, const uint64_t *d_jump_state,
+                                                            const uint32_t *d_query_stream, const uint64_t *d_query_first,
+                                                            const uint64_t *d_query_count, size_t n_queries,
+                                                            const uint64_t *d_piece_offsets, size_t n_pieces_total,
+                                                            int32_t *d_symbols_out, const uint64_t *d_out_offsets, void *d_scratch,
+                                                            int32_t *d_status, void *stream);
+cst_status cst_range_decode_categorical_perfect_ragged_select(cst_coder_config cfg, const uint32_t *d_words,
+                                                              const uint64_t *d_word_offsets, size_t stride_words, size_t words_capacity,
+                                                              const uint32_t *d_n_words, const void *d_probs, int32_t prob_bytes,
+                                                              int32_t n_symbols, size_t n_total, size_t max_piece_len,
+                                                              const uint64_t *d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                              const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                              const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
+                                                              const uint64_t *d_jump_range, const uint32_t *d_query_stream,
+                                                              const uint64_t *d_query_first, const uint64_t *d_query_count,
+                                                              size_t n_queries, const uint64_t *d_piece_offsets, size_t n_pieces_total,
+                                                              int32_t *d_symbols_out, const uint64_t *d_out_offsets, void *d_scratch,
+                                                              int32_t *d_status, void *stream);
 
 /* ABI 5: jump points for the per-symbol Gaussian calls of the RANGE coder (RangeEncoder::pos / RangeDecoder::seek, src/stream/queue.rs:172-196,
  * 900-926), as cst_ans_{encode,decode}_gaussian_batch_ckpt are for ANS: the fused encoder notes (words emitted including held-back ones,

@@ -9,8 +9,8 @@
 --jump-every N (a multiple of 16; default 0: not run): also (j) the same batch with a jump point every N symbols of every stream --
 `jump_every=N` of the encoder, and the decode of all chunks side by side -- timed beside the plain pair of (a) in the same run,
 alternating; recorded per alternation, with the size of the table against the words.  No condition on it.
---select N (default 0: not run; not with --family categorical): also (s) random access through
-batched.{coder}_decode_{family}_ragged_select on the batch of (a) -- with --jump-every's table where that is given -- timed in the same
+--select N (default 0: not run): also (s) random access through
+batched.{coder}_decode_{family}[_perfect]_ragged_select on the batch of (a) -- with --jump-every's table where that is given -- timed in the same
 run, alternating: N whole streams drawn at random through the select call; the full decode (whole streams, and through the jump table)
 followed by a device gather of the same streams (the gather's index is built beforehand and not timed), which is all a caller had
 before; N ranges of 64 symbols at random depths with the table and without it; and ALL streams in order through the select call beside
@@ -48,7 +48,6 @@ ap.add_argument("--skip-grouped", action="store_true", help="leave (b), one rect
 args = ap.parse_args()
 assert args.alternations >= 5 or args.streams < 16384, "the recorded figures are medians of at least five alternations"
 assert not args.perfect or args.family == "categorical", "--perfect goes with --family categorical"
-assert not args.select or args.family != "categorical", "--select: the Categorical ragged decoders have no select form"
 
 CFG, LO, HI = (32, 64, 24), -100, 100
 torch.manual_seed(1)
@@ -59,6 +58,7 @@ enc_rect, dec_rect = getattr(B, f"{args.coder}_encode_{args.family}"), getattr(B
 if args.perfect:
     enc_rect, dec_rect = functools.partial(enc_rect, perfect=True), functools.partial(dec_rect, perfect=True)
 JUMP_KERNEL = f"{args.coder}_decode_categorical_perfect_ragged_by_rows<jump>" if args.perfect else f"{args.coder}_decode_{args.family}_ragged_kernel<jump>"
+SELECT_KERNEL = JUMP_KERNEL.replace("<jump>", "<select>")
 NO_JUMP = {"jump_points": 0} if args.family == "gaussian" else {}      # (the family calls have no jump points to switch off)
 CATEGORICAL = args.family == "categorical"
 HEAD = () if CATEGORICAL else (LO, HI)                                  # what the calls take in front of the model's tensors
@@ -196,7 +196,7 @@ if args.jump_every:
 # ---- (s): random access, beside the full decode and a gather ----
 ok_s, t_s, select_info = True, {}, None
 if args.select:
-    sel_ragged = getattr(B, f"{args.coder}_decode_{args.family}_ragged_select")
+    sel_ragged = getattr(B, f"{args.coder}_decode_{FORM}_ragged_select")
     enc_t = enc_j if args.jump_every else enc                   # the batch with its table, where one was asked for
     enc_0 = enc                                                 # ... and the same words without one
     q_streams = torch.randint(0, n, (args.select,), dtype=torch.int64, device=dev)
@@ -222,7 +222,7 @@ if args.select:
               (sel_ragged(enc_0, offsets, *HEAD, *model, q_streams, q_first, q_count), want_range),
               (sel_ragged(enc_t, offsets, *HEAD, *model, every_stream, out=out_all), sym)]
     torch.cuda.synchronize()
-    ok_s = B.last_kernel() == f"{args.coder}_decode_{args.family}_ragged_kernel<select>" and \
+    ok_s = B.last_kernel() == SELECT_KERNEL and \
         all(bool(torch.equal(got, want)) and int(status.abs().sum()) == 0 for (got, _, status), want in checks)
     del checks
     candidates = {"select_whole": lambda: sel_ragged(enc_t, offsets, *HEAD, *model, q_streams),
