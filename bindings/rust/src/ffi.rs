@@ -3097,6 +3097,99 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    /// HOST function, needs no device.  Slab stride (in words) that holds any stream of n_per_stream symbols: every codeword 2 B + 1 bits,
+    /// the up to 31 bits a continued call (d_cont) starts with and the seal, rounded up to whole 64-byte units.  0 for a bad argument.
+    pub fn cst_exp_golomb_max_words(n_per_stream: usize, symbol_bytes: i32, semantics: i32) -> usize;
+
+    /// d_n_bits[s] (uint64 [n_streams]) = the exact bits of stream s, without a seal: what the encoders below report as d_n_bits, and
+    /// what sizes exact slabs for them (a stack needs one bit more).  d_sym_offsets (uint64 [n_streams + 1]) as in the ragged calls, or
+    /// NULL for a matrix [n_streams][n_per_stream]; a range that runs backwards counts 0.  cst_last_kernel_name:
+    /// "exp_golomb_count_bits_kernel".
+    pub fn cst_exp_golomb_count_bits(
+        d_symbols: *const c_void,
+        symbol_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        n_per_stream: usize,
+        d_n_bits: *mut u64,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// cst_huffman_encode_batch / cst_huffman_decode_batch without a codebook: the same slabs or packed words (d_offsets), words_capacity,
+    /// d_n_bits, d_cont (partial | nbits << 32; for the queue decoder the read position in bits) and d_n_words_out.
+    /// cst_last_kernel_name: "exp_golomb_encode_kernel" / "exp_golomb_decode_kernel".
+    pub fn cst_exp_golomb_encode_batch(
+        semantics: i32,
+        d_symbols: *const c_void,
+        symbol_bytes: i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_n_bits: *mut u64,
+        d_cont: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_exp_golomb_decode_batch(
+        semantics: i32,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_symbols: *mut c_void,
+        symbol_bytes: i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        d_cont: *mut u64,
+        d_n_words_out: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// Streams of different lengths, the layout of cst_ans_encode_ragged / cst_ans_decode_ragged without a model:
+    ///     symbols of stream s = d_symbols[d_sym_offsets[s] .. d_sym_offsets[s + 1])      (flat, of symbol_bytes each)
+    ///     slab of stream s    = d_words[d_word_offsets[s] .. d_word_offsets[s + 1])      or, with d_word_offsets = NULL,
+    ///                           d_words[s * stride_words .. + stride_words)
+    /// One lane codes one stream; a wave of 64 consecutive streams runs as long as its longest one.  d_n_bits (may be NULL) as above.  A
+    /// stream of length 0 yields 0 words (a stack: its seal, 1 word) and CST_STREAM_OK.  A symbol range that runs backwards or exceeds
+    /// 2^32 - 1 symbols: CST_STREAM_CAPACITY from the encoder, CST_STREAM_INVALID_DATA (nothing written) from the decoder; word offsets
+    /// that run backwards are a slab of no words.  The decoder reads d_word_offsets[s] and d_n_words[s] only and checks them against
+    /// words_capacity as cst_ans_decode_batch does.  cst_last_kernel_name: "exp_golomb_encode_ragged_kernel" /
+    /// "exp_golomb_decode_ragged_kernel".
+    pub fn cst_exp_golomb_encode_ragged(
+        semantics: i32,
+        d_symbols: *const c_void,
+        symbol_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_n_bits: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_exp_golomb_decode_ragged(
+        semantics: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_symbols: *mut c_void,
+        symbol_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// bit-exact f64 special functions on device (test hooks for the model kernels)
     /// out[i] = erf(x[i]) resp. Gaussian cdf, evaluated by the same device code the table kernels use.
     pub fn cst_debug_erf(d_x: *const f64, d_out: *mut f64, n: usize, stream: *mut c_void) -> CstStatus;

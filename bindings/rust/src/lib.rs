@@ -6212,3 +6212,122 @@ impl Drop for HuffmanCodebook {
         unsafe { ffi::cst_huffman_codebook_destroy(self.raw) };
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Exponential-Golomb symbol codes (constriction::symbol::exp_golomb)
+// ---------------------------------------------------------------------------------------------------------------------
+
+/// Zero-sized marker for Exponential-Golomb coding of `u32` symbols (`symbol::exp_golomb::ExpGolomb::<u32>`): there is no codebook to
+/// build.  Symbols travel as the bit pattern of `i32`, so `-1` is `u32::MAX`.  The batch calls stand beside those of
+/// [`HuffmanCodebook`] and fill the same [`HuffmanBatch`].
+#[derive(Clone, Copy, Debug, Default)]
+pub struct ExpGolomb;
+
+impl ExpGolomb {
+    pub fn new() -> Self {
+        ExpGolomb
+    }
+
+    /// Slab stride that holds any stream of `n_per_stream` symbols (every codeword 65 bits).
+    pub fn max_words(&self, n_per_stream: usize, semantics: SymbolSemantics) -> usize {
+        unsafe { ffi::cst_exp_golomb_max_words(n_per_stream, 4, semantics as i32) }
+    }
+
+    /// The exact bits of every row of the stream-major `symbols` matrix, without a stack's seal: sizes exact slabs.
+    pub fn count_bits(&self, symbols: &DeviceBuffer<i32>, n_streams: usize, n_per_stream: usize, stream: &Stream) -> Result<DeviceBuffer<u64>> {
+        if symbols.len() < n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)? {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_bits: DeviceBuffer<u64> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_exp_golomb_count_bits(symbols.as_ptr() as *const c_void, 4, core::ptr::null(), n_streams, n_per_stream,
+                                           n_bits.as_mut_ptr(), stream.as_raw())
+        })?;
+        Ok(n_bits)
+    }
+
+    /// One container per row of the stream-major `symbols` matrix (`n_streams` rows of `n_per_stream`), each sealed / flushed, in
+    /// slabs of `stride_words` (`max_words`, or what `count_bits` says the longest stream needs: CAPACITY for a stream that does
+    /// not fit).
+    pub fn encode(&self, symbols: &DeviceBuffer<i32>, n_streams: usize, n_per_stream: usize, semantics: SymbolSemantics,
+                  stride_words: usize, stream: &Stream) -> Result<HuffmanBatch> {
+        if symbols.len() < n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)? {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = HuffmanBatch {
+            words: DeviceBuffer::new(n_streams.checked_mul(stride_words).ok_or(Error::InvalidArgument)?)?,
+            n_words: DeviceBuffer::new(n_streams)?,
+            n_bits: DeviceBuffer::new(n_streams)?,
+            status: DeviceBuffer::new(n_streams)?,
+            stride_words,
+            n_streams,
+            semantics,
+        };
+        check(unsafe {
+            ffi::cst_exp_golomb_encode_batch(semantics as i32, symbols.as_ptr() as *const c_void, 4, n_streams, n_per_stream,
+                                             out.words.as_mut_ptr(), stride_words, out.n_words.as_mut_ptr(), out.n_bits.as_mut_ptr(),
+                                             core::ptr::null_mut(), out.status.as_mut_ptr(), stream.as_raw())
+        })?;
+        Ok(out)
+    }
+
+    /// `n_per_stream` symbols of every stream of `batch`; writes `symbols` (stream-major) and one status per stream
+    /// (`INVALID_DATA` for an invalid codeword, the symbols from there on 0).
+    pub fn decode(&self, batch: &HuffmanBatch, n_per_stream: usize, symbols: &mut DeviceBuffer<i32>, status: &mut DeviceBuffer<i32>,
+                  stream: &Stream) -> Result<()> {
+        if symbols.len() < batch.n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)? || status.len() < batch.n_streams {
+            return Err(Error::InvalidArgument);
+        }
+        check(unsafe {
+            ffi::cst_exp_golomb_decode_batch(batch.semantics as i32, batch.words.as_ptr(), core::ptr::null(), batch.stride_words,
+                                             batch.words.len(), batch.n_words.as_ptr(), symbols.as_mut_ptr() as *mut c_void, 4,
+                                             batch.n_streams, n_per_stream, core::ptr::null_mut(), core::ptr::null_mut(),
+                                             status.as_mut_ptr(), stream.as_raw())
+        })
+    }
+
+    /// Streams of different lengths in one launch: stream `s` owns `[sym_offsets[s], sym_offsets[s + 1])` of the flat `symbols` and
+    /// writes into the slab `[word_offsets[s], word_offsets[s + 1])` of `words`.  Returns (n_words, n_bits, status) per stream.
+    ///
+    /// # Safety
+    /// The offsets are DEVICE memory: this wrapper cannot check them.  Every `sym_offsets` pair must lie inside `symbols`, every
+    /// slab inside `words`, in ascending order.
+    pub unsafe fn encode_ragged(&self, symbols: &DeviceBuffer<i32>, sym_offsets: &DeviceBuffer<u64>, word_offsets: &DeviceBuffer<u64>,
+                                words: &mut DeviceBuffer<u32>, semantics: SymbolSemantics, stream: &Stream)
+                                -> Result<(DeviceBuffer<u32>, DeviceBuffer<u64>, DeviceBuffer<i32>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut n_bits: DeviceBuffer<u64> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_exp_golomb_encode_ragged(semantics as i32, symbols.as_ptr() as *const c_void, 4, sym_offsets.as_ptr(), n_streams,
+                                              words.as_mut_ptr(), word_offsets.as_ptr(), 0, n_words.as_mut_ptr(), n_bits.as_mut_ptr(),
+                                              status.as_mut_ptr(), stream.as_raw())
+        })?;
+        Ok((n_words, n_bits, status))
+    }
+
+    /// The decoder of [`ExpGolomb::encode_ragged`].
+    ///
+    /// # Safety
+    /// `sym_offsets` (device memory) must delimit ranges inside `symbols`.  The word slices ARE checked on the device against
+    /// `words.len()`.
+    pub unsafe fn decode_ragged(&self, words: &DeviceBuffer<u32>, word_offsets: &DeviceBuffer<u64>, n_words: &DeviceBuffer<u32>,
+                                sym_offsets: &DeviceBuffer<u64>, symbols: &mut DeviceBuffer<i32>, semantics: SymbolSemantics,
+                                stream: &Stream) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_exp_golomb_decode_ragged(semantics as i32, words.as_ptr(), word_offsets.as_ptr(), 0, words.len(), n_words.as_ptr(),
+                                              symbols.as_mut_ptr() as *mut c_void, 4, sym_offsets.as_ptr(), n_streams,
+                                              status.as_mut_ptr(), stream.as_raw())
+        })?;
+        Ok(status)
+    }
+}

@@ -36,6 +36,7 @@ FLAG_PACKED_W16 = 4
 CODER_ANS, CODER_RANGE = 0, 1
 
 HUFFMAN_STACK, HUFFMAN_QUEUE = 0, 1
+SYMBOL_STACK, SYMBOL_QUEUE = HUFFMAN_STACK, HUFFMAN_QUEUE    # (the same containers under any symbol code)
 HUFFMAN_MAX_SYMBOLS = 65536
 CATEGORICAL_PERFECT_MAX_K = 1024   # CST_CATEGORICAL_PERFECT_MAX_K: the slots of the device quantiser
 
@@ -249,6 +250,12 @@ SIGNATURES = {
     "cst_huffman_max_words": (_z, [_vp, _z, _i32]),
     "cst_huffman_encode_batch": (_i32, [_vp, _i32, _vp, _i32, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
     "cst_huffman_decode_batch": (_i32, [_vp, _i32, _vp, _vp, _z, _z, _vp, _vp, _i32, _z, _z, _vp, _vp, _vp, _vp]),
+    "cst_exp_golomb_max_words": (_z, [_z, _i32, _i32]),
+    "cst_exp_golomb_count_bits": (_i32, [_vp, _i32, _vp, _z, _z, _vp, _vp]),
+    "cst_exp_golomb_encode_batch": (_i32, [_i32, _vp, _i32, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_exp_golomb_decode_batch": (_i32, [_i32, _vp, _vp, _z, _z, _vp, _vp, _i32, _z, _z, _vp, _vp, _vp, _vp]),
+    "cst_exp_golomb_encode_ragged": (_i32, [_i32, _vp, _i32, _vp, _z, _vp, _vp, _z, _vp, _vp, _vp, _vp]),
+    "cst_exp_golomb_decode_ragged": (_i32, [_i32, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _vp, _vp]),
     "cst_debug_erf": (_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_tab": (_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_fast": (_i32, [_i32, _vp, _vp, _z, _vp]),

@@ -1,9 +1,11 @@
-"""`constriction.symbol`, computed on the MI355X: `StackCoder`, `QueueEncoder`, `QueueDecoder` and the `huffman` codebooks.
+"""`constriction.symbol`, computed on the MI355X: `StackCoder`, `QueueEncoder`, `QueueDecoder`, the `huffman` codebooks and the
+`exp_golomb` code.
 
 Mirror of src/pybindings/symbol/mod.rs (same constructors, method names, return dtypes and error types).  Each object keeps
 the reference's bit container on the host -- whole u32 words plus the partial word and its bit count (src/symbol/mod.rs:
 StackCoder / QueueEncoder / QueueDecoder) -- and all coding runs in the batched kernels (csrc/cst_huffman.hip) as one-stream
-launches that continue from that container (`d_cont`).  Consecutive `encode_symbol` calls are buffered and coded in one launch
+launches that continue from that container (`d_cont`); an `exp_golomb.ExpGolomb` codebook runs the kernels of
+csrc/cst_exp_golomb.hip on the same container, and the two kinds may alternate.  Consecutive `encode_symbol` calls are buffered and coded in one launch
 when the container is observed (`get_compressed*`, `decode_symbol`, `get_decoder`) or the codebook changes; every
 `decode_symbol` is one device round trip.  There is no CPU fallback."""
 from __future__ import annotations
@@ -13,10 +15,13 @@ import torch
 
 from .. import _native as N
 from ..batched import _ptr, _stream_ptr
-from . import huffman  # noqa: F401
+from . import exp_golomb, huffman  # noqa: F401
+from .exp_golomb import ExpGolomb
 from .huffman import DecoderHuffmanTree, EncoderHuffmanTree
 
 _OUT_OF_DATA = "Ran out of bits in compressed data."
+_INVALID_CODEWORD = "Invalid codeword for Exp-Golomb code."
+_EG_DTYPES = {1: (np.uint8, np.uint8), 2: (np.uint16, np.int16), 4: (np.uint32, np.int32)}     # symbol_bytes -> (unsigned, tensor type)
 
 
 def _as_words(compressed) -> np.ndarray:
@@ -27,13 +32,17 @@ def _as_words(compressed) -> np.ndarray:
 
 
 def _check_symbol(symbol, codebook) -> int:
-    if not isinstance(codebook, EncoderHuffmanTree):
-        raise TypeError("codebook must be a constriction_amd.symbol.huffman.EncoderHuffmanTree")
+    if not isinstance(codebook, (EncoderHuffmanTree, ExpGolomb)):
+        raise TypeError("codebook must be a constriction_amd.symbol.huffman.EncoderHuffmanTree or an exp_golomb.ExpGolomb")
     if isinstance(symbol, (bool, np.bool_)) or not isinstance(symbol, (int, np.integer)):
         raise TypeError(f"symbol must be an unsigned integer, not {type(symbol).__name__}")
     symbol = int(symbol)
     if symbol < 0:
         raise OverflowError("can't convert negative int to unsigned")
+    if isinstance(codebook, ExpGolomb):
+        if symbol >= codebook.num_symbols():
+            raise OverflowError(f"symbol does not fit an unsigned integer of {codebook.bits} bits")
+        return symbol
     if symbol >= codebook.num_symbols():
         raise KeyError("Tried to encode symbol that has zero probability under entropy model.")   # ImpossibleSymbol
     return symbol
@@ -47,17 +56,26 @@ def _encode(codebook, semantics, symbols, partial, nbits):
     """one launch: the buffered symbols (already in kernel order) after the partial word -> (completed words, partial, nbits)"""
     dev = _device()
     k = len(symbols)
-    sym = torch.tensor(symbols, dtype=torch.int32).to(dev).view(1, k)
+    eg = isinstance(codebook, exp_golomb._Code)
+    if eg:
+        unsigned, signed = _EG_DTYPES[codebook.symbol_bytes]
+        sym = torch.from_numpy(np.array(symbols, dtype=unsigned).view(signed)).to(dev).view(1, k)
+    else:
+        sym = torch.tensor(symbols, dtype=torch.int32).to(dev).view(1, k)
     stride = codebook.max_words(k, "stack" if semantics == N.HUFFMAN_STACK else "queue")
     words = torch.empty(stride, dtype=torch.int32, device=dev)
     n_words = torch.empty(1, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
     cont = torch.tensor([partial | (nbits << 32)], dtype=torch.int64).to(dev)
-    N.check(N.lib().cst_huffman_encode_batch(codebook._h, semantics, _ptr(sym), 4, 1, k, _ptr(words), stride, _ptr(n_words), None,
-                                             _ptr(cont), _ptr(status), _stream_ptr()), "cst_huffman_encode_batch")
+    if eg:
+        N.check(N.lib().cst_exp_golomb_encode_batch(semantics, _ptr(sym), codebook.symbol_bytes, 1, k, _ptr(words), stride, _ptr(n_words),
+                                                    None, _ptr(cont), _ptr(status), _stream_ptr()), "cst_exp_golomb_encode_batch")
+    else:
+        N.check(N.lib().cst_huffman_encode_batch(codebook._h, semantics, _ptr(sym), 4, 1, k, _ptr(words), stride, _ptr(n_words), None,
+                                                 _ptr(cont), _ptr(status), _stream_ptr()), "cst_huffman_encode_batch")
     st = int(status.cpu()[0])
     if st != N.STREAM_OK:
-        raise RuntimeError(f"Huffman encoder: stream status {st}")   # (symbols were range-checked at encode_symbol)
+        raise RuntimeError(f"symbol encoder: stream status {st}")   # (symbols were range-checked at encode_symbol)
     c = int(cont.cpu()[0])
     return words[: int(n_words.cpu()[0])].cpu().numpy().view(np.uint32), c & 0xFFFFFFFF, c >> 32
 
@@ -69,17 +87,31 @@ def _decode(codebook, semantics, words: np.ndarray, cont: int):
     n_words = torch.tensor([words.size], dtype=torch.int32).to(dev)
     c = torch.tensor([cont], dtype=torch.int64).to(dev)
     out = torch.empty(1, dtype=torch.int32, device=dev)
-    n_out = torch.empty(1, dtype=torch.int32, device=dev)
+    n_out = torch.zeros(1, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
+    if isinstance(codebook, exp_golomb._Code):
+        # (an int32 output for every width: a u8 / u16 symbol is written as such into its first bytes, the rest is cleared)
+        out.zero_()
+        N.check(N.lib().cst_exp_golomb_decode_batch(semantics, _ptr(dw), None, words.size, words.size, _ptr(n_words), _ptr(out),
+                                                    codebook.symbol_bytes, 1, 1, _ptr(c), _ptr(n_out), _ptr(status), _stream_ptr()),
+                "cst_exp_golomb_decode_batch")
+        return int(status.cpu()[0]), int(out.cpu()[0]) & 0xFFFFFFFF, int(c.cpu()[0]), int(n_out.cpu()[0])
     N.check(N.lib().cst_huffman_decode_batch(codebook._h, semantics, _ptr(dw), None, words.size, words.size, _ptr(n_words), _ptr(out),
                                              4, 1, 1, _ptr(c), _ptr(n_out), _ptr(status), _stream_ptr()), "cst_huffman_decode_batch")
     return int(status.cpu()[0]), int(out.cpu()[0]), int(c.cpu()[0]), int(n_out.cpu()[0])
 
 
 def _check_decoder_codebook(codebook):
-    if not isinstance(codebook, DecoderHuffmanTree):
-        raise TypeError("codebook must be a constriction_amd.symbol.huffman.DecoderHuffmanTree")
+    if not isinstance(codebook, (DecoderHuffmanTree, ExpGolomb)):
+        raise TypeError("codebook must be a constriction_amd.symbol.huffman.DecoderHuffmanTree or an exp_golomb.ExpGolomb")
     return codebook._cb
+
+
+def _check_decoded(st):
+    if st == N.STREAM_OUT_OF_DATA:
+        raise ValueError(_OUT_OF_DATA)
+    if st != N.STREAM_OK:
+        raise RuntimeError(f"Huffman decoder: stream status {st}")
 
 
 class _Container:
@@ -140,12 +172,11 @@ class StackCoder(_Container):
         # word (cst_huffman_max_words of one symbol bounds it)
         base = max(0, self._words.size - cb.max_words(1, "stack"))
         st, sym, cont, n_left = _decode(cb, N.HUFFMAN_STACK, self._words[base:], self._partial | (self._nbits << 32))
+        if isinstance(cb, exp_golomb._Code) and st == N.STREAM_INVALID_DATA:
+            raise ValueError(_INVALID_CODEWORD)      # (the container stays as it was: DESIGN.md 7)
         self._words = self._words[: base + n_left]
         self._partial, self._nbits = cont & 0xFFFFFFFF, cont >> 32
-        if st == N.STREAM_OUT_OF_DATA:
-            raise ValueError(_OUT_OF_DATA)
-        if st != N.STREAM_OK:
-            raise RuntimeError(f"Huffman decoder: stream status {st}")
+        _check_decoded(st)
         return sym
 
     def get_compressed_and_bitrate(self):
@@ -203,13 +234,13 @@ class QueueDecoder:
         first = self._pos // 32
         window = self._words[first: first + cb.max_words(1, "queue")]      # covers the longest codeword from any bit offset
         st, sym, cont, _ = _decode(cb, N.HUFFMAN_QUEUE, window, self._pos - 32 * first)
+        if isinstance(cb, exp_golomb._Code) and st == N.STREAM_INVALID_DATA:
+            raise ValueError(_INVALID_CODEWORD)      # (the read position stays where it was: DESIGN.md 7)
         if st == N.STREAM_OUT_OF_DATA:
             self._pos = 32 * int(self._words.size)
-            raise ValueError(_OUT_OF_DATA)
-        if st != N.STREAM_OK:
-            raise RuntimeError(f"Huffman decoder: stream status {st}")
+        _check_decoded(st)
         self._pos = 32 * first + cont
         return sym
 
 
-__all__ = ["StackCoder", "QueueEncoder", "QueueDecoder", "huffman"]
+__all__ = ["StackCoder", "QueueEncoder", "QueueDecoder", "huffman", "exp_golomb"]

@@ -1524,6 +1524,67 @@ cst_status cst_huffman_decode_batch(const void *codebook, int32_t semantics, con
                                     uint32_t *d_n_words_out, int32_t *d_status, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exponential-Golomb symbol codes: ExpGolomb<N> of src/symbol/exp_golomb.rs in the bit containers above
+ *
+ * A universal code for unsigned integers, with no codebook to build or ship.  symbol_bytes selects N: 1 = u8 (uint8), 2 = u16 (the
+ * bit pattern of int16), 4 = u32 (the bit pattern of int32: -1 is u32::MAX).  With m = symbol + 1 and len = floor(log2 m) the
+ * codeword is, in prefix order, len zeros and then the len + 1 bits of m from the most significant down: 2 len + 1 bits.  N::MAX
+ * wraps to m == 0 in the reference and codes as B zeros, a one, B zeros (B the bits of N: 17 / 33 / 65 bits).  A queue
+ * (CST_SYMBOL_QUEUE) writes prefix order, a stream's symbols front to back, without a seal, its last partial word zero-padded; a
+ * stack (CST_SYMBOL_STACK) writes every codeword in suffix order (prefix order reversed), a stream's symbols BACK TO FRONT, and one
+ * seal bit, so that row s decodes to symbols[s, 0..n) in order: the conventions of the Huffman calls.
+ * Every value of N has a codeword: an encoder reports CST_STREAM_OK or CST_STREAM_CAPACITY (n_words and n_bits 0, d_cont untouched).
+ * A decoder reports CST_STREAM_INVALID_DATA for an invalid codeword (exp_golomb.rs:135-171): the bits run out inside the zero run,
+ * the run is longer than B, the bits run out inside the len value bits, or len == B with value bits that are not all zero.  Running
+ * out of bits is an invalid codeword here and not CST_STREAM_OUT_OF_DATA: a queue read past its last symbol walks into the zero
+ * padding and ends this way.  A stack without words or with a zero last word is CST_STREAM_INVALID_DATA too.  The symbols from the
+ * failing one on read 0, and the stream's d_cont / d_n_words_out are left as they came in (the reference leaves the bits consumed up
+ * to the failure: DESIGN.md 7).
+ * CST_ERR_INVALID_ARGUMENT (NULL pointers, symbol_bytes outside {1, 2, 4}, unknown semantics) is returned before any device call.
+ * ---------------------------------------------------------------------------------------- */
+#define CST_SYMBOL_STACK CST_HUFFMAN_STACK
+#define CST_SYMBOL_QUEUE CST_HUFFMAN_QUEUE
+
+/* HOST function, needs no device.  Slab stride (in words) that holds any stream of n_per_stream symbols: every codeword 2 B + 1 bits,
+ * the up to 31 bits a continued call (d_cont) starts with and the seal, rounded up to whole 64-byte units.  0 for a bad argument. */
+size_t cst_exp_golomb_max_words(size_t n_per_stream, int32_t symbol_bytes, int32_t semantics);
+
+/* d_n_bits[s] (uint64 [n_streams]) = the exact bits of stream s, without a seal: what the encoders below report as d_n_bits, and
+ * what sizes exact slabs for them (a stack needs one bit more).  d_sym_offsets (uint64 [n_streams + 1]) as in the ragged calls, or
+ * NULL for a matrix [n_streams][n_per_stream]; a range that runs backwards counts 0.  cst_last_kernel_name:
+ * "exp_golomb_count_bits_kernel". */
+cst_status cst_exp_golomb_count_bits(const void *d_symbols, int32_t symbol_bytes, const uint64_t *d_sym_offsets, size_t n_streams,
+                                     size_t n_per_stream, uint64_t *d_n_bits, void *stream);
+
+/* cst_huffman_encode_batch / cst_huffman_decode_batch without a codebook: the same slabs or packed words (d_offsets), words_capacity,
+ * d_n_bits, d_cont (partial | nbits << 32; for the queue decoder the read position in bits) and d_n_words_out.
+ * cst_last_kernel_name: "exp_golomb_encode_kernel" / "exp_golomb_decode_kernel". */
+cst_status cst_exp_golomb_encode_batch(int32_t semantics, const void *d_symbols, int32_t symbol_bytes, size_t n_streams,
+                                       size_t n_per_stream, uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                       uint64_t *d_n_bits, uint64_t *d_cont, int32_t *d_status, void *stream);
+cst_status cst_exp_golomb_decode_batch(int32_t semantics, const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words,
+                                       size_t words_capacity, const uint32_t *d_n_words, void *d_symbols, int32_t symbol_bytes,
+                                       size_t n_streams, size_t n_per_stream, uint64_t *d_cont, uint32_t *d_n_words_out,
+                                       int32_t *d_status, void *stream);
+
+/* Streams of different lengths, the layout of cst_ans_encode_ragged / cst_ans_decode_ragged without a model:
+ *     symbols of stream s = d_symbols[d_sym_offsets[s] .. d_sym_offsets[s + 1])      (flat, of symbol_bytes each)
+ *     slab of stream s    = d_words[d_word_offsets[s] .. d_word_offsets[s + 1])      or, with d_word_offsets = NULL,
+ *                           d_words[s * stride_words .. + stride_words)
+ * One lane codes one stream; a wave of 64 consecutive streams runs as long as its longest one.  d_n_bits (may be NULL) as above.  A
+ * stream of length 0 yields 0 words (a stack: its seal, 1 word) and CST_STREAM_OK.  A symbol range that runs backwards or exceeds
+ * 2^32 - 1 symbols: CST_STREAM_CAPACITY from the encoder, CST_STREAM_INVALID_DATA (nothing written) from the decoder; word offsets
+ * that run backwards are a slab of no words.  The decoder reads d_word_offsets[s] and d_n_words[s] only and checks them against
+ * words_capacity as cst_ans_decode_batch does.  cst_last_kernel_name: "exp_golomb_encode_ragged_kernel" /
+ * "exp_golomb_decode_ragged_kernel". */
+cst_status cst_exp_golomb_encode_ragged(int32_t semantics, const void *d_symbols, int32_t symbol_bytes, const uint64_t *d_sym_offsets,
+                                        size_t n_streams, uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                        uint32_t *d_n_words, uint64_t *d_n_bits, int32_t *d_status, void *stream);
+cst_status cst_exp_golomb_decode_ragged(int32_t semantics, const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                        size_t words_capacity, const uint32_t *d_n_words, void *d_symbols, int32_t symbol_bytes,
+                                        const uint64_t *d_sym_offsets, size_t n_streams, int32_t *d_status, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * bit-exact f64 special functions on device (test hooks for the model kernels)
  * out[i] = erf(x[i]) resp. Gaussian cdf, evaluated by the same device code the table kernels use.
  * ---------------------------------------------------------------------------------------- */
