@@ -3097,6 +3097,130 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    /// d_n_bits[s] (uint64 [n_streams]) = the exact bits of stream s under the codebook, without a stack's seal: what the encoders report
+    /// as d_n_bits, and what sizes exact slabs for them (a stack needs one bit more).  d_sym_offsets (uint64 [n_streams + 1]) as in the
+    /// ragged calls below, or NULL for a matrix [n_streams][n_per_stream].  A symbol outside 0 .. n-1 counts 0 bits (the encoder is what
+    /// reports it) and so does a range that runs backwards; the sums are 64-bit (a codeword can have ~3000 bits).
+    /// cst_last_kernel_name: "huffman_count_bits_kernel".
+    pub fn cst_huffman_count_bits(
+        codebook: *const c_void,
+        d_symbols: *const c_void,
+        symbol_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        n_per_stream: usize,
+        d_n_bits: *mut u64,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// Streams of different lengths, the layout of cst_exp_golomb_encode_ragged / cst_exp_golomb_decode_ragged with a codebook:
+    ///     symbols of stream s = d_symbols[d_sym_offsets[s] .. d_sym_offsets[s + 1])      (flat, int32 or uint8: symbol_bytes 4 or 1)
+    ///     slab of stream s    = d_words[d_word_offsets[s] .. d_word_offsets[s + 1])      or, with d_word_offsets = NULL,
+    ///                           d_words[s * stride_words .. + stride_words)
+    /// One lane codes one stream, and the words of stream s are exactly what cst_huffman_encode_batch writes for it as a one-row batch
+    /// (the reference's StackCoder, symbols back to front and sealed, or QueueEncoder).  Statuses are those of the rectangular calls:
+    /// CST_STREAM_IMPOSSIBLE_SYMBOL and CST_STREAM_CAPACITY with 0 words and 0 bits, CST_STREAM_OUT_OF_DATA with the symbols from there
+    /// on 0, CST_STREAM_INVALID_DATA for a stack without its seal and for offsets or counts beyond words_capacity.  A stream of length 0
+    /// yields 0 words (a stack: its seal, 1 word) and CST_STREAM_OK.  A symbol range that runs backwards or exceeds 2^32 - 1 symbols:
+    /// CST_STREAM_CAPACITY from the encoder; a backwards one is CST_STREAM_INVALID_DATA (nothing written) from the decoder.  Word offsets
+    /// that run backwards are a slab of no words.  The decoder reads d_word_offsets[s] and d_n_words[s] only.  symbol_bytes 1 needs
+    /// n <= 256 to decode.  cst_last_kernel_name: "huffman_encode_ragged_kernel" / "huffman_decode_ragged_kernel", and
+    /// "huffman_encode_ragged_long_kernel" / "huffman_decode_ragged_long_kernel" for codewords of more than 32 / 12 bits.
+    pub fn cst_huffman_encode_ragged(
+        codebook: *const c_void,
+        semantics: i32,
+        d_symbols: *const c_void,
+        symbol_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_n_bits: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_huffman_decode_ragged(
+        codebook: *const c_void,
+        semantics: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_symbols: *mut c_void,
+        symbol_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// Jump points for the ragged Huffman calls.  The reference has none for symbol codes ("Pos and Seek for SymbolCoder and for
+    /// QueueDecoder" is a to-do at the top of src/symbol/mod.rs): the table is this library's own, the words are those of
+    /// cst_huffman_encode_ragged bit for bit, and a reader that ignores the table loses only speed.
+    ///   - A jump point of a prefix code is one bit index and no coder state.  jump_interval (I) is a positive multiple of 32, at most
+    ///     2^31 - 32; d_chunk_offsets[n_streams + 1] is the exclusive prefix sum of ceil(length / I), the layout of
+    ///     cst_ans_{encode,decode}_ragged_jump; entry d_chunk_offsets[s] + j of d_jump_bits (uint64) is the bit index in stream s's
+    ///     container at which a reader starts chunk j, i.e. symbols [j I, min((j + 1) I, length)):
+    ///         queue   the first bit of the chunk's first codeword = the bits of symbols[: j I]; read upwards;
+    ///         stack   one past the highest bit of the chunk's first codeword = the bits of symbols[j I :]; read downwards; entry 0 is
+    ///                 d_n_bits[s], where the seal sits.
+    ///     Either is the container's bit length when the encoder crosses that boundary.  The entries of a stream whose status is not
+    ///     CST_STREAM_OK are unspecified; the encoder writes no entry outside [d_chunk_offsets[s], d_chunk_offsets[s + 1]).
+    ///   - The decoder runs one lane per chunk (n_chunks_total: the entries of d_jump_bits, at least d_chunk_offsets[n_streams]) and
+    ///     writes one status per STREAM: the largest of its chunks' status values, i.e. CST_STREAM_OUT_OF_DATA before
+    ///     CST_STREAM_INVALID_DATA before CST_STREAM_OK -- the precedence of cst_ans_decode_ragged_jump, which also takes the maximum.
+    ///   - A table entry beyond its stream's bits -- above 32 * d_n_words[s] for a queue, above the position of the seal for a stack --
+    ///     is CST_STREAM_INVALID_DATA for that stream and touches no other; it is judged before any word at that position is read.  A
+    ///     chunk that fails leaves zeros from the failure to its own end; the other chunks of its stream keep their symbols.  A table
+    ///     that does not describe its stream (chunks != ceil(length / I), offsets that run backwards or beyond n_chunks_total) is
+    ///     CST_STREAM_INVALID_DATA and nothing is written for that stream.
+    /// cst_last_kernel_name: "huffman_encode_ragged_kernel" / "huffman_decode_ragged_jump_kernel" and their "_long_kernel" forms
+    /// ("huffman_encode_ragged_long_kernel", "huffman_decode_ragged_jump_long_kernel").
+    /// All five calls return CST_ERR_INVALID_ARGUMENT (NULL pointers, symbol_bytes outside {1, 4}, unknown semantics, a handle that is no
+    /// codebook, an interval that is not allowed) before any device call.
+    pub fn cst_huffman_encode_ragged_jump(
+        codebook: *const c_void,
+        semantics: i32,
+        d_symbols: *const c_void,
+        symbol_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_n_bits: *mut u64,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_bits: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_huffman_decode_ragged_jump(
+        codebook: *const c_void,
+        semantics: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_symbols: *mut c_void,
+        symbol_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_bits: *const u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// HOST function, needs no device.  Slab stride (in words) that holds any stream of n_per_stream symbols: every codeword 2 B + 1 bits,
     /// the up to 31 bits a continued call (d_cont) starts with and the seal, rounded up to whole 64-byte units.  0 for a bad argument.
     pub fn cst_exp_golomb_max_words(n_per_stream: usize, symbol_bytes: i32, semantics: i32) -> usize;

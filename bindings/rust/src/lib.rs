@@ -6205,6 +6205,93 @@ impl HuffmanCodebook {
                                           status.as_mut_ptr(), stream.as_raw())
         })
     }
+
+    /// The exact bits of every row of the stream-major `symbols` matrix under this codebook, without a stack's seal.
+    pub fn count_bits(&self, symbols: &DeviceBuffer<i32>, n_streams: usize, n_per_stream: usize, stream: &Stream) -> Result<DeviceBuffer<u64>> {
+        if symbols.len() < n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)? {
+            return Err(Error::InvalidArgument);
+        }
+        let mut n_bits: DeviceBuffer<u64> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_huffman_count_bits(self.raw, symbols.as_ptr() as *const c_void, 4, core::ptr::null(), n_streams, n_per_stream,
+                                        n_bits.as_mut_ptr(), stream.as_raw())
+        })?;
+        Ok(n_bits)
+    }
+
+    /// Streams of different lengths in one launch: stream `s` owns `[sym_offsets[s], sym_offsets[s + 1])` of the flat `symbols` and
+    /// writes into the slab `[word_offsets[s], word_offsets[s + 1])` of `words`.  With `jump` = (interval, chunk_offsets, jump_bits)
+    /// the encoder also notes the container's bit length at every `interval` symbols of every stream (a multiple of 32;
+    /// `chunk_offsets`: the exclusive prefix sum of ceil(length / interval)).  Returns (n_words, n_bits, status) per stream.
+    ///
+    /// # Safety
+    /// The offsets are DEVICE memory: this wrapper cannot check them.  Every `sym_offsets` pair must lie inside `symbols`, every
+    /// slab inside `words`, every chunk entry inside `jump_bits`, in ascending order.
+    pub unsafe fn encode_ragged(&self, symbols: &DeviceBuffer<i32>, sym_offsets: &DeviceBuffer<u64>, word_offsets: &DeviceBuffer<u64>,
+                                words: &mut DeviceBuffer<u32>, semantics: SymbolSemantics,
+                                jump: Option<(usize, &DeviceBuffer<u64>, &mut DeviceBuffer<u64>)>, stream: &Stream)
+                                -> Result<(DeviceBuffer<u32>, DeviceBuffer<u64>, DeviceBuffer<i32>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut n_bits: DeviceBuffer<u64> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        match jump {
+            None => check(unsafe {
+                ffi::cst_huffman_encode_ragged(self.raw, semantics as i32, symbols.as_ptr() as *const c_void, 4, sym_offsets.as_ptr(),
+                                               n_streams, words.as_mut_ptr(), word_offsets.as_ptr(), 0, n_words.as_mut_ptr(),
+                                               n_bits.as_mut_ptr(), status.as_mut_ptr(), stream.as_raw())
+            })?,
+            Some((interval, chunk_offsets, jump_bits)) => {
+                if chunk_offsets.len() != sym_offsets.len() {
+                    return Err(Error::InvalidArgument);
+                }
+                check(unsafe {
+                    ffi::cst_huffman_encode_ragged_jump(self.raw, semantics as i32, symbols.as_ptr() as *const c_void, 4,
+                                                        sym_offsets.as_ptr(), n_streams, words.as_mut_ptr(), word_offsets.as_ptr(), 0,
+                                                        n_words.as_mut_ptr(), n_bits.as_mut_ptr(), interval, chunk_offsets.as_ptr(),
+                                                        jump_bits.as_mut_ptr(), status.as_mut_ptr(), stream.as_raw())
+                })?
+            }
+        }
+        Ok((n_words, n_bits, status))
+    }
+
+    /// The decoder of [`HuffmanCodebook::encode_ragged`]; with `jump` every chunk is decoded by a lane of its own.
+    ///
+    /// # Safety
+    /// `sym_offsets` (device memory) must delimit ranges inside `symbols`.  The word slices and the jump table's entries ARE checked
+    /// on the device, against `words.len()`, the streams' word counts and `jump_bits.len()`.
+    pub unsafe fn decode_ragged(&self, words: &DeviceBuffer<u32>, word_offsets: &DeviceBuffer<u64>, n_words: &DeviceBuffer<u32>,
+                                sym_offsets: &DeviceBuffer<u64>, symbols: &mut DeviceBuffer<i32>, semantics: SymbolSemantics,
+                                jump: Option<(usize, &DeviceBuffer<u64>, &DeviceBuffer<u64>)>, stream: &Stream) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        match jump {
+            None => check(unsafe {
+                ffi::cst_huffman_decode_ragged(self.raw, semantics as i32, words.as_ptr(), word_offsets.as_ptr(), 0, words.len(),
+                                               n_words.as_ptr(), symbols.as_mut_ptr() as *mut c_void, 4, sym_offsets.as_ptr(), n_streams,
+                                               status.as_mut_ptr(), stream.as_raw())
+            })?,
+            Some((interval, chunk_offsets, jump_bits)) => {
+                if chunk_offsets.len() != sym_offsets.len() {
+                    return Err(Error::InvalidArgument);
+                }
+                check(unsafe {
+                    ffi::cst_huffman_decode_ragged_jump(self.raw, semantics as i32, words.as_ptr(), word_offsets.as_ptr(), 0, words.len(),
+                                                        n_words.as_ptr(), symbols.as_mut_ptr() as *mut c_void, 4, sym_offsets.as_ptr(),
+                                                        n_streams, interval, chunk_offsets.as_ptr(), jump_bits.len(), jump_bits.as_ptr(),
+                                                        status.as_mut_ptr(), stream.as_raw())
+                })?
+            }
+        }
+        Ok(status)
+    }
 }
 
 impl Drop for HuffmanCodebook {

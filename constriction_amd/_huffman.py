@@ -1,5 +1,6 @@
 """Batched Huffman symbol codes (re-exported by `constriction_amd.batched`): one bit container per stream, one codebook shared by
-the batch, coded by the kernels of csrc/cst_huffman.hip (include/constriction_amd.h, "Huffman symbol codes").
+the batch, coded by the kernels of csrc/cst_huffman.hip and, for streams of different lengths, csrc/cst_huffman_ragged.hip
+(include/constriction_amd.h, "Huffman symbol codes").
 
 A stack batch row s holds what the reference's `StackCoder` holds after `encode_symbol` of symbols[s] last to first and
 `get_compressed_and_bitrate()` (src/pybindings/symbol/mod.rs:207-221); it decodes to symbols[s] in order, the convention of
@@ -14,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .batched import EncodedBatch, _ptr, _require_cuda, _stream_ptr
+from .batched import RAGGED_JUMP_EVERY, EncodedBatch, RaggedBatch, _ptr, _require_coder, _require_cuda, _stream_ptr
 
 _SEMANTICS = {"stack": N.HUFFMAN_STACK, "queue": N.HUFFMAN_QUEUE}
 _SYMBOL_BYTES = {torch.int32: 4, torch.uint8: 1}
@@ -167,4 +168,145 @@ def huffman_decode(encoded, codebook: HuffmanCodebook, n_per_stream: int, semant
     N.check(N.lib().cst_huffman_decode_batch(codebook._h, sem, _ptr(words), _ptr(offsets), stride, words.numel(), _ptr(n_words),
                                              _ptr(out), _SYMBOL_BYTES[dtype], n_streams, n_per_stream, None, None, _ptr(status),
                                              _stream_ptr()), "cst_huffman_decode_batch")
+    return out, status
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# streams of different lengths: one container per document, all of them in one launch (csrc/cst_huffman_ragged.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+
+@dataclass
+class BitJump:
+    """Jump points of a ragged Huffman batch: chunk j of stream s (symbols j * interval .. of it) starts at bit bits[chunk_offsets[s] + j]
+    of the stream's container -- a queue is read from there upwards, a stack from there downwards.  A bit index is all a prefix
+    code needs: there is no coder state."""
+    interval: int
+    chunk_offsets: torch.Tensor   # int64 [n_streams + 1]: exclusive prefix sum of ceil(length / interval)
+    bits: torch.Tensor            # int64 [>= total chunks] (what lies behind chunk_offsets[-1] entries is not written or read)
+
+
+def _never_null(t: torch.Tensor):
+    """the address of `t`, or of a small buffer on its device if it has no elements (the ABI refuses NULL)"""
+    return _ptr(t) if t.numel() else _ptr(torch.empty(4, dtype=torch.int32, device=t.device))
+
+
+def _flat_symbols(symbols: torch.Tensor, sym_offsets: torch.Tensor):
+    if not symbols.is_cuda:
+        raise ValueError("symbols must live in device memory (HBM)")
+    if symbols.dtype not in _SYMBOL_BYTES:
+        raise TypeError("Huffman symbols are int32 or uint8")
+    sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
+    n_streams = sym_offsets.numel() - 1
+    if symbols.dim() != 1 or n_streams < 0:
+        raise ValueError("symbols must be flat and sym_offsets hold n_streams + 1 entries")
+    return symbols.contiguous(), _SYMBOL_BYTES[symbols.dtype], sym_offsets, n_streams
+
+
+def huffman_count_bits(symbols: torch.Tensor, codebook: HuffmanCodebook, sym_offsets: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The exact bits of every stream under `codebook` (int64 [n_streams], without a stack's seal): rows of a matrix, or with
+    `sym_offsets` (int64 [n_streams + 1]) the ranges of flat `symbols`.  A symbol outside the alphabet counts 0 bits: the encoder
+    is what reports it."""
+    if sym_offsets is None:
+        symbols, sb = _symbols_arg(symbols)
+        n_streams, n_per = symbols.shape
+    else:
+        symbols, sb, sym_offsets, n_streams = _flat_symbols(symbols, sym_offsets)
+        n_per = 0
+    n_bits = torch.empty(n_streams, dtype=torch.int64, device=symbols.device)
+    N.check(N.lib().cst_huffman_count_bits(codebook._h, _never_null(symbols), sb, _ptr(sym_offsets), n_streams, n_per, _ptr(n_bits),
+                                           _stream_ptr()), "cst_huffman_count_bits")
+    return n_bits
+
+
+def _jump_every(jump_every) -> object:
+    """the `jump_every` argument, judged before any tensor is looked at: "auto", or an int that is 0 or a positive multiple of 32"""
+    if isinstance(jump_every, str):
+        if jump_every != "auto":
+            raise ValueError("jump_every: 'auto', 0 or a multiple of 32")
+        return "auto"
+    jump_every = int(jump_every or 0)
+    if jump_every < 0 or jump_every % 32 != 0 or jump_every > 0x7fffffff:
+        raise ValueError("jump_every: 'auto', 0 or a multiple of 32")
+    return jump_every
+
+
+def huffman_encode_ragged(symbols: torch.Tensor, sym_offsets: torch.Tensor, codebook: HuffmanCodebook, semantics="stack",
+                          jump_every=0) -> RaggedBatch:
+    """One container per stream, streams of different lengths (`symbols` flat, int32 or uint8; stream s =
+    symbols[sym_offsets[s]:sym_offsets[s+1]]) in one launch.  The slabs are exact: a count pass sizes each to its stream's bits (and
+    a stack's seal), rounded up to 16 bytes.  Returns a RaggedBatch with coder="huffman" (the ANS, range and Exp-Golomb decoders
+    refuse it), config = (semantics, symbol dtype) and the bit counts as `.n_bits`; `stream(s)` is what `huffman_encode` gives for
+    that stream as a one-row batch.  A stream with a symbol outside 0..n-1 reports IMPOSSIBLE_SYMBOL and has 0 words.
+
+    jump_every: 0 (default) -- no jump points.  A positive multiple of 32: the encoder also notes the container's bit length at
+    every jump_every symbols of every stream (the words are unchanged) and the batch carries the table as `.jump` (a BitJump);
+    huffman_decode_ragged then decodes all chunks side by side, and a launch lasts jump_every symbols instead of its longest
+    stream.  "auto": RAGGED_JUMP_EVERY where the streams average more than RAGGED_JUMP_EVERY symbols, else 0 -- the range coder's
+    rule, measured for these kernels on 100 000 documents: at 20 .. 2000 symbols per document the table makes the
+    decode 4 times faster for 2-7 % of encode time; at 200 symbols per document the round trip is a wash, and "auto" leaves it out."""
+    sem = _semantics(semantics)
+    jump_every = _jump_every(jump_every)
+    symbols, sb, sym_offsets, n_streams = _flat_symbols(symbols, sym_offsets)
+    dev = symbols.device
+    bits = huffman_count_bits(symbols, codebook, sym_offsets)
+    slabs = ((bits + ((sem == N.HUFFMAN_STACK) + 31)) // 32 + 3) // 4 * 4
+    word_offsets = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(slabs, 0, out=word_offsets[1:])
+    total = int(word_offsets[-1].item()) if n_streams else 0
+    out = RaggedBatch(torch.empty(max(total, 4), dtype=torch.int32, device=dev), word_offsets,
+                      torch.empty(n_streams, dtype=torch.int32, device=dev), torch.empty(n_streams, dtype=torch.int32, device=dev),
+                      (semantics, symbols.dtype), coder="huffman")
+    out.n_bits = torch.empty(n_streams, dtype=torch.int64, device=dev)
+    if jump_every == "auto":
+        jump_every = RAGGED_JUMP_EVERY if symbols.numel() > n_streams * RAGGED_JUMP_EVERY else 0
+    if not jump_every:
+        N.check(N.lib().cst_huffman_encode_ragged(codebook._h, sem, _never_null(symbols), sb, _ptr(sym_offsets), n_streams, _ptr(out.words),
+                                                  _ptr(word_offsets), 0, _ptr(out.n_words), _ptr(out.n_bits), _ptr(out.status),
+                                                  _stream_ptr()), "cst_huffman_encode_ragged")
+        return out
+    lengths = sym_offsets[1:] - sym_offsets[:-1]
+    chunk_offsets = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
+    torch.cumsum((lengths + (jump_every - 1)) // jump_every, 0, out=chunk_offsets[1:])
+    n_chunks = max(symbols.numel() // jump_every + n_streams, 1)      # (an upper bound: no read-back)
+    out.jump = BitJump(jump_every, chunk_offsets, torch.empty(n_chunks, dtype=torch.int64, device=dev))
+    N.check(N.lib().cst_huffman_encode_ragged_jump(codebook._h, sem, _never_null(symbols), sb, _ptr(sym_offsets), n_streams, _ptr(out.words),
+                                                   _ptr(word_offsets), 0, _ptr(out.n_words), _ptr(out.n_bits), jump_every,
+                                                   _ptr(chunk_offsets), _ptr(out.jump.bits), _ptr(out.status), _stream_ptr()),
+            "cst_huffman_encode_ragged_jump")
+    return out
+
+
+def huffman_decode_ragged(encoded: RaggedBatch, codebook: HuffmanCodebook, sym_offsets: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """Stream s yields sym_offsets[s + 1] - sym_offsets[s] symbols at out[sym_offsets[s]:], in the dtype the batch was encoded from (or
+    that of `out`).  Returns (symbols flat, status per stream).  A batch with jump points (`jump_every` of the encoder) is decoded
+    chunk by chunk, all chunks side by side; a stream's status is then the largest of its chunks' (OUT_OF_DATA before INVALID_DATA),
+    and a chunk that fails reads 0 from the failure to its own end while the other chunks keep their symbols."""
+    _require_coder(encoded, "huffman")
+    semantics, dtype = encoded.config
+    sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
+    n_streams = sym_offsets.numel() - 1
+    if n_streams != encoded.n_words.numel():
+        raise ValueError("sym_offsets must hold one entry per stream of the batch, and one more")
+    dev = encoded.words.device
+    total = int(sym_offsets[-1].item()) if n_streams > 0 else 0
+    if out is None:
+        out = torch.empty(total, dtype=dtype, device=dev)
+    elif not out.is_cuda or not out.is_contiguous() or out.numel() < total or out.dtype not in _SYMBOL_BYTES:
+        raise ValueError("out must be a contiguous int32 or uint8 device tensor with room for every symbol")
+    status = torch.empty(max(n_streams, 0), dtype=torch.int32, device=dev)
+    jump = encoded.jump
+    if jump is None:
+        N.check(N.lib().cst_huffman_decode_ragged(codebook._h, _semantics(semantics), _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
+                                                  encoded.words.numel(), _ptr(encoded.n_words), _never_null(out), _SYMBOL_BYTES[out.dtype],
+                                                  _ptr(sym_offsets), n_streams, _ptr(status), _stream_ptr()), "cst_huffman_decode_ragged")
+        return out, status
+    if not isinstance(jump, BitJump):
+        raise ValueError("the batch's jump points are not those of a Huffman batch")
+    if jump.chunk_offsets.numel() != n_streams + 1:
+        raise ValueError("the jump table must describe every stream of the batch")
+    N.check(N.lib().cst_huffman_decode_ragged_jump(codebook._h, _semantics(semantics), _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
+                                                   encoded.words.numel(), _ptr(encoded.n_words), _never_null(out), _SYMBOL_BYTES[out.dtype],
+                                                   _ptr(sym_offsets), n_streams, jump.interval, _ptr(jump.chunk_offsets),
+                                                   jump.bits.numel(), _ptr(jump.bits), _ptr(status), _stream_ptr()),
+            "cst_huffman_decode_ragged_jump")
     return out, status

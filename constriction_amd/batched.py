@@ -575,7 +575,8 @@ class RaggedBatch:
     jump: Optional["RaggedJump"] = None    # jump points the encoder noted (ans_encode_ragged, jump_every): ans_decode_ragged decodes the chunks side by side
     #                                        (a range batch carries a RangeRaggedJump here: range_encode_ragged_jump / range_decode_ragged)
     coder: str = "ans"                     # "ans" (a stack) or "range" (a queue): which coder wrote the words -- the other one's decoders refuse them
-    #                                        ("exp_golomb": exp_golomb_encode_ragged; config is then (semantics, symbol dtype))
+    #                                        ("exp_golomb": exp_golomb_encode_ragged, "huffman": huffman_encode_ragged; config is then
+    #                                        (semantics, symbol dtype), and a Huffman batch's `jump` is a BitJump)
     n_bits = None                          # (no field: set by the symbol codes) int64 [n_streams], the written bits of every stream
 
     def stream(self, s: int) -> np.ndarray:
@@ -2407,6 +2408,7 @@ def ans_decode_gaussian_checkpointed(encoded: EncodedBatch, checkpoints: Checkpo
 # Huffman symbol codes (constriction.symbol): one bit container per stream, a shared codebook (_huffman.py)
 # ---------------------------------------------------------------------------------------------------------------------
 
-from ._huffman import HuffmanBatch, HuffmanCodebook, huffman_decode, huffman_encode, huffman_tree  # noqa: E402,F401
+from ._huffman import (BitJump, HuffmanBatch, HuffmanCodebook, huffman_count_bits, huffman_decode, huffman_decode_ragged,  # noqa: E402,F401
+                       huffman_encode, huffman_encode_ragged, huffman_tree)
 from ._exp_golomb import (exp_golomb_count_bits, exp_golomb_decode, exp_golomb_decode_ragged, exp_golomb_encode,  # noqa: E402,F401
                           exp_golomb_encode_ragged, exp_golomb_max_words)
