@@ -3221,6 +3221,56 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    /// Random access into a ragged Huffman batch: selected documents, or ranges of documents.  The contract is that of
+    /// cst_ans_decode_ragged_select -- queries (stream, first, count) in any order, repeats, overlaps and count 0 allowed, both of
+    /// d_query_first / d_query_count NULL for whole documents; a ragged output (query q owns d_symbols_out[d_out_offsets[q] ..
+    /// d_out_offsets[q + 1]), symbols of symbol_bytes 1 or 4) and one status per QUERY; d_piece_offsets[n_queries + 1] the exclusive
+    /// prefix sum of the pieces per query (with a table one per chunk touched, ceil((first % I + count) / I); without one 1; none for
+    /// count 0), n_pieces_total an upper bound of them; d_scratch of cst_ragged_select_scratch_bytes(n_pieces_total) bytes -- with the
+    /// table of cst_huffman_encode_ragged_jump (d_chunk_offsets, d_jump_bits), or without one (jump_interval 0, both pointers NULL).
+    ///   - With a table the first piece of a query seeks to entry first / I and decodes and drops first % I symbols.  Without one a query
+    ///     is one piece that starts where its document starts (a queue at bit 0, a stack at its seal) and drops `first` symbols.
+    ///   - A refused query reports CST_STREAM_INVALID_DATA and WRITES NOTHING: no such stream, a range beyond its document (no 64-bit
+    ///     wrap), a slice of d_out_offsets or d_piece_offsets that is not its own, words that leave words_capacity, a slice of the table
+    ///     that does not describe the stream, a stack without a seal, or ANY TABLE ENTRY IT TOUCHES BEYOND ITS STREAM'S BITS (above
+    ///     32 * d_n_words[s] for a queue, above the seal for a stack; judged before any word at the entry is read).  A document longer than
+    ///     2^32 - 1 symbols is CST_STREAM_CAPACITY.  Otherwise a query's status is the largest of its pieces' (CST_STREAM_OUT_OF_DATA
+    ///     before CST_STREAM_INVALID_DATA); a piece that fails writes zeros from the failure to its own end, all of them if it fails inside
+    ///     the symbols it drops.
+    ///   - CST_ERR_INVALID_ARGUMENT before the device is touched: what cst_huffman_decode_ragged refuses, an interval that is neither 0 nor
+    ///     a multiple of 32, a table given in part, n_chunks_total or n_pieces_total above 2^32 - 1, exactly one of d_query_first /
+    ///     d_query_count NULL, and with n_queries > 0 a NULL among the query, output, scratch or status pointers.  n_queries == 0 returns
+    ///     CST_OK and launches nothing.
+    /// Every piece is a lane of the SELECT form of the jump decoder.  cst_last_kernel_name: "huffman_decode_ragged_jump_kernel<select>" /
+    /// "huffman_decode_ragged_jump_long_kernel<select>".
+    pub fn cst_huffman_decode_ragged_select(
+        codebook: *const c_void,
+        semantics: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_bits: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut c_void,
+        symbol_bytes: i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// HOST function, needs no device.  Slab stride (in words) that holds any stream of n_per_stream symbols: every codeword 2 B + 1 bits,
     /// the up to 31 bits a continued call (d_cont) starts with and the seal, rounded up to whole 64-byte units.  0 for a bad argument.
     pub fn cst_exp_golomb_max_words(n_per_stream: usize, symbol_bytes: i32, semantics: i32) -> usize;
@@ -3310,6 +3360,89 @@ extern "C" {
         symbol_bytes: i32,
         d_sym_offsets: *const u64,
         n_streams: usize,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// Jump points for the ragged Exp-Golomb calls: the table of cst_huffman_encode_ragged_jump with Exp-Golomb codeword lengths.
+    /// jump_interval (I) is a positive multiple of 32, at most 2^31 - 32; d_chunk_offsets[n_streams + 1] is the exclusive prefix sum of
+    /// ceil(length / I); entry d_chunk_offsets[s] + j of d_jump_bits (uint64) is the bit index at which a reader starts chunk j -- a queue
+    /// the bits of symbols[: j I], read upwards; a stack the bits of symbols[j I :], read downwards, entry 0 being d_n_bits[s], where the
+    /// seal sits.  The words are those of cst_exp_golomb_encode_ragged bit for bit.  The encoder adds one 8-byte store per chunk, always
+    /// between two whole codewords (a u32 symbol from 2^17 - 1 on is put in two pieces; no entry lies between them), and writes no entry
+    /// outside [d_chunk_offsets[s], d_chunk_offsets[s + 1]); the entries of a stream whose status is not CST_STREAM_OK are unspecified.
+    /// The decoder runs one lane per chunk (n_chunks_total: the entries of d_jump_bits) and writes one status per STREAM, the largest of its
+    /// chunks'.  There is no CST_STREAM_OUT_OF_DATA: a chunk that runs out of bits or meets an invalid codeword is
+    /// CST_STREAM_INVALID_DATA and leaves zeros from the failure to its own end, while the other chunks keep their symbols.  A table entry
+    /// beyond its stream's bits (above 32 * d_n_words[s] for a queue, above the seal for a stack; judged before any word at the entry is
+    /// read) and a stack without words or with a zero last word are CST_STREAM_INVALID_DATA for that stream only.  A table that does not
+    /// describe its stream (chunks != ceil(length / I), offsets that run backwards or beyond n_chunks_total) is CST_STREAM_INVALID_DATA
+    /// and nothing is written for that stream.  CST_ERR_INVALID_ARGUMENT (NULL pointers, symbol_bytes outside {1, 2, 4}, unknown
+    /// semantics, an interval that is 0, no multiple of 32 or too large) is returned before any device call.
+    /// cst_last_kernel_name: "exp_golomb_encode_ragged_jump_kernel" / "exp_golomb_decode_ragged_jump_kernel".
+    pub fn cst_exp_golomb_encode_ragged_jump(
+        semantics: i32,
+        d_symbols: *const c_void,
+        symbol_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_n_bits: *mut u64,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_bits: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_exp_golomb_decode_ragged_jump(
+        semantics: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_symbols: *mut c_void,
+        symbol_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_bits: *const u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    /// cst_huffman_decode_ragged_select without a codebook: the same queries, pieces, refusals and argument errors (symbol_bytes in
+    /// {1, 2, 4}), with the table of cst_exp_golomb_encode_ragged_jump or without one.  A piece that fails is CST_STREAM_INVALID_DATA.
+    /// cst_last_kernel_name: "exp_golomb_decode_ragged_jump_kernel<select>".
+    pub fn cst_exp_golomb_decode_ragged_select(
+        semantics: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_bits: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut c_void,
+        symbol_bytes: i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
         d_status: *mut i32,
         stream: *mut c_void,
     ) -> CstStatus;

@@ -6292,6 +6292,86 @@ impl HuffmanCodebook {
         }
         Ok(status)
     }
+
+    /// Random access into a ragged batch (`cst_huffman_decode_ragged_select`): query q decodes symbols `[first[q], first[q] + count[q])` of
+    /// document `query_stream[q]` (`query_range = None`: whole documents) into `symbols[out_offsets[q] .. out_offsets[q + 1]]`, and
+    /// nothing else is decoded.  With `jump = Some((interval, chunk_offsets, jump_bits))` every query seeks to the jump point in front
+    /// of `first`, discards `first % interval` symbols, and each chunk it touches is a lane of its own; without, a query starts where
+    /// its document starts and discards `first` symbols.  `piece_offsets`: the exclusive prefix sum of
+    /// `ceil((first % interval + count) / interval)` (0 for `count == 0`; without jump points 1 per non-empty query),
+    /// `n_pieces_total` its last entry or an upper bound.  One status per QUERY, the worst of its pieces' (`OUT_OF_DATA` before `INVALID_DATA`).
+    ///
+    /// # Safety
+    /// As for `decode_ragged`.  Queries, piece offsets and the jump table are checked on the device; `symbols` must hold
+    /// `out_offsets[n_queries]` symbols.
+    pub unsafe fn seek_and_decode_ragged(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        sym_offsets: &DeviceBuffer<u64>,
+        semantics: SymbolSemantics,
+        jump: Option<(usize, &DeviceBuffer<u64>, &DeviceBuffer<u64>)>,
+        query_stream: &DeviceBuffer<u32>,
+        query_range: Option<(&DeviceBuffer<u64>, &DeviceBuffer<u64>)>,
+        piece_offsets: &DeviceBuffer<u64>,
+        n_pieces_total: usize,
+        symbols: &mut DeviceBuffer<i32>,
+        out_offsets: &DeviceBuffer<u64>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_queries = query_stream.len();
+        if piece_offsets.len() != n_queries + 1 || out_offsets.len() != n_queries + 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if let Some((first, count)) = query_range {
+            if first.len() != n_queries || count.len() != n_queries {
+                return Err(Error::InvalidArgument);
+            }
+        }
+        if let Some((interval, chunk_offsets, _)) = jump {
+            if chunk_offsets.len() != sym_offsets.len() || interval == 0 || interval % 32 != 0 {
+                return Err(Error::InvalidArgument);
+            }
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_queries)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_ragged_select_scratch_bytes(n_pieces_total) })?;
+        check(unsafe {
+            ffi::cst_huffman_decode_ragged_select(
+                self.raw,
+                semantics as i32,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                jump.map_or(0, |j| j.0),
+                jump.map_or(core::ptr::null(), |j| j.1.as_ptr()),
+                jump.map_or(0, |j| j.2.len()),
+                jump.map_or(core::ptr::null(), |j| j.2.as_ptr()),
+                query_stream.as_ptr(),
+                query_range.map_or(core::ptr::null(), |r| r.0.as_ptr()),
+                query_range.map_or(core::ptr::null(), |r| r.1.as_ptr()),
+                n_queries,
+                piece_offsets.as_ptr(),
+                n_pieces_total,
+                symbols.as_mut_ptr() as *mut c_void,
+                4,
+                out_offsets.as_ptr(),
+                scratch.as_mut_ptr() as *mut c_void,
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
+        Ok(status)
+    }
 }
 
 impl Drop for HuffmanCodebook {
@@ -6415,6 +6495,137 @@ impl ExpGolomb {
                                               symbols.as_mut_ptr() as *mut c_void, 4, sym_offsets.as_ptr(), n_streams,
                                               status.as_mut_ptr(), stream.as_raw())
         })?;
+        Ok(status)
+    }
+
+    /// [`ExpGolomb::encode_ragged`] with jump points (`cst_exp_golomb_encode_ragged_jump`): the encoder also notes the container's bit
+    /// length at every `interval` symbols of every stream (a multiple of 32; `chunk_offsets`: the exclusive prefix sum of
+    /// ceil(length / interval)) in `jump_bits`.  The words are unchanged.  Returns (n_words, n_bits, status) per stream.
+    ///
+    /// # Safety
+    /// As for `encode_ragged`; every chunk entry must lie inside `jump_bits`.
+    pub unsafe fn encode_ragged_with_jump_points(&self, symbols: &DeviceBuffer<i32>, sym_offsets: &DeviceBuffer<u64>,
+                                                 word_offsets: &DeviceBuffer<u64>, words: &mut DeviceBuffer<u32>, semantics: SymbolSemantics,
+                                                 interval: usize, chunk_offsets: &DeviceBuffer<u64>, jump_bits: &mut DeviceBuffer<u64>,
+                                                 stream: &Stream) -> Result<(DeviceBuffer<u32>, DeviceBuffer<u64>, DeviceBuffer<i32>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || chunk_offsets.len() != sym_offsets.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut n_bits: DeviceBuffer<u64> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_exp_golomb_encode_ragged_jump(semantics as i32, symbols.as_ptr() as *const c_void, 4, sym_offsets.as_ptr(), n_streams,
+                                                   words.as_mut_ptr(), word_offsets.as_ptr(), 0, n_words.as_mut_ptr(),
+                                                   n_bits.as_mut_ptr(), interval, chunk_offsets.as_ptr(), jump_bits.as_mut_ptr(),
+                                                   status.as_mut_ptr(), stream.as_raw())
+        })?;
+        Ok((n_words, n_bits, status))
+    }
+
+    /// The decoder of [`ExpGolomb::encode_ragged_with_jump_points`] (`cst_exp_golomb_decode_ragged_jump`): every chunk is decoded by a
+    /// lane of its own.
+    ///
+    /// # Safety
+    /// `sym_offsets` (device memory) must delimit ranges inside `symbols`.  The word slices and the jump table's entries ARE checked
+    /// on the device, against `words.len()`, the streams' word counts and `jump_bits.len()`.
+    pub unsafe fn decode_ragged_with_jump_points(&self, words: &DeviceBuffer<u32>, word_offsets: &DeviceBuffer<u64>,
+                                                 n_words: &DeviceBuffer<u32>, sym_offsets: &DeviceBuffer<u64>,
+                                                 symbols: &mut DeviceBuffer<i32>, semantics: SymbolSemantics, interval: usize,
+                                                 chunk_offsets: &DeviceBuffer<u64>, jump_bits: &DeviceBuffer<u64>, stream: &Stream)
+                                                 -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1
+            || chunk_offsets.len() != sym_offsets.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            ffi::cst_exp_golomb_decode_ragged_jump(semantics as i32, words.as_ptr(), word_offsets.as_ptr(), 0, words.len(),
+                                                   n_words.as_ptr(), symbols.as_mut_ptr() as *mut c_void, 4, sym_offsets.as_ptr(),
+                                                   n_streams, interval, chunk_offsets.as_ptr(), jump_bits.len(), jump_bits.as_ptr(),
+                                                   status.as_mut_ptr(), stream.as_raw())
+        })?;
+        Ok(status)
+    }
+
+    /// Random access into a ragged batch (`cst_exp_golomb_decode_ragged_select`): query q decodes symbols `[first[q], first[q] + count[q])` of
+    /// document `query_stream[q]` (`query_range = None`: whole documents) into `symbols[out_offsets[q] .. out_offsets[q + 1]]`, and
+    /// nothing else is decoded.  With `jump = Some((interval, chunk_offsets, jump_bits))` every query seeks to the jump point in front
+    /// of `first`, discards `first % interval` symbols, and each chunk it touches is a lane of its own; without, a query starts where
+    /// its document starts and discards `first` symbols.  `piece_offsets`: the exclusive prefix sum of
+    /// `ceil((first % interval + count) / interval)` (0 for `count == 0`; without jump points 1 per non-empty query),
+    /// `n_pieces_total` its last entry or an upper bound.  One status per QUERY (`INVALID_DATA` for a piece that fails).
+    ///
+    /// # Safety
+    /// As for `decode_ragged`.  Queries, piece offsets and the jump table are checked on the device; `symbols` must hold
+    /// `out_offsets[n_queries]` symbols.
+    pub unsafe fn seek_and_decode_ragged(
+        &self,
+        words: &DeviceBuffer<u32>,
+        word_offsets: &DeviceBuffer<u64>,
+        n_words: &DeviceBuffer<u32>,
+        sym_offsets: &DeviceBuffer<u64>,
+        semantics: SymbolSemantics,
+        jump: Option<(usize, &DeviceBuffer<u64>, &DeviceBuffer<u64>)>,
+        query_stream: &DeviceBuffer<u32>,
+        query_range: Option<(&DeviceBuffer<u64>, &DeviceBuffer<u64>)>,
+        piece_offsets: &DeviceBuffer<u64>,
+        n_pieces_total: usize,
+        symbols: &mut DeviceBuffer<i32>,
+        out_offsets: &DeviceBuffer<u64>,
+        stream: &Stream,
+    ) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_queries = query_stream.len();
+        if piece_offsets.len() != n_queries + 1 || out_offsets.len() != n_queries + 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if let Some((first, count)) = query_range {
+            if first.len() != n_queries || count.len() != n_queries {
+                return Err(Error::InvalidArgument);
+            }
+        }
+        if let Some((interval, chunk_offsets, _)) = jump {
+            if chunk_offsets.len() != sym_offsets.len() || interval == 0 || interval % 32 != 0 {
+                return Err(Error::InvalidArgument);
+            }
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_queries)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_ragged_select_scratch_bytes(n_pieces_total) })?;
+        check(unsafe {
+            ffi::cst_exp_golomb_decode_ragged_select(
+                semantics as i32,
+                words.as_ptr(),
+                word_offsets.as_ptr(),
+                0,
+                words.len(),
+                n_words.as_ptr(),
+                sym_offsets.as_ptr(),
+                n_streams,
+                jump.map_or(0, |j| j.0),
+                jump.map_or(core::ptr::null(), |j| j.1.as_ptr()),
+                jump.map_or(0, |j| j.2.len()),
+                jump.map_or(core::ptr::null(), |j| j.2.as_ptr()),
+                query_stream.as_ptr(),
+                query_range.map_or(core::ptr::null(), |r| r.0.as_ptr()),
+                query_range.map_or(core::ptr::null(), |r| r.1.as_ptr()),
+                n_queries,
+                piece_offsets.as_ptr(),
+                n_pieces_total,
+                symbols.as_mut_ptr() as *mut c_void,
+                4,
+                out_offsets.as_ptr(),
+                scratch.as_mut_ptr() as *mut c_void,
+                status.as_mut_ptr(),
+                stream.as_raw(),
+            )
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
         Ok(status)
     }
 }

@@ -12,8 +12,8 @@ from typing import Optional
 import torch
 
 from . import _native as N
-from ._huffman import HuffmanBatch, _semantics
-from .batched import RaggedBatch, _ptr, _require_coder, _require_cuda, _stream_ptr
+from ._huffman import BitJump, HuffmanBatch, _jump_every, _semantics
+from .batched import RAGGED_JUMP_EVERY, RaggedBatch, _ptr, _require_coder, _require_cuda, _stream_ptr
 
 _SYMBOL_BYTES = {torch.uint8: 1, torch.int16: 2, torch.int32: 4}
 
@@ -134,12 +134,21 @@ def exp_golomb_decode(encoded, n_per_stream: int, semantics=None, offsets: Optio
     return out, status
 
 
-def exp_golomb_encode_ragged(symbols: torch.Tensor, sym_offsets: torch.Tensor, semantics="stack") -> RaggedBatch:
+def exp_golomb_encode_ragged(symbols: torch.Tensor, sym_offsets: torch.Tensor, semantics="stack", jump_every=0) -> RaggedBatch:
     """One container per stream, streams of different lengths (`symbols` flat, stream s = symbols[sym_offsets[s]:sym_offsets[s+1]]) in
     one launch.  The slabs are exact: a count pass sizes each to its stream's bits (and a stack's seal), rounded up to 16 bytes.
     Returns a RaggedBatch with coder="exp_golomb" (the ANS and range decoders refuse it), config = (semantics, symbol dtype) and the
-    bit counts as `.n_bits`."""
+    bit counts as `.n_bits`.
+
+    jump_every: 0 (default) -- no jump points.  A positive multiple of 32: the encoder also notes the container's bit length at
+    every jump_every symbols of every stream (the words are unchanged) and the batch carries the table as `.jump` (a BitJump);
+    exp_golomb_decode_ragged then decodes all chunks side by side, and exp_golomb_decode_ragged_select reads parts of documents.
+    "auto": RAGGED_JUMP_EVERY where the streams average more than RAGGED_JUMP_EVERY symbols, else 0 -- the Huffman coder's rule,
+    which the measurement on 100 000 documents supports for this coder too: at 20 .. 2000 symbols per document the
+    table makes the decode 4.1-4.5 times faster for -1 .. +10 % of the encode call; at 200 symbols per document, one chunk each, the
+    decode gains 0.04 ms and the encode call loses 0.03 ms, a wash, and "auto" leaves the table out."""
     sem = _semantics(semantics)
+    jump_every = _jump_every(jump_every)
     if not symbols.is_cuda:
         raise ValueError("symbols must live in device memory (HBM)")
     sb = _symbol_bytes(symbols.dtype)
@@ -158,15 +167,30 @@ def exp_golomb_encode_ragged(symbols: torch.Tensor, sym_offsets: torch.Tensor, s
                       torch.empty(n_streams, dtype=torch.int32, device=dev), torch.empty(n_streams, dtype=torch.int32, device=dev),
                       (semantics, symbols.dtype), coder="exp_golomb")
     out.n_bits = torch.empty(n_streams, dtype=torch.int64, device=dev)
-    N.check(N.lib().cst_exp_golomb_encode_ragged(sem, _never_null(symbols), sb, _ptr(sym_offsets), n_streams, _ptr(out.words),
-                                                 _ptr(word_offsets), 0, _ptr(out.n_words), _ptr(out.n_bits), _ptr(out.status), _stream_ptr()),
-            "cst_exp_golomb_encode_ragged")
+    if jump_every == "auto":
+        jump_every = RAGGED_JUMP_EVERY if symbols.numel() > n_streams * RAGGED_JUMP_EVERY else 0
+    if not jump_every:
+        N.check(N.lib().cst_exp_golomb_encode_ragged(sem, _never_null(symbols), sb, _ptr(sym_offsets), n_streams, _ptr(out.words),
+                                                     _ptr(word_offsets), 0, _ptr(out.n_words), _ptr(out.n_bits), _ptr(out.status),
+                                                     _stream_ptr()), "cst_exp_golomb_encode_ragged")
+        return out
+    lengths = sym_offsets[1:] - sym_offsets[:-1]
+    chunk_offsets = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
+    torch.cumsum((lengths + (jump_every - 1)) // jump_every, 0, out=chunk_offsets[1:])
+    n_chunks = max(symbols.numel() // jump_every + n_streams, 1)      # (an upper bound: no read-back)
+    out.jump = BitJump(jump_every, chunk_offsets, torch.empty(n_chunks, dtype=torch.int64, device=dev))
+    N.check(N.lib().cst_exp_golomb_encode_ragged_jump(sem, _never_null(symbols), sb, _ptr(sym_offsets), n_streams, _ptr(out.words),
+                                                      _ptr(word_offsets), 0, _ptr(out.n_words), _ptr(out.n_bits), jump_every,
+                                                      _ptr(chunk_offsets), _ptr(out.jump.bits), _ptr(out.status), _stream_ptr()),
+            "cst_exp_golomb_encode_ragged_jump")
     return out
 
 
 def exp_golomb_decode_ragged(encoded: RaggedBatch, sym_offsets: torch.Tensor, out: Optional[torch.Tensor] = None):
     """Stream s yields sym_offsets[s + 1] - sym_offsets[s] symbols at out[sym_offsets[s]:], in the dtype the batch was encoded from (or
-    that of `out`).  Returns (symbols flat, status per stream)."""
+    that of `out`).  Returns (symbols flat, status per stream).  A batch with jump points (`jump_every` of the encoder) is decoded
+    chunk by chunk, all chunks side by side; a stream's status is then the largest of its chunks', and a chunk that fails reads 0
+    from the failure to its own end while the other chunks keep their symbols."""
     _require_coder(encoded, "exp_golomb")
     semantics, dtype = encoded.config
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
@@ -180,7 +204,28 @@ def exp_golomb_decode_ragged(encoded: RaggedBatch, sym_offsets: torch.Tensor, ou
     elif not out.is_cuda or not out.is_contiguous() or out.numel() < total:
         raise ValueError("out must be a contiguous device tensor with room for every symbol")
     status = torch.empty(max(n_streams, 0), dtype=torch.int32, device=dev)
-    N.check(N.lib().cst_exp_golomb_decode_ragged(_semantics(semantics), _ptr(encoded.words), _ptr(encoded.word_offsets), 0, encoded.words.numel(),
-                                                 _ptr(encoded.n_words), _never_null(out), _symbol_bytes(out.dtype), _ptr(sym_offsets), n_streams,
-                                                 _ptr(status), _stream_ptr()), "cst_exp_golomb_decode_ragged")
+    jump = encoded.jump
+    if jump is None:
+        N.check(N.lib().cst_exp_golomb_decode_ragged(_semantics(semantics), _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
+                                                     encoded.words.numel(), _ptr(encoded.n_words), _never_null(out), _symbol_bytes(out.dtype),
+                                                     _ptr(sym_offsets), n_streams, _ptr(status), _stream_ptr()), "cst_exp_golomb_decode_ragged")
+        return out, status
+    if not isinstance(jump, BitJump):
+        raise ValueError("the batch's jump points are not those of an Exp-Golomb batch")
+    if jump.chunk_offsets.numel() != n_streams + 1:
+        raise ValueError("the jump table must describe every stream of the batch")
+    N.check(N.lib().cst_exp_golomb_decode_ragged_jump(_semantics(semantics), _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
+                                                      encoded.words.numel(), _ptr(encoded.n_words), _never_null(out), _symbol_bytes(out.dtype),
+                                                      _ptr(sym_offsets), n_streams, jump.interval, _ptr(jump.chunk_offsets),
+                                                      jump.bits.numel(), _ptr(jump.bits), _ptr(status), _stream_ptr()),
+            "cst_exp_golomb_decode_ragged_jump")
     return out, status
+
+
+def exp_golomb_decode_ragged_select(encoded: RaggedBatch, sym_offsets: torch.Tensor, streams, first=None, count=None,
+                                    out: Optional[torch.Tensor] = None):
+    """`batched.huffman_decode_ragged_select` for an Exp-Golomb batch: the same queries and the same three results (symbols flat in the
+    batch's dtype or that of `out`, out_offsets, status per query).  A piece that fails reports INVALID_DATA."""
+    from .batched import _symbol_decode_ragged_select
+    return _symbol_decode_ragged_select("exp_golomb", encoded, sym_offsets, streams, first, count, out, _SYMBOL_BYTES,
+                                        "cst_exp_golomb_decode_ragged_select", tuple)

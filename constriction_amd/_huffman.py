@@ -310,3 +310,18 @@ def huffman_decode_ragged(encoded: RaggedBatch, codebook: HuffmanCodebook, sym_o
                                                    jump.bits.numel(), _ptr(jump.bits), _ptr(status), _stream_ptr()),
             "cst_huffman_decode_ragged_jump")
     return out, status
+
+
+def huffman_decode_ragged_select(encoded: RaggedBatch, codebook: HuffmanCodebook, sym_offsets: torch.Tensor, streams, first=None, count=None,
+                                 out: Optional[torch.Tensor] = None):
+    """Random access into a ragged Huffman batch: query q decodes symbols [first[q], first[q] + count[q]) of document streams[q], and
+    nothing else is decoded -- the queries and the three results (symbols flat, out_offsets int64 [n_queries + 1], status int32
+    [n_queries]) of `batched.ans_decode_ragged_select`.  The symbols come in the dtype the batch was encoded from, or in that of `out`
+    (int32 or uint8).  With jump points (`encoded.jump`, a BitJump) every query seeks to the bit index in front of `first`, decodes and
+    drops first % interval symbols, and every chunk it touches runs on a lane of its own; without them a query starts where its
+    document starts and drops `first` symbols.  A query the device refuses (no such document, a range beyond its document, a table
+    entry beyond its stream's bits, a stack without its seal) reports INVALID_DATA and writes nothing; otherwise a query's status is
+    the worst of its pieces' (OUT_OF_DATA before INVALID_DATA), and a piece that fails reads 0 from the failure to its own end."""
+    from .batched import _symbol_decode_ragged_select
+    return _symbol_decode_ragged_select("huffman", encoded, sym_offsets, streams, first, count, out, _SYMBOL_BYTES,
+                                        "cst_huffman_decode_ragged_select", lambda: (codebook._h,))

@@ -255,12 +255,16 @@ SIGNATURES = {
     "cst_huffman_decode_ragged": (_i32, [_vp, _i32, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _vp, _vp]),
     "cst_huffman_encode_ragged_jump": (_i32, [_vp, _i32, _vp, _i32, _vp, _z, _vp, _vp, _z, _vp, _vp, _z, _vp, _vp, _vp, _vp]),
     "cst_huffman_decode_ragged_jump": (_i32, [_vp, _i32, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _z, _vp, _z, _vp, _vp, _vp]),
+    "cst_huffman_decode_ragged_select": (_i32, [_vp, _i32, _vp, _vp, _z, _z, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _z, _vp, _z, _vp, _i32, _vp, _vp, _vp, _vp]),
     "cst_exp_golomb_max_words": (_z, [_z, _i32, _i32]),
     "cst_exp_golomb_count_bits": (_i32, [_vp, _i32, _vp, _z, _z, _vp, _vp]),
     "cst_exp_golomb_encode_batch": (_i32, [_i32, _vp, _i32, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
     "cst_exp_golomb_decode_batch": (_i32, [_i32, _vp, _vp, _z, _z, _vp, _vp, _i32, _z, _z, _vp, _vp, _vp, _vp]),
     "cst_exp_golomb_encode_ragged": (_i32, [_i32, _vp, _i32, _vp, _z, _vp, _vp, _z, _vp, _vp, _vp, _vp]),
     "cst_exp_golomb_decode_ragged": (_i32, [_i32, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _vp, _vp]),
+    "cst_exp_golomb_encode_ragged_jump": (_i32, [_i32, _vp, _i32, _vp, _z, _vp, _vp, _z, _vp, _vp, _z, _vp, _vp, _vp, _vp]),
+    "cst_exp_golomb_decode_ragged_jump": (_i32, [_i32, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _z, _vp, _z, _vp, _vp, _vp]),
+    "cst_exp_golomb_decode_ragged_select": (_i32, [_i32, _vp, _vp, _z, _z, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _z, _vp, _z, _vp, _i32, _vp, _vp, _vp, _vp]),
     "cst_debug_erf": (_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_tab": (_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_fast": (_i32, [_i32, _vp, _vp, _z, _vp]),

@@ -909,12 +909,13 @@ class _SelectQueries:
                  "total", "n_pieces", "out", "status", "max_piece")
 
 
-def _select_queries(encoded, jump, sym_offsets, streams, first, count, out, piece_bound=False) -> _SelectQueries:
+def _select_queries(encoded, jump, sym_offsets, streams, first, count, out, piece_bound=False, dtype=None, dtypes=None) -> _SelectQueries:
     """The query preparation of every select call (shared-table and per-symbol models alike), once the batch's coder and the type of its
     jump table are judged: the queries as tensors, their sizes and pieces, the two prefix sums, the single read-back (the output
     total), an upper bound of the pieces, the output and the statuses.  `jump`: the batch's table or None.  `piece_bound`: also
     `max_piece`, an upper bound of the symbols any piece decodes, dropped ones included -- the interval, or without a table the largest
-    first + count of the queries the device can accept, which travels with the output total in the same read-back."""
+    first + count of the queries the device can accept, which travels with the output total in the same read-back.  `dtype` / `dtypes`
+    (the symbol codes): the type of a fresh output and the types an `out` may have; by default both are int32."""
     r = _SelectQueries()
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
     n_streams = sym_offsets.numel() - 1
@@ -960,9 +961,12 @@ def _select_queries(encoded, jump, sym_offsets, streams, first, count, out, piec
     # a query of `count` symbols has at most count // I + 2 pieces: an upper bound of the pieces, without a second read-back
     n_pieces = (total // interval + 2 * n_queries) if interval else n_queries
     if out is None:
-        out = torch.empty(total, dtype=torch.int32, device=dev)
+        out = torch.empty(total, dtype=dtype or torch.int32, device=dev)
     else:
-        out = _require_cuda(out, torch.int32, "out")
+        if dtypes is None:
+            out = _require_cuda(out, torch.int32, "out")
+        elif not isinstance(out, torch.Tensor) or not out.is_cuda or not out.is_contiguous() or out.dtype not in dtypes:
+            raise ValueError("out must be a contiguous device tensor of one of the coder's symbol types")
         if out.dim() != 1 or out.numel() < total:
             raise ValueError("out must be flat and hold every query's symbols")
     r.sym_offsets, r.n_streams, r.n_queries, r.whole, r.query_stream, r.first, r.count = sym_offsets, n_streams, n_queries, whole, query_stream, first, count
@@ -976,6 +980,30 @@ def _select_tail(r: _SelectQueries):
     """the query block and the output of a select entry point, up to d_out_offsets"""
     return (_ptr(r.query_stream), None if r.whole else _ptr(r.first), None if r.whole else _ptr(r.count), r.n_queries, _ptr(r.piece_offsets),
             r.n_pieces, _ptr(r.out), _ptr(r.out_offsets))
+
+
+def _symbol_decode_ragged_select(coder, encoded, sym_offsets, streams, first, count, out, dtypes, entry, head):
+    """the body of huffman_decode_ragged_select and exp_golomb_decode_ragged_select (`dtypes`: symbol type -> symbol_bytes; `head`: the
+    arguments in front of `semantics`, made once the batch has been judged)"""
+    from ._huffman import BitJump, _semantics
+    _require_coder(encoded, coder)
+    jump = encoded.jump
+    if jump is not None and not isinstance(jump, BitJump):
+        raise ValueError("the batch carries the jump points of another coder")
+    semantics, dtype = encoded.config
+    r = _select_queries(encoded, jump, sym_offsets, streams, first, count, out, dtype=dtype, dtypes=dtypes)
+    if r.n_queries == 0:
+        return r.out[:0], r.out_offsets, r.status
+    L = N.lib()
+    table = (r.interval, _ptr(jump.chunk_offsets), int(jump.bits.numel()), _ptr(jump.bits)) if r.interval else (0, None, 0, None)
+    scratch = _ckpt_scratch("ragged_select", encoded.words.device, L.cst_ragged_select_scratch_bytes(r.n_pieces))
+    out_ptr = _ptr(r.out) if r.out.numel() else _ptr(torch.empty(4, dtype=torch.int32, device=r.out.device))     # (the ABI refuses NULL)
+    N.check(getattr(L, entry)(*head(), _semantics(semantics), _ptr(encoded.words), _ptr(encoded.word_offsets), 0, encoded.words.numel(),
+                              _ptr(encoded.n_words), _ptr(r.sym_offsets), r.n_streams, *table, _ptr(r.query_stream),
+                              None if r.whole else _ptr(r.first), None if r.whole else _ptr(r.count), r.n_queries, _ptr(r.piece_offsets),
+                              r.n_pieces, out_ptr, dtypes[r.out.dtype], _ptr(r.out_offsets), _ptr(scratch), _ptr(r.status), _stream_ptr()),
+            entry)
+    return r.out[:r.total], r.out_offsets, r.status
 
 
 def _decode_ragged_select(coder, jump_type, encoded, model, sym_offsets, streams, first, count, out):
@@ -2409,6 +2437,6 @@ def ans_decode_gaussian_checkpointed(encoded: EncodedBatch, checkpoints: Checkpo
 # ---------------------------------------------------------------------------------------------------------------------
 
 from ._huffman import (BitJump, HuffmanBatch, HuffmanCodebook, huffman_count_bits, huffman_decode, huffman_decode_ragged,  # noqa: E402,F401
-                       huffman_encode, huffman_encode_ragged, huffman_tree)
-from ._exp_golomb import (exp_golomb_count_bits, exp_golomb_decode, exp_golomb_decode_ragged, exp_golomb_encode,  # noqa: E402,F401
-                          exp_golomb_encode_ragged, exp_golomb_max_words)
+                       huffman_decode_ragged_select, huffman_encode, huffman_encode_ragged, huffman_tree)
+from ._exp_golomb import (exp_golomb_count_bits, exp_golomb_decode, exp_golomb_decode_ragged, exp_golomb_decode_ragged_select,  # noqa: E402,F401
+                          exp_golomb_encode, exp_golomb_encode_ragged, exp_golomb_max_words)

@@ -9,8 +9,9 @@
 // follow: one lane per stream, a 64-bit accumulator (encoder) or window (decoder), symbols through wave-private LDS tiles, words in
 // 16-byte groups.  There is no table: the length is a count-leading-zeros of m, the zero run a find-first-set of the window.
 #include <algorithm>
+#include <type_traits>
 
-#include "cst_common.hpp"
+#include "cst_symbol_select.hpp"
 
 namespace cst {
 
@@ -299,6 +300,28 @@ struct EgReader {
     }
     __device__ __forceinline__ void close() { nw = 0; wi = 0; buf = 0; have = 0; pf = 0; }
 
+    // the highest bit index a reader may start at: 32 n_words of a queue, the position of a stack's seal.  false: a stack without
+    // words or with a zero last word
+    __device__ __forceinline__ static bool limit(const uint32_t* words, size_t n_words, uint64_t& bits) {
+        return symbol_bit_limit<STACK>(words, n_words, bits);
+    }
+
+    // at bit index p <= limit(): a queue reads p, p + 1, ...; a stack p - 1, p - 2, ...
+    __device__ __forceinline__ void seek(const uint32_t* words, size_t n_words, uint64_t p) {
+        w = words; nw = n_words; buf = 0;
+        wi = (size_t)(p >> 5);
+        const uint32_t r = (uint32_t)(p & 31u);
+        if (STACK) {
+            have = r;
+            if (r) buf = (uint64_t)w[wi] << (64 - r);       // (the bits from p upwards leave the window at its top)
+            pf = wi > 0 ? w[wi - 1] : 0u;
+        } else {
+            have = 0;
+            if (r) { buf = w[wi++] >> r; have = 32u - r; }
+            pf = wi < nw ? w[wi] : 0u;
+        }
+    }
+
     // at least 33 valid bits, or all that is left of the stream
     __device__ __forceinline__ void refill() {
         if (STACK) {
@@ -447,6 +470,193 @@ __global__ void __launch_bounds__(kBlock) exp_golomb_decode_ragged_kernel(EgRagg
     a.status[s] = st;
 }
 
+// ---- jump points: entry d_chunk_offsets[s] + j of d_jump_bits is the bit index in stream s's container at which a
+// reader starts symbols [j I, min((j + 1) I, length)) -- the BitJump of the Huffman coders with Exp-Golomb codeword lengths ----
+
+struct EgJumpEncArgs {
+    EgRaggedEncArgs r;
+    uint64_t interval;                  // symbols per chunk,
+    const uint64_t* chunk_offsets;      // [n_streams + 1], and
+    uint64_t* jump_bits;                // the table
+};
+
+struct EgJumpDecArgs {
+    EgRaggedDecArgs r;
+    uint64_t interval;                  // symbols per chunk,
+    const uint64_t* chunk_offsets;      // [n_streams + 1],
+    size_t n_chunks_total;              // the entries of
+    const uint64_t* jump_bits;          // the table
+    SymbolSelectLanes sel;              // SELECT: one lane per piece in place of one per chunk
+};
+
+// One lane per stream, chunk by chunk in coding order, so that the symbol loop is the plain encoder's.  A queue notes the
+// container's length in front of chunk j (the bits of symbols[: j I]), a stack behind it (the bits of symbols[j I :]): one 8-byte
+// store per chunk, always between two whole codewords, and none outside the stream's own entries.
+template <bool STACK, int SB>
+__global__ void __launch_bounds__(kBlock) exp_golomb_encode_ragged_jump_kernel(EgJumpEncArgs j) {
+    const EgRaggedEncArgs& a = j.r;
+    const size_t s = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= a.n_streams) return;
+    const uint64_t lo = a.sym_offsets[s], hi = a.sym_offsets[s + 1];
+    size_t base = s * a.stride, cap = a.stride;
+    if (a.word_offsets) {
+        const uint64_t w0 = a.word_offsets[s], w1 = a.word_offsets[s + 1];
+        base = (size_t)w0;
+        cap = w1 >= w0 ? (size_t)(w1 - w0) : 0;     // (offsets that run backwards: a slab of no words)
+    }
+    int32_t st = CST_STREAM_OK;
+    if (hi < lo || hi - lo > 0xffffffffull) st = CST_STREAM_CAPACITY;
+    EgWordSink sink{a.words + base, cap, 0u, make_uint4(0, 0, 0, 0), a.vec && (base & 3u) == 0};
+    uint64_t acc = 0;
+    uint32_t nb = 0;
+    if (st == CST_STREAM_OK) {
+        const uint32_t n = (uint32_t)(hi - lo);
+        const uint32_t I = (uint32_t)j.interval;
+        const uint32_t chunks = n / I + (n % I != 0);
+        const uint64_t c0 = j.chunk_offsets[s], c1 = j.chunk_offsets[s + 1];
+        const uint64_t slots = c1 > c0 ? c1 - c0 : 0;      // (a table that does not describe the stream is not written beyond them)
+        for (uint32_t k = 0; k < chunks && st == CST_STREAM_OK; ++k) {
+            const uint32_t c = STACK ? chunks - 1 - k : k;
+            const uint32_t first = c * I, len = n - first < I ? n - first : I;      // (c I < n <= 2^32 - 1)
+            if constexpr (!STACK) {
+                if (c < slots) j.jump_bits[c0 + c] = 32ull * sink.nw + nb;
+            }
+            for (uint32_t i = 0; i < len; ++i) {
+                const uint32_t x = eg_load<SB>(a.symbols, (size_t)(lo + first + (STACK ? len - 1 - i : i)));
+                if (!eg_put_symbol<STACK, SB>(x, acc, nb, sink)) { st = CST_STREAM_CAPACITY; break; }
+            }
+            if constexpr (STACK) {
+                if (st == CST_STREAM_OK && c < slots) j.jump_bits[c0 + c] = 32ull * sink.nw + nb;
+            }
+        }
+    }
+    const uint64_t bits = 32ull * sink.nw + nb;
+    st = eg_finish<STACK>(st, false, acc, nb, sink);
+    a.n_words[s] = st == CST_STREAM_OK ? sink.nw : 0u;
+    if (a.n_bits) a.n_bits[s] = st == CST_STREAM_OK ? bits : 0ull;
+    a.status[s] = st;
+}
+
+// the chunk-lane decoder's wave-private tiles: 64 chunk rows x kEgTile symbols.  There is no code table, so the tiles are all the
+// LDS of a block.  u8 and u16 symbols lie in 16-bit elements, row stride 17 words; u32 symbols in 32-bit elements, row stride 33
+// words: both odd, so the lane-per-row writes of a wave meet no bank twice.  17 KiB or 33 KiB a block: four blocks share a CU.
+template <int SB>
+struct EgJumpTile {
+    using T = std::conditional_t<SB == 4, uint32_t, uint16_t>;
+    static constexpr int kStride = SB == 4 ? kEgTile + 1 : kEgTile + 2;     // in elements
+    static constexpr int kElems = (kBlock / kWave) * kWave * kStride;
+};
+
+// One lane per CHUNK: lane c finds its stream by a search of chunk_offsets, judges jump_bits[c] against the stream's bit limit,
+// opens the window there and decodes at most `interval` symbols, 32 at a time into its tile row; the wave then stores every row as
+// one contiguous run of the flat output.  d_status has been zeroed (CST_STREAM_OK): a chunk that fails raises its stream's status
+// with an atomic max, and thread t also judges stream t's table (INVALID_DATA if it does not describe the stream).
+// SELECT: one lane per PIECE of a select call (cst_symbol_select.hpp); (out_lo, skip, len) come from the piece's record, the
+// lane decodes and drops `skip` symbols first, and its status goes to the record.
+template <bool STACK, int SB, bool SELECT>
+__global__ void __launch_bounds__(kBlock) exp_golomb_decode_ragged_jump_kernel(EgJumpDecArgs j) {
+    using Tile = EgJumpTile<SB>;
+    __shared__ typename Tile::T s_tiles[Tile::kElems];
+    const EgRaggedDecArgs& a = j.r;
+    const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if constexpr (!SELECT) {
+        if (t < a.n_streams) {
+            const uint64_t lo = a.sym_offsets[t], hi = a.sym_offsets[t + 1];
+            const uint64_t c0 = j.chunk_offsets[t], c1 = j.chunk_offsets[t + 1];
+            if (hi < lo || c1 < c0 || c1 > j.n_chunks_total || c1 - c0 != (hi - lo + j.interval - 1) / j.interval)
+                atomicMax(a.status + t, (int32_t)CST_STREAM_INVALID_DATA);
+        }
+    }
+    const size_t n_lanes = SELECT ? j.sel.n_pieces : j.n_chunks_total;
+    const int lane = threadIdx.x & (kWave - 1);
+    if (t - (size_t)lane >= n_lanes) return;      // (wave-uniform: the whole wave lies past the chunks)
+    typename Tile::T* tile = s_tiles + (size_t)(threadIdx.x / kWave) * kWave * Tile::kStride;
+
+    uint64_t obase = 0;       // where the lane's symbols go
+    uint32_t clen = 0;        // how many it stores (0: no chunk of a well-described stream / no piece of a query, nothing is written)
+    uint32_t skip = 0;        // SELECT: symbols decoded and dropped first
+    size_t s = 0;
+    int32_t st = CST_STREAM_OK;
+    EgReader<STACK> rd;
+    rd.close();
+    if constexpr (SELECT) {
+        if (t < n_lanes) {
+            clen = j.sel.len[t];
+            if (clen) {
+                obase = j.sel.out_lo[t];
+                skip = j.sel.skip[t];
+                const uint32_t* w = a.words + j.sel.word_off[t];      // (a slice the pieces kernel has checked)
+                const size_t nw = j.sel.n_words[t];
+                const uint32_t e = j.sel.entry[t];
+                uint64_t bits;
+                if (EgReader<STACK>::limit(w, nw, bits)) {
+                    const uint64_t p = e == kSelectNoEntry ? (STACK ? bits : 0ull) : j.sel.jump_bits[e];
+                    if (p <= bits) rd.seek(w, nw, p);
+                    else st = CST_STREAM_INVALID_DATA;
+                } else st = CST_STREAM_INVALID_DATA;
+            }
+        }
+    } else {
+        // chunk t belongs to the stream s with chunk_offsets[s] <= t < chunk_offsets[s + 1]
+        for (size_t hi_s = a.n_streams; hi_s - s > 1;) {
+            const size_t mid = s + (hi_s - s) / 2;
+            if (j.chunk_offsets[mid] <= t) s = mid;
+            else hi_s = mid;
+        }
+        if (t < n_lanes) {
+            const uint64_t lo = a.sym_offsets[s], hi = a.sym_offsets[s + 1];
+            const uint64_t c0 = j.chunk_offsets[s], c1 = j.chunk_offsets[s + 1];
+            if (hi >= lo && c0 <= t && t < c1 && c1 <= j.n_chunks_total && c1 - c0 == (hi - lo + j.interval - 1) / j.interval) {
+                obase = lo + (t - c0) * j.interval;
+                clen = (uint32_t)(hi - obase < j.interval ? hi - obase : j.interval);
+                const size_t base = a.word_offsets ? (size_t)a.word_offsets[s] : s * a.stride;
+                const size_t nw = a.n_words[s];
+                const bool inside = !((!a.word_offsets && nw > a.stride) || (a.capacity && (base > a.capacity || nw > a.capacity - base)));
+                uint64_t bits;
+                const uint64_t p = j.jump_bits[t];
+                // before any word at the jump point is read: the point lies inside the stream's bits
+                if (inside && EgReader<STACK>::limit(a.words + base, nw, bits) && p <= bits) rd.seek(a.words + base, nw, p);
+                else st = CST_STREAM_INVALID_DATA;
+            }
+        }
+    }
+    int32_t worst = st;
+    if constexpr (SELECT) {
+        for (uint32_t i = 0; i < skip && st == CST_STREAM_OK; ++i) {
+            uint32_t sym;
+            if (!rd.template decode<SB>(sym)) worst = st = CST_STREAM_INVALID_DATA;
+        }
+    }
+    uint32_t wmax = clen;     // the wave's longest chunk
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, d, kWave));
+    const uint32_t col = (uint32_t)lane & 31u;
+    const uint32_t obase_lo = (uint32_t)obase, obase_hi = (uint32_t)(obase >> 32);
+    for (uint32_t t0 = 0; t0 < wmax; t0 += kEgTile) {
+        const uint32_t tlen = clen > t0 ? (clen - t0 < (uint32_t)kEgTile ? clen - t0 : (uint32_t)kEgTile) : 0u;
+        for (uint32_t i = 0; i < tlen; ++i) {
+            uint32_t sym = 0;          // (from the failure to the chunk's end: 0)
+            if (st == CST_STREAM_OK && !rd.template decode<SB>(sym)) { worst = st = CST_STREAM_INVALID_DATA; sym = 0; }
+            tile[lane * Tile::kStride + i] = (typename Tile::T)sym;
+        }
+        eg_lds_fence();
+        // lane l stores column (l & 31) of rows (l >> 5) + 2k, each row at its own place in the flat output
+#pragma unroll 8
+        for (int k = 0; k < kWave / 2; ++k) {
+            const int row = (lane >> 5) + 2 * k;
+            const uint64_t rbase = (uint64_t)(uint32_t)__shfl((int)obase_lo, row, kWave) | ((uint64_t)(uint32_t)__shfl((int)obase_hi, row, kWave) << 32);
+            const uint32_t rlen = (uint32_t)__shfl((int)clen, row, kWave);
+            if (t0 + col < rlen) eg_store<SB>(a.symbols, (size_t)(rbase + t0 + col), tile[row * Tile::kStride + col]);
+        }
+        eg_lds_fence();
+    }
+    if constexpr (SELECT) {
+        if (t < n_lanes) j.sel.status[t] = worst;
+    } else {
+        if (worst != CST_STREAM_OK) atomicMax(a.status + s, worst);
+    }
+}
+
 // ---- the exact bit count of every stream: one wave per stream, 16 bytes of symbols per lane and step ----
 
 template <int SB>
@@ -521,6 +731,20 @@ cst_status launch_eg(K kernel, size_t blocks, hipStream_t hs, A... args) {
 inline bool eg_semantics_ok(int32_t semantics) { return semantics == CST_HUFFMAN_STACK || semantics == CST_HUFFMAN_QUEUE; }
 inline bool eg_width_ok(int32_t symbol_bytes) { return symbol_bytes == 1 || symbol_bytes == 2 || symbol_bytes == 4; }
 inline size_t eg_blocks(size_t n_streams) { return (n_streams + kBlock - 1) / kBlock; }
+// chunks of 32 .. 2^31 - 32 symbols, a multiple of the symbol tile's width
+inline bool eg_interval_ok(size_t interval) { return interval > 0 && interval % kEgTile == 0 && interval <= 0x7fffffffull; }
+
+// exp_golomb_decode_ragged_jump_kernel<STACK, SB, SELECT> over `lanes` chunks or pieces
+template <bool SELECT>
+cst_status eg_jump_decode(bool stack, int32_t sb, size_t lanes, hipStream_t hs, const EgJumpDecArgs& a) {
+    const size_t blocks = eg_blocks(lanes);
+    if (stack) return sb == 1 ? launch_eg(exp_golomb_decode_ragged_jump_kernel<true, 1, SELECT>, blocks, hs, a)
+                    : sb == 2 ? launch_eg(exp_golomb_decode_ragged_jump_kernel<true, 2, SELECT>, blocks, hs, a)
+                              : launch_eg(exp_golomb_decode_ragged_jump_kernel<true, 4, SELECT>, blocks, hs, a);
+    return sb == 1 ? launch_eg(exp_golomb_decode_ragged_jump_kernel<false, 1, SELECT>, blocks, hs, a)
+         : sb == 2 ? launch_eg(exp_golomb_decode_ragged_jump_kernel<false, 2, SELECT>, blocks, hs, a)
+                   : launch_eg(exp_golomb_decode_ragged_jump_kernel<false, 4, SELECT>, blocks, hs, a);
+}
 
 } // namespace
 
@@ -618,6 +842,75 @@ cst_status cst_exp_golomb_decode_ragged(int32_t semantics, const uint32_t* d_wor
     hipStream_t hs = (hipStream_t)stream;
     return note_kernel("exp_golomb_decode_ragged_kernel",
                        CST_EG_DISPATCH(exp_golomb_decode_ragged_kernel, semantics == CST_HUFFMAN_STACK, symbol_bytes, eg_blocks(n_streams), hs, a));
+}
+
+cst_status cst_exp_golomb_encode_ragged_jump(int32_t semantics, const void* d_symbols, int32_t symbol_bytes, const uint64_t* d_sym_offsets,
+                                             size_t n_streams, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                             uint32_t* d_n_words, uint64_t* d_n_bits, size_t jump_interval, const uint64_t* d_chunk_offsets,
+                                             uint64_t* d_jump_bits, int32_t* d_status, void* stream) {
+    if (!d_symbols || !d_sym_offsets || !d_words || !d_n_words || !d_status) return CST_ERR_INVALID_ARGUMENT;
+    if (!eg_semantics_ok(semantics) || !eg_width_ok(symbol_bytes)) return CST_ERR_INVALID_ARGUMENT;
+    if (!eg_interval_ok(jump_interval) || !d_chunk_offsets || !d_jump_bits) return CST_ERR_INVALID_ARGUMENT;
+    if (n_streams == 0) return CST_OK;
+    EgJumpEncArgs j{};
+    EgRaggedEncArgs& a = j.r;
+    a.symbols = d_symbols; a.sym_offsets = d_sym_offsets; a.n_streams = n_streams;
+    a.words = d_words; a.word_offsets = d_word_offsets; a.stride = stride_words;
+    a.n_words = d_n_words; a.n_bits = d_n_bits; a.status = d_status;
+    a.vec = (reinterpret_cast<uintptr_t>(d_words) & 15u) == 0 && (d_word_offsets || stride_words % 4 == 0);
+    j.interval = jump_interval; j.chunk_offsets = d_chunk_offsets; j.jump_bits = d_jump_bits;
+    hipStream_t hs = (hipStream_t)stream;
+    return note_kernel("exp_golomb_encode_ragged_jump_kernel",
+                       CST_EG_DISPATCH(exp_golomb_encode_ragged_jump_kernel, semantics == CST_HUFFMAN_STACK, symbol_bytes, eg_blocks(n_streams), hs, j));
+}
+
+cst_status cst_exp_golomb_decode_ragged_jump(int32_t semantics, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                             size_t words_capacity, const uint32_t* d_n_words, void* d_symbols, int32_t symbol_bytes,
+                                             const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                             const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint64_t* d_jump_bits,
+                                             int32_t* d_status, void* stream) {
+    if (!d_words || !d_n_words || !d_symbols || !d_sym_offsets || !d_status) return CST_ERR_INVALID_ARGUMENT;
+    if (!eg_semantics_ok(semantics) || !eg_width_ok(symbol_bytes)) return CST_ERR_INVALID_ARGUMENT;
+    if (!eg_interval_ok(jump_interval) || !d_chunk_offsets || !d_jump_bits) return CST_ERR_INVALID_ARGUMENT;
+    if (n_streams == 0) return CST_OK;
+    EgJumpDecArgs j{};
+    EgRaggedDecArgs& a = j.r;
+    a.words = d_words; a.word_offsets = d_word_offsets; a.stride = stride_words; a.capacity = words_capacity; a.n_words = d_n_words;
+    a.symbols = d_symbols; a.sym_offsets = d_sym_offsets; a.n_streams = n_streams; a.status = d_status;
+    j.interval = jump_interval; j.chunk_offsets = d_chunk_offsets; j.n_chunks_total = n_chunks_total; j.jump_bits = d_jump_bits;
+    hipStream_t hs = (hipStream_t)stream;
+    CST_HIP_TRY(hipMemsetAsync(d_status, 0, n_streams * sizeof(int32_t), hs));      // CST_STREAM_OK: the kernel only raises it
+    const size_t lanes = std::max(n_streams, n_chunks_total);      // a lane per chunk, and one per stream for the table's check
+    return note_kernel("exp_golomb_decode_ragged_jump_kernel", eg_jump_decode<false>(semantics == CST_HUFFMAN_STACK, symbol_bytes, lanes, hs, j));
+}
+
+cst_status cst_exp_golomb_decode_ragged_select(int32_t semantics, const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                               size_t words_capacity, const uint32_t* d_n_words, const uint64_t* d_sym_offsets, size_t n_streams,
+                                               size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                               const uint64_t* d_jump_bits, const uint32_t* d_query_stream, const uint64_t* d_query_first,
+                                               const uint64_t* d_query_count, size_t n_queries, const uint64_t* d_piece_offsets,
+                                               size_t n_pieces_total, void* d_symbols_out, int32_t symbol_bytes, const uint64_t* d_out_offsets,
+                                               void* d_scratch, int32_t* d_status, void* stream) {
+    if (!d_words || !d_n_words || !d_sym_offsets) return CST_ERR_INVALID_ARGUMENT;
+    if (!eg_semantics_ok(semantics) || !eg_width_ok(symbol_bytes)) return CST_ERR_INVALID_ARGUMENT;
+    const int table = (d_chunk_offsets != nullptr) + (d_jump_bits != nullptr);
+    if (!symbol_select_args_ok(jump_interval, table, n_chunks_total, d_query_first, d_query_count, n_pieces_total)) return CST_ERR_INVALID_ARGUMENT;
+    if (n_queries > 0 && (!d_query_stream || !d_piece_offsets || !d_symbols_out || !d_out_offsets || !d_scratch || !d_status))
+        return CST_ERR_INVALID_ARGUMENT;
+    if (n_queries == 0) return CST_OK;
+    if (n_queries > ((size_t)0x7fffffff) * 256) return CST_ERR_INVALID_ARGUMENT;
+    const RaggedSelect b = symbol_select_batch(d_word_offsets, stride_words, words_capacity, d_n_words, d_sym_offsets, n_streams, jump_interval,
+                                               d_chunk_offsets, n_chunks_total, d_query_stream, d_query_first, d_query_count, n_queries,
+                                               d_piece_offsets, n_pieces_total, d_out_offsets);
+    const RaggedSelectPieces v(d_scratch, n_pieces_total);
+    EgJumpDecArgs j{};
+    j.r.words = d_words; j.r.symbols = d_symbols_out;
+    j.sel = symbol_select_lanes(v, d_jump_bits, n_pieces_total);
+    hipStream_t hs = (hipStream_t)stream;
+    const bool stack = semantics == CST_HUFFMAN_STACK;
+    return note_kernel("exp_golomb_decode_ragged_jump_kernel<select>", symbol_select_run(stack, b, d_words, d_jump_bits, v, d_status, hs, [&] {
+                           return eg_jump_decode<true>(stack, symbol_bytes, n_pieces_total, hs, j);
+                       }));
 }
 
 }  // extern "C"

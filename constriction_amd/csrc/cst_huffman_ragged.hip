@@ -8,8 +8,10 @@
 // entry 0 is n_bits, where the seal sits).  Either way it is the container's length when the encoder crosses that boundary, so
 // the encoder notes it on its way, and the jump decoder runs one lane per CHUNK: the longest chain of a launch is I symbols.
 #include <algorithm>
+#include <type_traits>
 
 #include "cst_huffman.hpp"
+#include "cst_symbol_select.hpp"
 
 namespace cst {
 
@@ -51,6 +53,11 @@ struct HrDecArgs {
     const uint64_t* chunk_offsets;      // [n_streams + 1],
     size_t n_chunks_total;              // the entries of
     const uint64_t* jump_bits;          // the table
+};
+
+// the SELECT form of the jump decoder: one lane per piece of a select call (cst_symbol_select.hpp)
+struct HrSelArgs : HrDecArgs {
+    SymbolSelectLanes sel;
 };
 
 // dynamic LDS: [codeword table (LDS_TAB)].  One lane per stream, its symbols read where they lie.
@@ -136,12 +143,7 @@ struct HuffReader {
     // the highest bit index a reader may start at: the container's bit length.  A stack's is the position of its seal, the
     // HIGHEST set bit of its last word.  false: a stack without words or with a zero last word
     __device__ __forceinline__ static bool limit(const uint32_t* words, size_t n_words, uint64_t& bits) {
-        if (!STACK) { bits = 32ull * n_words; return true; }
-        if (n_words == 0) return false;
-        const uint32_t last = words[n_words - 1];
-        if (last == 0u) return false;
-        bits = 32ull * (n_words - 1) + (31u - (uint32_t)__clz((int)last));
-        return true;
+        return symbol_bit_limit<STACK>(words, n_words, bits);
     }
 
     // at bit index p <= limit(): a queue reads p, p + 1, ...; a stack p - 1, p - 2, ...
@@ -262,35 +264,58 @@ constexpr size_t kJumpTileBytesPerBlock = (size_t)(kBlock / kWave) * kWave * kJu
 // row; the wave then stores every row as one contiguous run of the flat output (128 B of int32, 32 B of uint8).
 // d_status has been zeroed (CST_STREAM_OK): a chunk that fails raises its stream's status with an atomic max, and thread t also
 // judges stream t's table (INVALID_DATA if it does not describe the stream).
-template <bool STACK, bool LONG, int SB>
-__global__ void __launch_bounds__(kBlock) huffman_decode_ragged_jump_kernel(HrDecArgs a) {
+// SELECT: one lane per PIECE of a select call; (out_lo, skip, len) come from the piece's record in place of (obase, clen), the
+// lane decodes and drops `skip` symbols first, and its status goes to the record.
+template <bool STACK, bool LONG, int SB, bool SELECT = false>
+__global__ void __launch_bounds__(kBlock) huffman_decode_ragged_jump_kernel(std::conditional_t<SELECT, HrSelArgs, HrDecArgs> a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_dec_lds[];
     const uint32_t lut_n = 1u << a.lut_bits;
     const uint32_t* s_lut = stage_lut(s_dec_lds, a.lut, lut_n);
     const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t < a.n_streams) {
-        const uint64_t lo = a.sym_offsets[t], hi = a.sym_offsets[t + 1];
-        const uint64_t c0 = a.chunk_offsets[t], c1 = a.chunk_offsets[t + 1];
-        if (hi < lo || c1 < c0 || c1 > a.n_chunks_total || c1 - c0 != (hi - lo + a.interval - 1) / a.interval)
-            atomicMax(a.status + t, (int32_t)CST_STREAM_INVALID_DATA);
+    if constexpr (!SELECT) {
+        if (t < a.n_streams) {
+            const uint64_t lo = a.sym_offsets[t], hi = a.sym_offsets[t + 1];
+            const uint64_t c0 = a.chunk_offsets[t], c1 = a.chunk_offsets[t + 1];
+            if (hi < lo || c1 < c0 || c1 > a.n_chunks_total || c1 - c0 != (hi - lo + a.interval - 1) / a.interval)
+                atomicMax(a.status + t, (int32_t)CST_STREAM_INVALID_DATA);
+        }
     }
+    size_t n_lanes = a.n_chunks_total;
+    if constexpr (SELECT) n_lanes = a.sel.n_pieces;
     const int lane = threadIdx.x & (kWave - 1);
-    if (t - (size_t)lane >= a.n_chunks_total) return;      // (wave-uniform: the whole wave lies past the chunks)
+    if (t - (size_t)lane >= n_lanes) return;      // (wave-uniform: the whole wave lies past the chunks)
     uint16_t* tile = reinterpret_cast<uint16_t*>(s_dec_lds + ((lut_n + 3) & ~3u)) + (size_t)(threadIdx.x / kWave) * kWave * kJumpTileStride;
 
     // chunk t belongs to the stream s with chunk_offsets[s] <= t < chunk_offsets[s + 1]
     size_t s = 0;
-    for (size_t hi_s = a.n_streams; hi_s - s > 1;) {
-        const size_t mid = s + (hi_s - s) / 2;
-        if (a.chunk_offsets[mid] <= t) s = mid;
-        else hi_s = mid;
+    if constexpr (!SELECT) {
+        for (size_t hi_s = a.n_streams; hi_s - s > 1;) {
+            const size_t mid = s + (hi_s - s) / 2;
+            if (a.chunk_offsets[mid] <= t) s = mid;
+            else hi_s = mid;
+        }
     }
     uint64_t obase = 0;       // where the chunk's symbols go
     uint32_t clen = 0;        // how many it has (0: no chunk of a well-described stream, nothing is written)
     int32_t st = CST_STREAM_OK;
     HuffReader<STACK> rd;
     rd.close();
-    if (t < a.n_chunks_total) {
+    uint32_t skip = 0;        // SELECT: symbols decoded and dropped first
+    if constexpr (SELECT) {
+        if (t < n_lanes && (clen = a.sel.len[t]) != 0) {
+            obase = a.sel.out_lo[t];
+            skip = a.sel.skip[t];
+            const uint32_t* w = a.words + a.sel.word_off[t];      // (a slice the pieces kernel has checked)
+            const size_t nw = a.sel.n_words[t];
+            const uint32_t e = a.sel.entry[t];
+            uint64_t bits;
+            if (HuffReader<STACK>::limit(w, nw, bits)) {
+                const uint64_t p = e == kSelectNoEntry ? (STACK ? bits : 0ull) : a.sel.jump_bits[e];
+                if (p <= bits) rd.seek(w, nw, p);
+                else st = CST_STREAM_INVALID_DATA;
+            } else st = CST_STREAM_INVALID_DATA;
+        }
+    } else if (t < a.n_chunks_total) {
         const uint64_t lo = a.sym_offsets[s], hi = a.sym_offsets[s + 1];
         const uint64_t c0 = a.chunk_offsets[s], c1 = a.chunk_offsets[s + 1];
         if (hi >= lo && c0 <= t && t < c1 && c1 <= a.n_chunks_total && c1 - c0 == (hi - lo + a.interval - 1) / a.interval) {
@@ -311,6 +336,12 @@ __global__ void __launch_bounds__(kBlock) huffman_decode_ragged_jump_kernel(HrDe
     const uint32_t col = (uint32_t)lane & 31u;
     const uint32_t obase_lo = (uint32_t)obase, obase_hi = (uint32_t)(obase >> 32);
     int32_t worst = st;
+    if constexpr (SELECT) {
+        for (; skip > 0 && st == CST_STREAM_OK; --skip) {
+            uint32_t sym;
+            worst = st = rd.template decode<LONG>(s_lut, a.child, a.n_sym, L, lmask, sym);
+        }
+    }
     for (uint32_t t0 = 0; t0 < wmax; t0 += kTile) {
         const uint32_t tlen = clen > t0 ? (clen - t0 < (uint32_t)kTile ? clen - t0 : (uint32_t)kTile) : 0u;
         for (uint32_t j = 0; j < tlen; ++j) {
@@ -332,7 +363,11 @@ __global__ void __launch_bounds__(kBlock) huffman_decode_ragged_jump_kernel(HrDe
         }
         wave_lds_fence();
     }
-    if (worst != CST_STREAM_OK) atomicMax(a.status + s, worst);
+    if constexpr (SELECT) {
+        if (t < n_lanes) a.sel.status[t] = worst;
+    } else {
+        if (worst != CST_STREAM_OK) atomicMax(a.status + s, worst);
+    }
 }
 
 // ---- the exact bit count of every stream: one wave per stream, 16 bytes of symbols per lane and step ----
@@ -406,6 +441,18 @@ cst_status encode_ragged(const HuffCodebook* c, int32_t semantics, const HrEncAr
                 : (symbol_bytes == 1 ? launch_huff(KERNEL<true, false, 1>, lanes, lds, hs, a) : launch_huff(KERNEL<true, false, 4>, lanes, lds, hs, a)))     \
          : (lng ? (symbol_bytes == 1 ? launch_huff(KERNEL<false, true, 1>, lanes, lds, hs, a) : launch_huff(KERNEL<false, true, 4>, lanes, lds, hs, a))      \
                 : (symbol_bytes == 1 ? launch_huff(KERNEL<false, false, 1>, lanes, lds, hs, a) : launch_huff(KERNEL<false, false, 4>, lanes, lds, hs, a))))
+
+// huffman_decode_ragged_jump_kernel<STACK, LONG, SB, true> over the pieces of a select call
+template <bool STACK, bool LONG>
+cst_status decode_select_sb(const HrSelArgs& a, int32_t symbol_bytes, size_t lds, hipStream_t hs) {
+    if (symbol_bytes == 1) return launch_huff(huffman_decode_ragged_jump_kernel<STACK, LONG, 1, true>, a.sel.n_pieces, lds, hs, a);
+    return launch_huff(huffman_decode_ragged_jump_kernel<STACK, LONG, 4, true>, a.sel.n_pieces, lds, hs, a);
+}
+
+cst_status decode_select(bool stack, bool lng, const HrSelArgs& a, int32_t symbol_bytes, size_t lds, hipStream_t hs) {
+    if (stack) return lng ? decode_select_sb<true, true>(a, symbol_bytes, lds, hs) : decode_select_sb<true, false>(a, symbol_bytes, lds, hs);
+    return lng ? decode_select_sb<false, true>(a, symbol_bytes, lds, hs) : decode_select_sb<false, false>(a, symbol_bytes, lds, hs);
+}
 
 inline bool semantics_ok(int32_t semantics) { return semantics == CST_HUFFMAN_STACK || semantics == CST_HUFFMAN_QUEUE; }
 inline bool width_ok(int32_t symbol_bytes) { return symbol_bytes == 1 || symbol_bytes == 4; }
@@ -540,6 +587,40 @@ cst_status cst_huffman_decode_ragged_jump(const void* cb, int32_t semantics, con
     const size_t lanes = std::max(n_streams, n_chunks_total);      // a lane per chunk, and one per stream for the table's check
     return note_kernel(lng ? "huffman_decode_ragged_jump_long_kernel" : "huffman_decode_ragged_jump_kernel",
                        CST_HR_DECODE(huffman_decode_ragged_jump_kernel, lanes, lut_bytes(c) + kJumpTileBytesPerBlock));
+}
+
+cst_status cst_huffman_decode_ragged_select(const void* cb, int32_t semantics, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                            size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const uint64_t* d_sym_offsets,
+                                            size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                            const uint64_t* d_jump_bits, const uint32_t* d_query_stream, const uint64_t* d_query_first,
+                                            const uint64_t* d_query_count, size_t n_queries, const uint64_t* d_piece_offsets,
+                                            size_t n_pieces_total, void* d_symbols_out, int32_t symbol_bytes, const uint64_t* d_out_offsets,
+                                            void* d_scratch, int32_t* d_status, void* stream) {
+    if (!valid_cb(cb) || !d_words || !d_n_words || !d_sym_offsets) return CST_ERR_INVALID_ARGUMENT;
+    if (!semantics_ok(semantics) || !width_ok(symbol_bytes)) return CST_ERR_INVALID_ARGUMENT;
+    if (symbol_bytes == 1 && static_cast<const HuffCodebook*>(cb)->n > 256) return CST_ERR_INVALID_ARGUMENT;    // the alphabet does not fit the type
+    const int table = (d_chunk_offsets != nullptr) + (d_jump_bits != nullptr);
+    if (!symbol_select_args_ok(jump_interval, table, n_chunks_total, d_query_first, d_query_count, n_pieces_total)) return CST_ERR_INVALID_ARGUMENT;
+    if (n_queries > 0 && (!d_query_stream || !d_piece_offsets || !d_symbols_out || !d_out_offsets || !d_scratch || !d_status))
+        return CST_ERR_INVALID_ARGUMENT;
+    if (n_queries == 0) return CST_OK;
+    if (n_queries > ((size_t)0x7fffffff) * 256) return CST_ERR_INVALID_ARGUMENT;
+    const HuffCodebook* c = static_cast<const HuffCodebook*>(cb);
+    if (!on_device(c)) return CST_ERR_INVALID_ARGUMENT;
+    const RaggedSelect b = symbol_select_batch(d_word_offsets, stride_words, words_capacity, d_n_words, d_sym_offsets, n_streams, jump_interval,
+                                               d_chunk_offsets, n_chunks_total, d_query_stream, d_query_first, d_query_count, n_queries,
+                                               d_piece_offsets, n_pieces_total, d_out_offsets);
+    const RaggedSelectPieces v(d_scratch, n_pieces_total);
+    HrSelArgs a{};
+    a.lut = c->d_lut; a.child = c->d_child; a.n_sym = (uint32_t)c->n; a.lut_bits = c->lut_bits;
+    a.words = d_words; a.symbols = d_symbols_out;
+    a.sel = symbol_select_lanes(v, d_jump_bits, n_pieces_total);
+    hipStream_t hs = (hipStream_t)stream;
+    const bool stack = semantics == CST_HUFFMAN_STACK, lng = c->max_len > c->lut_bits;
+    return note_kernel(lng ? "huffman_decode_ragged_jump_long_kernel<select>" : "huffman_decode_ragged_jump_kernel<select>",
+                       symbol_select_run(stack, b, d_words, d_jump_bits, v, d_status, hs, [&] {
+                           return decode_select(stack, lng, a, symbol_bytes, lut_bytes(c) + kJumpTileBytesPerBlock, hs);
+                       }));
 }
 
 }  // extern "C"

@@ -10,7 +10,11 @@ symbols' empirical distribution: huffman_encode_ragged plain and with jump_every
 table, and the Exp-Golomb ragged pair on the same symbols.  The calls of one row alternate, so that drift of a shared machine hits
 all of them; every time is the median of REPEATS event timings (each the median of 20 launches), `*_spread_ms` their min .. max.
 The encode calls include their count pass, the prefix sum of the slabs and its read-back; `encode_kernel` / `encode_jump_kernel`
-are the two encoder kernels alone, through the C ABI into buffers that exist."""
+are the two encoder kernels alone, through the C ABI into buffers that exist.
+
+bench_huffman.py --ragged --select N [n_documents]: on the same batches only scripts/bench_symbol_select.py's measurements (DESIGN.md
+4.28): N whole documents and N ranges of 64 symbols through huffman_decode_ragged_select, with the table and without, against the
+full jump decode and a gather."""
 import json
 import sys
 from pathlib import Path
@@ -42,7 +46,7 @@ def timed_alternating(calls):
     return {name: (round(sorted(v)[len(v) // 2], 4), [round(min(v), 4), round(max(v), 4)]) for name, v in t.items()}
 
 
-def ragged(n_docs):
+def ragged(n_docs, n_select=0):
     rng = np.random.default_rng(1)          # the generator and the order of draws of scripts/bench_ragged.py
     n_alphabet = 64
     doc_probs = rng.dirichlet(np.ones(n_alphabet) * 0.5)
@@ -56,6 +60,14 @@ def ragged(n_docs):
             for semantics in ("stack", "queue"):
                 plain = B.huffman_encode_ragged(flat, offsets, book, semantics)
                 jump = B.huffman_encode_ragged(flat, offsets, book, semantics, jump_every=JUMP_EVERY)
+                if n_select:
+                    from bench_symbol_select import select_rows
+                    line(what="huffman_ragged_select", batch=batch_name, semantics=semantics, symbols=str(flat.dtype).replace("torch.", ""),
+                         documents=n_docs, jump_every=JUMP_EVERY,
+                         **select_rows(flat, offsets, jump, plain, lambda b, o: B.huffman_decode_ragged(b, book, offsets, out=o),
+                                       lambda b, s, f, c, o: B.huffman_decode_ragged_select(b, book, offsets, s, f, c, out=o), n_select))
+                    del plain, jump
+                    continue
                 eg = B.exp_golomb_encode_ragged(flat, offsets, semantics)
                 out = torch.empty_like(flat)
                 # the two encoder kernels alone, into the batches' own buffers (no count pass, no prefix sums, no allocation)
@@ -102,7 +114,13 @@ def ragged(n_docs):
 
 if "--ragged" in sys.argv:
     rest = [a for a in sys.argv[1:] if a != "--ragged"]
-    ragged(int(rest[0]) if rest else 100_000)
+    n_select = 0
+    if "--select" in rest:
+        i = rest.index("--select")
+        n_select = int(rest[i + 1])
+        del rest[i: i + 2]
+        sys.path.insert(0, str(Path(__file__).resolve().parent))
+    ragged(int(rest[0]) if rest else 100_000, n_select)
     sys.exit(0)
 
 n, k = (int(sys.argv[1]) if len(sys.argv) > 1 else bench.N_STREAMS), (int(sys.argv[2]) if len(sys.argv) > 2 else bench.N_PER)
