@@ -6629,3 +6629,106 @@ impl ExpGolomb {
         Ok(status)
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Indexed table coding: every symbol names one of K tabulated models (cst_indexed.hip).  Pass-throughs only: one call per entry
+// point, the defaults of the C ABI (no optional outputs).
+// ---------------------------------------------------------------------------------------------------------------------
+
+/// K cdfs that share a support and a precision (`cst_table_set`): `encode_symbols_reverse(symbols.zip(indices.map(|k| &tables[k])))`
+/// (src/stream/stack.rs:784-849) resp. `encode_symbols` (src/stream/queue.rs:612-705) for a whole batch of coders.
+pub struct TableSet {
+    raw: *mut c_void,
+}
+
+impl TableSet {
+    /// `cdfs`: `n_tables` rows of `n_symbols + 1` cumulatives, back to back.
+    pub fn from_cdfs(cdfs: &[u32], n_tables: usize, min_symbol: i32, precision: i32) -> Result<Self> {
+        if n_tables == 0 || n_tables > 256 || cdfs.len() % n_tables != 0 || cdfs.len() / n_tables < 3 {
+            return Err(Error::InvalidArgument);
+        }
+        let mut raw: *mut c_void = core::ptr::null_mut();
+        check(unsafe {
+            ffi::cst_table_set_create(precision, min_symbol, (cdfs.len() / n_tables - 1) as i32, n_tables as i32, cdfs.as_ptr(), &mut raw)
+        })?;
+        Ok(TableSet { raw })
+    }
+
+    pub fn precision(&self) -> i32 {
+        unsafe { ffi::cst_table_set_precision(self.raw) }
+    }
+
+    pub fn min_symbol(&self) -> i32 {
+        unsafe { ffi::cst_table_set_min_symbol(self.raw) }
+    }
+
+    pub fn n_symbols(&self) -> i32 {
+        unsafe { ffi::cst_table_set_n_symbols(self.raw) }
+    }
+
+    pub fn n_tables(&self) -> i32 {
+        unsafe { ffi::cst_table_set_n_tables(self.raw) }
+    }
+
+    fn config(&self) -> CoderConfig {
+        CoderConfig { word_bits: 32, state_bits: 64, precision: self.precision() }
+    }
+
+    /// One `AnsCoder` (`range`: one `RangeEncoder`) per row of the stream-major `symbols` matrix; `indices`: uint8, of its shape.
+    pub fn encode(&self, range: bool, symbols: &DeviceBuffer<i32>, indices: &DeviceBuffer<u8>, n_streams: usize, n_per_stream: usize,
+                  stream: &Stream) -> Result<EncodedBatch> {
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        if symbols.len() < count || indices.len() < count {
+            return Err(Error::InvalidArgument);
+        }
+        let config = self.config();
+        let stride = unsafe { if range { ffi::cst_range_max_words(n_per_stream, config) } else { ffi::cst_ans_max_words(n_per_stream, config) } };
+        let mut out = EncodedBatch::allocate(n_streams, stride, config)?;
+        check(unsafe {
+            if range {
+                ffi::cst_range_encode_indexed_batch(self.raw, config, symbols.as_ptr(), indices.as_ptr() as *const c_void, 1, n_streams,
+                                                    n_per_stream, ffi::CST_LAYOUT_STREAM_MAJOR, out.words.as_mut_ptr(), stride,
+                                                    out.n_words.as_mut_ptr(), core::ptr::null_mut(), out.status.as_mut_ptr(),
+                                                    ffi::CST_FLAG_NONE, stream.as_raw())
+            } else {
+                ffi::cst_ans_encode_indexed_batch(self.raw, config, symbols.as_ptr(), indices.as_ptr() as *const c_void, 1, n_streams,
+                                                  n_per_stream, ffi::CST_LAYOUT_STREAM_MAJOR, out.words.as_mut_ptr(), stride,
+                                                  out.n_words.as_mut_ptr(), core::ptr::null_mut(), out.status.as_mut_ptr(),
+                                                  ffi::CST_FLAG_NONE, stream.as_raw())
+            }
+        })?;
+        Ok(out)
+    }
+
+    /// `n_per_stream` symbols of every stream of `encoded` with the tables `indices` names.
+    pub fn decode(&self, range: bool, encoded: &EncodedBatch, indices: &DeviceBuffer<u8>, n_per_stream: usize, stream: &Stream)
+                  -> Result<DecodedBatch> {
+        let n_streams = encoded.n_streams;
+        let count = n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)?;
+        if indices.len() < count {
+            return Err(Error::InvalidArgument);
+        }
+        let mut out = DecodedBatch { symbols: DeviceBuffer::new(count)?, status: DeviceBuffer::new(n_streams)? };
+        check(unsafe {
+            if range {
+                ffi::cst_range_decode_indexed_batch(self.raw, encoded.config, encoded.words.as_ptr(), core::ptr::null(), encoded.stride_words,
+                                                    encoded.words.len(), encoded.n_words.as_ptr(), indices.as_ptr() as *const c_void, 1,
+                                                    out.symbols.as_mut_ptr(), n_streams, n_per_stream, ffi::CST_LAYOUT_STREAM_MAJOR,
+                                                    core::ptr::null_mut(), out.status.as_mut_ptr(), ffi::CST_FLAG_NONE, stream.as_raw())
+            } else {
+                ffi::cst_ans_decode_indexed_batch(self.raw, encoded.config, encoded.words.as_ptr(), core::ptr::null(), encoded.stride_words,
+                                                  encoded.words.len(), encoded.n_words.as_ptr(), indices.as_ptr() as *const c_void, 1,
+                                                  out.symbols.as_mut_ptr(), n_streams, n_per_stream, ffi::CST_LAYOUT_STREAM_MAJOR,
+                                                  core::ptr::null_mut(), core::ptr::null_mut(), out.status.as_mut_ptr(), ffi::CST_FLAG_NONE,
+                                                  stream.as_raw())
+            }
+        })?;
+        Ok(out)
+    }
+}
+
+impl Drop for TableSet {
+    fn drop(&mut self) {
+        unsafe { ffi::cst_table_set_destroy(self.raw) };
+    }
+}

@@ -265,6 +265,16 @@ SIGNATURES = {
     "cst_exp_golomb_encode_ragged_jump": (_i32, [_i32, _vp, _i32, _vp, _z, _vp, _vp, _z, _vp, _vp, _z, _vp, _vp, _vp, _vp]),
     "cst_exp_golomb_decode_ragged_jump": (_i32, [_i32, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _z, _vp, _z, _vp, _vp, _vp]),
     "cst_exp_golomb_decode_ragged_select": (_i32, [_i32, _vp, _vp, _z, _z, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp, _vp, _z, _vp, _z, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "cst_table_set_create": (_i32, [_i32, _i32, _i32, _i32, _vp, C.POINTER(_vp)]),
+    "cst_table_set_destroy": (_i32, [_vp]),
+    "cst_table_set_precision": (_i32, [_vp]),
+    "cst_table_set_min_symbol": (_i32, [_vp]),
+    "cst_table_set_n_symbols": (_i32, [_vp]),
+    "cst_table_set_n_tables": (_i32, [_vp]),
+    "cst_ans_encode_indexed_batch": (_i32, [_vp, CoderConfig, _vp, _vp, _i32, _z, _z, _i32, _vp, _z, _vp, _vp, _vp, _u32, _vp]),
+    "cst_ans_decode_indexed_batch": (_i32, [_vp, CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _z, _i32, _vp, _vp, _vp, _u32, _vp]),
+    "cst_range_encode_indexed_batch": (_i32, [_vp, CoderConfig, _vp, _vp, _i32, _z, _z, _i32, _vp, _z, _vp, _vp, _vp, _u32, _vp]),
+    "cst_range_decode_indexed_batch": (_i32, [_vp, CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _z, _i32, _vp, _vp, _u32, _vp]),
     "cst_debug_erf": (_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_tab": (_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_fast": (_i32, [_i32, _vp, _vp, _z, _vp]),

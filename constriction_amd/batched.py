@@ -2440,3 +2440,162 @@ from ._huffman import (BitJump, HuffmanBatch, HuffmanCodebook, huffman_count_bit
                        huffman_decode_ragged_select, huffman_encode, huffman_encode_ragged, huffman_tree)
 from ._exp_golomb import (exp_golomb_count_bits, exp_golomb_decode, exp_golomb_decode_ragged, exp_golomb_decode_ragged_select,  # noqa: E402,F401
                           exp_golomb_encode, exp_golomb_encode_ragged, exp_golomb_max_words)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# indexed table coding: every symbol names one of K tabulated models (csrc/cst_indexed.hip) -- what a learned
+# codec does whose hyperprior quantises every latent's scale to one of K levels:
+#     coder.encode_symbols_reverse(symbols.zip(indices.map(|k| &tables[k])))      src/stream/stack.rs:784-849
+# ---------------------------------------------------------------------------------------------------------------------
+
+class TableSet:
+    """K cdfs that share a support and a precision (include/constriction_amd.h, cst_table_set): at most 256 tables whose LDS image
+    fits beside the coder's rings and tiles (64 tables of 255 symbols at any precision, 256 tables of 64 symbols up to P = 16)."""
+
+    def __init__(self, handle, cdfs: np.ndarray, min_symbol: int, precision: int):
+        self._h = handle
+        self._cdfs = cdfs
+        self._min_symbol, self._precision = int(min_symbol), int(precision)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                N.load_library().cst_table_set_destroy(h)
+            except Exception:
+                pass
+
+    @classmethod
+    def from_cdfs(cls, cdfs, min_symbol: int, precision: int) -> "TableSet":
+        """cdfs [K, n + 1], every row with cdf[0] = 0 < cdf[1] < ... < cdf[n] = 2^P (ValueError otherwise, and for a set that does
+        not fit)."""
+        cdfs = np.ascontiguousarray(cdfs, dtype=np.uint32)
+        if cdfs.ndim != 2 or cdfs.shape[1] < 3:
+            raise ValueError("cdfs must be 2-d: one row of n_symbols + 1 >= 3 cumulatives per table")
+        if not 1 <= cdfs.shape[0] <= 256:
+            raise ValueError("a table set holds 1 to 256 tables")
+        if not 1 <= int(precision) <= 24:
+            raise ValueError("precision must be 1 .. 24")
+        h = C.c_void_p()
+        N.check(N.load_library().cst_table_set_create(int(precision), int(min_symbol), cdfs.shape[1] - 1, cdfs.shape[0], cdfs.ctypes.data,
+                                                      C.byref(h)), "cst_table_set_create")
+        return cls(h, cdfs, min_symbol, precision)
+
+    @classmethod
+    def quantized_gaussians(cls, min_symbol: int, max_symbol: int, means, stds, precision: int) -> "TableSet":
+        """K tables LeakyQuantizer(min..=max) x Gaussian(means[k], stds[k]), tabulated on the GPU in bit-exact f64 by the kernel behind
+        Model.quantized_gaussian / Model.quantized_gaussian_per_stream."""
+        means = torch.as_tensor(means, dtype=torch.float64).reshape(-1)
+        stds = torch.as_tensor(stds, dtype=torch.float64).reshape(-1)
+        if means.numel() != stds.numel() or not 1 <= means.numel() <= 256:
+            raise ValueError("means and stds: one entry per table, 1 to 256 tables")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if precision <= 16:
+            rows = Model.quantized_gaussian_per_stream(min_symbol, max_symbol, means.to(dev), stds.to(dev), precision).cdfs_device()
+            cdfs = rows.cpu().numpy().view(np.uint32)
+        else:       # (per-stream models stop at 16 bits: one shared-table model per level, the same kernel)
+            cdfs = np.stack([Model.quantized_gaussian(min_symbol, max_symbol, float(m), float(s), precision).cdf()
+                             for m, s in zip(means.tolist(), stds.tolist())])
+        return cls.from_cdfs(cdfs, min_symbol, precision)
+
+    @property
+    def precision(self):
+        return self._precision
+
+    @property
+    def min_symbol(self):
+        return self._min_symbol
+
+    @property
+    def n_symbols(self):
+        return self._cdfs.shape[1] - 1
+
+    @property
+    def n_tables(self):
+        return self._cdfs.shape[0]
+
+    def cdfs(self) -> np.ndarray:
+        """uint32 [n_tables, n_symbols + 1]: the rows the set was built from"""
+        return self._cdfs.copy()
+
+
+def _indexed_args(symbols_shape, device, indices, tables, config):
+    """the checks of the indexed calls that need no device: ValueError before any native call"""
+    if not isinstance(tables, TableSet):
+        raise ValueError("tables must be a batched.TableSet")
+    if tuple(config[:2]) != (32, 64) or int(config[2]) != tables.precision:
+        raise ValueError("indexed coding: config must be (32, 64, precision of the table set)")
+    if not isinstance(indices, torch.Tensor) or indices.dtype not in (torch.uint8, torch.int32):
+        raise ValueError("indices must be a torch.uint8 or torch.int32 tensor")
+    if tuple(indices.shape) != tuple(symbols_shape):
+        raise ValueError("indices must have the shape of the symbol matrix")
+    if not indices.is_cuda or indices.device != device:
+        raise ValueError("indices must live in device memory (HBM), on the device of the symbols / words")
+    return indices.contiguous(), (1 if indices.dtype == torch.uint8 else 4)
+
+
+def _encode_indexed(fn_name, max_words_fn, symbols, indices, tables, config, stride, out):
+    if not isinstance(symbols, torch.Tensor) or symbols.dim() != 2 or symbols.dtype != torch.int32 or not symbols.is_cuda:
+        raise ValueError("symbols must be a 2-d torch.int32 tensor [n_streams, n_per_stream] in device memory (HBM)")
+    indices, index_bytes = _indexed_args(symbols.shape, symbols.device, indices, tables, config)
+    symbols = symbols.contiguous()
+    n_streams, n_per = symbols.shape
+    if out is None:
+        out = _new_batch(n_streams, stride or max_words_fn(n_per, config), symbols.device, config)
+    N.check(getattr(N.lib(), fn_name)(tables._h, _cfg(*config), _ptr(symbols), _ptr(indices), index_bytes, n_streams, n_per,
+                                      N.LAYOUT_STREAM_MAJOR, _ptr(out.words), out.words.shape[1], _ptr(out.n_words), None, _ptr(out.status),
+                                      N.FLAG_NONE, _stream_ptr()), fn_name)
+    out.jump = None
+    return out
+
+
+def ans_encode_indexed(symbols, indices, tables: TableSet, config=(32, 64, 16), stride: Optional[int] = None,
+                       out: Optional[EncodedBatch] = None) -> EncodedBatch:
+    """One AnsCoder per stream: encode_symbols_reverse(symbols[s] zipped with tables[indices[s]]) + get_compressed.  `indices`:
+    torch.uint8 or torch.int32, the symbols' shape.  No jump points; the batch works with compact / reverse_words / container.save."""
+    return _encode_indexed("cst_ans_encode_indexed_batch", max_words, symbols, indices, tables, config, stride, out)
+
+
+def range_encode_indexed(symbols, indices, tables: TableSet, config=(32, 64, 16), stride: Optional[int] = None,
+                         out: Optional[EncodedBatch] = None) -> EncodedBatch:
+    """One RangeEncoder per stream: encode_symbols(symbols[s] zipped with tables[indices[s]]) + get_compressed."""
+    return _encode_indexed("cst_range_encode_indexed_batch", range_max_words, symbols, indices, tables, config, stride, out)
+
+
+def _decode_indexed(fn_name, ans, encoded, indices, tables, n_per_stream, offsets, out):
+    if isinstance(encoded, EncodedBatch):
+        words, n_words = encoded.words, encoded.n_words
+        stride = words.shape[1]
+    else:
+        words, n_words = encoded
+        stride = words.shape[1] if words.dim() == 2 else 0
+    if not isinstance(tables, TableSet):
+        raise ValueError("tables must be a batched.TableSet")
+    n_streams = n_words.numel()
+    indices, index_bytes = _indexed_args((n_streams, int(n_per_stream)), words.device, indices, tables, (32, 64, tables.precision))
+    if isinstance(encoded, EncodedBatch) and tuple(encoded.config) != (32, 64, tables.precision):
+        raise ValueError("the batch was not coded with (32, 64, precision of the table set)")
+    if stride == 0 and offsets is None:
+        raise ValueError("packed words need their offsets")
+    if out is None:
+        out = torch.empty((n_streams, int(n_per_stream)), dtype=torch.int32, device=words.device)
+    elif tuple(out.shape) != (n_streams, int(n_per_stream)) or out.dtype != torch.int32 or out.device != words.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous int32 tensor [n_streams, n_per_stream] on the device of the words")
+    status = torch.empty(n_streams, dtype=torch.int32, device=words.device)
+    args = [tables._h, _cfg(32, 64, tables.precision), _ptr(words), _ptr(offsets), stride, words.numel(), _ptr(n_words), _ptr(indices),
+            index_bytes, _ptr(out), n_streams, int(n_per_stream), N.LAYOUT_STREAM_MAJOR, None]
+    if ans:
+        args.append(None)          # d_n_words_out
+    N.check(getattr(N.lib(), fn_name)(*args, _ptr(status), N.FLAG_NONE, _stream_ptr()), fn_name)
+    return out, status
+
+
+def ans_decode_indexed(encoded, indices, tables: TableSet, n_per_stream: int, offsets=None, out=None):
+    """One AnsCoder per stream: AnsCoder(words[s]).decode_symbols(tables[indices[s]]).  `encoded`: an EncodedBatch, or
+    (packed, n_words) with offsets= (compact()).  Returns (symbols, status)."""
+    return _decode_indexed("cst_ans_decode_indexed_batch", True, encoded, indices, tables, n_per_stream, offsets, out)
+
+
+def range_decode_indexed(encoded, indices, tables: TableSet, n_per_stream: int, offsets=None, out=None):
+    """One RangeDecoder per stream: RangeDecoder(words[s]).decode_symbols(tables[indices[s]]).  Returns (symbols, status)."""
+    return _decode_indexed("cst_range_decode_indexed_batch", False, encoded, indices, tables, n_per_stream, offsets, out)

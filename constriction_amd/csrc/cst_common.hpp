@@ -157,10 +157,14 @@ struct Knobs {
     int auto_jump = 1;                // CST_AUTO_JUMP=0: cst_jump_points_auto answers 0 (the plain decoders everywhere)
     int ragged_group = 16;            // CST_RAGGED_GROUP=8|16|32: symbols per memory point of the ragged encoder (cst_ans_ragged.hip)
     int categorical_route = 0;        // CST_CATEGORICAL_ROUTE=fused|rows: 1 / 2 forces a route of the per-symbol Categorical decoders (0: by shape)
+    int indexed_bucket_bits = 8;      // CST_INDEXED_BUCKET_BITS=0..8: the most bucket bits a table set built from now on takes (0: its decoders search whole rows)
     size_t perfect_ragged_budget = (size_t)16 << 20;   // CST_PERFECT_RAGGED_BUDGET=words: the tabulated rows of one step of the ragged
                                                        // Categorical(perfect=True) decoders (64 MiB; 1 .. 2^31 - 1)
 };
 const Knobs& knobs();
+
+// a host cdf[n + 1] that a table model accepts: cdf[0] = 0 < cdf[1] < ... < cdf[n] = 2^P (cst_model.hip)
+bool cdf_valid(const uint32_t* cdf, int n, int P);
 
 // thread-local record of the last HIP failure (cst_last_hip_error)
 void set_hip_error(hipError_t e, const char* what);

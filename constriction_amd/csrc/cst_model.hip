@@ -259,7 +259,7 @@ __global__ void debug_lcp_kernel(int P, int prob_bits, int32_t lo, int32_t hi, c
     left[i] = l; prob[i] = p;
 }
 
-static bool cdf_valid(const uint32_t* cdf, int n, int P) {
+bool cdf_valid(const uint32_t* cdf, int n, int P) {       // (declared in cst_common.hpp: cst_table_set_create keeps the same rules)
     if (cdf[0] != 0u) return false;
     if (cdf[n] != (uint32_t)((uint64_t)1 << P)) return false;         // (2^32 wraps to 0: Probability = u32 at PRECISION = 32)
     for (int i = 0; i + 1 < n; ++i)

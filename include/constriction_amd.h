@@ -838,6 +838,7 @@ size_t cst_jump_points_auto_gaussian(cst_coder_config cfg, int32_t coder, size_t
  *   CST_FUSED_MIN_STREAMS=n  from how many streams the fused per-symbol encoder runs         CST_CATEGORICAL_ROUTE=fused|rows   per-symbol Categorical decoders: the route
  *   CST_AUTO_JUMP=0          cst_jump_points_auto* answer 0                  CST_RAGGED_GROUP=8|16|32   ragged encoder: symbols per memory point
  *   CST_PERFECT_RAGGED_BUDGET=n   ragged Categorical(perfect=True) decoders: 32-bit words of tabulated rows per step (default 16777216 = 64 MiB)
+ *   CST_INDEXED_BUCKET_BITS=0..8  table sets built from now on: the most bits of bucket index (default 8; 0: the indexed decoders search whole rows)
  * (CST_RCCL_LIB=<path>, read at the first collective call, names the RCCL library to open.)
  * cst_debug_reload_knobs re-reads them: for tests that drive several paths inside one process; not thread-safe against
  * concurrent coder calls. */
@@ -1718,6 +1719,73 @@ cst_status cst_exp_golomb_decode_ragged_select(int32_t semantics, const uint32_t
                                                const uint64_t *d_query_count, size_t n_queries, const uint64_t *d_piece_offsets,
                                                size_t n_pieces_total, void *d_symbols_out, int32_t symbol_bytes,
                                                const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * indexed table coding: every symbol names one of K tabulated models
+ *
+ * The common way to drive an entropy coder from a learned codec: a hyperprior or context model predicts one scale (or class)
+ * per latent, the prediction is quantised to one of K levels, and the coder uses that level's pre-tabulated model:
+ *     coder.encode_symbols_reverse(symbols.zip(indices.map(|k| &tables[k])))      src/stream/stack.rs:784-849
+ *     encoder.encode_symbols(symbols.zip(indices.map(|k| &tables[k])))            src/stream/queue.rs:612-705
+ * with every tables[k] a ContiguousCategoricalEntropyModel (src/stream/model/categorical/contiguous.rs:673-700).  Only K distinct
+ * models ever exist, so they live in LDS and a symbol costs its index (1 or 4 bytes) of side traffic.
+ *
+ * A cst_table_set is K cdfs that share a support [min_symbol, min_symbol + n_symbols) and a precision: an opaque handle of its
+ * own, passed as void * like the Huffman codebook (*out of cst_table_set_create; valid for the calls below and
+ * cst_table_set_destroy; the getters answer 0 for anything else).  It is NOT a cst_model: a cst_model with several tables means
+ * "one table per stream" to every other entry point.
+ * Limits: 1 <= n_tables <= 256 and 1 <= precision <= 24 (else CST_ERR_INVALID_ARGUMENT); n_symbols >= 2, and the set's LDS image
+ * must fit beside the coder's rings and tiles: n_tables * (n_symbols + 1) * E bytes of rows, rounded up to 16, E = 2 for
+ * precision <= 16 and 4 above, plus at least n_tables * 2 * B bytes of bucket index, rounded up to 16, B = 1 for n_symbols <= 256
+ * and 2 above, in 90 KiB (92 160 bytes) -- else CST_ERR_MODEL.  64 tables of 255 symbols fit at every precision, 256 tables of
+ * 64 symbols at precision <= 16.  Every row h_cdfs[k][0 .. n_symbols] is validated as cst_model_create_table validates its one
+ * row (0 = cdf[0] < cdf[1] < ... < cdf[n_symbols] = 2^precision); a bad row: CST_ERR_MODEL.  Argument errors are reported
+ * before the device is touched; without a device: CST_ERR_NO_DEVICE.  The device image is built once, here. */
+cst_status cst_table_set_create(int32_t precision, int32_t min_symbol, int32_t n_symbols, int32_t n_tables, const uint32_t *h_cdfs,
+                                void **out);
+cst_status cst_table_set_destroy(void *tables);
+int32_t cst_table_set_precision(const void *tables);
+int32_t cst_table_set_min_symbol(const void *tables);
+int32_t cst_table_set_n_symbols(const void *tables);
+int32_t cst_table_set_n_tables(const void *tables);
+
+/* cst_ans_encode_batch / cst_ans_decode_batch / cst_range_encode_batch / cst_range_decode_batch with the table set in the model's
+ * place and two more arguments: d_indices, of the symbol matrix's shape and layout, and index_bytes = 1 (uint8) or 4 (int32).
+ * Symbol t of stream s is coded with table d_indices[s][t]; every stream's words, count and final state are those of the reference
+ * coder fed that sequence of models (the ANS coder walks a row last symbol first, as encode_symbols_reverse does), in the slab /
+ * offset / words_capacity conventions of the plain calls.
+ * Scope: cfg = (32, 64, precision of the set), int32 symbols, CST_LAYOUT_STREAM_MAJOR, flags = CST_FLAG_NONE, any number of streams
+ * and symbols per stream.  Anything else, a NULL pointer (d_state, d_rstate and d_n_words_out excepted) or a handle that is not a
+ * live table set: CST_ERR_INVALID_ARGUMENT before any device call.
+ * Optional outputs (NULL = discard): the encoders leave the coder state in front of its seal in d_state[s] (the ANS state whose
+ * words end the stream) resp. d_rstate[s] (lower, range, inverted_n, inverted_first); the decoders leave what remains of the coder
+ * in d_state[s] and d_n_words_out[s] (words not consumed) resp. d_rstate[s] (lower, range, point, position = words consumed).
+ * Per-stream status: a symbol outside the support, or an encoder index >= n_tables (no table gives that symbol a probability):
+ * CST_STREAM_IMPOSSIBLE_SYMBOL; a slab too small: CST_STREAM_CAPACITY -- d_n_words[s] is then 0, the slab's content and the optional
+ * state are unspecified, as after cst_ans_encode_batch.  A decoder index >= n_tables: CST_STREAM_INVALID_DATA, and that stream's
+ * symbols from there on, its state and counts are unspecified (the index is clamped before any table is read).  A failing stream
+ * never disturbs its neighbours and writes nothing outside its own row and slab.  Decoding past the end of the words and corrupt
+ * counts or offsets behave as in cst_ans_decode_batch / cst_range_decode_batch.
+ * cst_last_kernel_name: "ans_encode_indexed_kernel", "ans_decode_indexed_kernel", "range_encode_indexed_kernel",
+ * "range_decode_indexed_kernel". */
+cst_status cst_ans_encode_indexed_batch(const void *tables, cst_coder_config cfg, const int32_t *d_symbols,
+                                        const void *d_indices, int32_t index_bytes, size_t n_streams, size_t n_per_stream,
+                                        cst_layout layout, uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                        uint64_t *d_state, int32_t *d_status, uint32_t flags, void *stream);
+cst_status cst_ans_decode_indexed_batch(const void *tables, cst_coder_config cfg, const uint32_t *d_words,
+                                        const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
+                                        const uint32_t *d_n_words, const void *d_indices, int32_t index_bytes, int32_t *d_symbols,
+                                        size_t n_streams, size_t n_per_stream, cst_layout layout, uint64_t *d_state,
+                                        uint32_t *d_n_words_out, int32_t *d_status, uint32_t flags, void *stream);
+cst_status cst_range_encode_indexed_batch(const void *tables, cst_coder_config cfg, const int32_t *d_symbols,
+                                          const void *d_indices, int32_t index_bytes, size_t n_streams, size_t n_per_stream,
+                                          cst_layout layout, uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                          cst_range_state *d_rstate, int32_t *d_status, uint32_t flags, void *stream);
+cst_status cst_range_decode_indexed_batch(const void *tables, cst_coder_config cfg, const uint32_t *d_words,
+                                          const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
+                                          const uint32_t *d_n_words, const void *d_indices, int32_t index_bytes, int32_t *d_symbols,
+                                          size_t n_streams, size_t n_per_stream, cst_layout layout, cst_range_state *d_rstate,
+                                          int32_t *d_status, uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * bit-exact f64 special functions on device (test hooks for the model kernels)
