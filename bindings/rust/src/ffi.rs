@@ -3583,6 +3583,195 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    /// Indexed table coding for streams of DIFFERENT lengths, plain and with jump points: the per-symbol ragged calls
+    /// (cst_{ans,range}_{encode,decode}_gaussian_ragged[_jump] above) with the table set and the index array in the model's place.
+    /// Stream s owns elements [d_sym_offsets[s], d_sym_offsets[s + 1]) of the flat d_symbols (int32) and d_indices (index_bytes = 1: uint8,
+    /// 4: int32; the same element numbering); symbol t of a stream is coded with table d_indices[that element].  The ANS coder codes a
+    /// stream last symbol first, the range coder first symbol first.  Every stream's words, count and status are those of
+    /// cst_{ans,range}_encode_indexed_batch for that stream alone, and those of the reference coder fed that sequence of models.
+    ///   - Slabs: d_word_offsets[n_streams + 1] (slab of stream s = [off[s], off[s + 1])), or NULL with stride_words > 0 (s * stride_words).
+    ///     A stream of n symbols fills at most min(n, ceil(n P / 32)) + 2 words under either coder (the two words of the ANS state, resp.
+    ///     the two words that seal a range coder).  d_order: NULL, or [n_streams] lane slot -> stream (cst_ans_encode_ragged's schedule; an
+    ///     entry that is not a stream codes nothing); results are indexed by stream whatever the order.
+    ///   - Jump points: layout and semantics of the table are those of cst_{ans,range}_encode_gaussian_ragged_jump -- jump_interval a
+    ///     positive multiple of 16; chunk j of stream s is entry d_chunk_offsets[s] + j; ANS notes (words in the bulk, state) AFTER the
+    ///     chunk's first symbol has been coded, the range coder (words emitted including held-back ones, lower, range) BEFORE it; no chunk
+    ///     starts at the end of a stream.  The words are bit-identical to the plain call's.  The jump decoders take no d_order and
+    ///     d_scratch of cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) bytes; they run every table entry as a coder of its own.
+    ///   - Per-stream status.  Encode: a symbol outside the support or an index >= n_tables: CST_STREAM_IMPOSSIBLE_SYMBOL with d_n_words[s]
+    ///     = 0, for that stream alone; a slab too small, or offsets that run backwards: CST_STREAM_CAPACITY; a stream of length 0: 0 words,
+    ///     CST_STREAM_OK.  Decode: an index >= n_tables is clamped before any table is read and its stream reports
+    ///     CST_STREAM_INVALID_DATA (the worst of its chunks' statuses in the jump form); a slice that leaves words_capacity:
+    ///     CST_STREAM_INVALID_DATA; a jump table that does not describe its stream, or a d_jump_pos beyond d_n_words:
+    ///     CST_STREAM_INVALID_DATA for that stream -- the others decode, and nothing outside words_capacity or the stream's own symbols is
+    ///     touched.  No index byte outside [d_indices, d_indices + index_bytes * d_sym_offsets[n_streams]) is read: a uint8 row may start at
+    ///     any byte, an int32 row at any 4-byte boundary.
+    ///   - CST_ERR_INVALID_ARGUMENT, before the device is touched: a NULL `tables` or a handle that is not a live table set; a NULL
+    ///     d_symbols / d_indices / d_sym_offsets / d_words / d_n_words / d_status; index_bytes not 1 or 4; a preset other than (32, 64);
+    ///     cfg.precision not the set's; d_word_offsets == NULL with stride_words == 0; n_streams > 2^32 - 1; in the jump forms also
+    ///     jump_interval 0, not a multiple of 16 or > 2^31 - 1, a NULL d_chunk_offsets or table array, n_chunks_total > 2^32 - 1, a NULL
+    ///     d_scratch.  n_streams == 0 (with arguments that pass): CST_OK, nothing is launched.
+    /// cst_last_kernel_name(): {ans,range}_{encode,decode}_indexed_ragged_kernel, with <jump> appended for the jump forms.
+    pub fn cst_ans_encode_indexed_ragged(
+        cfg: CstCoderConfig,
+        tables: *const c_void,
+        d_symbols: *const i32,
+        d_indices: *const c_void,
+        index_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_encode_indexed_ragged(
+        cfg: CstCoderConfig,
+        tables: *const c_void,
+        d_symbols: *const i32,
+        d_indices: *const c_void,
+        index_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_indexed_ragged(
+        cfg: CstCoderConfig,
+        tables: *const c_void,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_indices: *const c_void,
+        index_bytes: i32,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_indexed_ragged(
+        cfg: CstCoderConfig,
+        tables: *const c_void,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_indices: *const c_void,
+        index_bytes: i32,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_encode_indexed_ragged_jump(
+        cfg: CstCoderConfig,
+        tables: *const c_void,
+        d_symbols: *const i32,
+        d_indices: *const c_void,
+        index_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32,
+        d_jump_state: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_encode_indexed_ragged_jump(
+        cfg: CstCoderConfig,
+        tables: *const c_void,
+        d_symbols: *const i32,
+        d_indices: *const c_void,
+        index_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32,
+        d_jump_lower: *mut u64,
+        d_jump_range: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_indexed_ragged_jump(
+        cfg: CstCoderConfig,
+        tables: *const c_void,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_indices: *const c_void,
+        index_bytes: i32,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_indexed_ragged_jump(
+        cfg: CstCoderConfig,
+        tables: *const c_void,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_indices: *const c_void,
+        index_bytes: i32,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// bit-exact f64 special functions on device (test hooks for the model kernels)
     /// out[i] = erf(x[i]) resp. Gaussian cdf, evaluated by the same device code the table kernels use.
     pub fn cst_debug_erf(d_x: *const f64, d_out: *mut f64, n: usize, stream: *mut c_void) -> CstStatus;

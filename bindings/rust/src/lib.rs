@@ -6725,6 +6725,99 @@ impl TableSet {
         })?;
         Ok(out)
     }
+
+    /// Streams of different lengths (`cst_{ans,range}_encode_indexed_ragged[_jump]`, cst_indexed_ragged.hip): stream `s` owns elements
+    /// `sym_offsets[s] .. sym_offsets[s + 1]` of the flat `symbols` / `indices` (uint8) and the slab `word_offsets[s] .. word_offsets[s + 1]`
+    /// of `words`.  `jump`: `(jump_interval, chunk_offsets, pos, state or lower, range)` -- the encoder then notes the coder's `pos()` in
+    /// front of every chunk (the fifth buffer is used by the range coder only).  Returns one word count and one status per stream.
+    ///
+    /// # Safety
+    /// The offsets are device data: they must lie inside `symbols` / `indices` / `words`, and the table buffers must hold an entry per chunk.
+    pub unsafe fn encode_ragged(&self, range: bool, symbols: &DeviceBuffer<i32>, indices: &DeviceBuffer<u8>, sym_offsets: &DeviceBuffer<u64>,
+                                order: Option<&DeviceBuffer<u32>>, words: &mut DeviceBuffer<u32>, word_offsets: &DeviceBuffer<u64>,
+                                jump: Option<(usize, &DeviceBuffer<u64>, &mut DeviceBuffer<u32>, &mut DeviceBuffer<u64>, &mut DeviceBuffer<u64>)>,
+                                stream: &Stream) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>)> {
+        if sym_offsets.is_empty() || word_offsets.len() != sym_offsets.len() || indices.len() < symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let config = self.config();
+        let order = order.map_or(core::ptr::null(), |o| o.as_ptr());
+        let mut n_words: DeviceBuffer<u32> = DeviceBuffer::new(n_streams)?;
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        check(unsafe {
+            match (jump, range) {
+                (None, false) => ffi::cst_ans_encode_indexed_ragged(config, self.raw, symbols.as_ptr(), indices.as_ptr() as *const c_void, 1,
+                                                                    sym_offsets.as_ptr(), n_streams, order, words.as_mut_ptr(), word_offsets.as_ptr(), 0,
+                                                                    n_words.as_mut_ptr(), status.as_mut_ptr(), stream.as_raw()),
+                (None, true) => ffi::cst_range_encode_indexed_ragged(config, self.raw, symbols.as_ptr(), indices.as_ptr() as *const c_void, 1,
+                                                                     sym_offsets.as_ptr(), n_streams, order, words.as_mut_ptr(), word_offsets.as_ptr(), 0,
+                                                                     n_words.as_mut_ptr(), status.as_mut_ptr(), stream.as_raw()),
+                (Some((interval, chunk_offsets, pos, a, _)), false) => ffi::cst_ans_encode_indexed_ragged_jump(
+                    config, self.raw, symbols.as_ptr(), indices.as_ptr() as *const c_void, 1, sym_offsets.as_ptr(), n_streams, order,
+                    words.as_mut_ptr(), word_offsets.as_ptr(), 0, n_words.as_mut_ptr(), interval, chunk_offsets.as_ptr(), pos.as_mut_ptr(),
+                    a.as_mut_ptr(), status.as_mut_ptr(), stream.as_raw()),
+                (Some((interval, chunk_offsets, pos, a, b)), true) => ffi::cst_range_encode_indexed_ragged_jump(
+                    config, self.raw, symbols.as_ptr(), indices.as_ptr() as *const c_void, 1, sym_offsets.as_ptr(), n_streams, order,
+                    words.as_mut_ptr(), word_offsets.as_ptr(), 0, n_words.as_mut_ptr(), interval, chunk_offsets.as_ptr(), pos.as_mut_ptr(),
+                    a.as_mut_ptr(), b.as_mut_ptr(), status.as_mut_ptr(), stream.as_raw()),
+            }
+        })?;
+        Ok((n_words, status))
+    }
+
+    /// The decoder of `encode_ragged` (`cst_{ans,range}_decode_indexed_ragged[_jump]`).  `jump`: `(jump_interval, chunk_offsets, pos, state
+    /// or lower, range, n_chunks_total)` -- every chunk is then decoded as a coder of its own and `order` is not used.  One status per stream.
+    ///
+    /// # Safety
+    /// As for `encode_ragged`; the slices and the jump table are checked against the word counts on the device.
+    pub unsafe fn decode_ragged(&self, range: bool, words: &DeviceBuffer<u32>, word_offsets: &DeviceBuffer<u64>, n_words: &DeviceBuffer<u32>,
+                                indices: &DeviceBuffer<u8>, sym_offsets: &DeviceBuffer<u64>, symbols: &mut DeviceBuffer<i32>,
+                                order: Option<&DeviceBuffer<u32>>,
+                                jump: Option<(usize, &DeviceBuffer<u64>, &DeviceBuffer<u32>, &DeviceBuffer<u64>, &DeviceBuffer<u64>, usize)>,
+                                stream: &Stream) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 || indices.len() < symbols.len() {
+            return Err(Error::InvalidArgument);
+        }
+        let n_streams = sym_offsets.len() - 1;
+        let config = self.config();
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_streams)?;
+        match jump {
+            None => {
+                let order = order.map_or(core::ptr::null(), |o| o.as_ptr());
+                check(unsafe {
+                    if range {
+                        ffi::cst_range_decode_indexed_ragged(config, self.raw, words.as_ptr(), word_offsets.as_ptr(), 0, words.len(), n_words.as_ptr(),
+                                                             indices.as_ptr() as *const c_void, 1, symbols.as_mut_ptr(), sym_offsets.as_ptr(),
+                                                             n_streams, order, status.as_mut_ptr(), stream.as_raw())
+                    } else {
+                        ffi::cst_ans_decode_indexed_ragged(config, self.raw, words.as_ptr(), word_offsets.as_ptr(), 0, words.len(), n_words.as_ptr(),
+                                                           indices.as_ptr() as *const c_void, 1, symbols.as_mut_ptr(), sym_offsets.as_ptr(),
+                                                           n_streams, order, status.as_mut_ptr(), stream.as_raw())
+                    }
+                })?;
+            }
+            Some((interval, chunk_offsets, pos, a, b, n_chunks_total)) => {
+                let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) })?;
+                check(unsafe {
+                    if range {
+                        ffi::cst_range_decode_indexed_ragged_jump(config, self.raw, words.as_ptr(), word_offsets.as_ptr(), 0, words.len(),
+                                                                  n_words.as_ptr(), indices.as_ptr() as *const c_void, 1, symbols.as_mut_ptr(),
+                                                                  sym_offsets.as_ptr(), n_streams, interval, chunk_offsets.as_ptr(), n_chunks_total,
+                                                                  pos.as_ptr(), a.as_ptr(), b.as_ptr(), scratch.as_mut_ptr() as *mut c_void,
+                                                                  status.as_mut_ptr(), stream.as_raw())
+                    } else {
+                        ffi::cst_ans_decode_indexed_ragged_jump(config, self.raw, words.as_ptr(), word_offsets.as_ptr(), 0, words.len(),
+                                                                n_words.as_ptr(), indices.as_ptr() as *const c_void, 1, symbols.as_mut_ptr(),
+                                                                sym_offsets.as_ptr(), n_streams, interval, chunk_offsets.as_ptr(), n_chunks_total,
+                                                                pos.as_ptr(), a.as_ptr(), scratch.as_mut_ptr() as *mut c_void, status.as_mut_ptr(),
+                                                                stream.as_raw())
+                    }
+                })?;
+            }
+        }
+        Ok(status)
+    }
 }
 
 impl Drop for TableSet {

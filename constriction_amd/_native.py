@@ -275,6 +275,17 @@ SIGNATURES = {
     "cst_ans_decode_indexed_batch": (_i32, [_vp, CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _z, _i32, _vp, _vp, _vp, _u32, _vp]),
     "cst_range_encode_indexed_batch": (_i32, [_vp, CoderConfig, _vp, _vp, _i32, _z, _z, _i32, _vp, _z, _vp, _vp, _vp, _u32, _vp]),
     "cst_range_decode_indexed_batch": (_i32, [_vp, CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _z, _i32, _vp, _vp, _u32, _vp]),
+    "cst_ans_encode_indexed_ragged": (_i32, [CoderConfig, _vp, _vp, _vp, _i32, _vp, _z, _vp, _vp, _vp, _z, _vp, _vp, _vp]),
+    "cst_range_encode_indexed_ragged": (_i32, [CoderConfig, _vp, _vp, _vp, _i32, _vp, _z, _vp, _vp, _vp, _z, _vp, _vp, _vp]),
+    "cst_ans_decode_indexed_ragged": (_i32, [CoderConfig, _vp, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _vp, _z, _vp, _vp, _vp]),
+    "cst_range_decode_indexed_ragged": (_i32, [CoderConfig, _vp, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _vp, _z, _vp, _vp, _vp]),
+    "cst_ans_encode_indexed_ragged_jump": (_i32, [CoderConfig, _vp, _vp, _vp, _i32, _vp, _z, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_range_encode_indexed_ragged_jump": (_i32, [CoderConfig, _vp, _vp, _vp, _i32, _vp, _z, _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp,
+                                                    _vp]),
+    "cst_ans_decode_indexed_ragged_jump": (_i32, [CoderConfig, _vp, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp, _vp,
+                                                  _vp]),
+    "cst_range_decode_indexed_ragged_jump": (_i32, [CoderConfig, _vp, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp, _vp,
+                                                    _vp, _vp]),
     "cst_debug_erf": (_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_tab": (_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_fast": (_i32, [_i32, _vp, _vp, _z, _vp]),

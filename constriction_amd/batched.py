@@ -2599,3 +2599,91 @@ def ans_decode_indexed(encoded, indices, tables: TableSet, n_per_stream: int, of
 def range_decode_indexed(encoded, indices, tables: TableSet, n_per_stream: int, offsets=None, out=None):
     """One RangeDecoder per stream: RangeDecoder(words[s]).decode_symbols(tables[indices[s]]).  Returns (symbols, status)."""
     return _decode_indexed("cst_range_decode_indexed_batch", False, encoded, indices, tables, n_per_stream, offsets, out)
+
+
+# ---- ... for streams of different lengths, plain and with jump points (csrc/cst_indexed_ragged.hip, DESIGN.md 4.30) ----
+
+def _indexed_ragged_args(n_elements, device, indices, tables, config):
+    """_indexed_args for flat arrays: the checks of the ragged indexed calls that need no device handle.  `n_elements`: the numel the
+    indices must have, or None (the decoders: the indices say how many symbols there are)"""
+    if not isinstance(tables, TableSet):
+        raise ValueError("tables must be a batched.TableSet")
+    if tuple(config[:2]) != (32, 64) or int(config[2]) != tables.precision:
+        raise ValueError("indexed coding: config must be (32, 64, precision of the table set)")
+    if not isinstance(indices, torch.Tensor) or indices.dtype not in (torch.uint8, torch.int32):
+        raise ValueError("indices must be a torch.uint8 or torch.int32 tensor")
+    if indices.dim() != 1 or (n_elements is not None and indices.numel() != n_elements):
+        raise ValueError("indices must be flat, one per symbol")
+    if not indices.is_cuda or (device is not None and indices.device != device):
+        raise ValueError("indices must live in device memory (HBM), on the device of the symbols / words")
+    return indices.contiguous(), (1 if indices.dtype == torch.uint8 else 4)
+
+
+def _indexed_ragged_offsets(sym_offsets, device):
+    if not isinstance(sym_offsets, torch.Tensor) or sym_offsets.dtype != torch.int64 or sym_offsets.dim() != 1 or sym_offsets.numel() < 1:
+        raise ValueError("sym_offsets must be a flat torch.int64 tensor [n_streams + 1]")
+    if not sym_offsets.is_cuda or sym_offsets.device != device:
+        raise ValueError("sym_offsets must live in device memory (HBM), on the device of the symbols / words")
+    # (no read-back: that the offsets run from 0 to the number of symbols is the caller's word, as in every ragged call)
+    return sym_offsets.contiguous(), sym_offsets.numel() - 1
+
+
+def _encode_indexed_ragged(fn_name, coder, symbols, indices, sym_offsets, tables, config, order, jump_every):
+    # "auto": see DESIGN.md 4.30 for what the rule of _encode_ragged_slabs gives here
+    jump_every = _persymbol_jump_every(jump_every)
+    if not isinstance(tables, TableSet):
+        raise ValueError("tables must be a batched.TableSet")
+    if tuple(config[:2]) != (32, 64) or int(config[2]) != tables.precision:
+        raise ValueError("indexed coding: config must be (32, 64, precision of the table set)")
+    if not isinstance(symbols, torch.Tensor) or symbols.dim() != 1 or symbols.dtype != torch.int32 or not symbols.is_cuda:
+        raise ValueError("symbols must be a flat torch.int32 tensor in device memory (HBM)")
+    indices, index_bytes = _indexed_ragged_args(symbols.numel(), symbols.device, indices, tables, config)
+    symbols = symbols.contiguous()
+    sym_offsets, n_streams = _indexed_ragged_offsets(sym_offsets, symbols.device)
+    model = (tables._h, _ptr(_never_null(symbols)), _ptr(_never_null(indices)), index_bytes)
+    return _encode_ragged_slabs(fn_name, coder, symbols, sym_offsets, n_streams, tuple(int(c) for c in config), order, jump_every, model)
+
+
+@_keeps_plain_signature
+def ans_encode_indexed_ragged(symbols, indices, sym_offsets, tables: TableSet, config=(32, 64, 16), order="auto", *, jump_every=0) -> RaggedBatch:
+    """ans_encode_indexed for streams of different lengths, in ONE launch: stream s is encode_symbols_reverse(symbols[lo:hi] zipped with
+    tables[indices[lo:hi]]) + get_compressed, (lo, hi) = sym_offsets[s], sym_offsets[s + 1].  `symbols` flat int32; `indices` flat
+    torch.uint8 or torch.int32 of the same numel; `sym_offsets` int64 [n + 1] as `ragged` returns it.  Every stream's words are those of
+    ans_encode_indexed for that stream alone.  Slabs, the schedule (`order`, carried in `.order`) and `jump_every` (0, a positive
+    multiple of 16, or "auto"; the table travels as `.jump`, a RaggedJump) are those of ans_encode_gaussian_ragged."""
+    return _encode_indexed_ragged("cst_ans_encode_indexed_ragged", "ans", symbols, indices, sym_offsets, tables, config, order, jump_every)
+
+
+@_keeps_plain_signature
+def range_encode_indexed_ragged(symbols, indices, sym_offsets, tables: TableSet, config=(32, 64, 16), order="auto", *, jump_every=0) -> RaggedBatch:
+    """range_encode_indexed for streams of different lengths: ans_encode_indexed_ragged for the queue.  The batch says `.coder == "range"`
+    and carries a RangeRaggedJump where jump points were asked for."""
+    return _encode_indexed_ragged("cst_range_encode_indexed_ragged", "range", symbols, indices, sym_offsets, tables, config, order, jump_every)
+
+
+def _decode_indexed_ragged(fn_name, coder, encoded, indices, sym_offsets, tables, out, order):
+    if not isinstance(tables, TableSet):
+        raise ValueError("tables must be a batched.TableSet")
+    if not isinstance(encoded, RaggedBatch):
+        raise ValueError("encoded must be a RaggedBatch")
+    jump = _ragged_jump_of(encoded, coder)
+    if tuple(encoded.config) != (32, 64, tables.precision):
+        raise ValueError("the batch was not coded with (32, 64, precision of the table set)")
+    indices, index_bytes = _indexed_ragged_args(None, None, indices, tables, encoded.config)
+    if indices.device != encoded.words.device:
+        raise ValueError("indices must live on the device of the words")
+    sym_offsets, n_streams = _indexed_ragged_offsets(sym_offsets, indices.device)
+    return _decode_ragged_slabs(fn_name, coder, encoded, jump, sym_offsets, n_streams, indices.numel(), out, order, (tables._h,),
+                                (_ptr(_never_null(indices)), index_bytes))
+
+
+def ans_decode_indexed_ragged(encoded: RaggedBatch, indices, sym_offsets, tables: TableSet, out: Optional[torch.Tensor] = None, order="auto"):
+    """AnsCoder(words of stream s).decode_symbols(tables[indices[lo:hi]]) for every stream of a RaggedBatch: stream s yields
+    sym_offsets[s + 1] - sym_offsets[s] symbols at out[sym_offsets[s]:].  Returns (symbols flat, status per stream).  A batch with a
+    jump table decodes its chunks side by side when `order` is None or "auto", and by whole streams when a schedule is handed in."""
+    return _decode_indexed_ragged("cst_ans_decode_indexed_ragged", "ans", encoded, indices, sym_offsets, tables, out, order)
+
+
+def range_decode_indexed_ragged(encoded: RaggedBatch, indices, sym_offsets, tables: TableSet, out: Optional[torch.Tensor] = None, order="auto"):
+    """RangeDecoder(words of stream s).decode_symbols(tables[indices[lo:hi]]) for every stream: ans_decode_indexed_ragged for the queue."""
+    return _decode_indexed_ragged("cst_range_decode_indexed_ragged", "range", encoded, indices, sym_offsets, tables, out, order)

@@ -1787,6 +1787,80 @@ cst_status cst_range_decode_indexed_batch(const void *tables, cst_coder_config c
                                           size_t n_streams, size_t n_per_stream, cst_layout layout, cst_range_state *d_rstate,
                                           int32_t *d_status, uint32_t flags, void *stream);
 
+/* Indexed table coding for streams of DIFFERENT lengths, plain and with jump points: the per-symbol ragged calls
+ * (cst_{ans,range}_{encode,decode}_gaussian_ragged[_jump] above) with the table set and the index array in the model's place.
+ * Stream s owns elements [d_sym_offsets[s], d_sym_offsets[s + 1]) of the flat d_symbols (int32) and d_indices (index_bytes = 1: uint8,
+ * 4: int32; the same element numbering); symbol t of a stream is coded with table d_indices[that element].  The ANS coder codes a
+ * stream last symbol first, the range coder first symbol first.  Every stream's words, count and status are those of
+ * cst_{ans,range}_encode_indexed_batch for that stream alone, and those of the reference coder fed that sequence of models.
+ *   - Slabs: d_word_offsets[n_streams + 1] (slab of stream s = [off[s], off[s + 1])), or NULL with stride_words > 0 (s * stride_words).
+ *     A stream of n symbols fills at most min(n, ceil(n P / 32)) + 2 words under either coder (the two words of the ANS state, resp.
+ *     the two words that seal a range coder).  d_order: NULL, or [n_streams] lane slot -> stream (cst_ans_encode_ragged's schedule; an
+ *     entry that is not a stream codes nothing); results are indexed by stream whatever the order.
+ *   - Jump points: layout and semantics of the table are those of cst_{ans,range}_encode_gaussian_ragged_jump -- jump_interval a
+ *     positive multiple of 16; chunk j of stream s is entry d_chunk_offsets[s] + j; ANS notes (words in the bulk, state) AFTER the
+ *     chunk's first symbol has been coded, the range coder (words emitted including held-back ones, lower, range) BEFORE it; no chunk
+ *     starts at the end of a stream.  The words are bit-identical to the plain call's.  The jump decoders take no d_order and
+ *     d_scratch of cst_persymbol_ragged_jump_scratch_bytes(n_chunks_total) bytes; they run every table entry as a coder of its own.
+ *   - Per-stream status.  Encode: a symbol outside the support or an index >= n_tables: CST_STREAM_IMPOSSIBLE_SYMBOL with d_n_words[s]
+ *     = 0, for that stream alone; a slab too small, or offsets that run backwards: CST_STREAM_CAPACITY; a stream of length 0: 0 words,
+ *     CST_STREAM_OK.  Decode: an index >= n_tables is clamped before any table is read and its stream reports
+ *     CST_STREAM_INVALID_DATA (the worst of its chunks' statuses in the jump form); a slice that leaves words_capacity:
+ *     CST_STREAM_INVALID_DATA; a jump table that does not describe its stream, or a d_jump_pos beyond d_n_words:
+ *     CST_STREAM_INVALID_DATA for that stream -- the others decode, and nothing outside words_capacity or the stream's own symbols is
+ *     touched.  No index byte outside [d_indices, d_indices + index_bytes * d_sym_offsets[n_streams]) is read: a uint8 row may start at
+ *     any byte, an int32 row at any 4-byte boundary.
+ *   - CST_ERR_INVALID_ARGUMENT, before the device is touched: a NULL `tables` or a handle that is not a live table set; a NULL
+ *     d_symbols / d_indices / d_sym_offsets / d_words / d_n_words / d_status; index_bytes not 1 or 4; a preset other than (32, 64);
+ *     cfg.precision not the set's; d_word_offsets == NULL with stride_words == 0; n_streams > 2^32 - 1; in the jump forms also
+ *     jump_interval 0, not a multiple of 16 or > 2^31 - 1, a NULL d_chunk_offsets or table array, n_chunks_total > 2^32 - 1, a NULL
+ *     d_scratch.  n_streams == 0 (with arguments that pass): CST_OK, nothing is launched.
+ * cst_last_kernel_name(): {ans,range}_{encode,decode}_indexed_ragged_kernel, with <jump> appended for the jump forms. */
+cst_status cst_ans_encode_indexed_ragged(cst_coder_config cfg, const void *tables, const int32_t *d_symbols, const void *d_indices,
+                                         int32_t index_bytes, const uint64_t *d_sym_offsets, size_t n_streams,
+                                         const uint32_t *d_order, uint32_t *d_words, const uint64_t *d_word_offsets,
+                                         size_t stride_words, uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_range_encode_indexed_ragged(cst_coder_config cfg, const void *tables, const int32_t *d_symbols, const void *d_indices,
+                                           int32_t index_bytes, const uint64_t *d_sym_offsets, size_t n_streams,
+                                           const uint32_t *d_order, uint32_t *d_words, const uint64_t *d_word_offsets,
+                                           size_t stride_words, uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_indexed_ragged(cst_coder_config cfg, const void *tables, const uint32_t *d_words,
+                                         const uint64_t *d_word_offsets, size_t stride_words, size_t words_capacity,
+                                         const uint32_t *d_n_words, const void *d_indices, int32_t index_bytes, int32_t *d_symbols,
+                                         const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                         int32_t *d_status, void *stream);
+cst_status cst_range_decode_indexed_ragged(cst_coder_config cfg, const void *tables, const uint32_t *d_words,
+                                           const uint64_t *d_word_offsets, size_t stride_words, size_t words_capacity,
+                                           const uint32_t *d_n_words, const void *d_indices, int32_t index_bytes, int32_t *d_symbols,
+                                           const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                           int32_t *d_status, void *stream);
+cst_status cst_ans_encode_indexed_ragged_jump(cst_coder_config cfg, const void *tables, const int32_t *d_symbols,
+                                              const void *d_indices, int32_t index_bytes, const uint64_t *d_sym_offsets,
+                                              size_t n_streams, const uint32_t *d_order, uint32_t *d_words,
+                                              const uint64_t *d_word_offsets, size_t stride_words, uint32_t *d_n_words,
+                                              size_t jump_interval, const uint64_t *d_chunk_offsets, uint32_t *d_jump_pos,
+                                              uint64_t *d_jump_state, int32_t *d_status, void *stream);
+cst_status cst_range_encode_indexed_ragged_jump(cst_coder_config cfg, const void *tables, const int32_t *d_symbols,
+                                                const void *d_indices, int32_t index_bytes, const uint64_t *d_sym_offsets,
+                                                size_t n_streams, const uint32_t *d_order, uint32_t *d_words,
+                                                const uint64_t *d_word_offsets, size_t stride_words, uint32_t *d_n_words,
+                                                size_t jump_interval, const uint64_t *d_chunk_offsets, uint32_t *d_jump_pos,
+                                                uint64_t *d_jump_lower, uint64_t *d_jump_range, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_indexed_ragged_jump(cst_coder_config cfg, const void *tables, const uint32_t *d_words,
+                                              const uint64_t *d_word_offsets, size_t stride_words, size_t words_capacity,
+                                              const uint32_t *d_n_words, const void *d_indices, int32_t index_bytes,
+                                              int32_t *d_symbols, const uint64_t *d_sym_offsets, size_t n_streams,
+                                              size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                              const uint32_t *d_jump_pos, const uint64_t *d_jump_state, void *d_scratch,
+                                              int32_t *d_status, void *stream);
+cst_status cst_range_decode_indexed_ragged_jump(cst_coder_config cfg, const void *tables, const uint32_t *d_words,
+                                                const uint64_t *d_word_offsets, size_t stride_words, size_t words_capacity,
+                                                const uint32_t *d_n_words, const void *d_indices, int32_t index_bytes,
+                                                int32_t *d_symbols, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
+                                                const uint64_t *d_jump_range, void *d_scratch, int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * bit-exact f64 special functions on device (test hooks for the model kernels)
  * out[i] = erf(x[i]) resp. Gaussian cdf, evaluated by the same device code the table kernels use.
