@@ -12,8 +12,6 @@ Run:  python scripts/gen_decode_loop.py   (rewrites the .inc; the .inc is checke
 import os
 from pathlib import Path
 
-OUT = Path(os.environ.get("GEN_CSRC") or Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc") / "cst_decode_loop.inc"
-OUT_SM = OUT.with_name("cst_decode_loop_sm.inc")
 # SYMBOL_MAJOR (cst_decode_loop_sm.inc): symbols[t][stream].  Only the way the previous tile leaves differs: quad k reads
 # tile[32 (k & 1) + 4 (lane & 7) + c][(lane >> 3) + 8 (k >> 1)], c = 0..3 (four ds_read_b32, two lanes per bank) and stores the
 # 16 bytes at symbol row (lane >> 3) + 8 (k >> 1), streams 32 (k & 1) + 4 (lane & 7) .. + 3: every store instruction writes eight
@@ -33,7 +31,7 @@ AHEAD_M1 = 23         # kDecAhead - 1  (want_lo = max(rd + shift - kDecAhead, 0)
 import os
 import sys
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements  # noqa: E402
 
 
 import os
@@ -269,16 +267,17 @@ def gen():
 
 def main():
     global SYMBOL_MAJOR
-    for SYMBOL_MAJOR, out in ((False, OUT), (True, OUT_SM)):
+    out = Statements(__file__)
+    for SYMBOL_MAJOR, name in ((False, "cst_decode_loop.inc"), (True, "cst_decode_loop_sm.inc")):
         if SYMBOL_MAJOR and EARLY_STORES:
             continue
-        emit(out)
+        emit(out, name)
+    return out
 
 
-def emit(out):
+def emit(out, name):
     a, clobbers = gen()
-    header = ["// GENERATED by scripts/gen_decode_loop.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Main loop of the hand-scheduled (32,64) ANS decoder: see ans_decode_tiles_loop in cst_ans_kernels.hpp."]
+    about = ["// Main loop of the hand-scheduled (32,64) ANS decoder: see ans_decode_tiles_loop in cst_ans_kernels.hpp."]
     ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [rd] "+v"(rd), [lo_issued] "+v"(lo_issued), [rowcur] "+v"(row_cur), [rowprev] "+v"(row_prev),',
            '      [trcur] "+v"(tr_cur), [trprev] "+v"(tr_prev)',
            '    : [lut] "s"(lut_addr), [mask] "s"(mask), [P] "s"(P), [cmask] "s"(ring_mask), [wbase] "s"(words_base), [gbase] "s"(store_base),',
@@ -287,10 +286,10 @@ def emit(out):
            '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in clobbers) + ");"]
     if SYMBOL_MAJOR:
-        header[1] = "// Main loop of the hand-scheduled (32,64) ANS decoder, symbols[t][stream]: see ans_decode_tiles_loop_sm in cst_ans_asm.hpp."
-    out.write_text(a.render(header, ops))
-    print(f"wrote {out} ({a.n_instr()} instructions per iteration incl. loop control)")
+        about = ["// Main loop of the hand-scheduled (32,64) ANS decoder, symbols[t][stream]: see ans_decode_tiles_loop_sm in cst_ans_asm.hpp."]
+    out.add(name, a, about, ops, "instructions per iteration incl. loop control")
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_decode_loop"]))

@@ -22,30 +22,28 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements, knobs  # noqa: E402
 
-OUT = Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc" / "cst_decode_loop_b16.inc"
-# GEN_B16_NARROW=1 / 2 (round 5: cst_decode_loop_b16_n8.inc / _n16.inc, ans_decode_b16_narrow_kernel): int8 / int16 symbol matrices.  A
+NARROW, SMALL = knobs(globals(), narrow=0, small=False)
+# narrow=1 / 2 (round 5: cst_decode_loop_b16_n8.inc / _n16.inc, ans_decode_b16_narrow_kernel): int8 / int16 symbol matrices.  A
 # decoded quad is packed (two v_perm_b32 + v_or for int8, two v_perm_b32 for int16) into the lane's row of ONE byte tile -- rows of 128
 # bytes + 4: a line of the matrix -- and the group of 128 / 64 symbols leaves when its last tile is done, in a block of eight row
 # blocks (four ds_read_b32 + one 16-byte store each) that a scalar branch skips on the other tiles.  Nobody covers that block's ~300
 # cycles (one wave per SIMD), but they come once per 128 / 64 symbols of ~214 cycles each; in exchange the statement's body stays ONE
 # tile.  The block's memory operations are not in the wait-count book: operations the book does not know can only make a wait
 # LONGER (they are younger than what it waits for, or older and retired with it), never shorter.
-NARROW = int(os.environ.get("GEN_B16_NARROW", "0"))
-# GEN_B16_SMALL=1 with GEN_B16_NARROW=1 / 2 / 4 (cst_decode_loop_b16_s8.inc / _s16.inc / _s32.inc, ans_decode_b16_narrow_kernel<BYTES, true>): the
+# small with narrow=1 / 2 / 4 (cst_decode_loop_b16_s8.inc / _s16.inc / _s32.inc, ans_decode_b16_narrow_kernel<BYTES, true>): the
 # SMALL-FOOTPRINT form for two waves per SIMD (more than 256 streams per CU: a C5-sized shard, or the virtual streams of a batch decoded through
 # jump points).  Rings of 16 slots -- a window every QUARTER tile: 8 symbols take at most 6 words, two chunks -- and the one tile per wave of the
-# narrow form, for int32 too (GEN_B16_NARROW=4: rows of 36 words, the tile leaves in the block behind its landing): eight waves in 140 KiB.
-SMALL = int(os.environ.get("GEN_B16_SMALL", "0"))
+# narrow form, for int32 too (narrow=4: rows of 36 words, the tile leaves in the block behind its landing): eight waves in 140 KiB.
 assert not SMALL or NARROW in (1, 2, 4), "the small-footprint form: int8, int16 or int32 through the one-tile block"
 assert NARROW != 4 or SMALL
 N8_ROW = 144 if NARROW == 4 else 132
 TILES_PER_GROUP = {0: 1, 1: 4, 2: 2, 4: 1}[NARROW]
 if SMALL:
-    OUT = OUT.with_name({1: "cst_decode_loop_b16_s8.inc", 2: "cst_decode_loop_b16_s16.inc", 4: "cst_decode_loop_b16_s32.inc"}[NARROW])
-elif NARROW:
-    OUT = OUT.with_name("cst_decode_loop_b16_n8.inc" if NARROW == 1 else "cst_decode_loop_b16_n16.inc")
+    NAME = {1: "cst_decode_loop_b16_s8.inc", 2: "cst_decode_loop_b16_s16.inc", 4: "cst_decode_loop_b16_s32.inc"}[NARROW]
+else:
+    NAME = {0: "cst_decode_loop_b16.inc", 1: "cst_decode_loop_b16_n8.inc", 2: "cst_decode_loop_b16_n16.inc"}[NARROW]
 
 # bucket entries: 2^11 as the model tabulates them, 2^12 in the one-wave narrow kernels (LDS to spare: B16NarrowGeo::kTableBits)
 BUCKET_BITS = 12 if (NARROW in (1, 2) and not SMALL) else 11
@@ -62,7 +60,6 @@ def tup(base, n=4):
 # previous tile leaves as streams 32 (k & 1) + 4 (lane & 7) .. + 3 of symbol row (lane >> 3) + 8 (k >> 1); full waves only
 # (the base moves by %[tilestep] per tile).
 SYMBOL_MAJOR = False
-OUT_SM = OUT.with_name("cst_decode_loop_b16_sm.inc")
 
 
 def gen():
@@ -331,15 +328,16 @@ def gen():
 
 def main():
     global SYMBOL_MAJOR
-    for SYMBOL_MAJOR, out in (((False, OUT),) if NARROW else ((False, OUT), (True, OUT_SM))):
-        emit(out)
+    out = Statements(__file__)
+    for SYMBOL_MAJOR, name in ((False, NAME),) if NARROW else ((False, NAME), (True, "cst_decode_loop_b16_sm.inc")):
+        emit(out, name)
     SYMBOL_MAJOR = False
+    return out
 
 
-def emit(out):
+def emit(out, name):
     a, clobbers = gen()
-    header = ["// GENERATED by scripts/gen_decode_loop_b16.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Main loop of the hand-scheduled (32,64) ANS decoder for 12 < P <= 24 (bucket entries): see cst_ans_b16.hip."]
+    about = ["// Main loop of the hand-scheduled (32,64) ANS decoder for 12 < P <= 24 (bucket entries): see cst_ans_b16.hip."]
     ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [rd] "+v"(rd), [lo_issued] "+v"(lo_issued), [rowcur] "+v"(row_cur), [rowprev] "+v"(row_prev),',
            '      [trcur] "+v"(tr_cur), [trprev] "+v"(tr_prev)',
            '    : [lut] "s"(lut_addr), [cdf] "s"(cdf_addr), [mask] "s"(mask), [P] "s"(P), [bsh] "s"(bucket_shift), [minsym] "v"(min_symbol), [cfield] "s"(c_field_mask), [ishift] "s"(index_shift),',
@@ -347,9 +345,9 @@ def emit(out):
            '      [shm1] "v"(shift_minus_1), [lanebase] "v"(ring_lane_addr), [dump] "v"(dump_addr), [woff] "v"(words_off)' + (', [tilestep] "s"(tile_step_bytes)' if SYMBOL_MAJOR else '') +
            (', [sel01] "s"(0x0c0c0400u), [sel23] "s"(0x04000c0cu)' if NARROW == 1 else ', [sel01] "s"(0x05040100u)' if NARROW == 2 else ''),
            "    : " + ", ".join(f'"{c}"' for c in clobbers) + ");"]
-    out.write_text(a.render(header, ops))
-    print(f"wrote {out} ({a.n_instr()} instructions per iteration incl. loop control)")
+    out.add(name, a, about, ops, "instructions per iteration incl. loop control")
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_decode_loop_b16"]))

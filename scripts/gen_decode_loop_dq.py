@@ -23,9 +23,8 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements  # noqa: E402
 
-OUT = Path(os.environ.get("GEN_CSRC") or Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc") / "cst_decode_loop_dq.inc"
 STORE_MOD = '" CST_STORE_MOD "'
 AHEAD_M1 = 23         # kDecAhead - 1  (want_lo = max(rd + shift - kDecAhead, 0) = sat_sub(rd + (shift-1), kDecAhead-1))
 NO_STORE = bool(os.environ.get("GEN_NO_STORE"))
@@ -173,17 +172,18 @@ def gen():
 
 def main():
     a, clobbers = gen()
-    header = ["// GENERATED by scripts/gen_decode_loop_dq.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Main loop of the (32,64), P <= 12 ANS decoder with lane-quad word loads: see ans_decode_dq_loop in cst_ans_dq.hip."]
+    about = ["// Main loop of the (32,64), P <= 12 ANS decoder with lane-quad word loads: see ans_decode_dq_loop in cst_ans_dq.hip."]
     ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [rd] "+v"(rd), [lo_issued] "+v"(lo_issued)',
            '    : [rowcur] "v"(row_addr), [tr] "v"(tr_addr), [lut] "s"(lut_addr), [mask] "s"(mask), [P] "s"(P), [cmask] "s"(ring_mask), [c7f] "s"(0x7fffffffu),',
            '      [wbase] "s"(words_base), [gbase] "s"(store_base), [ntiles] "s"(n_tiles), [shm1] "v"(shift_minus_1), [lanebase] "v"(ring_lane_addr),',
            '      [dump] "v"(dump_addr), [woff] "v"(words_off),',
            '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in clobbers) + ");"]
-    OUT.write_text(a.render(header, ops))
-    print(f"wrote {OUT} ({a.n_instr()} instructions per iteration incl. loop control)")
+    out = Statements(__file__)
+    out.add("cst_decode_loop_dq.inc", a, about, ops, "instructions per iteration incl. loop control")
+    return out
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_decode_loop_dq"]))

@@ -22,13 +22,12 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements, knobs  # noqa: E402
 
-# GEN_N16=1: the same statement for INT16 matrices (cst_decode_loop_n16.inc).  A 128-byte line is 64 symbols, so a pass is TWO tiles;
+# n16: the same statement for INT16 matrices (cst_decode_loop_n16.inc).  A 128-byte line is 64 symbols, so a pass is TWO tiles;
 # a quad is two dwords (one v_perm_b32 per pair of symbols, two ds_write_b32), and the previous group leaves four row blocks per tile.
-N16 = bool(os.environ.get("GEN_N16"))
-OUT = Path(os.environ.get("GEN_CSRC") or Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc") / \
-    ("cst_decode_loop_n16.inc" if N16 else "cst_decode_loop_n8.inc")
+(N16,) = knobs(globals(), n16=False)
+NAME = "cst_decode_loop_n16.inc" if N16 else "cst_decode_loop_n8.inc"
 
 K_CHUNKS = 3          # window chunks requested per tile (32 symbols * 12 bits = 12 words = 3 chunks)
 AHEAD_M1 = 23         # kDecAhead - 1
@@ -163,8 +162,7 @@ def gen():
 
 def main():
     a, clobbers = gen()
-    header = ["// GENERATED by scripts/gen_decode_loop_n8.py -- do not edit by hand (edit the generator and re-run it).",
-              f"// Main loop of the hand-scheduled (32,64) ANS decoder for {'int16' if N16 else 'int8'} symbol matrices: see ans_decode_n8_loop in cst_ans_n8.hip."]
+    about = [f"// Main loop of the hand-scheduled (32,64) ANS decoder for {'int16' if N16 else 'int8'} symbol matrices: see ans_decode_n8_loop in cst_ans_n8.hip."]
     ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [rd] "+v"(rd), [lo_issued] "+v"(lo_issued), [rowcur] "+v"(row_cur), [rowprev] "+v"(row_prev),',
            '      [trcur] "+v"(tr_cur), [trprev] "+v"(tr_prev)',
            '    : [lut] "s"(lut_addr), [mask] "s"(mask), [P] "s"(P), [cmask] "s"(ring_mask), [wbase] "s"(words_base), [gbase] "s"(store_base),',
@@ -172,9 +170,11 @@ def main():
            ('      [sel01] "s"(0x05040100u),' if N16 else '      [sel01] "s"(0x0c0c0400u), [sel23] "s"(0x04000c0cu),'),
            '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in clobbers) + ");"]
-    OUT.write_text(a.render(header, ops))
-    print(f"wrote {OUT} ({a.n_instr()} instructions per iteration incl. loop control)")
+    out = Statements(__file__)
+    out.add(NAME, a, about, ops, "instructions per iteration incl. loop control")
+    return out
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_decode_loop_n8"]))

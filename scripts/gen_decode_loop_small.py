@@ -14,14 +14,14 @@ Per symbol the serial chain is  entry -> (q - c, p) -> N = (state >> P) * p + (q
 
 Run:  python scripts/gen_decode_loop_small.py   (rewrites the .inc; the .inc is checked in)
 """
-import os
 import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements, knobs  # noqa: E402
 
-# GEN_SMALL_N8=1 (round 5): the same loop for INT8 symbol matrices (ans_decode_small_n8_kernel, cst_ans_n8.hip).  A decoded symbol
+(WIDTH,) = knobs(globals(), n8=0)
+# n8=8 (round 5): the same loop for INT8 symbol matrices (ans_decode_small_n8_kernel, cst_ans_n8.hip).  A decoded symbol
 # leaves its step as a BYTE of the quad's register (the SDWA add that forms  min_symbol + index  writes byte `pos` and preserves
 # the others: no instruction more than the int32 form), a quad is one ds_write_b32 into the lane's row of a byte tile -- rows of 128
 # symbols + 4 bytes of padding, one line of the matrix -- and the loop body is FOUR tiles: the group of 128 symbols leaves at the
@@ -30,14 +30,13 @@ from asmgen import Asm  # noqa: E402
 # ds_read_u8 straight from the quantile: 15.25 VALU per symbol instead of 17.  The D16 byte loads that would have merged two symbols per
 # register ZERO the other half on this chip (scripts/microbench/ds_d16.hip: SRAM-ECC), and the kernel ran in the same 0.350 ms with
 # the shorter step as with this one: the third LDS read per symbol costs what the two VALU instructions saved.)
-N8 = bool(os.environ.get("GEN_SMALL_N8"))
-# GEN_SMALL_N8=16: INT16 matrices (cst_decode_loop_small_n16.inc) -- a line is 64 symbols: two tiles per pass, a symbol is a HALF of
+N8 = bool(WIDTH)
+# n8=16: INT16 matrices (cst_decode_loop_small_n16.inc) -- a line is 64 symbols: two tiles per pass, a symbol is a HALF of
 # one of the quad's two registers (dst_sel:WORD_n), a quad is two ds_write_b32.
-N16 = os.environ.get("GEN_SMALL_N8") == "16"
+N16 = WIDTH == 16
 N8_ROW = 132
 SUBTILES = 2 if N16 else 4 if N8 else 1
-OUT = Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc" / \
-    ("cst_decode_loop_small_n16.inc" if N16 else "cst_decode_loop_small_n8.inc" if N8 else "cst_decode_loop_small.inc")
+NAME = "cst_decode_loop_small_n16.inc" if N16 else "cst_decode_loop_small_n8.inc" if N8 else "cst_decode_loop_small.inc"
 
 K_CHUNKS = 3          # window chunks requested per tile (32 symbols * 12 bits = 12 words = 3 chunks)
 AHEAD_M1 = 23         # kPtAhead - 1
@@ -192,21 +191,20 @@ def gen():
 
 def main():
     a, notes = gen()
-    header = ["// GENERATED by scripts/gen_decode_loop_small.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Main loop of the hand-scheduled (32,64) ANS decoder, small LDS footprint" +
-              (", int16 symbol matrices: see decode_groups_loop_small_n8 in cst_ans_n8.hip." if N16 else
-               ", int8 symbol matrices: see decode_groups_loop_small_n8 in cst_ans_n8.hip." if N8 else ": see decode_tiles_loop_small in cst_ans_small.hip.")]
+    about = ["// Main loop of the hand-scheduled (32,64) ANS decoder, small LDS footprint" +
+             (", int16 symbol matrices: see decode_groups_loop_small_n8 in cst_ans_n8.hip." if N16 else
+              ", int8 symbol matrices: see decode_groups_loop_small_n8 in cst_ans_n8.hip." if N8 else ": see decode_tiles_loop_small in cst_ans_small.hip.")]
     ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [rd] "+v"(rd), [lo_issued] "+v"(lo_issued)',
            '    : [lut] "s"(lut_addr), [mask] "s"(mask), [cmask] "s"(ring_mask), [P] "s"(P), [wbase] "s"(words_base), [gbase] "s"(store_base),',
            '      [ntiles] "s"(n_tiles), [minsym] "v"(min_symbol), [shm1] "v"(shift_minus_1), [lanebase] "v"(ring_lane_addr),',
            '      [dump] "v"(dump_addr), [woff] "v"(words_off), [rowcur] "v"(tile_row_addr), [trcur] "v"(tile_tr_addr),',
            '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in CLOBBERS) + ");"]
-    OUT.write_text(a.render(header, ops))
-    print(f"wrote {OUT} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+    out = Statements(__file__)
+    out.add(NAME, a, about, ops, notes=notes)
+    return out
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_decode_loop_small"]))

@@ -15,20 +15,18 @@ values ([position][lane] halfwords, 8 KiB per wave as before), written by four d
 
 Run:  python scripts/gen_decode_loop_w16.py   (rewrites the .inc; the .inc is checked in)
 """
-import os
 import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements, knobs  # noqa: E402
 
-# GEN_W16_PACKED=1 (round 5, CST_FLAG_PACKED_W16): two words per 32-bit slot in HBM, as the reference's Vec<u16> (stack.rs:153).
+# packed (round 5, CST_FLAG_PACKED_W16): two words per 32-bit slot in HBM, as the reference's Vec<u16> (stack.rs:153).
 # A 16-byte chunk then carries EIGHT words: half as many chunk loads per symbol -- the loads were what this decoder waited for
 # (SQ_WAIT_INST_ANY 55 - 60 cycles per symbol).  Two chunk slots per half tile instead of three, lo_issued moves by 8, the byte
 # offset of a chunk is 2 lo_issued, and a chunk lands with eight ds_write_b16 (low halves with ds_write_b16, high halves with
 # ds_write_b16_d16_hi).  Written to cst_decode_loop_w16_pk.inc (stream-major).
-PACKED = bool(os.environ.get("GEN_W16_PACKED"))
-OUT = Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc" / ("cst_decode_loop_w16_pk.inc" if PACKED else "cst_decode_loop_w16.inc")
+(PACKED,) = knobs(globals(), packed=False)
 
 CHUNK = 8 if PACKED else 4     # words per 16-byte chunk
 K_CHUNKS = 2 if PACKED else 3  # window chunks requested per HALF tile (16 symbols * 12 bits = 12 words)
@@ -41,7 +39,6 @@ def tup(base, n=4):
 
 # SYMBOL_MAJOR (cst_decode_loop_w16_sm.inc): symbols[t][stream], staged like gen_decode_loop_b16.py's SYMBOL_MAJOR (full waves only)
 SYMBOL_MAJOR = False
-OUT_SM = OUT.with_name("cst_decode_loop_w16_sm.inc")
 
 
 def gen():
@@ -165,24 +162,25 @@ def gen():
 
 def main():
     global SYMBOL_MAJOR
-    for SYMBOL_MAJOR, out in (((False, OUT),) if PACKED else ((False, OUT), (True, OUT_SM))):
-        emit(out)
+    out = Statements(__file__)
+    for SYMBOL_MAJOR, name in ((False, "cst_decode_loop_w16_pk.inc"),) if PACKED else ((False, "cst_decode_loop_w16.inc"), (True, "cst_decode_loop_w16_sm.inc")):
+        emit(out, name)
     SYMBOL_MAJOR = False
+    return out
 
 
-def emit(out):
+def emit(out, name):
     a, clobbers = gen()
-    header = ["// GENERATED by scripts/gen_decode_loop_w16.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Main loop of the hand-scheduled (16,32) ANS decoder: see cst_ans_w16.hip."]
+    about = ["// Main loop of the hand-scheduled (16,32) ANS decoder: see cst_ans_w16.hip."]
     ops = ['    : [st] "+v"(st), [rd] "+v"(rd), [lo_issued] "+v"(lo_issued), [rowcur] "+v"(row_cur), [rowprev] "+v"(row_prev),',
            '      [trcur] "+v"(tr_cur), [trprev] "+v"(tr_prev)',
            '    : [lut] "s"(lut_addr), [mask] "s"(mask), [P] "s"(P), [cmask] "s"(ring_mask), [wbase] "s"(words_base), [gbase] "s"(store_base),',
            '      [ntiles] "s"(n_tiles),',
            '      [shm1] "v"(shift_minus_1), [lanebase] "v"(ring_lane_addr), [dump] "v"(dump_addr), [woff] "v"(words_off)' + (', [tilestep] "s"(tile_step_bytes)' if SYMBOL_MAJOR else ''),
            "    : " + ", ".join(f'"{c}"' for c in clobbers) + ");"]
-    out.write_text(a.render(header, ops))
-    print(f"wrote {out} ({a.n_instr()} instructions per iteration incl. loop control)")
+    out.add(name, a, about, ops, "instructions per iteration incl. loop control")
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_decode_loop_w16"]))

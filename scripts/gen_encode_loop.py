@@ -24,12 +24,8 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements  # noqa: E402
 
-CSRC = Path(os.environ.get("GEN_CSRC") or Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc")
-OUT = CSRC / "cst_encode_loop.inc"
-OUT_SINGLE = CSRC / "cst_encode_loop_1buf.inc"
-OUT_SM = CSRC / "cst_encode_loop_sm.inc"
 # SINGLE: ONE tile buffer per wave and a 32-slot word ring (cst_encode_loop_1buf.inc): 17 KiB of LDS per wave instead of
 # 34, so that two workgroups share a CU when a batch has more than one wave per SIMD.  The next tile is staged between
 # the last read of the current tile (quad 0's symbols, requested in quad 2) and the first read of the next one (its
@@ -415,16 +411,15 @@ def to_e64(text):
     return text
 
 
-def emit(out, single, symbol_major=False):
+def emit(out, name, single, symbol_major=False):
     global SINGLE, SYMBOL_MAJOR
     SINGLE, SYMBOL_MAJOR = single, symbol_major
     a, notes = gen()
     if E64:
         a.lines = [(to_e64(t), c) for t, c in a.lines]
-    header = ["// GENERATED by scripts/gen_encode_loop.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Main loop of the hand-scheduled (32,64) ANS encoder: see ans_encode_tiles_loop in cst_ans_kernels.hpp."]
+    about = ["// Main loop of the hand-scheduled (32,64) ANS encoder: see ans_encode_tiles_loop in cst_ans_kernels.hpp."]
     if single:
-        header[1] = "// Main loop of the hand-scheduled (32,64) ANS encoder, ONE tile buffer and a 32-slot ring per wave: see cst_ans_small.hip."
+        about = ["// Main loop of the hand-scheduled (32,64) ANS encoder, ONE tile buffer and a 32-slot ring per wave: see cst_ans_small.hip."]
         ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [wr] "+v"(wr), [flushed] "+v"(flushed), [smin] "+v"(smin), [smax] "+v"(smax)',
                '    : [row0] "v"(tile_row_addr), [tr0] "v"(tile_tr_addr),']
     else:
@@ -435,19 +430,19 @@ def emit(out, single, symbol_major=False):
             '      [sbase] "s"(symbols_base), [ntiles] "s"(n_tiles),' + (' [tilestep] "s"(tile_step_bytes),' if symbol_major else ''),
             '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
             "    : " + ", ".join(f'"{c}"' for c in CLOBBERS) + ");"]
-    out.write_text(a.render(header, ops))
-    print(f"wrote {out} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+    out.add(name, a, about, ops, notes=notes)
 
 
 def main():
-    emit(OUT, False)
+    out = Statements(__file__)
+    emit(out, "cst_encode_loop.inc", False)
     if NO_TILEWORK or LOCAL_RING or ADDR_MINMAX or BARRIER or SHIFT4 or E64 or RING_MASK or ADDR_MODE or WR_RESET or ABL or not QUAD_FLUSH:      # (ablations of the main loop only)
-        return
-    emit(OUT_SINGLE, True)
-    emit(OUT_SM, False, True)
+        return out
+    emit(out, "cst_encode_loop_1buf.inc", True)
+    emit(out, "cst_encode_loop_sm.inc", False, True)
+    return out
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_encode_loop"]))

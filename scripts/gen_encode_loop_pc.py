@@ -30,11 +30,8 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements  # noqa: E402
 
-CSRC = Path(os.environ.get("GEN_CSRC") or Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc")
-OUT = CSRC / "cst_encode_loop_pc.inc"
-OUT_CK = CSRC / "cst_encode_loop_pc_ck.inc"         # ... noting jump points (round 5: see ck_hook below)
 NO_BARRIER = bool(os.environ.get("GEN_NO_BARRIER"))     # timing experiment only (races with the helper)
 PRIO = int(os.environ.get("GEN_PRIO", "2"))             # s_setprio of the coder's wave (0 = leave it alone)
 
@@ -261,25 +258,24 @@ def gen():
     return a, notes
 
 
-def main():
+def main_int32(out):
     global JUMP, WIDE
-    for WIDE, JUMP, out in ((False, False, OUT), (False, True, OUT_CK), (True, False, OUT_W), (True, True, OUT_W_CK)):
-        emit_coder(out)
+    for WIDE, JUMP, name in ((False, False, "cst_encode_loop_pc.inc"),
+                             (False, True, "cst_encode_loop_pc_ck.inc"),         # ... noting jump points (round 5: see ck_hook)
+                             (True, False, "cst_encode_loop_pc_w.inc"),          # the int32 coders at 12 < P <= 24
+                             (True, True, "cst_encode_loop_pc_w_ck.inc")):
+        emit_coder(out, name)
     JUMP = WIDE = False
 
 
-def emit_coder(out):
+def emit_coder(out, name):
     a, notes = gen()
-    header = ["// GENERATED by scripts/gen_encode_loop_pc.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Coder half of the producer / consumer (32,64) ANS encoder: see ans_encode_pc_coder_loop in cst_ans_pc.hip."]
+    about = ["// Coder half of the producer / consumer (32,64) ANS encoder: see ans_encode_pc_coder_loop in cst_ans_pc.hip."]
     ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi)',
            '    : [row0] "v"(tile_row_addr[0]), [row1] "v"(tile_row_addr[1]), [lanebase] "v"(ring_lane_addr), [pub] "v"(publish_addr),',
            '      [twoP] "v"(1u << P), [P] "s"(P), [c3f00] "s"(0x3f00u), [ntiles] "s"(n_tiles)' + (', [sh] "s"(32u - P)' if WIDE else '') + ck_operands(),
            "    : " + ", ".join(f'"{c}"' for c in CLOBBERS + ck_clobbers()) + ");"]
-    out.write_text(a.render(header, ops))
-    print(f"wrote {out} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+    out.add(name, a, about, ops, notes=notes)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -341,7 +337,6 @@ def range_publish(a, accs, offsets):
 HAND_WAVE_BYTES = 4 * 64 * 4                               # kPcHandWaveBytes
 
 
-OUT_HELPER = CSRC / "cst_encode_loop_pc_helper.inc"
 NSETS = int(os.environ.get("GEN_NSETS", "3"))           # register sets of prefetched tiles: a tile is requested NSETS windows before it is staged
 HBASE = 234 - 32 * NSETS
 SETS = "ABCDE"[:NSETS]
@@ -478,20 +473,16 @@ def gen_helper():
     return a, notes
 
 
-def main_helper():
+def main_helper(out):
     a, notes = gen_helper()
-    header = ["// GENERATED by scripts/gen_encode_loop_pc.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Helper half of the producer / consumer (32,64) ANS encoder: see ans_encode_pc_helper_loop in cst_ans_pc.hip."]
+    about = ["// Helper half of the producer / consumer (32,64) ANS encoder: see ans_encode_pc_helper_loop in cst_ans_pc.hip."]
     ops = ['    : [flushed] "+v"(flushed)',
            '    : [tr0] "v"(tile_tr_addr[0]), [tr1] "v"(tile_tr_addr[1]), [lanebase] "v"(ring_lane_addr), [pub] "v"(publish_addr),',
            '      [cap] "v"(cap), [slaboff] "v"(slab_off), [c3f00] "s"(0x3f00u), [wbase] "s"(words_base), [sbase] "s"(symbols_base), [ntiles] "s"(n_tiles),',
            '      [tbl] "s"(table_bias), [symlo] "v"(sym_lo), [symhi] "v"(sym_hi), [bad] "v"(bad_addr),',
            '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in H_CLOBBERS) + ");"]
-    OUT_HELPER.write_text(a.render(header, ops))
-    print(f"wrote {OUT_HELPER} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+    out.add("cst_encode_loop_pc_helper.inc", a, about, ops, notes=notes)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -502,8 +493,6 @@ def main_helper():
 # instead of by stream: waves 4 and 5 only LOAD and stage (each for two coder waves), waves 6 and 7 only FLUSH (each for two
 # coder waves).  A loader's vmcnt sees loads only; a storer never waits for its stores inside the loop.
 # ---------------------------------------------------------------------------------------------------------------------
-OUT_LOADER = CSRC / "cst_encode_loop_pc_loader.inc"
-OUT_STORER = CSRC / "cst_encode_loop_pc_storer.inc"
 LSETS = int(os.environ.get("GEN_LSETS", "2"))           # register sets per coder wave in a loader (a tile is requested LSETS windows before it is staged)
 LSLEEP = int(os.environ.get("GEN_LSLEEP", "0"))         # experiment: spread a window's 16 requests over the window (64 LSLEEP cycles after each)
 LBASE = 228 - 64 * LSETS
@@ -731,36 +720,31 @@ def gen_storer():
     return a, []
 
 
-def main_split():
+def main_split(out):
     a, notes = gen_loader()
-    header = ["// GENERATED by scripts/gen_encode_loop_pc.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Loader wave of the producer / consumer (32,64) ANS encoder: see ans_encode_pc_loader_loop in cst_ans_pc.hip."]
+    about = ["// Loader wave of the producer / consumer (32,64) ANS encoder: see ans_encode_pc_loader_loop in cst_ans_pc.hip."]
     ops = ['    :',
            '    : [tr0] "v"(tile_tr_addr[0]), [tr1] "v"(tile_tr_addr[1]), [sbase] "s"(symbols_base), [rowblock] "s"(row_block_bytes), [ntiles] "s"(n_tiles),',
            '      [tbl] "s"(table_bias), [symlo] "v"(sym_lo), [symhi] "v"(sym_hi), [bad] "v"(bad_addr),',
            '      ' + ", ".join(f'[goff0_{k}] "v"(goff0[{k}])' for k in range(8)) + ",",
            '      ' + ", ".join(f'[goff1_{k}] "v"(goff1[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in [f"v{r}" for r in range(68, 100)] + L_CLOBBERS) + ");"]
-    OUT_LOADER.write_text(a.render(header, ops))
-    print(f"wrote {OUT_LOADER} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+    out.add("cst_encode_loop_pc_loader.inc", a, about, ops, notes=notes)
     global STORER_GROUPS
-    for STORER_GROUPS, out_storer in ((1, OUT_STORER), (2, OUT_STORER2)):
-        emit_storer(out_storer)
+    # (storer2 serves the coders at 12 < P <= 24: two 64-byte groups per tile -- 32 symbols can emit 24 words)
+    for STORER_GROUPS, name in ((1, "cst_encode_loop_pc_storer.inc"), (2, "cst_encode_loop_pc_storer2.inc")):
+        emit_storer(out, name)
     STORER_GROUPS = 1
 
 
-def emit_storer(out_storer):
+def emit_storer(out, name):
     a, notes = gen_storer()
-    header = ["// GENERATED by scripts/gen_encode_loop_pc.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Storer wave of the producer / consumer (32,64) ANS encoder: see ans_encode_pc_storer_loop in cst_ans_pc.hip."]
+    about = ["// Storer wave of the producer / consumer (32,64) ANS encoder: see ans_encode_pc_storer_loop in cst_ans_pc.hip."]
     ops = ['    : [flushed0] "+v"(flushed[0]), [flushed1] "+v"(flushed[1])',
            '    : [lanebase0] "v"(ring_lane_addr[0]), [lanebase1] "v"(ring_lane_addr[1]), [pub0] "v"(publish_addr[0]), [pub1] "v"(publish_addr[1]),',
            '      [cap0] "v"(cap[0]), [cap1] "v"(cap[1]), [slaboff0] "v"(slab_off[0]), [slaboff1] "v"(slab_off[1]), [c3f00] "s"(0x3f00u), [wbase] "s"(words_base), [ntiles] "s"(n_tiles)',
            "    : " + ", ".join(f'"{c}"' for c in S_CLOBBERS) + ");"]
-    out_storer.write_text(a.render(header, ops))
-    print(f"wrote {out_storer} ({a.n_instr()} instructions incl. prologue)")
+    out.add(name, a, about, ops, notes=notes)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -775,8 +759,6 @@ def emit_storer(out_storer):
 # The loop body still holds two tiles: the tile pointers live in two registers that leapfrog (one v_add per tile; every fourth
 # step jumps to the other line buffer: the jump alternates between J and 192 - J and comes from the scalar side).
 # ---------------------------------------------------------------------------------------------------------------------
-OUT_N8 = CSRC / "cst_encode_loop_pc_n8.inc"
-OUT_LOADER_N8 = CSRC / "cst_encode_loop_pc_loader_n8.inc"
 N8_ROW = 132                       # kN8RowBytes
 N8_LINEBUF = 64 * N8_ROW           # one line buffer of a coder wave: 8448 bytes
 S8 = [f"v{100 + i}" for i in range(4)]
@@ -954,54 +936,36 @@ def gen_loader_n8():
     return a, notes
 
 
-OUT_N8_CK = CSRC / "cst_encode_loop_pc_n8_ck.inc"
-OUT_W = CSRC / "cst_encode_loop_pc_w.inc"                 # the int32 coders at 12 < P <= 24
-OUT_W_CK = CSRC / "cst_encode_loop_pc_w_ck.inc"
-OUT_N8W = CSRC / "cst_encode_loop_pc_n8w.inc"             # the same coders at 12 < P <= 24 (step_wide)
-OUT_N8W_CK = CSRC / "cst_encode_loop_pc_n8w_ck.inc"
-OUT_N16W = CSRC / "cst_encode_loop_pc_n16w.inc"
-OUT_N16W_CK = CSRC / "cst_encode_loop_pc_n16w_ck.inc"
-OUT_STORER2 = CSRC / "cst_encode_loop_pc_storer2.inc"     # ... and their storer: two 64-byte groups per tile (32 symbols can emit 24 words)
-
-
-def main_n8():
+def main_n8(out):
     global JUMP, WIDE
-    for JUMP, out in ((False, OUT_N8), (True, OUT_N8_CK)):
-        emit_n8_coder(out)
-    WIDE = True                                             # 12 < P <= 24
-    for JUMP, out in ((False, OUT_N8W), (True, OUT_N8W_CK)):
-        emit_n8_coder(out)
+    for JUMP, name in ((False, "cst_encode_loop_pc_n8.inc"), (True, "cst_encode_loop_pc_n8_ck.inc")):
+        emit_n8_coder(out, name)
+    WIDE = True                                             # 12 < P <= 24 (step_wide)
+    for JUMP, name in ((False, "cst_encode_loop_pc_n8w.inc"), (True, "cst_encode_loop_pc_n8w_ck.inc")):
+        emit_n8_coder(out, name)
     JUMP = WIDE = False
-    emit_n8_loader()
+    emit_n8_loader(out)
 
 
-def emit_n8_coder(out):
+def emit_n8_coder(out, name):
     a, notes = gen_n8()
-    header = ["// GENERATED by scripts/gen_encode_loop_pc.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Coder half of the producer / consumer (32,64) ANS encoder for int8 symbol matrices: see ans_encode_pc_n8_coder_loop in cst_ans_pc.hip."]
+    about = ["// Coder half of the producer / consumer (32,64) ANS encoder for int8 symbol matrices: see ans_encode_pc_n8_coder_loop in cst_ans_pc.hip."]
     ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [smin] "+v"(smin), [smax] "+v"(smax)',
            '    : [row0] "v"(line_row_addr), [lanebase] "v"(ring_lane_addr), [pub] "v"(publish_addr), [four] "v"(4u),',
            '      [twoP] "v"(1u << P), [P] "s"(P), [c3f00] "s"(0x3f00u), [ntiles] "s"(n_tiles)' + (', [sh] "s"(32u - P)' if WIDE else '') + ck_operands(),
            "    : " + ", ".join(f'"{c}"' for c in N8_CLOBBERS + ck_clobbers()) + ");"]
-    out.write_text(a.render(header, ops))
-    print(f"wrote {out} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+    out.add(name, a, about, ops, notes=notes)
 
 
-def emit_n8_loader():
+def emit_n8_loader(out):
     a, notes = gen_loader_n8()
-    header = ["// GENERATED by scripts/gen_encode_loop_pc.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Loader wave of the producer / consumer (32,64) ANS encoder for int8 symbol matrices: see ans_encode_pc_n8_loader_loop in cst_ans_pc.hip."]
+    about = ["// Loader wave of the producer / consumer (32,64) ANS encoder for int8 symbol matrices: see ans_encode_pc_n8_loader_loop in cst_ans_pc.hip."]
     ops = ['    :',
            '    : [tr0] "v"(line_tr_addr[0]), [tr1] "v"(line_tr_addr[1]), [sbase] "s"(symbols_base), [rowblock] "s"(row_block_bytes), [ntiles] "s"(n_tiles),',
            '      ' + ", ".join(f'[goff0_{k}] "v"(goff0[{k}])' for k in range(8)) + ",",
            '      ' + ", ".join(f'[goff1_{k}] "v"(goff1[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in L_CLOBBERS) + ");"]
-    OUT_LOADER_N8.write_text(a.render(header, ops))
-    print(f"wrote {OUT_LOADER_N8} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+    out.add("cst_encode_loop_pc_loader_n8.inc", a, about, ops, notes=notes)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1012,9 +976,6 @@ def emit_n8_loader():
 # ADDRESSES with unsigned min3 / max3 (an address below the table wraps to a huge one).  The tile pointers leapfrog as for int8; with
 # two tiles per line EVERY second step jumps to the other line buffer (J, then 128 - J).  The loader stages a line in two windows.
 # ---------------------------------------------------------------------------------------------------------------------
-OUT_N16 = CSRC / "cst_encode_loop_pc_n16.inc"
-OUT_N16_CK = CSRC / "cst_encode_loop_pc_n16_ck.inc"
-OUT_LOADER_N16 = CSRC / "cst_encode_loop_pc_loader_n16.inc"
 S16 = [(f"v{100 + 2 * i}", f"v{101 + 2 * i}", tup(100 + 2 * i, 2)) for i in range(4)]        # a quad: two dwords
 N16_CLOBBERS = [f"v{r}" for r in range(100, 170)] + ["s82", "s83", "s84", "s85", "s87", "s88", "vcc", "scc", "memory"]
 EA16 = [[f"v{108 + 4 * e + i}" for i in range(4)] for e in range(2)]                          # v108 .. v115 (PA, PB move to v170 / v171 ... see below)
@@ -1149,38 +1110,38 @@ def gen_loader_n16():
     return a, notes
 
 
-def main_n16():
+def main_n16(out):
     global JUMP, WIDE
-    for WIDE, JUMP, out in ((False, False, OUT_N16), (False, True, OUT_N16_CK), (True, False, OUT_N16W), (True, True, OUT_N16W_CK)):
+    for WIDE, JUMP, name in ((False, False, "cst_encode_loop_pc_n16.inc"), (False, True, "cst_encode_loop_pc_n16_ck.inc"),
+                             (True, False, "cst_encode_loop_pc_n16w.inc"), (True, True, "cst_encode_loop_pc_n16w_ck.inc")):
         a, notes = gen_n16()
-        header = ["// GENERATED by scripts/gen_encode_loop_pc.py -- do not edit by hand (edit the generator and re-run it).",
-                  "// Coder half of the producer / consumer (32,64) ANS encoder for int16 symbol matrices: see ans_encode_pc_n16_coder_loop in cst_ans_pc.hip."]
+        about = ["// Coder half of the producer / consumer (32,64) ANS encoder for int16 symbol matrices: see ans_encode_pc_n16_coder_loop in cst_ans_pc.hip."]
         ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [smin] "+v"(smin), [smax] "+v"(smax)',
                '    : [row0] "v"(line_row_addr), [lanebase] "v"(ring_lane_addr), [pub] "v"(publish_addr), [tbl] "s"(table_bias),',
                '      [twoP] "v"(1u << P), [P] "s"(P), [c3f00] "s"(0x3f00u), [ntiles] "s"(n_tiles)' + (', [sh] "s"(32u - P)' if WIDE else '') + ck_operands(),
                "    : " + ", ".join(f'"{c}"' for c in N16_CLOBBERS + [PA16, PB16] + ck_clobbers()) + ");"]
-        out.write_text(a.render(header, ops))
-        print(f"wrote {out} ({a.n_instr()} instructions incl. prologue)")
+        out.add(name, a, about, ops, notes=notes)
     JUMP = WIDE = False
     a, notes = gen_loader_n16()
-    header = ["// GENERATED by scripts/gen_encode_loop_pc.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Loader wave of the producer / consumer (32,64) ANS encoder for int16 symbol matrices: see ans_encode_pc_n16_loader_loop in cst_ans_pc.hip."]
+    about = ["// Loader wave of the producer / consumer (32,64) ANS encoder for int16 symbol matrices: see ans_encode_pc_n16_loader_loop in cst_ans_pc.hip."]
     ops = ['    :',
            '    : [tr0] "v"(line_tr_addr[0]), [tr1] "v"(line_tr_addr[1]), [sbase] "s"(symbols_base), [rowblock] "s"(row_block_bytes), [ntiles] "s"(n_tiles),',
            '      ' + ", ".join(f'[goff0_{k}] "v"(goff0[{k}])' for k in range(8)) + ",",
            '      ' + ", ".join(f'[goff1_{k}] "v"(goff1[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in L_CLOBBERS) + ");"]
-    OUT_LOADER_N16.write_text(a.render(header, ops))
-    print(f"wrote {OUT_LOADER_N16} ({a.n_instr()} instructions incl. prologue)")
+    out.add("cst_encode_loop_pc_loader_n16.inc", a, about, ops, notes=notes)
 
 
-def main_all():
-    main()
-    main_helper()
-    main_split()
-    main_n8()
-    main_n16()
+def main():
+    out = Statements(__file__)
+    main_int32(out)
+    main_helper(out)
+    main_split(out)
+    main_n8(out)
+    main_n16(out)
+    return out
 
 
 if __name__ == "__main__":
-    main_all()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_encode_loop_pc"]))

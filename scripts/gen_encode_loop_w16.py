@@ -14,28 +14,25 @@ stay zero without masking the word.
 
 Run:  python scripts/gen_encode_loop_w16.py   (rewrites the .inc; the .inc is checked in)
 """
-import os
 import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import gen_encode_loop as G  # noqa: E402
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements, knobs  # noqa: E402
 
-# GEN_W16_PACKED=1 (round 5, CST_FLAG_PACKED_W16): the slab holds the words as the reference does -- a Vec<u16>, two words per
+PACKED, CKPT = knobs(globals(), packed=False, ck=False)
+# packed (round 5, CST_FLAG_PACKED_W16): the slab holds the words as the reference does -- a Vec<u16>, two words per
 # 32-bit slot (stack.rs:153) -- so a 64-byte group is THIRTY-TWO words and at most one leaves per tile (32 symbols emit at most
 # 24).  The ring keeps one word per 32-bit slot (upper halves zero: ds_write_b16 into a zeroed ring); the flush reads eight
 # 4-word chunks per group (quads 7, 6 and 4, 3 as before), packs pairs with v_lshl_or_b32 (16 VALU per group: 0.4 per symbol)
 # and stores 32 bytes at quad 5 and 32 at quad 2.  A chunk read late is never overwritten: word flushed + 4 c is written again
 # when wr reaches flushed + 64 + 4 c, and wr - flushed stays below 55 + 12.  Written to cst_encode_loop_w16_pk.inc.
-PACKED = bool(os.environ.get("GEN_W16_PACKED"))
-# GEN_W16_CK=1 (round 6, with GEN_W16_PACKED): the same loop with JUMP POINTS -- the reference's Pos side information (stack.rs:1107-1139:
+# ck (round 6, with packed): the same loop with JUMP POINTS -- the reference's Pos side information (stack.rs:1107-1139:
 # words in the bulk, state), which depends on neither the word type nor how the words are stored: after the last step of every
 # ck_tiles-th tile the lanes store (wr, state) at element ck_index of the two jump arrays and step to the chunk in front (as
-# gen_pt_encode_loop.py's GEN_PT_CK does).  Written to cst_encode_loop_w16_pk_ck.inc.
-CKPT = bool(os.environ.get("GEN_W16_CK"))
+# gen_pt_encode_loop.py's ck does).  Written to cst_encode_loop_w16_pk_ck.inc.
 assert not CKPT or PACKED
-OUT = G.CSRC / ("cst_encode_loop_w16_pk_ck.inc" if CKPT else "cst_encode_loop_w16_pk.inc" if PACKED else "cst_encode_loop_w16.inc")
 CKST, CKZ, CKA, CKCNT = "v218", "v219", "v220", "s92"          # v[218:219] = [state, 0]: the jump table holds 64-bit states
 A_, SH, QE, R_, T_, CKS = (f"v{r}" for r in range(212, 218))
 RA, NCH, LIM, FADDR, FOFF, FD, SAVE = G.RA, G.NCH, G.LIM, G.FADDR, G.FOFF, G.FD, G.SAVE
@@ -214,21 +211,19 @@ def gen():
     return a, notes
 
 
-OUT_SM = OUT.with_name("cst_encode_loop_w16_sm.inc")
-
-
 def main():
-    emit(OUT, False)
+    out = Statements(__file__)
+    emit(out, "cst_encode_loop_w16_pk_ck.inc" if CKPT else "cst_encode_loop_w16_pk.inc" if PACKED else "cst_encode_loop_w16.inc", False)
     if not PACKED:
-        emit(OUT_SM, True)          # symbols[t][stream]: gen_encode_loop.py's SYMBOL_MAJOR staging
+        emit(out, "cst_encode_loop_w16_sm.inc", True)          # symbols[t][stream]: gen_encode_loop.py's SYMBOL_MAJOR staging
+    return out
 
 
-def emit(out, symbol_major):
+def emit(out, name, symbol_major):
     G.SYMBOL_MAJOR = symbol_major
     a, notes = gen()
     G.SYMBOL_MAJOR = False
-    header = ["// GENERATED by scripts/gen_encode_loop_w16.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Main loop of the hand-scheduled (16,32) ANS encoder: see cst_ans_w16.hip."]
+    about = ["// Main loop of the hand-scheduled (16,32) ANS encoder: see cst_ans_w16.hip."]
     ops = ['    : [st] "+v"(st), [wr] "+v"(wr), [flushed] "+v"(flushed), [smin] "+v"(smin), [smax] "+v"(smax)' + (', [ckidx] "+v"(ck_index)' if CKPT else ""),
            '    : [row0] "v"(tile_row_addr[0]), [row1] "v"(tile_row_addr[1]), [tr0] "v"(tile_tr_addr[0]), [tr1] "v"(tile_tr_addr[1]),',
            '      [lanebase] "v"(ring_lane_addr), [cap] "v"(cap), [slaboff] "v"(slab_off),',
@@ -237,11 +232,9 @@ def emit(out, symbol_major):
            + (' [ckpos] "s"(ck_pos_base), [ckstate] "s"(ck_state_base), [cktiles] "s"(ck_tiles),' if CKPT else ''),
            '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in G.CLOBBERS) + ");"]
-    out.write_text(a.render(header, ops))
-    print(f"wrote {out} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+    out.add(name, a, about, ops, notes=notes)
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_encode_loop_w16"]))

@@ -13,9 +13,8 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import gen_encode_loop as G  # noqa: E402
 import gen_encode_loop_w16 as W  # noqa: E402
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements  # noqa: E402
 
-OUT = G.CSRC / "cst_encode_loop_wide.inc"
 A0, A1, W0, W1, U0, U1, T0, T1, SM0, SM1, Q0, Q1 = G.A0, G.A1, G.W0, G.W1, G.U0, G.U1, G.T0, G.T1, G.SM0, G.SM1, G.Q0, G.Q1
 A_T, W_T, U_T, T_T, SM_T, Q_T = G.A_T, G.W_T, G.U_T, G.T_T, G.SM_T, G.Q_T
 RR, PSHL, CK, RA, SD, LO, HI, ST_T = G.RR, G.PSHL, G.CK, G.RA, G.SD, G.LO, G.HI, G.ST_T
@@ -50,15 +49,14 @@ def step(a, c, p, m0, m1):
     a.i(f"v_mad_u64_u32 {ST_T}, {SD}, {Q0}, %[twoP], {A_T}", "state = q_est 2^P + r + c + fix 2^P")
 
 
-OUT_SM = G.CSRC / "cst_encode_loop_wide_sm.inc"
-
-
 def main():
-    emit(OUT, False)
-    emit(OUT_SM, True)              # symbols[t][stream]: gen_encode_loop.py's SYMBOL_MAJOR staging
+    out = Statements(__file__)
+    emit(out, "cst_encode_loop_wide.inc", False)
+    emit(out, "cst_encode_loop_wide_sm.inc", True)              # symbols[t][stream]: gen_encode_loop.py's SYMBOL_MAJOR staging
+    return out
 
 
-def emit(out, symbol_major):
+def emit(out, name, symbol_major):
     W.step = step                     # the (16,32) generator's tile body (two word groups per tile) around this step
     G.SINGLE = False
     G.SYMBOL_MAJOR = symbol_major
@@ -97,8 +95,7 @@ def emit(out, symbol_major):
     a.i(f"v_mov_b32 %[hi], {HI}")
     a.wait_vm_all("nothing may land in the scratch registers after the statement")
     a.wait_lds_all()
-    header = ["// GENERATED by scripts/gen_encode_loop_wide.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Main loop of the hand-scheduled (32,64) ANS encoder for 12 < P <= 24: see cst_ans_b16.hip."]
+    about = ["// Main loop of the hand-scheduled (32,64) ANS encoder for 12 < P <= 24: see cst_ans_b16.hip."]
     ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [wr] "+v"(wr), [flushed] "+v"(flushed), [smin] "+v"(smin), [smax] "+v"(smax)',
            '    : [row0] "v"(tile_row_addr[0]), [row1] "v"(tile_row_addr[1]), [tr0] "v"(tile_tr_addr[0]), [tr1] "v"(tile_tr_addr[1]),',
            '      [lanebase] "v"(ring_lane_addr), [cap] "v"(cap), [slaboff] "v"(slab_off),',
@@ -106,12 +103,10 @@ def emit(out, symbol_major):
            '      [sbase] "s"(symbols_base), [ntiles] "s"(n_tiles),' + (' [tilestep] "s"(tile_step_bytes),' if symbol_major else ''),
            '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in G.CLOBBERS) + ");"]
-    out.write_text(a.render(header, ops))
-    print(f"wrote {out} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+    out.add(name, a, about, ops, notes=notes)
     G.SYMBOL_MAJOR = False
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_encode_loop_wide"]))

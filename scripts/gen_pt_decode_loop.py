@@ -23,35 +23,34 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements, knobs  # noqa: E402
 
-# GEN_PT_SUB=1 (round 5): the loop of the SUB-LANE decoder (ans_decode_pt_sub_kernel: k jump points per stream, 512-thread
+LANES, N8 = knobs(globals(), sub=0, n8=False)
+# sub=1 (round 5): the loop of the SUB-LANE decoder (ans_decode_pt_sub_kernel: k jump points per stream, 512-thread
 # workgroups, two waves per SIMD).  What a second resident wave costs is LDS, so the symbol tile holds BYTES: the decoded
 # index (< 256 on this path) goes into byte `pos` of the quad's register with one SDWA add (dst_sel:BYTE_n,
 # UNUSED_PRESERVE: the same instruction count as the v_add3 of the int32 tile; the v_and that isolated the index is gone,
 # the select for runs takes its slot between the vcc write and its reader), a quad is ONE ds_write_b32, rows are 36 bytes
 # apart (2304 bytes per wave instead of 9216), and the tile leaves as int32 symbols: each 4-byte piece read back is widened
 # by four SDWA adds of min_symbol (src1_sel:BYTE_n) in front of its 16-byte store.
-SUB = bool(os.environ.get("GEN_PT_SUB"))
-# GEN_PT_SUB=2: the same for FOUR waves per SIMD (sixteen per workgroup).  The ring shrinks to 16 slots (4 KiB per wave), which
+SUB = bool(LANES)
+# sub=2: the same for FOUR waves per SIMD (sixteen per workgroup).  The ring shrinks to 16 slots (4 KiB per wave), which
 # cannot hold two tiles' worth of words, so the window moves every HALF tile: 16 symbols consume at most 6 words, the ring keeps the 12
 # below the read position (two halves), two chunk slots are requested at steps 0 and 16 and landed after steps 15 and 31 -- a chunk
 # with words 4c .. 4c + 3 lands on the slots of words 4c + 16 ..., which lie at or above rd_top + 1 and are dead by then.  The first
 # refill candidate of the NEXT half is read behind the landing (it may be in the chunk that has just landed).  And the statement's
 # registers are renumbered from v100 - v177 down to v48 - v125: sixteen waves per workgroup leave every wave 128.
-SUB16 = os.environ.get("GEN_PT_SUB") == "2"
+SUB16 = LANES == 2
 REG_SHIFT = 52 if SUB16 else 0
 SUB_ROW = 36          # bytes between the rows of the byte tile (9 dwords: the lanes' quad writes hit 64 different banks)
-# GEN_PT_N8=1 (round 6, with GEN_PT_SUB): the sub-lane decoders writing an INT8 symbol matrix themselves.  A four-byte piece of the byte
+# n8 (round 6, with sub): the sub-lane decoders writing an INT8 symbol matrix themselves.  A four-byte piece of the byte
 # tile (four symbol INDICES) becomes four int8 symbols by ONE packed add of min_symbol to every byte (carries between the bytes
 # suppressed: five VALU instructions instead of four SDWA adds) and leaves with one global_store_dword; a tile is 32 bytes of a row.
 # (Adding min_symbol to the index bytes of the staged rows instead would be free -- and wrong: the search compares whole entries, and a
 # run mark 0xfff with index byte 0xff exceeds the key's 0xffffe.)
-N8 = bool(os.environ.get("GEN_PT_N8"))
 assert not N8 or SUB
-OUT = Path(os.environ.get("GEN_CSRC") or Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc") / \
-    (("cst_pt_decode_loop_sub16_n8.inc" if SUB16 else "cst_pt_decode_loop_sub_n8.inc") if N8 else
-     "cst_pt_decode_loop_sub16.inc" if SUB16 else "cst_pt_decode_loop_sub.inc" if SUB else "cst_pt_decode_loop.inc")
+NAME = ("cst_pt_decode_loop_sub16_n8.inc" if SUB16 else "cst_pt_decode_loop_sub_n8.inc") if N8 else \
+    "cst_pt_decode_loop_sub16.inc" if SUB16 else "cst_pt_decode_loop_sub.inc" if SUB else "cst_pt_decode_loop.inc"
 
 K_CHUNKS = 2 if SUB16 else 3      # window chunks requested per tile (32 symbols * 12 bits = 12 words = 3 chunks) / per half tile
 AHEAD_M1 = 11 if SUB16 else 23    # kPtAhead - 1
@@ -325,8 +324,7 @@ def gen():
 
 def main():
     a, notes = gen()
-    header = ["// GENERATED by scripts/gen_pt_decode_loop.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Main loop of the hand-scheduled per-stream-table ANS decoder" + (", int8 symbol matrix" if N8 else "") + ": see pt_decode_tiles_loop in cst_ans_pt.hip."]
+    about = ["// Main loop of the hand-scheduled per-stream-table ANS decoder" + (", int8 symbol matrix" if N8 else "") + ": see pt_decode_tiles_loop in cst_ans_pt.hip."]
     ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [rd] "+v"(rd), [lo_issued] "+v"(lo_issued)',
            '    : [bmask] "s"(bucket_mask), [cmask] "s"(ring_mask), [P] "s"(P), [fffe] "s"(0xffffeu), [fff] "s"(0xfffu), [minsym] "s"(min_symbol),',
            '      [wbase] "s"(words_base), [gbase] "s"(store_base), [ntiles] "s"(n_tiles),',
@@ -334,19 +332,18 @@ def main():
            '      [dump] "v"(dump_addr), [woff] "v"(words_off), [rowcur] "v"(tile_row_addr), [trcur] "v"(tile_tr_addr),',
            '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in CLOBBERS) + ");"]
-    text = a.render(header, ops)
+    out = Statements(__file__)
+    out.add(NAME, a, about, ops, notes=notes)
     if REG_SHIFT:
         import re
         def shift(m):
             n = int(m.group(2))
             return f"{m.group(1)}{n - REG_SHIFT}" if n >= 100 else m.group(0)
-        text = re.sub(r"(\bv\[?)(\d+)", shift, text)                     # v123, v[123
-        text = re.sub(r"(v\[\d+:)(\d+)", shift, text)                    # the upper end of v[123:126]
-    OUT.write_text(text)
-    print(f"wrote {OUT} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+        text = re.sub(r"(\bv\[?)(\d+)", shift, out[NAME])                # v123, v[123
+        out[NAME] = re.sub(r"(v\[\d+:)(\d+)", shift, text)               # the upper end of v[123:126]
+    return out
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_pt_decode_loop"]))

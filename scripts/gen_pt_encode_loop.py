@@ -18,23 +18,21 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements, knobs  # noqa: E402
 
 import os
 
-# GEN_PT_CK=1 (round 5): the same loop with JUMP POINTS -- the reference's Pos side information (stack.rs:1107-1139): every
+CKPT, N8 = knobs(globals(), ck=False, n8=False)
+# ck (round 5): the same loop with JUMP POINTS -- the reference's Pos side information (stack.rs:1107-1139): every
 # `cktiles` tiles (one chunk of the stream) the lanes note (words in the bulk, coder state) = AnsCoder::pos() in front of that
 # chunk.  A scalar countdown and a branch per tile; the three instructions of a checkpoint run k times per stream, end with
 # vmcnt(0) (they are not in the generator's book: waiting for MORE than the book knows is always safe) and cost nothing
 # measurable.  The compressed words are those of the plain loop.
-CKPT = bool(os.environ.get("GEN_PT_CK"))
-# GEN_PT_N8=1 (round 6, with GEN_PT_CK): the same loop over an INT8 symbol matrix (C3's support -127 .. 127 fits the type; the reference's
+# n8 (round 6, with ck): the same loop over an INT8 symbol matrix (C3's support -127 .. 127 fits the type; the reference's
 # Symbol is generic, quantize.rs:229-255).  A tile is 32 BYTES of a row: one global_load_dword per lane and quad into the quad's last
 # register, sign-extended into the quad (three v_bfe_i32 and a shift) in front of the transposed ds_write_b128.  cst_pt_encode_loop_ck_n8.inc
-N8 = bool(os.environ.get("GEN_PT_N8"))
 assert not N8 or CKPT
-OUT = Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc" / \
-    ("cst_pt_encode_loop_ck_n8.inc" if N8 else "cst_pt_encode_loop_ck.inc" if CKPT else "cst_pt_encode_loop.inc")
+NAME = "cst_pt_encode_loop_ck_n8.inc" if N8 else "cst_pt_encode_loop_ck.inc" if CKPT else "cst_pt_encode_loop.inc"
 
 
 def regs(base, n=4):
@@ -292,8 +290,7 @@ def gen():
 
 def main():
     a, notes = gen()
-    header = ["// GENERATED by scripts/gen_pt_encode_loop.py -- do not edit by hand (edit the generator and re-run it).",
-              "// Main loop of the hand-scheduled per-stream-table ANS encoder" + (", int8 symbol matrix" if N8 else "") + ": see pt_encode_tiles_loop in cst_ans_pt.hip."]
+    about = ["// Main loop of the hand-scheduled per-stream-table ANS encoder" + (", int8 symbol matrix" if N8 else "") + ": see pt_encode_tiles_loop in cst_ans_pt.hip."]
     ops = ['    : [lo] "+v"(lo), [hi] "+v"(hi), [wr] "+v"(wr), [flushed] "+v"(flushed), [smin] "+v"(smin), [smax] "+v"(smax)' +
            (', [ckidx] "+v"(ck_index)' if CKPT else ""),
            '    : [row0] "v"(tile_row_addr), [tr0] "v"(tile_tr_addr),',
@@ -304,11 +301,11 @@ def main():
            (' [ckpos] "s"(ck_pos_base), [ckstate] "s"(ck_state_base), [cktiles] "s"(ck_tiles),' if CKPT else ""),
            '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in CLOBBERS) + ");"]
-    OUT.write_text(a.render(header, ops))
-    print(f"wrote {OUT} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+    out = Statements(__file__)
+    out.add(NAME, a, about, ops, notes=notes)
+    return out
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_pt_encode_loop"]))

@@ -25,31 +25,26 @@ and decodes what the main one left.
 
 Run:  python scripts/gen_range_decode_loop.py   (rewrites the .inc files; they are checked in)
 """
-import os
 import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements, knobs  # noqa: E402
 
-# GEN_RANGE_SUB=1 (round 5): the loops of the SUB-LANE decoder (range_decode_sub_kernel: k jump points per stream, eight waves
-# per workgroup, two per SIMD).  As for the ANS sub-lane decoder (gen_pt_decode_loop.py, GEN_PT_SUB) the second wave is paid for
+SUB, N8 = knobs(globals(), sub=False, n8=False)
+# sub (round 5): the loops of the SUB-LANE decoder (range_decode_sub_kernel: k jump points per stream, eight waves
+# per workgroup, two per SIMD).  As for the ANS sub-lane decoder (gen_pt_decode_loop.py, sub) the second wave is paid for
 # by symbol tiles of BYTES: a step leaves its symbol INDEX (< 256) with ds_write_b8 in the lane's 36-byte row; the previous
 # tile's pieces are read back four bytes at a time and widened by four SDWA adds of min_symbol in front of their 16-byte store.
 # Written to cst_range_decode_loop{,_b16}_sub{,_ends}.inc (stream-major only).
-SUB = bool(os.environ.get("GEN_RANGE_SUB"))
 SUB_ROW = 36
-# GEN_RANGE_N8=1 (round 6, with GEN_RANGE_SUB): the sub-lane decoder that writes an INT8 symbol matrix itself (the reference's Symbol
+# n8 (round 6, with sub): the sub-lane decoder that writes an INT8 symbol matrix itself (the reference's Symbol
 # is generic: queue.rs:968, quantize.rs:229-255).  The byte tile then holds the symbols themselves (index + min_symbol, low byte:
 # P <= 12 through a biased index table, the bucket-entry form through the step's add), the previous tile's four bytes leave as they
 # are -- one global_store_dword per quad instead of four SDWA adds and a 16-byte store -- and a tile is 32 bytes of a row.
 # Written to cst_range_decode_loop{,_b16}_sub_n8{,_ends}.inc.
-N8 = bool(os.environ.get("GEN_RANGE_N8"))
 assert not N8 or SUB
-CSRC = Path(os.environ.get("GEN_CSRC") or Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc")
-OUT = {(False, False): CSRC / "cst_range_decode_loop.inc", (False, True): CSRC / "cst_range_decode_loop_ends.inc",
-       (True, False): CSRC / "cst_range_decode_loop_b16.inc", (True, True): CSRC / "cst_range_decode_loop_b16_ends.inc"}
-# SYMBOL_MAJOR (the same four files with _sm): symbols[t][stream], the staging of gen_decode_loop.py's SYMBOL_MAJOR (whole lines): quad k of the
+# SYMBOL_MAJOR (cst_range_decode_loop{,_b16}{,_ends}_sm.inc): symbols[t][stream], the staging of gen_decode_loop.py's SYMBOL_MAJOR (whole lines): quad k of the
 # previous tile leaves as streams 32 (k & 1) + 4 (lane & 7) .. + 3 of symbol row (lane >> 3) + 8 (k >> 1); full waves only
 # (the store base moves by %[tilestep] per tile).
 SYMBOL_MAJOR = False
@@ -348,13 +343,14 @@ def gen(ends):
 
 def main():
     global B16, SYMBOL_MAJOR
+    out = Statements(__file__)
     for sm, b16 in (((False, False), (False, True)) if SUB else ((False, False), (False, True), (True, False), (True, True))):
         B16, SYMBOL_MAJOR = b16, sm
         for ends in (False, True):
             a = gen(ends)
-            header = ["// GENERATED by scripts/gen_range_decode_loop.py -- do not edit by hand (edit the generator and re-run it).",
-                      "// Main loop of the hand-scheduled (32,64) range decoder" + (", 12 < P <= 24 (bucket entries)" if b16 else "") +
-                      (", end-of-data aware" if ends else "") + ": see cst_range_fast.hip."]
+            about = "// Main loop of the hand-scheduled (32,64) range decoder" + (", 12 < P <= 24 (bucket entries)" if b16 else "") + \
+                (", end-of-data aware" if ends else "") + (", int8 symbol matrix" if N8 else "") + (", symbols[t][stream]" if sm else "") + \
+                ": see cst_range_fast.hip."
             ops = ['    : [x0] "+v"(x0), [x1] "+v"(x1), [rg0] "+v"(rg0), [rg1] "+v"(rg1), [pos] "+v"(pos), [hi_issued] "+v"(hi_issued),',
                    '      [rowcur] "+v"(row_cur), [rowprev] "+v"(row_prev), [trcur] "+v"(tr_cur), [trprev] "+v"(tr_prev), [tiles] "+v"(tiles), [ginc] "+v"(ginc),',
                    '      [bad] "=v"(bad)',
@@ -365,18 +361,12 @@ def main():
                     (', [minsym] "v"(min_symbol)' if SUB else '')) +
                    (', [tilestep] "s"(tile_step_bytes)' if sm else ''),
                    "    : " + ", ".join(f'"{c}"' for c in CLOBBERS) + ");"]
-            out = OUT[(b16, ends)]
-            if SUB:
-                tag = "_sub_n8" if N8 else "_sub"
-                out = out.with_name(out.name.replace("_ends.inc", tag + "_ends.inc") if ends else out.name.replace(".inc", tag + ".inc"))
-                if N8:
-                    header[1] = header[1].replace(": see", ", int8 symbol matrix: see")
-            if sm:
-                out = out.with_name(out.name.replace(".inc", "_sm.inc"))
-                header[1] = header[1].replace(": see", ", symbols[t][stream]: see")
-            out.write_text(a.render(header, ops))
-            print(f"wrote {out} ({a.n_instr()} instructions incl. loop control)")
+            name = "cst_range_decode_loop" + ("_b16" if b16 else "") + ("_sub_n8" if N8 else "_sub" if SUB else "") + \
+                ("_ends" if ends else "") + ("_sm" if sm else "") + ".inc"
+            out.add(name, a, [about], ops, "instructions incl. loop control")
+    return out
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_range_decode_loop"]))

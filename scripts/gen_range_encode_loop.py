@@ -22,28 +22,23 @@ Variants: one word group (16 words) leaves per tile (P <= 16: a tile emits at mo
 
 Run:  python scripts/gen_range_encode_loop.py   (rewrites the .inc files; they are checked in)
 """
-import os
 import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from asmgen import Asm  # noqa: E402
+from asmgen import Asm, Statements, knobs  # noqa: E402
 
-# GEN_RANGE_CK=1 (round 5): the stream-major loops with JUMP POINTS -- RangeEncoder::pos() (queue.rs:182-196: words emitted
+CKPT, N8 = knobs(globals(), ck=False, n8=False)
+# ck (round 5): the stream-major loops with JUMP POINTS -- RangeEncoder::pos() (queue.rs:182-196: words emitted
 # including held-back ones, and the coder state (lower, range)) noted in front of every chunk of `cktiles` tiles: a scalar
 # countdown and a branch at the top of every tile, four instructions + three stores k times per stream.  The held word counts:
 # pos = wr + 1 (wr is -1 until the first word exists).  Written to cst_range_encode_loop{,_2f}_ck.inc; the words are the plain loop's.
-CKPT = bool(os.environ.get("GEN_RANGE_CK"))
-# GEN_RANGE_N8=1 (round 6, with GEN_RANGE_CK): the same loops over an INT8 symbol matrix (the reference's Symbol is generic:
+# n8 (round 6, with ck): the same loops over an INT8 symbol matrix (the reference's Symbol is generic:
 # queue.rs:612, quantize.rs:229-255).  A tile is 32 BYTES of a row: a lane requests four symbols with one global_load_dword into the last
 # register of its quad, and sign-extends them into the quad (three v_bfe_i32 and a shift) in front of the transposed ds_write_b128 --
 # one more VALU instruction per symbol, a quarter of the symbol bytes.  Written to cst_range_encode_loop{,_2f}_ck_n8.inc; the kernel
 # that runs them (range_encode_ckpt_kernel<FLUSHES, 1>) also serves the plain call (one chunk: the jump point is the start).
-N8 = bool(os.environ.get("GEN_RANGE_N8"))
 assert not N8 or CKPT
-CSRC = Path(os.environ.get("GEN_CSRC") or Path(__file__).resolve().parent.parent / "constriction_amd" / "csrc")
-OUT = {(1, False): CSRC / "cst_range_encode_loop.inc", (2, False): CSRC / "cst_range_encode_loop_2f.inc",
-       (1, True): CSRC / "cst_range_encode_loop_sm.inc", (2, True): CSRC / "cst_range_encode_loop_2f_sm.inc"}
 FLUSHES = 1
 # SYMBOL_MAJOR (cst_range_encode_loop*_sm.inc): symbols[t][stream].  Only the staging differs (gen_encode_loop.py): a load
 # instruction reads 16 symbol rows of 64 bytes (lane l: row l >> 2, streams 4 (l & 3) .. + 3), the four symbols of a
@@ -300,12 +295,12 @@ def gen():
     return a, notes
 
 
-def emit(flushes, symbol_major=False):
+def emit(out, flushes, symbol_major=False):
     global FLUSHES, SYMBOL_MAJOR
     FLUSHES, SYMBOL_MAJOR = flushes, symbol_major
     a, notes = gen()
-    header = ["// GENERATED by scripts/gen_range_encode_loop.py -- do not edit by hand (edit the generator and re-run it).",
-              f"// Main loop of the hand-scheduled (32,64) range encoder, {flushes} word group(s) per tile: see cst_range_fast.hip."]
+    about = f"// Main loop of the hand-scheduled (32,64) range encoder, {flushes} word group(s) per tile" + \
+        (", symbols[t][stream]" if symbol_major else "") + (", int8 symbol matrix" if N8 else "") + ": see cst_range_fast.hip."
     ops = ['    : [lo0] "+v"(lo0), [lo1] "+v"(lo1), [rg0] "+v"(rg0), [rg1] "+v"(rg1), [lw] "+v"(lw), [wr] "+v"(wr), [flushed] "+v"(flushed),',
            '      [smin] "+v"(smin), [smax] "+v"(smax), [slow] "=v"(slow)' + (', [ckidx] "+v"(ck_index)' if CKPT else ''),
            '    : [row0] "v"(tile_row_addr[0]), [row1] "v"(tile_row_addr[1]), [tr0] "v"(tile_tr_addr[0]), [tr1] "v"(tile_tr_addr[1]),',
@@ -315,24 +310,19 @@ def emit(flushes, symbol_major=False):
            (' [ckpos] "s"(ck_pos_base), [cklower] "s"(ck_lower_base), [ckrange] "s"(ck_range_base), [cktiles] "s"(ck_tiles),' if CKPT else ''),
            '      ' + ", ".join(f'[goff{k}] "v"(goff[{k}])' for k in range(8)),
            "    : " + ", ".join(f'"{c}"' for c in CLOBBERS) + ");"]
-    if symbol_major:
-        header[1] = header[1].replace(": see", ", symbols[t][stream]: see")
-    out = OUT[(flushes, symbol_major)]
-    if CKPT:
-        out = out.with_name(out.name.replace(".inc", "_ck_n8.inc" if N8 else "_ck.inc"))
-        if N8:
-            header[1] = header[1].replace(": see", ", int8 symbol matrix: see")
-    out.write_text(a.render(header, ops))
-    print(f"wrote {out} ({a.n_instr()} instructions incl. prologue)")
-    for n in notes:
-        print("  note:", n)
+    name = "cst_range_encode_loop" + ("_2f" if flushes == 2 else "") + ("_sm" if symbol_major else "") + \
+        ("_ck_n8" if N8 else "_ck" if CKPT else "") + ".inc"
+    out.add(name, a, [about], ops, notes=notes)
 
 
 def main():
+    out = Statements(__file__)
     for sm in ((False,) if CKPT else (False, True)):
-        emit(1, sm)
-        emit(2, sm)
+        emit(out, 1, sm)
+        emit(out, 2, sm)
+    return out
 
 
 if __name__ == "__main__":
-    main()
+    import loops
+    raise SystemExit(loops.main(["--only", "gen_range_encode_loop"]))
