@@ -76,7 +76,8 @@ def test_fast_erf_error_bound(B, O):
     assert worst <= 2.0 ** -46, f"fast erf deviates by {worst:.3e} at x = {x[int(err.argmax())]!r}"
     assert worst < 1e-15                                     # (in practice 2.2e-16: four orders of magnitude of room)
     # a NaN argument comes back as +-1 (no NaN test in the fast path): the caller's guard sends it to the exact evaluation,
-    # because free_weight * (1 +- 1) / 2 is an integer (test_quick_left_cumulatives_equal_the_exact_ones: overflowing scales)
+    # because free_weight * (1 +- 1) / 2 is an integer (test_quick_left_cumulatives_fall_back_on_a_nan_argument: overflowing and
+    # subnormal scales)
     nan = dev(np.array([np.nan]))
     o1 = torch.empty_like(nan)
     N.check(N.lib().cst_debug_erf_fast(0, nan.data_ptr(), o1.data_ptr(), 1, None), "cst_debug_erf_fast")
@@ -152,6 +153,54 @@ def test_quick_left_cumulatives_equal_the_exact_ones(B, O):
                                        len(want), None), "lcp")
     torch.cuda.synchronize()
     assert np.array_equal(l.cpu().numpy().view(np.uint32), want.astype(np.uint32))
+
+
+@pytest.mark.parametrize("lo,hi,P", [(-100, 100, 24), (0, 1, 24), (-127, 127, 12)])
+def test_quick_left_cumulatives_fall_back_on_a_nan_argument(B, O, lo, hi, P):
+    """The quick evaluation forms its argument with a reciprocal of sigma sqrt 2.  Where that product overflows (sigma > 1.27e308) or
+    is subnormal, the reciprocal breaks down, the argument is a NaN, and the evaluation must fall to the exact one -- for EVERY inner
+    index, which the fallback counter shows.  Every index of the support x scales at both ends of the f64 range x locations at
+    +-DBL_MAX, far outside the support, inside it, and exactly on the index's own bin edge (x - mu = 0 against the broken reciprocal):
+    quick == exact on the device, and the device's (left, prob) is the oracle's for every case."""
+    from constriction_amd import _native as N
+    lib, ol = N.lib(), O.load()
+    dbl_max = 1.7976931348623157e308
+    n = hi - lo + 1
+    rng = np.random.default_rng(n + P)
+    idx = np.arange(0, n + 1, dtype=np.int32)
+    edge = lo + idx.astype(np.float64) - 0.5                           # the left edge of index i: x - mu == 0 there
+    mus = [np.full(n + 1, dbl_max), np.full(n + 1, -dbl_max), np.full(n + 1, lo - 1e9), np.full(n + 1, hi + 1e9),
+           rng.uniform(lo - 50.0, hi + 50.0, n + 1), rng.uniform(lo, hi, n + 1), edge]
+    all_idx, all_mu = np.tile(idx, len(mus)), np.concatenate(mus)
+    inner = int(((all_idx > 0) & (all_idx < n)).sum())
+    prob_bits = 32 if P > 16 else 16
+    l, p = C.c_uint32(), C.c_uint32()
+    # (sigma, whether sigma sqrt 2 has no usable reciprocal): 1.27e308 sqrt 2 = 1.796e308 is the last product below DBL_MAX, the
+    # smallest normal number times sqrt 2 is normal; the two subnormal scales have an infinite reciprocal
+    for sd, broken in ((5e-324, True), (1e-310, True), (2.2250738585072014e-308, False), (1.27e308, False), (1.28e308, True),
+                       (1.3e308, True), (dbl_max, True)):
+        d_idx, d_mu, d_sd = dev(all_idx), dev(all_mu), dev(np.full(len(all_idx), sd))
+        counts = torch.zeros(2, dtype=torch.int64, device="cuda")
+        N.check(lib.cst_debug_gaussian_left_quick(P, lo, hi, d_idx.data_ptr(), d_mu.data_ptr(), d_sd.data_ptr(), len(all_idx), counts.data_ptr(), None), "quick")
+        torch.cuda.synchronize()
+        c = counts.cpu().numpy()
+        assert c[0] == 0, (sd, int(c[0]))
+        if broken:
+            assert c[1] == inner, (sd, int(c[1]), inner)              # (the ends of the table, 0 and 2^P, are not evaluated)
+        # (left, prob) of every symbol under every location
+        keep = all_idx < n
+        sym = (lo + all_idx[keep]).astype(np.int32)
+        mu = all_mu[keep]
+        dl = torch.empty(len(sym), dtype=torch.int32, device="cuda")
+        dp = torch.empty_like(dl)
+        d_sym, d_mu, d_sd = dev(sym), dev(mu), dev(np.full(len(sym), sd))
+        N.check(lib.cst_debug_gaussian_lcp(P, prob_bits, lo, hi, d_sym.data_ptr(), d_mu.data_ptr(), d_sd.data_ptr(), dl.data_ptr(), dp.data_ptr(),
+                                           len(sym), None), "lcp")
+        torch.cuda.synchronize()
+        gl, gp = dl.cpu().numpy().view(np.uint32), dp.cpu().numpy().view(np.uint32)
+        for i in range(len(sym)):
+            assert ol.cst_oracle_leaky_gaussian_lcp(int(sym[i]), lo, hi, P, prob_bits, float(mu[i]), sd, C.byref(l), C.byref(p)) == 0
+            assert (int(gl[i]), int(gp[i])) == (l.value, p.value), (sd, int(sym[i]), float(mu[i]))
 
 
 @pytest.mark.parametrize("lo,hi,P,prob_bits", [(-100, 100, 24, 32), (-50, 50, 12, 16), (-127, 127, 12, 16), (0, 1, 1, 16),
