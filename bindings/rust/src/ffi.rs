@@ -3772,6 +3772,91 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    /// Random access into a ragged indexed batch: cst_{ans,range}_decode_ragged_select (where queries, pieces,
+    /// d_out_offsets, d_piece_offsets and the per-query statuses are described) for the indexed ragged decoders above.  The arguments are
+    /// the model block of cst_{ans,range}_decode_indexed_ragged_jump (cfg, tables, the words block, d_indices / index_bytes -- the batch's
+    /// FULL index array, laid out exactly as the plain decode call takes it -- d_sym_offsets, n_streams), then the table block and the query
+    /// block of cst_{ans,range}_decode_gaussian_ragged_select with the same conventions: jump_interval 0 and every table pointer NULL is no
+    /// table; both of d_query_first / d_query_count NULL is whole streams; d_status has one entry per QUERY; n_queries == 0 returns CST_OK
+    /// and launches nothing.
+    ///   - A piece reads its indices from the element of its jump point on: element d_sym_offsets[s] + (first / jump_interval + j) *
+    ///     jump_interval for piece j of a query, d_sym_offsets[s] without a table.  The symbols in front of `first` are decoded with their
+    ///     own tables and dropped.  No index byte outside [that first element, d_sym_offsets[s] + first + count) of a piece is read (a uint8
+    ///     piece may start at any byte, an int32 piece at any 4-byte boundary), so ONLY those indices can influence any result or status:
+    ///     everything else in d_indices may hold anything, the indices behind a query's end in the same chunk included.
+    ///   - Statuses, one per QUERY: CST_STREAM_INVALID_DATA (nothing is written) for every query cst_{ans,range}_decode_ragged_select
+    ///     refuse.  An index >= n_tables inside a query's decoded range, the dropped symbols included, is clamped before any table is read
+    ///     and the query reports CST_STREAM_INVALID_DATA; it may leave anything inside its own output slice, nothing outside it; the other
+    ///     queries are unaffected.
+    ///   - d_scratch: cst_persymbol_ragged_select_scratch_bytes(n_pieces_total) bytes.
+    ///   - CST_ERR_INVALID_ARGUMENT, before the device is touched: every refusal of the plain indexed ragged decode (d_symbols_out in the
+    ///     place of d_symbols; d_order does not exist here); with a table, every refusal of the _jump decoders (jump_interval not a
+    ///     multiple of 16 or > 2^31 - 1, a NULL d_chunk_offsets or table array, n_chunks_total > 2^32 - 1); table arrays without an interval;
+    ///     n_pieces_total > 2^32 - 1; exactly one of d_query_first / d_query_count NULL; with n_queries > 0 a NULL d_query_stream,
+    ///     d_piece_offsets, d_out_offsets or d_scratch.
+    /// Four launches: the queries kernel, the per-symbol piece builder, the decoder (a lane per piece), the status kernel.
+    /// cst_last_kernel_name(): {ans,range}_decode_indexed_ragged_kernel<select>.
+    pub fn cst_ans_decode_indexed_ragged_select(
+        cfg: CstCoderConfig,
+        tables: *const c_void,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_indices: *const c_void,
+        index_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_indexed_ragged_select(
+        cfg: CstCoderConfig,
+        tables: *const c_void,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_indices: *const c_void,
+        index_bytes: i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     /// bit-exact f64 special functions on device (test hooks for the model kernels)
     /// out[i] = erf(x[i]) resp. Gaussian cdf, evaluated by the same device code the table kernels use.
     pub fn cst_debug_erf(d_x: *const f64, d_out: *mut f64, n: usize, stream: *mut c_void) -> CstStatus;

@@ -6818,6 +6818,71 @@ impl TableSet {
         }
         Ok(status)
     }
+
+    /// Random access into a ragged indexed batch (`cst_{ans,range}_decode_indexed_ragged_select`): the queries, piece offsets and results
+    /// of [`BatchedAnsCoder::seek_and_decode_ragged`] on the batches of `encode_ragged`.  `jump`: as for `decode_ragged`.  `indices` is the
+    /// batch's FULL array, as the plain decoder takes it: a piece reads its indices from the element of its jump point on (from its
+    /// stream's first element without jump points), decodes the symbols in front of `first` with their own tables and drops them.  Only
+    /// the indices from there to the query's end are read.  One status per QUERY.
+    ///
+    /// # Safety
+    /// As for `decode_ragged`.  Queries, piece offsets and the jump table are checked on the device; `symbols` must hold
+    /// `out_offsets[n_queries]` symbols, `indices` one entry per symbol of the batch.
+    pub unsafe fn seek_and_decode_indexed_ragged(&self, range: bool, words: &DeviceBuffer<u32>, word_offsets: &DeviceBuffer<u64>,
+                                                 n_words: &DeviceBuffer<u32>, indices: &DeviceBuffer<u8>, sym_offsets: &DeviceBuffer<u64>,
+                                                 jump: Option<(usize, &DeviceBuffer<u64>, &DeviceBuffer<u32>, &DeviceBuffer<u64>, &DeviceBuffer<u64>, usize)>,
+                                                 query_stream: &DeviceBuffer<u32>, query_range: Option<(&DeviceBuffer<u64>, &DeviceBuffer<u64>)>,
+                                                 piece_offsets: &DeviceBuffer<u64>, n_pieces_total: usize, symbols: &mut DeviceBuffer<i32>,
+                                                 out_offsets: &DeviceBuffer<u64>, stream: &Stream) -> Result<DeviceBuffer<i32>> {
+        if sym_offsets.is_empty() || word_offsets.len() < sym_offsets.len() - 1 || n_words.len() < sym_offsets.len() - 1 {
+            return Err(Error::InvalidArgument);
+        }
+        let n_queries = query_stream.len();
+        if piece_offsets.len() != n_queries + 1 || out_offsets.len() != n_queries + 1 {
+            return Err(Error::InvalidArgument);
+        }
+        if let Some((first, count)) = query_range {
+            if first.len() != n_queries || count.len() != n_queries {
+                return Err(Error::InvalidArgument);
+            }
+        }
+        let (interval, n_chunks_total) = jump.map_or((0, 0), |j| (j.0, j.5));
+        if let Some((_, chunk_offsets, pos, a, b, _)) = jump {
+            if chunk_offsets.len() != sym_offsets.len() || interval == 0 || interval % 16 != 0 || pos.len() < n_chunks_total
+                || a.len() < n_chunks_total || (range && b.len() < n_chunks_total) {
+                return Err(Error::InvalidArgument);
+            }
+        }
+        let chunk_offsets = jump.map_or(core::ptr::null(), |j| j.1.as_ptr());
+        let pos = jump.map_or(core::ptr::null(), |j| j.2.as_ptr());
+        let a = jump.map_or(core::ptr::null(), |j| j.3.as_ptr());
+        let b = jump.map_or(core::ptr::null(), |j| j.4.as_ptr());
+        let first = query_range.map_or(core::ptr::null(), |r| r.0.as_ptr());
+        let count = query_range.map_or(core::ptr::null(), |r| r.1.as_ptr());
+        let n_streams = sym_offsets.len() - 1;
+        let config = self.config();
+        let mut status: DeviceBuffer<i32> = DeviceBuffer::new(n_queries)?;
+        let mut scratch: DeviceBuffer<u8> = DeviceBuffer::new(unsafe { ffi::cst_persymbol_ragged_select_scratch_bytes(n_pieces_total) })?;
+        check(unsafe {
+            if range {
+                ffi::cst_range_decode_indexed_ragged_select(config, self.raw, words.as_ptr(), word_offsets.as_ptr(), 0, words.len(),
+                                                            n_words.as_ptr(), indices.as_ptr() as *const c_void, 1, sym_offsets.as_ptr(),
+                                                            n_streams, interval, chunk_offsets, n_chunks_total, pos, a, b,
+                                                            query_stream.as_ptr(), first, count, n_queries, piece_offsets.as_ptr(),
+                                                            n_pieces_total, symbols.as_mut_ptr(), out_offsets.as_ptr(),
+                                                            scratch.as_mut_ptr() as *mut c_void, status.as_mut_ptr(), stream.as_raw())
+            } else {
+                ffi::cst_ans_decode_indexed_ragged_select(config, self.raw, words.as_ptr(), word_offsets.as_ptr(), 0, words.len(),
+                                                          n_words.as_ptr(), indices.as_ptr() as *const c_void, 1, sym_offsets.as_ptr(),
+                                                          n_streams, interval, chunk_offsets, n_chunks_total, pos, a,
+                                                          query_stream.as_ptr(), first, count, n_queries, piece_offsets.as_ptr(),
+                                                          n_pieces_total, symbols.as_mut_ptr(), out_offsets.as_ptr(),
+                                                          scratch.as_mut_ptr() as *mut c_void, status.as_mut_ptr(), stream.as_raw())
+            }
+        })?;
+        stream.synchronize()?; // (the scratch buffer is dropped on return)
+        Ok(status)
+    }
 }
 
 impl Drop for TableSet {

@@ -286,7 +286,11 @@ SIGNATURES = {
                                                   _vp]),
     "cst_range_decode_indexed_ragged_jump": (_i32, [CoderConfig, _vp, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _vp, _z, _z, _vp, _z, _vp, _vp, _vp, _vp,
                                                     _vp, _vp]),
-    "cst_debug_erf": (_i32, [_vp, _vp, _z, _vp]),
+    "cst_ans_decode_indexed_ragged_select": (_i32, [CoderConfig, _vp, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _z, _vp, _z, _vp, _vp,
+                                                    _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_range_decode_indexed_ragged_select": (_i32, [CoderConfig, _vp, _vp, _vp, _z, _z, _vp, _vp, _i32, _vp, _z, _z, _vp, _z, _vp, _vp, _vp,
+                                                      _vp, _vp, _vp, _z, _vp, _z, _vp, _vp, _vp, _vp, _vp]),
+    "cst_debug_erf":(_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_tab": (_i32, [_vp, _vp, _z, _vp]),
     "cst_debug_erf_fast": (_i32, [_i32, _vp, _vp, _z, _vp]),
     "cst_debug_gaussian_left_quick": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _z, _vp, _vp]),

@@ -2687,3 +2687,44 @@ def ans_decode_indexed_ragged(encoded: RaggedBatch, indices, sym_offsets, tables
 def range_decode_indexed_ragged(encoded: RaggedBatch, indices, sym_offsets, tables: TableSet, out: Optional[torch.Tensor] = None, order="auto"):
     """RangeDecoder(words of stream s).decode_symbols(tables[indices[lo:hi]]) for every stream: ans_decode_indexed_ragged for the queue."""
     return _decode_indexed_ragged("cst_range_decode_indexed_ragged", "range", encoded, indices, sym_offsets, tables, out, order)
+
+
+# ... and random access into them: selected streams, or ranges of streams (DESIGN.md 4.31)
+
+def _decode_indexed_ragged_select(fn_name, coder, encoded, indices, sym_offsets, tables, streams, first, count, out):
+    """the body of {ans,range}_decode_indexed_ragged_select: the queries of _select_queries on the arguments of _decode_indexed_ragged"""
+    if not isinstance(tables, TableSet):
+        raise ValueError("tables must be a batched.TableSet")
+    if not isinstance(encoded, RaggedBatch):
+        raise ValueError("encoded must be a RaggedBatch")
+    jump = _ragged_jump_of(encoded, coder)
+    if tuple(encoded.config) != (32, 64, tables.precision):
+        raise ValueError("the batch was not coded with (32, 64, precision of the table set)")
+    indices, index_bytes = _indexed_ragged_args(None, None, indices, tables, encoded.config)
+    if indices.device != encoded.words.device:
+        raise ValueError("indices must live on the device of the words")
+    sym_offsets, _ = _indexed_ragged_offsets(sym_offsets, indices.device)
+    r = _select_queries(encoded, jump, sym_offsets, streams, first, count, out)
+    return _persymbol_select_call(fn_name, coder, encoded, jump, r, (tables._h,), (_ptr(_never_null(indices)), index_bytes))
+
+
+def ans_decode_indexed_ragged_select(encoded: RaggedBatch, indices, sym_offsets, tables: TableSet, streams, first=None, count=None,
+                                     out: Optional[torch.Tensor] = None):
+    """Random access into a batch of ans_encode_indexed_ragged: query q decodes symbols [first[q], first[q] + count[q]) of stream
+    streams[q], and nothing else is decoded.  `indices`: the batch's FULL flat array, exactly as ans_decode_indexed_ragged takes it;
+    `streams`, `first`, `count` and the three results (symbols flat int32, out_offsets int64 [n_queries + 1], status int32 [n_queries])
+    as in ans_decode_ragged_select.  With jump points (`jump_every` of the encoder) a query starts at the jump point in front of
+    `first`, decodes and discards first % interval symbols with THEIR tables, and every chunk it touches runs on a lane of its own;
+    without them it starts where its stream starts.  Only the indices from that starting point to the query's end are read: the rest of
+    `indices` may hold anything.  A query that meets an index >= n_tables, in its discarded part too, reports INVALID_DATA (3) and may
+    leave anything in its own slice; a refused one reports INVALID_DATA and writes nothing."""
+    return _decode_indexed_ragged_select("cst_ans_decode_indexed_ragged_select", "ans", encoded, indices, sym_offsets, tables, streams, first, count,
+                                         out)
+
+
+def range_decode_indexed_ragged_select(encoded: RaggedBatch, indices, sym_offsets, tables: TableSet, streams, first=None, count=None,
+                                       out: Optional[torch.Tensor] = None):
+    """ans_decode_indexed_ragged_select for a batch of range_encode_indexed_ragged: a piece seeks to its (pos, lower, range) entry and
+    reads forward."""
+    return _decode_indexed_ragged_select("cst_range_decode_indexed_ragged_select", "range", encoded, indices, sym_offsets, tables, streams, first,
+                                         count, out)

@@ -14,9 +14,10 @@
 //             encode_entries_ragged_kernel does (cst_persymbol_categorical_ragged.hip)
 //   decode    DirectDecoder with the 16-slot word window and the 16-symbol output tile of decode_gaussian_ragged_kernel, the model
 //             search replaced by indexed_lookup.  MODE kRgPlain: a lane per stream; kRgJump: a lane per table entry, between the two
-//             kernels of decode_jump_chunks
+//             kernels of decode_jump_chunks; kRgSelect: a lane per PIECE of a query, between the queries and status
+//             kernels of cst_ragged_select.hpp and the per-symbol piece builder
 #include "cst_indexed.hpp"
-#include "cst_persymbol_ragged.hpp"
+#include "cst_persymbol_ragged_select.hpp"
 
 namespace cst {
 
@@ -281,13 +282,24 @@ struct IndexedRaggedDecodeArgs {
     const void* indices;
 };
 
+// SELECT form: every "stream" of p is a PIECE of a query (PerSymbolSelectPieces).  sym_lo is then the element of the
+// piece's first INDEX -- its jump point's, or its stream's start without a table -- and the row is skip + len long: the dropped symbols
+// run through the fetch, the window and the tile as the stored ones do, and symbol t >= skip goes to p.symbols[out_lo + (t - skip)].
+// `raw`: the pieces start from the raw state of a jump point (p.state / p.rstate per piece), else from all of their stream's words.
+struct IndexedRaggedSelectArgs : IndexedRaggedDecodeArgs {
+    const uint64_t* out_lo;          // [n pieces]: first symbol stored, in p.symbols
+    const uint32_t* skip;            // [n pieces]: symbols decoded and dropped (skip + len <= 2^32 - 1)
+    bool raw;
+};
+template <int MODE> using IndexedRaggedDecodeArgsOf = std::conditional_t<MODE == kRgSelect, IndexedRaggedSelectArgs, IndexedRaggedDecodeArgs>;
+
 // LDS: [rows and buckets of the image][per wave: the 16-symbol output tile, the word window]
 // decode_gaussian_ragged_kernel's loop: tiles of kIrGroup symbols, the words of the tile after next requested while this one is decoded,
 // the indices of the next tile likewise (per lane: eight clamped indices packed into two registers, picked by a shift).
 template <int KIND, class IDX, bool WIDE, int MODE>
-__global__ __launch_bounds__(kBlock) void indexed_ragged_decode_kernel(const IndexedRaggedDecodeArgs ra) {
+__global__ __launch_bounds__(kBlock) void indexed_ragged_decode_kernel(const IndexedRaggedDecodeArgsOf<MODE> ra) {
     static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
-    static_assert(MODE == kRgPlain || MODE == kRgJump, "whole streams, or the entries of a jump table");
+    static_assert(MODE == kRgPlain || MODE == kRgJump || MODE == kRgSelect, "whole streams, the entries of a jump table, or pieces of queries");
     static_assert(2 * kIrGroup == kIrWindow && kIrGroup == 8, "the window holds this tile's words and the next one's");
     const PerSymbolDecodeArgs& a = ra.p;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -304,7 +316,7 @@ __global__ __launch_bounds__(kBlock) void indexed_ragged_decode_kernel(const Ind
     if (slot - lane >= a.n_streams) return;                     // whole wave idle (after the only barrier)
     bool active;
     size_t s;
-    if constexpr (MODE == kRgJump) { active = slot < a.n_streams; s = slot; }
+    if constexpr (MODE != kRgPlain) { active = slot < a.n_streams; s = slot; }
     else s = persymbol_ragged_stream(ra.order, slot, a.n_streams, active);
     const size_t se = active ? s : 0;                           // idle lanes look at stream 0's words and decode nothing
     uint64_t sym_lo = 0, sym_hi = 0;
@@ -315,11 +327,19 @@ __global__ __launch_bounds__(kBlock) void indexed_ragged_decode_kernel(const Ind
             const bool keep = owner != kPjNoOwner && ra.stream_status[owner] == CST_STREAM_OK;
             sym_lo = ra.sym_lo[s]; sym_hi = sym_lo + (keep ? (uint64_t)ra.len[s] : 0);
         }
+        // (a piece that belongs to no accepted query is empty: the builder gave it no symbols and no words)
+        else if constexpr (MODE == kRgSelect) { sym_lo = ra.sym_lo[s]; sym_hi = sym_lo + (uint64_t)ra.skip[s] + (uint64_t)ra.len[s]; }
         else { sym_lo = ra.sym_offsets[s]; sym_hi = ra.sym_offsets[s + 1]; }
     }
     const bool too_long = sym_hi - sym_lo > 0xffffffffull || sym_hi < sym_lo;      // (never a chunk: at most jump_interval symbols)
     const uint32_t len = too_long ? 0u : (uint32_t)(sym_hi - sym_lo);
     const uint32_t off_lo = (uint32_t)sym_lo, off_hi = (uint32_t)(sym_lo >> 32);
+    // SELECT: where the lane's symbols go, and how many of the decoded ones stay out (`len` is skip + len of the piece)
+    uint32_t out_lo = 0, out_hi = 0, skip = 0;
+    if constexpr (MODE == kRgSelect) {
+        const uint64_t o = active ? ra.out_lo[s] : 0;
+        out_lo = (uint32_t)o; out_hi = (uint32_t)(o >> 32); skip = active ? ra.skip[s] : 0u;
+    }
     const uint32_t mx = persymbol_wave_max(len);
     const int P = a.precision;
     const uint32_t K = (uint32_t)ra.n_tables, pitch = (uint32_t)ra.pitch, pmask = (1u << P) - 1u;
@@ -330,7 +350,8 @@ __global__ __launch_bounds__(kBlock) void indexed_ragged_decode_kernel(const Ind
     const IDX* irow = indices + (len ? sym_lo : 0);
 
     DirectDecoder<32, 64, KIND> D;
-    D.init(a, se, MODE == kRgJump);                             // (JUMP: AnsCoder::seek / RangeDecoder::seek have been done for it)
+    if constexpr (MODE == kRgSelect) D.init(a, se, ra.raw);     // (a call with a table: the piece builder has done the seek)
+    else D.init(a, se, MODE == kRgJump);                        // (JUMP: AnsCoder::seek / RangeDecoder::seek have been done for it)
 
     // ---- word window: as in decode_gaussian_ragged_kernel (a tile of 8 symbols takes at most 8 words; the range coder's first two words
     // are taken by init, before the window starts).  ANS reads downwards from its position: every index from 0 up to it exists.  The
@@ -429,7 +450,8 @@ __global__ __launch_bounds__(kBlock) void indexed_ragged_decode_kernel(const Ind
             tile[lane * kIrOutStride + (int)(t % kIrOutSyms)] = sym;
             if (t % kIrOutSyms == kIrOutSyms - 1) {
                 wave_lds_fence();
-                store_symbol_tile_ragged(a.symbols, off_lo, off_hi, len, (uint64_t)t - (kIrOutSyms - 1), lane, tile);
+                if constexpr (MODE == kRgSelect) store_symbol_tile_select(a.symbols, out_lo, out_hi, skip, len, (uint64_t)t - (kIrOutSyms - 1), lane, tile);
+                else store_symbol_tile_ragged(a.symbols, off_lo, off_hi, len, (uint64_t)t - (kIrOutSyms - 1), lane, tile);
                 wave_lds_fence();
             }
         }
@@ -437,7 +459,8 @@ __global__ __launch_bounds__(kBlock) void indexed_ragged_decode_kernel(const Ind
     }
     if (mx % kIrOutSyms != 0) {
         wave_lds_fence();
-        store_symbol_tile_ragged(a.symbols, off_lo, off_hi, len, (uint64_t)(mx - mx % kIrOutSyms), lane, tile);
+        if constexpr (MODE == kRgSelect) store_symbol_tile_select(a.symbols, out_lo, out_hi, skip, len, (uint64_t)(mx - mx % kIrOutSyms), lane, tile);
+        else store_symbol_tile_ragged(a.symbols, off_lo, off_hi, len, (uint64_t)(mx - mx % kIrOutSyms), lane, tile);
     }
     if (!active) return;
     a.status[s] = too_long ? (int32_t)CST_STREAM_CAPACITY : (bad_index ? (int32_t)CST_STREAM_INVALID_DATA : D.status);
@@ -522,7 +545,7 @@ static cst_status encode_indexed_ragged(cst_coder_config cfg, const cst_table_se
 }
 
 template <int KIND, int MODE>
-static cst_status launch_decode_indexed_ragged(const cst_table_set* tables, IndexedRaggedDecodeArgs a, int32_t index_bytes, hipStream_t hs) {
+static cst_status launch_decode_indexed_ragged(const cst_table_set* tables, IndexedRaggedDecodeArgsOf<MODE> a, int32_t index_bytes, hipStream_t hs) {
     if (cst_status st = check_indexed_ragged_device(tables, a.p.n_streams)) return st;
     a.p.min_symbol = tables->min_symbol; a.p.n_symbols = tables->n_symbols; a.p.precision = tables->precision;
     a.image = tables->d_image; a.rows_bytes = tables->rows_bytes; a.image_bytes = tables->image_bytes;
@@ -575,6 +598,59 @@ static cst_status decode_indexed_ragged_jump(cst_coder_config cfg, const cst_tab
         const cst_status rc = launch_decode_indexed_ragged<KIND, kRgJump>(tables, a, index_bytes, hs);
         return rc == CST_OK ? rc : note_kernel(name, rc);
     });
+}
+
+// random access: decode_ragged_select of cst_persymbol_ragged_select.hip with the indexed decoder between the queries
+// kernel, the per-symbol piece builder and the status kernel.  No precheck: a query whose stream the table does not describe is
+// refused by the queries kernel, gets no piece and writes nothing.
+static constexpr const char* kIrSelectNames[2] = {"ans_decode_indexed_ragged_kernel<select>", "range_decode_indexed_ragged_kernel<select>"};
+
+template <int KIND>
+static cst_status decode_indexed_ragged_select(cst_coder_config cfg, const cst_table_set* tables, const uint32_t* d_words,
+                                               const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                               const void* d_indices, int32_t index_bytes, const uint64_t* d_sym_offsets, size_t n_streams,
+                                               size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint32_t* d_jump_pos,
+                                               const uint64_t* d_jump_a, const uint64_t* d_jump_b, const uint32_t* d_query_stream,
+                                               const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                               const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                               const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, hipStream_t hs) {
+    // a table is an interval and ALL its arrays (jump_table_bad: the jump decoders' rule, whole tiles of 16 included), or nothing at all
+    const bool table = jump_interval != 0 || d_chunk_offsets || d_jump_pos || d_jump_a || d_jump_b;
+    if (table && (jump_table_bad<KIND>(jump_interval, d_chunk_offsets, d_jump_pos, d_jump_a, d_jump_b) || n_chunks_total > 0xffffffffull))
+        return CST_ERR_INVALID_ARGUMENT;
+    if (n_pieces_total > 0xffffffffull || (d_query_first == nullptr) != (d_query_count == nullptr)) return CST_ERR_INVALID_ARGUMENT;
+    if (cst_status st = check_indexed_ragged_args(tables, cfg, d_symbols_out, d_indices, index_bytes, d_sym_offsets, d_words, d_word_offsets,
+                                                  stride_words, d_n_words, d_status, n_streams)) return st;
+    if (n_queries > 0 && (!d_query_stream || !d_piece_offsets || !d_out_offsets || !d_scratch)) return CST_ERR_INVALID_ARGUMENT;
+    if (n_queries == 0) return CST_OK;
+    if (n_queries > ((size_t)0x7fffffff) * 256) return CST_ERR_INVALID_ARGUMENT;
+    if (cst_status st = check_indexed_ragged_device(tables, n_pieces_total)) return st;
+    RaggedSelect b{};
+    b.sym_offsets = d_sym_offsets; b.word_offsets = d_word_offsets; b.stride_words = stride_words; b.n_words = d_n_words; b.n_streams = n_streams;
+    // (slab form without a capacity: the slabs themselves bound every slice, as in the jump decoders)
+    b.words_capacity = words_capacity ? words_capacity : (d_word_offsets ? 0 : (uint64_t)n_streams * stride_words);
+    b.interval = (uint32_t)jump_interval; b.chunk_offsets = d_chunk_offsets; b.n_chunks_total = n_chunks_total; b.jump_pos = d_jump_pos;
+    b.query_stream = d_query_stream; b.query_first = d_query_first; b.query_count = d_query_count; b.n_queries = n_queries;
+    b.piece_offsets = d_piece_offsets; b.n_pieces_total = n_pieces_total; b.out_offsets = d_out_offsets;
+    const PerSymbolSelectPieces v(d_scratch, n_pieces_total);
+    const unsigned q_grid = (unsigned)((n_queries + 255) / 256);
+    hipLaunchKernelGGL(ragged_select_queries_kernel<0>, dim3(q_grid), dim3(256), 0, hs, b, d_status);
+    CST_HIP_TRY(hipGetLastError());
+    if (n_pieces_total > 0) {
+        const unsigned p_grid = (unsigned)((n_pieces_total + 255) / 256);
+        hipLaunchKernelGGL((persymbol_select_pieces_kernel<32, 64, KIND>), dim3(p_grid), dim3(256), 0, hs, b, d_words, d_jump_a, d_jump_b, d_status, v);
+        CST_HIP_TRY(hipGetLastError());
+        // (the slices handed on are absolute offsets that passed the check, or empty: the capacity bounds them once more)
+        IndexedRaggedSelectArgs a{};
+        a.p.words = d_words; a.p.offsets = v.word_off; a.p.stride_words = 0; a.p.n_words = v.n_words; a.p.words_capacity = b.words_capacity;
+        a.p.symbols = d_symbols_out; a.p.n_streams = n_pieces_total; a.p.status = v.status; a.p.state = v.state; a.p.rstate = v.rstate;
+        a.sym_lo = v.par_lo; a.len = v.len; a.out_lo = v.out_lo; a.skip = v.skip; a.raw = jump_interval != 0; a.indices = d_indices;
+        const cst_status rc = launch_decode_indexed_ragged<KIND, kRgSelect>(tables, a, index_bytes, hs);
+        if (rc != CST_OK) return note_kernel(kIrSelectNames[KIND == kRange], rc);
+    }
+    hipLaunchKernelGGL(ragged_select_status_kernel<0>, dim3(q_grid), dim3(256), 0, hs, b, v.folded(), d_status);
+    CST_HIP_TRY(hipGetLastError());
+    return note_kernel(kIrSelectNames[KIND == kRange], CST_OK);
 }
 
 } // namespace cst
@@ -652,6 +728,35 @@ cst_status cst_range_decode_indexed_ragged_jump(cst_coder_config cfg, const void
     return decode_indexed_ragged_jump<kRange>(cfg, as_table_set(tables), d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_indices,
                                               index_bytes, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos,
                                               d_jump_lower, d_jump_range, d_scratch, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_indexed_ragged_select(cst_coder_config cfg, const void* tables, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const void* d_indices,
+                                                int32_t index_bytes, const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint32_t* d_jump_pos,
+                                                const uint64_t* d_jump_state, const uint32_t* d_query_stream, const uint64_t* d_query_first,
+                                                const uint64_t* d_query_count, size_t n_queries, const uint64_t* d_piece_offsets,
+                                                size_t n_pieces_total, int32_t* d_symbols_out, const uint64_t* d_out_offsets, void* d_scratch,
+                                                int32_t* d_status, void* stream) {
+    return decode_indexed_ragged_select<kAns>(cfg, as_table_set(tables), d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_indices,
+                                              index_bytes, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos,
+                                              d_jump_state, nullptr, d_query_stream, d_query_first, d_query_count, n_queries, d_piece_offsets,
+                                              n_pieces_total, d_symbols_out, d_out_offsets, d_scratch, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_indexed_ragged_select(cst_coder_config cfg, const void* tables, const uint32_t* d_words, const uint64_t* d_word_offsets,
+                                                  size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const void* d_indices,
+                                                  int32_t index_bytes, const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                  const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint32_t* d_jump_pos,
+                                                  const uint64_t* d_jump_lower, const uint64_t* d_jump_range, const uint32_t* d_query_stream,
+                                                  const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                                  const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                                  const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    return decode_indexed_ragged_select<kRange>(cfg, as_table_set(tables), d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                                                d_indices, index_bytes, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+                                                d_jump_pos, d_jump_lower, d_jump_range, d_query_stream, d_query_first, d_query_count, n_queries,
+                                                d_piece_offsets, n_pieces_total, d_symbols_out, d_out_offsets, d_scratch, d_status,
+                                                (hipStream_t)stream);
 }
 
 } // extern "C"

@@ -1,6 +1,7 @@
 // cst_persymbol_ragged_select.hpp -- what the SELECT forms of the per-symbol ragged decoders share: the record of a
-// piece and the kernel that builds it, for cst_persymbol_ragged_select.hip (Gaussian, Laplace, Cauchy) and
-// cst_persymbol_categorical_ragged.hip (Categorical, both quantisers).  A piece of a per-symbol batch needs what a piece of a
+// piece and the kernel that builds it, for cst_persymbol_ragged_select.hip (Gaussian, Laplace, Cauchy),
+// cst_persymbol_categorical_ragged.hip (Categorical, both quantisers) and cst_indexed_ragged.hip (indexed tables, DESIGN.md 4.31: the
+// "parameters" are the indices).  A piece of a per-symbol batch needs what a piece of a
 // shared-table batch does not: the element its PARAMETERS (or probability rows) start at -- the jump point's, not the first stored
 // symbol's -- and the coder's raw state there, prepared as persymbol_jump_chunks_kernel prepares a chunk's.  Templates: each unit's
 // code object carries its own copy (no relocatable device code).

@@ -10,8 +10,8 @@
 //                                     table entry, skip, length, output position and its stream's checked slice of the words -> scratch;
 //   3. ragged_select_status_kernel    one thread per query: the worst of its pieces' statuses.
 // The kernels are templates so that each translation unit that launches them carries its own copy (no relocatable device code):
-// cst_ans_ragged.hip, cst_range_ragged.hip, cst_persymbol_ragged_select.hip and cst_persymbol_categorical_ragged.hip, whose pieces
-// carry more (their own piece builder, cst_persymbol_ragged_select.hpp), and cst_huffman_ragged.hip and cst_exp_golomb.hip, whose
+// cst_ans_ragged.hip, cst_range_ragged.hip, cst_persymbol_ragged_select.hip, cst_persymbol_categorical_ragged.hip and
+// cst_indexed_ragged.hip, whose pieces carry more (their own piece builder, cst_persymbol_ragged_select.hpp), and cst_huffman_ragged.hip and cst_exp_golomb.hip, whose
 // tables hold bit indices (their own queries kernel, cst_symbol_select.hpp).
 #pragma once
 #include "cst_common.hpp"

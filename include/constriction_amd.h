@@ -1861,6 +1861,50 @@ cst_status cst_range_decode_indexed_ragged_jump(cst_coder_config cfg, const void
                                                 const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
                                                 const uint64_t *d_jump_range, void *d_scratch, int32_t *d_status, void *stream);
 
+/* Random access into a ragged indexed batch: cst_{ans,range}_decode_ragged_select (where queries, pieces,
+ * d_out_offsets, d_piece_offsets and the per-query statuses are described) for the indexed ragged decoders above.  The arguments are
+ * the model block of cst_{ans,range}_decode_indexed_ragged_jump (cfg, tables, the words block, d_indices / index_bytes -- the batch's
+ * FULL index array, laid out exactly as the plain decode call takes it -- d_sym_offsets, n_streams), then the table block and the query
+ * block of cst_{ans,range}_decode_gaussian_ragged_select with the same conventions: jump_interval 0 and every table pointer NULL is no
+ * table; both of d_query_first / d_query_count NULL is whole streams; d_status has one entry per QUERY; n_queries == 0 returns CST_OK
+ * and launches nothing.
+ *   - A piece reads its indices from the element of its jump point on: element d_sym_offsets[s] + (first / jump_interval + j) *
+ *     jump_interval for piece j of a query, d_sym_offsets[s] without a table.  The symbols in front of `first` are decoded with their
+ *     own tables and dropped.  No index byte outside [that first element, d_sym_offsets[s] + first + count) of a piece is read (a uint8
+ *     piece may start at any byte, an int32 piece at any 4-byte boundary), so ONLY those indices can influence any result or status:
+ *     everything else in d_indices may hold anything, the indices behind a query's end in the same chunk included.
+ *   - Statuses, one per QUERY: CST_STREAM_INVALID_DATA (nothing is written) for every query cst_{ans,range}_decode_ragged_select
+ *     refuse.  An index >= n_tables inside a query's decoded range, the dropped symbols included, is clamped before any table is read
+ *     and the query reports CST_STREAM_INVALID_DATA; it may leave anything inside its own output slice, nothing outside it; the other
+ *     queries are unaffected.
+ *   - d_scratch: cst_persymbol_ragged_select_scratch_bytes(n_pieces_total) bytes.
+ *   - CST_ERR_INVALID_ARGUMENT, before the device is touched: every refusal of the plain indexed ragged decode (d_symbols_out in the
+ *     place of d_symbols; d_order does not exist here); with a table, every refusal of the _jump decoders (jump_interval not a
+ *     multiple of 16 or > 2^31 - 1, a NULL d_chunk_offsets or table array, n_chunks_total > 2^32 - 1); table arrays without an interval;
+ *     n_pieces_total > 2^32 - 1; exactly one of d_query_first / d_query_count NULL; with n_queries > 0 a NULL d_query_stream,
+ *     d_piece_offsets, d_out_offsets or d_scratch.
+ * Four launches: the queries kernel, the per-symbol piece builder, the decoder (a lane per piece), the status kernel.
+ * cst_last_kernel_name(): {ans,range}_decode_indexed_ragged_kernel<select>. */
+cst_status cst_ans_decode_indexed_ragged_select(cst_coder_config cfg, const void *tables, const uint32_t *d_words,
+                                                const uint64_t *d_word_offsets, size_t stride_words, size_t words_capacity,
+                                                const uint32_t *d_n_words, const void *d_indices, int32_t index_bytes,
+                                                const uint64_t *d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                const uint64_t *d_chunk_offsets, size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                                const uint64_t *d_jump_state, const uint32_t *d_query_stream,
+                                                const uint64_t *d_query_first, const uint64_t *d_query_count, size_t n_queries,
+                                                const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
+                                                const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status, void *stream);
+cst_status cst_range_decode_indexed_ragged_select(cst_coder_config cfg, const void *tables, const uint32_t *d_words,
+                                                  const uint64_t *d_word_offsets, size_t stride_words, size_t words_capacity,
+                                                  const uint32_t *d_n_words, const void *d_indices, int32_t index_bytes,
+                                                  const uint64_t *d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                  const uint64_t *d_chunk_offsets, size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                                  const uint64_t *d_jump_lower, const uint64_t *d_jump_range,
+                                                  const uint32_t *d_query_stream, const uint64_t *d_query_first,
+                                                  const uint64_t *d_query_count, size_t n_queries,
+                                                  const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
+                                                  const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * bit-exact f64 special functions on device (test hooks for the model kernels)
  * out[i] = erf(x[i]) resp. Gaussian cdf, evaluated by the same device code the table kernels use.

@@ -10,8 +10,16 @@ int32 indices; lanes scheduled longest stream first (batched.ragged_order) for e
 The entry points are called directly on buffers made once (the Python calls size their slabs with a read-back).  Times are medians of
 single launches between HIP events after a warm-up (bench.event_ms), the rounds of the candidates interleaved; `auto_rule` says whether
 encode + decode with jump points was below plain in EVERY round.
-usage: bench_indexed_ragged.py [--coder ans|range|both] [--jump-every I] [--streams N] [--rounds R] [--out profiles/indexed_ragged.json]"""
+--select N (default 0: not run): also (s) random access through batched.{coder}_decode_indexed_ragged_select on the
+batch of (a) with --jump-every's table, in the same run, alternating single calls: N whole streams drawn at random through the select call
+beside the route without it -- the full decode through the jump table (and by whole streams) plus a device gather of the same symbols;
+N ranges of 64 symbols at random depths with the table and without it; and ALL streams in order through the select call beside the jump
+decode of the same batch (what the SELECT form itself costs, call against call).  `*_prepared`: the entry point alone on queries
+prepared once (no sizing read-back).  --only-select leaves (a) .. (c) out.
+usage: bench_indexed_ragged.py [--coder ans|range|both] [--jump-every I] [--streams N] [--rounds R] [--select N [--only-select]]
+                               [--out profiles/indexed_ragged.json]"""
 import argparse
+import dataclasses
 import json
 import sys
 from pathlib import Path
@@ -89,6 +97,93 @@ def native_calls(coder, enc, model_enc, head, model_dec, off, order, out, every)
     return encode, decode
 
 
+def timed(fn):
+    """one run of fn() between two device events on the current stream: ms"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def alternate(candidates, n):
+    """every candidate once for warm-up, then n rounds of all of them in turn, one call each: {name: [ms per round]}"""
+    for fn in candidates.values():
+        fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in candidates}
+    for _ in range(n):
+        for k, fn in candidates.items():
+            times[k].append(timed(fn))
+    return times
+
+
+def select_section(coder, tables, sym, idx, off, lengths, order, every, n_sel, rounds):
+    """(s) of the module text for one coder and one index type: checked against the input, then timed"""
+    n = off.numel() - 1
+    dec_ix, sel = getattr(B, f"{coder}_decode_indexed_ragged"), getattr(B, f"{coder}_decode_indexed_ragged_select")
+    enc_t = getattr(B, f"{coder}_encode_indexed_ragged")(sym, idx, off, tables, CFG, order=order, jump_every=every)
+    enc_0 = dataclasses.replace(enc_t, jump=None)
+    assert int(enc_t.status.abs().sum().item()) == 0
+    g = torch.Generator(device="cuda").manual_seed(7)
+    q_streams = torch.randint(0, n, (n_sel,), generator=g, dtype=torch.int64, device="cuda")
+    q_len = lengths[q_streams]
+    q_count = torch.clamp(q_len, max=64)
+    q_first = (torch.rand(n_sel, generator=g, dtype=torch.float64, device="cuda") * (q_len - q_count + 1).to(torch.float64)).to(torch.int64)
+    q_first = torch.minimum(q_first, q_len - q_count)
+
+    def gather_index(first, count):
+        """the elements of `sym` that the queries (q_streams, first, count) ask for, in their order"""
+        ends = torch.cumsum(count, 0)
+        starts = ends - count
+        k = torch.arange(int(ends[-1]), dtype=torch.int64, device="cuda")
+        q = torch.searchsorted(ends, k, right=True)
+        return off[q_streams[q]] + first[q] + (k - starts[q])
+
+    idx_whole, idx_range = gather_index(torch.zeros_like(q_len), q_len), gather_index(q_first, q_count)
+    every_stream = torch.arange(n, dtype=torch.int64, device="cuda")
+    dec, out_all = torch.empty_like(sym), torch.empty_like(sym)
+    checks = [(sel(enc_t, idx, off, tables, q_streams), sym[idx_whole]), (sel(enc_t, idx, off, tables, q_streams, q_first, q_count), sym[idx_range]),
+              (sel(enc_0, idx, off, tables, q_streams, q_first, q_count), sym[idx_range]), (sel(enc_t, idx, off, tables, every_stream, out=out_all), sym)]
+    torch.cuda.synchronize()
+    kernel = B.last_kernel()
+    ok = kernel == f"{coder}_decode_indexed_ragged_kernel<select>" and \
+        all(bool(torch.equal(got, want)) and int(status.abs().sum()) == 0 for (got, _, status), want in checks)
+    del checks
+    # the entry point alone: the queries prepared once, as _decode_indexed_ragged_select prepares them
+    name = f"cst_{coder}_decode_indexed_ragged_select"
+    model = (B._ptr(idx), idx.element_size())
+    prepared = {}
+    for tag, e, (first, count), out in (("whole", enc_t, (None, None), None), ("ranges", enc_t, (q_first, q_count), None),
+                                        ("ranges_no_table", enc_0, (q_first, q_count), None), ("all", enc_t, (None, None), out_all)):
+        r = B._select_queries(e, e.jump, off, every_stream if tag == "all" else q_streams, first, count, out)
+        prepared[tag] = (e, r)
+    pieces = {tag: int(r.piece_offsets[-1].item()) for tag, (_, r) in prepared.items()}
+    call = lambda tag: B._persymbol_select_call(name, coder, prepared[tag][0], prepared[tag][0].jump, prepared[tag][1], (tables._h,), model)
+    candidates = {"select_whole": lambda: sel(enc_t, idx, off, tables, q_streams),
+                  "full_jump_gather": lambda: dec_ix(enc_t, idx, off, tables, out=dec)[0][idx_whole],
+                  "full_plain_gather": lambda: dec_ix(enc_0, idx, off, tables, out=dec, order=order)[0][idx_whole],
+                  "select_ranges": lambda: sel(enc_t, idx, off, tables, q_streams, q_first, q_count),
+                  "select_ranges_no_table": lambda: sel(enc_0, idx, off, tables, q_streams, q_first, q_count),
+                  "select_all": lambda: sel(enc_t, idx, off, tables, every_stream, out=out_all),
+                  "full_jump": lambda: dec_ix(enc_t, idx, off, tables, out=dec),
+                  "select_whole_prepared": lambda: call("whole"), "select_ranges_prepared": lambda: call("ranges"),
+                  "select_ranges_no_table_prepared": lambda: call("ranges_no_table"), "select_all_prepared": lambda: call("all")}
+    times = alternate(candidates, rounds)
+    med = summary(times)
+    m = lambda k: med[k]["median_ms"]
+    return {"ok": ok, "kernel": kernel, "queries": n_sel, "whole_symbols": int(idx_whole.numel()), "range_symbols": int(idx_range.numel()),
+            "table_every": every, "launches": 4, "pieces": pieces, "times": med, "per_round_ms": {k: [round(x, 4) for x in v] for k, v in times.items()},
+            "ratios": {"select_whole_over_full_jump_gather": round(m("select_whole") / m("full_jump_gather"), 3),
+                       "select_whole_prepared_over_full_jump_gather": round(m("select_whole_prepared") / m("full_jump_gather"), 3),
+                       "select_ranges_over_full_jump_gather": round(m("select_ranges") / m("full_jump_gather"), 3),
+                       "select_ranges_over_no_table": round(m("select_ranges") / m("select_ranges_no_table"), 3),
+                       "select_ranges_prepared_over_no_table_prepared": round(m("select_ranges_prepared") / m("select_ranges_no_table_prepared"), 3),
+                       "select_all_over_full_jump": round(m("select_all") / m("full_jump"), 3),
+                       "select_all_prepared_over_full_jump": round(m("select_all_prepared") / m("full_jump"), 3)}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--coder", default="both", choices=["ans", "range", "both"])
@@ -97,6 +192,8 @@ def main():
     ap.add_argument("--min-len", type=int, default=256)
     ap.add_argument("--max-len", type=int, default=8192)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--select", type=int, default=0, help="also time random access: N whole streams, and N ranges of 64 symbols")
+    ap.add_argument("--only-select", action="store_true", help="with --select: leave (a), (b) and (c) out")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     n, every = a.streams, a.jump_every
@@ -117,7 +214,15 @@ def main():
     result = {"workload": {"streams": n, "lengths": [a.min_len, a.max_len], "symbols": total, "support": [LO, HI], "tables": K, "stds": [0.11, 64.0],
                            "precision": P, "jump_every": every, "order": "longest first"}, "coders": {}}
 
+    if a.select and not every:
+        ap.error("--select times the table's routes: give --jump-every")
     for coder in (("ans", "range") if a.coder == "both" else (a.coder,)):
+        if a.select:
+            result.setdefault("select", {})[coder] = {tag: select_section(coder, tables, sym, idx, off, lengths, order, every, a.select, a.rounds)
+                                                      for tag, idx in (("u8", idx8), ("i32", idx32))}
+            torch.cuda.empty_cache()
+            if a.only_select:
+                continue
         enc_ix, dec_ix = getattr(B, f"{coder}_encode_indexed_ragged"), getattr(B, f"{coder}_decode_indexed_ragged")
         enc_g, dec_g = getattr(B, f"{coder}_encode_gaussian_ragged"), getattr(B, f"{coder}_decode_gaussian_ragged")
         fns, kernels = {}, {}
