@@ -583,6 +583,24 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_ans_encode_gaussian_ragged_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_ans_decode_gaussian_ragged(
         cfg: CstCoderConfig,
         min_symbol: i32,
@@ -594,6 +612,25 @@ extern "C" {
         d_n_words: *const u32,
         d_means: *const f64,
         d_stds: *const f64,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_gaussian_ragged_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
         d_symbols: *mut i32,
         d_sym_offsets: *const u64,
         n_streams: usize,
@@ -629,6 +666,24 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_range_encode_gaussian_ragged_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_range_decode_gaussian_ragged(
         cfg: CstCoderConfig,
         min_symbol: i32,
@@ -648,6 +703,25 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_range_decode_gaussian_ragged_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_ans_encode_family_ragged(
         cfg: CstCoderConfig,
         family: i32,
@@ -656,6 +730,25 @@ extern "C" {
         d_symbols: *const i32,
         d_a: *const f64,
         d_b: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_encode_family_ragged_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_a: *const c_void,
+        d_b: *const c_void,
         d_sym_offsets: *const u64,
         n_streams: usize,
         d_order: *const u32,
@@ -687,6 +780,26 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_ans_decode_family_ragged_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const c_void,
+        d_b: *const c_void,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_range_encode_family_ragged(
         cfg: CstCoderConfig,
         family: i32,
@@ -695,6 +808,25 @@ extern "C" {
         d_symbols: *const i32,
         d_a: *const f64,
         d_b: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_encode_family_ragged_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_a: *const c_void,
+        d_b: *const c_void,
         d_sym_offsets: *const u64,
         n_streams: usize,
         d_order: *const u32,
@@ -718,6 +850,26 @@ extern "C" {
         d_n_words: *const u32,
         d_a: *const f64,
         d_b: *const f64,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_family_ragged_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const c_void,
+        d_b: *const c_void,
         d_symbols: *mut i32,
         d_sym_offsets: *const u64,
         n_streams: usize,
@@ -777,6 +929,28 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_ans_encode_gaussian_ragged_jump_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32,
+        d_jump_state: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_ans_decode_gaussian_ragged_jump(
         cfg: CstCoderConfig,
         min_symbol: i32,
@@ -801,6 +975,30 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_ans_decode_gaussian_ragged_jump_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_range_encode_gaussian_ragged_jump(
         cfg: CstCoderConfig,
         min_symbol: i32,
@@ -808,6 +1006,29 @@ extern "C" {
         d_symbols: *const i32,
         d_means: *const f64,
         d_stds: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32,
+        d_jump_lower: *mut u64,
+        d_jump_range: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_encode_gaussian_ragged_jump_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
         d_sym_offsets: *const u64,
         n_streams: usize,
         d_order: *const u32,
@@ -849,6 +1070,31 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_range_decode_gaussian_ragged_jump_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_ans_encode_family_ragged_jump(
         cfg: CstCoderConfig,
         family: i32,
@@ -857,6 +1103,29 @@ extern "C" {
         d_symbols: *const i32,
         d_a: *const f64,
         d_b: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32,
+        d_jump_state: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_encode_family_ragged_jump_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_a: *const c_void,
+        d_b: *const c_void,
         d_sym_offsets: *const u64,
         n_streams: usize,
         d_order: *const u32,
@@ -897,6 +1166,31 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_ans_decode_family_ragged_jump_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const c_void,
+        d_b: *const c_void,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_range_encode_family_ragged_jump(
         cfg: CstCoderConfig,
         family: i32,
@@ -905,6 +1199,30 @@ extern "C" {
         d_symbols: *const i32,
         d_a: *const f64,
         d_b: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        d_order: *const u32,
+        d_words: *mut u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32,
+        d_jump_lower: *mut u64,
+        d_jump_range: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_encode_family_ragged_jump_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_a: *const c_void,
+        d_b: *const c_void,
         d_sym_offsets: *const u64,
         n_streams: usize,
         d_order: *const u32,
@@ -933,6 +1251,32 @@ extern "C" {
         d_n_words: *const u32,
         d_a: *const f64,
         d_b: *const f64,
+        d_symbols: *mut i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_family_ragged_jump_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const c_void,
+        d_b: *const c_void,
         d_symbols: *mut i32,
         d_sym_offsets: *const u64,
         n_streams: usize,
@@ -1003,6 +1347,37 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_ans_decode_gaussian_ragged_select_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_range_decode_gaussian_ragged_select(
         cfg: CstCoderConfig,
         min_symbol: i32,
@@ -1014,6 +1389,38 @@ extern "C" {
         d_n_words: *const u32,
         d_means: *const f64,
         d_stds: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_gaussian_ragged_select_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
         d_sym_offsets: *const u64,
         n_streams: usize,
         jump_interval: usize,
@@ -1067,6 +1474,38 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_ans_decode_family_ragged_select_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const c_void,
+        d_b: *const c_void,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_state: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_range_decode_family_ragged_select(
         cfg: CstCoderConfig,
         family: i32,
@@ -1079,6 +1518,39 @@ extern "C" {
         d_n_words: *const u32,
         d_a: *const f64,
         d_b: *const f64,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        jump_interval: usize,
+        d_chunk_offsets: *const u64,
+        n_chunks_total: usize,
+        d_jump_pos: *const u32,
+        d_jump_lower: *const u64,
+        d_jump_range: *const u64,
+        d_query_stream: *const u32,
+        d_query_first: *const u64,
+        d_query_count: *const u64,
+        n_queries: usize,
+        d_piece_offsets: *const u64,
+        n_pieces_total: usize,
+        d_symbols_out: *mut i32,
+        d_out_offsets: *const u64,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_family_ragged_select_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_word_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const c_void,
+        d_b: *const c_void,
         d_sym_offsets: *const u64,
         n_streams: usize,
         jump_interval: usize,
@@ -1476,6 +1948,26 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_ans_encode_gaussian_batch_ckpt_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        ckpt_interval: usize,
+        d_ckpt_pos: *mut u32,
+        d_ckpt_state: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_ans_decode_gaussian_batch_ckpt(
         cfg: CstCoderConfig,
         min_symbol: i32,
@@ -1489,6 +1981,27 @@ extern "C" {
         d_ckpt_state: *const u64,
         d_means: *const f64,
         d_stds: *const f64,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_gaussian_batch_ckpt_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        ckpt_interval: usize,
+        d_ckpt_pos: *const u32,
+        d_ckpt_state: *const u64,
+        d_means: *const c_void,
+        d_stds: *const c_void,
         d_symbols: *mut i32,
         n_streams: usize,
         n_per_stream: usize,
@@ -1753,6 +2266,25 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_ans_encode_gaussian_batch_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_state: *mut u64,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_ans_decode_gaussian_batch(
         cfg: CstCoderConfig,
         min_symbol: i32,
@@ -1764,6 +2296,28 @@ extern "C" {
         d_n_words: *const u32,
         d_means: *const f64,
         d_stds: *const f64,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_state: *mut u64,
+        d_n_words_out: *mut u32,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_gaussian_batch_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
         d_symbols: *mut i32,
         n_streams: usize,
         n_per_stream: usize,
@@ -1803,6 +2357,26 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_ans_encode_family_batch_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_a: *const c_void,
+        d_b: *const c_void,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_state: *mut u64,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_ans_decode_family_batch(
         cfg: CstCoderConfig,
         family: i32,
@@ -1815,6 +2389,29 @@ extern "C" {
         d_n_words: *const u32,
         d_a: *const f64,
         d_b: *const f64,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_state: *mut u64,
+        d_n_words_out: *mut u32,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_ans_decode_family_batch_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const c_void,
+        d_b: *const c_void,
         d_symbols: *mut i32,
         n_streams: usize,
         n_per_stream: usize,
@@ -2174,6 +2771,25 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_range_encode_gaussian_batch_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_rstate: *mut CstRangeState,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_range_decode_gaussian_batch(
         cfg: CstCoderConfig,
         min_symbol: i32,
@@ -2185,6 +2801,27 @@ extern "C" {
         d_n_words: *const u32,
         d_means: *const f64,
         d_stds: *const f64,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_rstate: *mut CstRangeState,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_gaussian_batch_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
         d_symbols: *mut i32,
         n_streams: usize,
         n_per_stream: usize,
@@ -2216,6 +2853,26 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_range_encode_family_batch_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_a: *const c_void,
+        d_b: *const c_void,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        d_rstate: *mut CstRangeState,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_range_decode_family_batch(
         cfg: CstCoderConfig,
         family: i32,
@@ -2228,6 +2885,28 @@ extern "C" {
         d_n_words: *const u32,
         d_a: *const f64,
         d_b: *const f64,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_rstate: *mut CstRangeState,
+        d_status: *mut i32,
+        flags: u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_family_batch_f32(
+        cfg: CstCoderConfig,
+        family: i32,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        d_a: *const c_void,
+        d_b: *const c_void,
         d_symbols: *mut i32,
         n_streams: usize,
         n_per_stream: usize,
@@ -2876,6 +3555,27 @@ extern "C" {
         stream: *mut c_void,
     ) -> CstStatus;
 
+    pub fn cst_range_encode_gaussian_batch_ckpt_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_symbols: *const i32,
+        d_means: *const c_void,
+        d_stds: *const c_void,
+        n_streams: usize,
+        n_per_stream: usize,
+        layout: CstLayout,
+        d_words: *mut u32,
+        stride_words: usize,
+        d_n_words: *mut u32,
+        ckpt_interval: usize,
+        d_ckpt_pos: *mut u32,
+        d_ckpt_lower: *mut u64,
+        d_ckpt_range: *mut u64,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
     pub fn cst_range_gaussian_ckpt_scratch_bytes(n_streams: usize, n_per_stream: usize, ckpt_interval: usize) -> usize;
 
     pub fn cst_range_decode_gaussian_batch_ckpt(
@@ -2893,6 +3593,29 @@ extern "C" {
         d_ckpt_range: *const u64,
         d_means: *const f64,
         d_stds: *const f64,
+        d_symbols: *mut i32,
+        n_streams: usize,
+        n_per_stream: usize,
+        d_scratch: *mut c_void,
+        d_status: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_range_decode_gaussian_batch_ckpt_f32(
+        cfg: CstCoderConfig,
+        min_symbol: i32,
+        max_symbol: i32,
+        d_words: *const u32,
+        d_offsets: *const u64,
+        stride_words: usize,
+        words_capacity: usize,
+        d_n_words: *const u32,
+        ckpt_interval: usize,
+        d_ckpt_pos: *const u32,
+        d_ckpt_lower: *const u64,
+        d_ckpt_range: *const u64,
+        d_means: *const c_void,
+        d_stds: *const c_void,
         d_symbols: *mut i32,
         n_streams: usize,
         n_per_stream: usize,

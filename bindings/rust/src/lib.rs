@@ -6890,3 +6890,294 @@ impl Drop for TableSet {
         unsafe { ffi::cst_table_set_destroy(self.raw) };
     }
 }
+
+/// The per-symbol parameter calls over `f32` arrays (the header's "float32 parameters"): `NAME_f32` for every call that takes `means` /
+/// `stds` (`a` / `b`) as `*const f64`.  The kernels read the floats and widen them in registers: the results are those of `NAME` on the
+/// arrays widened to `f64`, without the widened copy.  Thin forms: each is its entry point minus the `cst_` prefix, with the arguments of
+/// the `f64` call and `*const f32` where that takes `*const f64`.
+///
+/// # Safety
+/// Every pointer is a device pointer that satisfies what the `f64` call of the same name asks of its own.
+#[allow(clippy::too_many_arguments, clippy::missing_safety_doc)]
+pub mod params_f32 {
+    use super::ffi::{self, CstCoderConfig, CstLayout, CstRangeState, CstStatus};
+    use core::ffi::c_void;
+
+    pub unsafe fn ans_encode_gaussian_ragged_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_symbols: *const i32, d_means: *const f32,
+        d_stds: *const f32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_words: *mut u32, d_word_offsets: *const u64,
+        stride_words: usize, d_n_words: *mut u32, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_encode_gaussian_ragged_f32(cfg, min_symbol, max_symbol, d_symbols, d_means as *const c_void, d_stds as *const c_void,
+            d_sym_offsets, n_streams, d_order, d_words, d_word_offsets, stride_words, d_n_words, d_status, stream)
+    }
+
+    pub unsafe fn ans_decode_gaussian_ragged_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_means: *const f32, d_stds: *const f32,
+        d_symbols: *mut i32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_status: *mut i32,
+        stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_decode_gaussian_ragged_f32(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+            d_means as *const c_void, d_stds as *const c_void, d_symbols, d_sym_offsets, n_streams, d_order, d_status, stream)
+    }
+
+    pub unsafe fn range_encode_gaussian_ragged_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_symbols: *const i32,
+        d_means: *const f32, d_stds: *const f32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_words: *mut u32,
+        d_word_offsets: *const u64, stride_words: usize, d_n_words: *mut u32, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_encode_gaussian_ragged_f32(cfg, min_symbol, max_symbol, d_symbols, d_means as *const c_void, d_stds as *const c_void,
+            d_sym_offsets, n_streams, d_order, d_words, d_word_offsets, stride_words, d_n_words, d_status, stream)
+    }
+
+    pub unsafe fn range_decode_gaussian_ragged_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_means: *const f32, d_stds: *const f32,
+        d_symbols: *mut i32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_status: *mut i32,
+        stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_decode_gaussian_ragged_f32(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+            d_means as *const c_void, d_stds as *const c_void, d_symbols, d_sym_offsets, n_streams, d_order, d_status, stream)
+    }
+
+    pub unsafe fn ans_encode_family_ragged_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_symbols: *const i32,
+        d_a: *const f32, d_b: *const f32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_words: *mut u32,
+        d_word_offsets: *const u64, stride_words: usize, d_n_words: *mut u32, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_encode_family_ragged_f32(cfg, family, min_symbol, max_symbol, d_symbols, d_a as *const c_void, d_b as *const c_void,
+            d_sym_offsets, n_streams, d_order, d_words, d_word_offsets, stride_words, d_n_words, d_status, stream)
+    }
+
+    pub unsafe fn ans_decode_family_ragged_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_a: *const f32, d_b: *const f32,
+        d_symbols: *mut i32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_status: *mut i32,
+        stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_decode_family_ragged_f32(cfg, family, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+            d_a as *const c_void, d_b as *const c_void, d_symbols, d_sym_offsets, n_streams, d_order, d_status, stream)
+    }
+
+    pub unsafe fn range_encode_family_ragged_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_symbols: *const i32,
+        d_a: *const f32, d_b: *const f32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_words: *mut u32,
+        d_word_offsets: *const u64, stride_words: usize, d_n_words: *mut u32, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_encode_family_ragged_f32(cfg, family, min_symbol, max_symbol, d_symbols, d_a as *const c_void, d_b as *const c_void,
+            d_sym_offsets, n_streams, d_order, d_words, d_word_offsets, stride_words, d_n_words, d_status, stream)
+    }
+
+    pub unsafe fn range_decode_family_ragged_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_a: *const f32, d_b: *const f32,
+        d_symbols: *mut i32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_status: *mut i32,
+        stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_decode_family_ragged_f32(cfg, family, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity,
+            d_n_words, d_a as *const c_void, d_b as *const c_void, d_symbols, d_sym_offsets, n_streams, d_order, d_status, stream)
+    }
+
+    pub unsafe fn ans_encode_gaussian_ragged_jump_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_symbols: *const i32,
+        d_means: *const f32, d_stds: *const f32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_words: *mut u32,
+        d_word_offsets: *const u64, stride_words: usize, d_n_words: *mut u32, jump_interval: usize, d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32, d_jump_state: *mut u64, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_encode_gaussian_ragged_jump_f32(cfg, min_symbol, max_symbol, d_symbols, d_means as *const c_void, d_stds as *const c_void,
+            d_sym_offsets, n_streams, d_order, d_words, d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos,
+            d_jump_state, d_status, stream)
+    }
+
+    pub unsafe fn ans_decode_gaussian_ragged_jump_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_means: *const f32, d_stds: *const f32,
+        d_symbols: *mut i32, d_sym_offsets: *const u64, n_streams: usize, jump_interval: usize, d_chunk_offsets: *const u64, n_chunks_total: usize,
+        d_jump_pos: *const u32, d_jump_state: *const u64, d_scratch: *mut c_void, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_decode_gaussian_ragged_jump_f32(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+            d_means as *const c_void, d_stds as *const c_void, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+            d_jump_pos, d_jump_state, d_scratch, d_status, stream)
+    }
+
+    pub unsafe fn range_encode_gaussian_ragged_jump_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_symbols: *const i32,
+        d_means: *const f32, d_stds: *const f32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_words: *mut u32,
+        d_word_offsets: *const u64, stride_words: usize, d_n_words: *mut u32, jump_interval: usize, d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32, d_jump_lower: *mut u64, d_jump_range: *mut u64, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_encode_gaussian_ragged_jump_f32(cfg, min_symbol, max_symbol, d_symbols, d_means as *const c_void, d_stds as *const c_void,
+            d_sym_offsets, n_streams, d_order, d_words, d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos,
+            d_jump_lower, d_jump_range, d_status, stream)
+    }
+
+    pub unsafe fn range_decode_gaussian_ragged_jump_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_means: *const f32, d_stds: *const f32,
+        d_symbols: *mut i32, d_sym_offsets: *const u64, n_streams: usize, jump_interval: usize, d_chunk_offsets: *const u64, n_chunks_total: usize,
+        d_jump_pos: *const u32, d_jump_lower: *const u64, d_jump_range: *const u64, d_scratch: *mut c_void, d_status: *mut i32,
+        stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_decode_gaussian_ragged_jump_f32(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity,
+            d_n_words, d_means as *const c_void, d_stds as *const c_void, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets,
+            n_chunks_total, d_jump_pos, d_jump_lower, d_jump_range, d_scratch, d_status, stream)
+    }
+
+    pub unsafe fn ans_encode_family_ragged_jump_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_symbols: *const i32,
+        d_a: *const f32, d_b: *const f32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_words: *mut u32,
+        d_word_offsets: *const u64, stride_words: usize, d_n_words: *mut u32, jump_interval: usize, d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32, d_jump_state: *mut u64, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_encode_family_ragged_jump_f32(cfg, family, min_symbol, max_symbol, d_symbols, d_a as *const c_void, d_b as *const c_void,
+            d_sym_offsets, n_streams, d_order, d_words, d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos,
+            d_jump_state, d_status, stream)
+    }
+
+    pub unsafe fn ans_decode_family_ragged_jump_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_a: *const f32, d_b: *const f32,
+        d_symbols: *mut i32, d_sym_offsets: *const u64, n_streams: usize, jump_interval: usize, d_chunk_offsets: *const u64, n_chunks_total: usize,
+        d_jump_pos: *const u32, d_jump_state: *const u64, d_scratch: *mut c_void, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_decode_family_ragged_jump_f32(cfg, family, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity,
+            d_n_words, d_a as *const c_void, d_b as *const c_void, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets,
+            n_chunks_total, d_jump_pos, d_jump_state, d_scratch, d_status, stream)
+    }
+
+    pub unsafe fn range_encode_family_ragged_jump_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_symbols: *const i32,
+        d_a: *const f32, d_b: *const f32, d_sym_offsets: *const u64, n_streams: usize, d_order: *const u32, d_words: *mut u32,
+        d_word_offsets: *const u64, stride_words: usize, d_n_words: *mut u32, jump_interval: usize, d_chunk_offsets: *const u64,
+        d_jump_pos: *mut u32, d_jump_lower: *mut u64, d_jump_range: *mut u64, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_encode_family_ragged_jump_f32(cfg, family, min_symbol, max_symbol, d_symbols, d_a as *const c_void, d_b as *const c_void,
+            d_sym_offsets, n_streams, d_order, d_words, d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos,
+            d_jump_lower, d_jump_range, d_status, stream)
+    }
+
+    pub unsafe fn range_decode_family_ragged_jump_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_a: *const f32, d_b: *const f32,
+        d_symbols: *mut i32, d_sym_offsets: *const u64, n_streams: usize, jump_interval: usize, d_chunk_offsets: *const u64, n_chunks_total: usize,
+        d_jump_pos: *const u32, d_jump_lower: *const u64, d_jump_range: *const u64, d_scratch: *mut c_void, d_status: *mut i32,
+        stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_decode_family_ragged_jump_f32(cfg, family, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity,
+            d_n_words, d_a as *const c_void, d_b as *const c_void, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets,
+            n_chunks_total, d_jump_pos, d_jump_lower, d_jump_range, d_scratch, d_status, stream)
+    }
+
+    pub unsafe fn ans_decode_gaussian_ragged_select_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_means: *const f32, d_stds: *const f32,
+        d_sym_offsets: *const u64, n_streams: usize, jump_interval: usize, d_chunk_offsets: *const u64, n_chunks_total: usize,
+        d_jump_pos: *const u32, d_jump_state: *const u64, d_query_stream: *const u32, d_query_first: *const u64, d_query_count: *const u64,
+        n_queries: usize, d_piece_offsets: *const u64, n_pieces_total: usize, d_symbols_out: *mut i32, d_out_offsets: *const u64,
+        d_scratch: *mut c_void, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_decode_gaussian_ragged_select_f32(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity,
+            d_n_words, d_means as *const c_void, d_stds as *const c_void, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+            d_jump_pos, d_jump_state, d_query_stream, d_query_first, d_query_count, n_queries, d_piece_offsets, n_pieces_total, d_symbols_out,
+            d_out_offsets, d_scratch, d_status, stream)
+    }
+
+    pub unsafe fn range_decode_gaussian_ragged_select_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_means: *const f32, d_stds: *const f32,
+        d_sym_offsets: *const u64, n_streams: usize, jump_interval: usize, d_chunk_offsets: *const u64, n_chunks_total: usize,
+        d_jump_pos: *const u32, d_jump_lower: *const u64, d_jump_range: *const u64, d_query_stream: *const u32, d_query_first: *const u64,
+        d_query_count: *const u64, n_queries: usize, d_piece_offsets: *const u64, n_pieces_total: usize, d_symbols_out: *mut i32,
+        d_out_offsets: *const u64, d_scratch: *mut c_void, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_decode_gaussian_ragged_select_f32(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity,
+            d_n_words, d_means as *const c_void, d_stds as *const c_void, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+            d_jump_pos, d_jump_lower, d_jump_range, d_query_stream, d_query_first, d_query_count, n_queries, d_piece_offsets, n_pieces_total,
+            d_symbols_out, d_out_offsets, d_scratch, d_status, stream)
+    }
+
+    pub unsafe fn ans_decode_family_ragged_select_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_a: *const f32, d_b: *const f32,
+        d_sym_offsets: *const u64, n_streams: usize, jump_interval: usize, d_chunk_offsets: *const u64, n_chunks_total: usize,
+        d_jump_pos: *const u32, d_jump_state: *const u64, d_query_stream: *const u32, d_query_first: *const u64, d_query_count: *const u64,
+        n_queries: usize, d_piece_offsets: *const u64, n_pieces_total: usize, d_symbols_out: *mut i32, d_out_offsets: *const u64,
+        d_scratch: *mut c_void, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_decode_family_ragged_select_f32(cfg, family, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity,
+            d_n_words, d_a as *const c_void, d_b as *const c_void, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+            d_jump_pos, d_jump_state, d_query_stream, d_query_first, d_query_count, n_queries, d_piece_offsets, n_pieces_total, d_symbols_out,
+            d_out_offsets, d_scratch, d_status, stream)
+    }
+
+    pub unsafe fn range_decode_family_ragged_select_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_word_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_a: *const f32, d_b: *const f32,
+        d_sym_offsets: *const u64, n_streams: usize, jump_interval: usize, d_chunk_offsets: *const u64, n_chunks_total: usize,
+        d_jump_pos: *const u32, d_jump_lower: *const u64, d_jump_range: *const u64, d_query_stream: *const u32, d_query_first: *const u64,
+        d_query_count: *const u64, n_queries: usize, d_piece_offsets: *const u64, n_pieces_total: usize, d_symbols_out: *mut i32,
+        d_out_offsets: *const u64, d_scratch: *mut c_void, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_decode_family_ragged_select_f32(cfg, family, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity,
+            d_n_words, d_a as *const c_void, d_b as *const c_void, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+            d_jump_pos, d_jump_lower, d_jump_range, d_query_stream, d_query_first, d_query_count, n_queries, d_piece_offsets, n_pieces_total,
+            d_symbols_out, d_out_offsets, d_scratch, d_status, stream)
+    }
+
+    pub unsafe fn ans_encode_gaussian_batch_ckpt_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_symbols: *const i32,
+        d_means: *const f32, d_stds: *const f32, n_streams: usize, n_per_stream: usize, layout: CstLayout, d_words: *mut u32, stride_words: usize,
+        d_n_words: *mut u32, ckpt_interval: usize, d_ckpt_pos: *mut u32, d_ckpt_state: *mut u64, d_status: *mut i32,
+        stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_encode_gaussian_batch_ckpt_f32(cfg, min_symbol, max_symbol, d_symbols, d_means as *const c_void, d_stds as *const c_void,
+            n_streams, n_per_stream, layout, d_words, stride_words, d_n_words, ckpt_interval, d_ckpt_pos, d_ckpt_state, d_status, stream)
+    }
+
+    pub unsafe fn ans_decode_gaussian_batch_ckpt_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_offsets: *const u64, stride_words: usize, words_capacity: usize, ckpt_interval: usize, d_ckpt_pos: *const u32, d_ckpt_state: *const u64,
+        d_means: *const f32, d_stds: *const f32, d_symbols: *mut i32, n_streams: usize, n_per_stream: usize, d_scratch: *mut c_void,
+        d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_decode_gaussian_batch_ckpt_f32(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, ckpt_interval,
+            d_ckpt_pos, d_ckpt_state, d_means as *const c_void, d_stds as *const c_void, d_symbols, n_streams, n_per_stream, d_scratch, d_status,
+            stream)
+    }
+
+    pub unsafe fn ans_encode_gaussian_batch_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_symbols: *const i32, d_means: *const f32,
+        d_stds: *const f32, n_streams: usize, n_per_stream: usize, layout: CstLayout, d_words: *mut u32, stride_words: usize, d_n_words: *mut u32,
+        d_state: *mut u64, d_status: *mut i32, flags: u32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_encode_gaussian_batch_f32(cfg, min_symbol, max_symbol, d_symbols, d_means as *const c_void, d_stds as *const c_void, n_streams,
+            n_per_stream, layout, d_words, stride_words, d_n_words, d_state, d_status, flags, stream)
+    }
+
+    pub unsafe fn ans_decode_gaussian_batch_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_words: *const u32, d_offsets: *const u64,
+        stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_means: *const f32, d_stds: *const f32, d_symbols: *mut i32,
+        n_streams: usize, n_per_stream: usize, layout: CstLayout, d_state: *mut u64, d_n_words_out: *mut u32, d_status: *mut i32, flags: u32,
+        stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_decode_gaussian_batch_f32(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words,
+            d_means as *const c_void, d_stds as *const c_void, d_symbols, n_streams, n_per_stream, layout, d_state, d_n_words_out, d_status, flags,
+            stream)
+    }
+
+    pub unsafe fn ans_encode_family_batch_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_symbols: *const i32,
+        d_a: *const f32, d_b: *const f32, n_streams: usize, n_per_stream: usize, layout: CstLayout, d_words: *mut u32, stride_words: usize,
+        d_n_words: *mut u32, d_state: *mut u64, d_status: *mut i32, flags: u32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_encode_family_batch_f32(cfg, family, min_symbol, max_symbol, d_symbols, d_a as *const c_void, d_b as *const c_void, n_streams,
+            n_per_stream, layout, d_words, stride_words, d_n_words, d_state, d_status, flags, stream)
+    }
+
+    pub unsafe fn ans_decode_family_batch_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_a: *const f32, d_b: *const f32,
+        d_symbols: *mut i32, n_streams: usize, n_per_stream: usize, layout: CstLayout, d_state: *mut u64, d_n_words_out: *mut u32,
+        d_status: *mut i32, flags: u32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_ans_decode_family_batch_f32(cfg, family, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words,
+            d_a as *const c_void, d_b as *const c_void, d_symbols, n_streams, n_per_stream, layout, d_state, d_n_words_out, d_status, flags, stream)
+    }
+
+    pub unsafe fn range_encode_gaussian_batch_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_symbols: *const i32, d_means: *const f32,
+        d_stds: *const f32, n_streams: usize, n_per_stream: usize, layout: CstLayout, d_words: *mut u32, stride_words: usize, d_n_words: *mut u32,
+        d_rstate: *mut CstRangeState, d_status: *mut i32, flags: u32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_encode_gaussian_batch_f32(cfg, min_symbol, max_symbol, d_symbols, d_means as *const c_void, d_stds as *const c_void,
+            n_streams, n_per_stream, layout, d_words, stride_words, d_n_words, d_rstate, d_status, flags, stream)
+    }
+
+    pub unsafe fn range_decode_gaussian_batch_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_words: *const u32, d_offsets: *const u64,
+        stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_means: *const f32, d_stds: *const f32, d_symbols: *mut i32,
+        n_streams: usize, n_per_stream: usize, layout: CstLayout, d_rstate: *mut CstRangeState, d_status: *mut i32, flags: u32,
+        stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_decode_gaussian_batch_f32(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words,
+            d_means as *const c_void, d_stds as *const c_void, d_symbols, n_streams, n_per_stream, layout, d_rstate, d_status, flags, stream)
+    }
+
+    pub unsafe fn range_encode_family_batch_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_symbols: *const i32,
+        d_a: *const f32, d_b: *const f32, n_streams: usize, n_per_stream: usize, layout: CstLayout, d_words: *mut u32, stride_words: usize,
+        d_n_words: *mut u32, d_rstate: *mut CstRangeState, d_status: *mut i32, flags: u32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_encode_family_batch_f32(cfg, family, min_symbol, max_symbol, d_symbols, d_a as *const c_void, d_b as *const c_void,
+            n_streams, n_per_stream, layout, d_words, stride_words, d_n_words, d_rstate, d_status, flags, stream)
+    }
+
+    pub unsafe fn range_decode_family_batch_f32(cfg: CstCoderConfig, family: i32, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, d_a: *const f32, d_b: *const f32,
+        d_symbols: *mut i32, n_streams: usize, n_per_stream: usize, layout: CstLayout, d_rstate: *mut CstRangeState, d_status: *mut i32, flags: u32,
+        stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_decode_family_batch_f32(cfg, family, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words,
+            d_a as *const c_void, d_b as *const c_void, d_symbols, n_streams, n_per_stream, layout, d_rstate, d_status, flags, stream)
+    }
+
+    pub unsafe fn range_encode_gaussian_batch_ckpt_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_symbols: *const i32,
+        d_means: *const f32, d_stds: *const f32, n_streams: usize, n_per_stream: usize, layout: CstLayout, d_words: *mut u32, stride_words: usize,
+        d_n_words: *mut u32, ckpt_interval: usize, d_ckpt_pos: *mut u32, d_ckpt_lower: *mut u64, d_ckpt_range: *mut u64, d_status: *mut i32,
+        stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_encode_gaussian_batch_ckpt_f32(cfg, min_symbol, max_symbol, d_symbols, d_means as *const c_void, d_stds as *const c_void,
+            n_streams, n_per_stream, layout, d_words, stride_words, d_n_words, ckpt_interval, d_ckpt_pos, d_ckpt_lower, d_ckpt_range, d_status,
+            stream)
+    }
+
+    pub unsafe fn range_decode_gaussian_batch_ckpt_f32(cfg: CstCoderConfig, min_symbol: i32, max_symbol: i32, d_words: *const u32,
+        d_offsets: *const u64, stride_words: usize, words_capacity: usize, d_n_words: *const u32, ckpt_interval: usize, d_ckpt_pos: *const u32,
+        d_ckpt_lower: *const u64, d_ckpt_range: *const u64, d_means: *const f32, d_stds: *const f32, d_symbols: *mut i32, n_streams: usize,
+        n_per_stream: usize, d_scratch: *mut c_void, d_status: *mut i32, stream: *mut c_void) -> CstStatus {
+        ffi::cst_range_decode_gaussian_batch_ckpt_f32(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words,
+            ckpt_interval, d_ckpt_pos, d_ckpt_lower, d_ckpt_range, d_means as *const c_void, d_stds as *const c_void, d_symbols, n_streams,
+            n_per_stream, d_scratch, d_status, stream)
+    }
+}

@@ -297,6 +297,15 @@ SIGNATURES = {
     "cst_debug_gaussian_lcp": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _z, _vp]),
 }
 
+# The calls that take per-symbol parameter arrays (means / stds, a / b) have NAME_f32 twins over float32 arrays ("float32 parameters" in
+# the header): the originals' argument lists, pointer for pointer.
+PARAMS_F32 = tuple(
+    [f"cst_{c}_{d}_{f}_{form}" for c in ("ans", "range") for d in ("encode", "decode") for f in ("gaussian", "family")
+     for form in ("batch", "ragged", "ragged_jump")]
+    + [f"cst_{c}_{d}_gaussian_batch_ckpt" for c in ("ans", "range") for d in ("encode", "decode")]
+    + [f"cst_{c}_decode_{f}_ragged_select" for c in ("ans", "range") for f in ("gaussian", "family")])
+SIGNATURES.update({name + "_f32": SIGNATURES[name] for name in PARAMS_F32})
+
 _lib = None
 
 

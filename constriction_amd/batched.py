@@ -1247,29 +1247,42 @@ def range_decode(encoded, model: Model, n_per_stream: int, layout="stream_major"
 # ---------------------------------------------------------------------------------------------------------------------
 # per-symbol quantized Gaussians: the reference's flagship call for many streams at once
 #     coder.encode_reverse(symbols, QuantizedGaussian(lo, hi), means, stds) / coder.decode(family, means, stds)
-# (src/pybindings/stream/stack.rs:567-588, 733-751): every symbol has its own (mean, std); `means` / `stds` are float64
-# tensors of the shape and layout of the symbol matrix (float32 callers widen first, src/pybindings/mod.rs:211-216).
+# (src/pybindings/stream/stack.rs:567-588, 733-751): every symbol has its own (mean, std); `means` / `stds` are float64 or
+# float32 tensors of the shape and layout of the symbol matrix.  The models of float32 parameters are those of the values
+# widened to f64, as in the reference (src/pybindings/mod.rs:211-216): a PAIR of float32 tensors is read by the kernels
+# themselves and widened in registers (the _f32 entry points, DESIGN.md 4.32: no widened copy); a float32 tensor next to a
+# float64 one is widened here.  The chain-coder calls widen both.
 # ---------------------------------------------------------------------------------------------------------------------
 
-def _gaussian_args(symbols_shape, means, stds):
-    # float32 parameter matrices are widened, exactly as the reference's Python API does (PyReadonlyFloatArray::cast_f64,
-    # src/pybindings/mod.rs:187-214; its own doc example passes float32 arrays): the models are those of the widened values
-    if means.dtype == torch.float32:
-        means = means.to(torch.float64)
-    if stds.dtype == torch.float32:
-        stds = stds.to(torch.float64)
-    means = _require_cuda(means, torch.float64, "means")
-    stds = _require_cuda(stds, torch.float64, "stds")
+def _gaussian_args(symbols_shape, means, stds, f32=False):
+    """the parameter matrices of a per-symbol call as its entry point takes them.  f32: the call has an _f32 twin (_f32_name) -- a pair
+    of float32 tensors then goes through as it is.  Anything else float32 is widened, exactly as the reference's Python API does
+    (PyReadonlyFloatArray::cast_f64, src/pybindings/mod.rs:187-214; its own doc example passes float32 arrays): the models are those
+    of the widened values either way."""
+    dtype = torch.float32 if f32 and means.dtype == torch.float32 and stds.dtype == torch.float32 else torch.float64
+    if dtype == torch.float64:
+        if means.dtype == torch.float32:
+            means = means.to(torch.float64)
+        if stds.dtype == torch.float32:
+            stds = stds.to(torch.float64)
+    means = _require_cuda(means, dtype, "means")
+    stds = _require_cuda(stds, dtype, "stds")
     if tuple(means.shape) != tuple(symbols_shape) or tuple(stds.shape) != tuple(symbols_shape):
         raise ValueError("means and stds must have the shape of the symbol matrix")
     return means, stds
+
+
+def _f32_name(fn_name, means):
+    """the entry point for parameter matrices that went through _gaussian_args(..., f32=True)"""
+    return fn_name + "_f32" if means.dtype == torch.float32 else fn_name
 
 
 def _encode_gaussian(fn_name, max_words_fn, symbols, min_symbol, max_symbol, means, stds, config, layout, stride, out, family=()):
     # family: () for the Gaussian entry points, (CST_FAMILY_*,) for cst_*_family_batch, which take it after the configuration
     symbols = _require_cuda(symbols, torch.int32, "symbols")
     n_streams, n_per, lay = _layout_shape(symbols, layout)
-    means, stds = _gaussian_args(symbols.shape, means, stds)
+    means, stds = _gaussian_args(symbols.shape, means, stds, f32=True)
+    fn_name = _f32_name(fn_name, means)
     if out is None:
         stride = stride or max_words_fn(n_per, config)
         dev = symbols.device
@@ -1314,14 +1327,14 @@ def range_encode_gaussian(symbols, min_symbol, max_symbol, means, stds, config=(
         if layout != "stream_major":
             raise ValueError("jump_points: stream-major batches only")
         symbols = _require_cuda(symbols, torch.int32, "symbols")
-        means, stds = _gaussian_args(symbols.shape, means, stds)
+        means, stds = _gaussian_args(symbols.shape, means, stds, f32=True)
+        fn = _f32_name("cst_range_encode_gaussian_batch_ckpt", means)
         if out is None:
             out = _new_batch(n_streams, stride or range_max_words(n_per, config), symbols.device, config)
         ck = _jump_table(out, RangeCheckpoints, interval, n_streams, n_per, symbols.device)
-        N.check(N.lib().cst_range_encode_gaussian_batch_ckpt(_cfg(*config), int(min_symbol), int(max_symbol), _ptr(symbols), _ptr(means), _ptr(stds),
-                                                             n_streams, n_per, lay, _ptr(out.words), out.words.shape[1], _ptr(out.n_words), interval,
-                                                             _ptr(ck.pos), _ptr(ck.lower), _ptr(ck.range), _ptr(out.status), _stream_ptr()),
-                "cst_range_encode_gaussian_batch_ckpt")
+        N.check(getattr(N.lib(), fn)(_cfg(*config), int(min_symbol), int(max_symbol), _ptr(symbols), _ptr(means), _ptr(stds),
+                                     n_streams, n_per, lay, _ptr(out.words), out.words.shape[1], _ptr(out.n_words), interval,
+                                     _ptr(ck.pos), _ptr(ck.lower), _ptr(ck.range), _ptr(out.status), _stream_ptr()), fn)
         out.jump = ck
         return out
     out = _encode_gaussian("cst_range_encode_gaussian_batch", range_max_words, symbols, min_symbol, max_symbol, means, stds,
@@ -1343,7 +1356,8 @@ def _decode_gaussian(fn_name, ans, encoded, min_symbol, max_symbol, means, stds,
     n_streams, n_per, lay = _layout_shape(means, layout)
     if n_streams != n_words.numel():
         raise ValueError("means / stds do not match the number of streams")
-    means, stds = _gaussian_args(means.shape, means, stds)
+    means, stds = _gaussian_args(means.shape, means, stds, f32=True)
+    fn_name = _f32_name(fn_name, means)
     dev = words.device
     if out is None:
         out = torch.empty(tuple(means.shape), dtype=torch.int32, device=dev)
@@ -1431,18 +1445,18 @@ def range_decode_gaussian(encoded, min_symbol, max_symbol, means, stds, layout="
     if isinstance(jump, RangeCheckpoints) and offsets is None and layout == "stream_major" and means.dim() == 2 and \
             tuple(means.shape) == (jump.pos.shape[0], jump.interval * jump.pos.shape[1]) and jump.pos.shape[0] == encoded.n_words.numel():
         n_streams, n_per = means.shape
-        means, stds = _gaussian_args(means.shape, means, stds)
+        means, stds = _gaussian_args(means.shape, means, stds, f32=True)
+        fn = _f32_name("cst_range_decode_gaussian_batch_ckpt", means)
         dev = encoded.words.device
         if out is None:
             out = torch.empty((n_streams, n_per), dtype=torch.int32, device=dev)
         part_status = torch.empty(tuple(jump.pos.shape), dtype=torch.int32, device=dev)
         L = N.lib()
         scratch = _ckpt_scratch("range_gaussian_ckpt", dev, L.cst_range_gaussian_ckpt_scratch_bytes(n_streams, n_per, jump.interval))
-        N.check(L.cst_range_decode_gaussian_batch_ckpt(_cfg(*encoded.config), int(min_symbol), int(max_symbol), _ptr(encoded.words), None,
-                                                       encoded.words.shape[1], encoded.words.numel(), _ptr(encoded.n_words), jump.interval,
-                                                       _ptr(jump.pos), _ptr(jump.lower), _ptr(jump.range), _ptr(means), _ptr(stds), _ptr(out),
-                                                       n_streams, n_per, _ptr(scratch), _ptr(part_status), _stream_ptr()),
-                "cst_range_decode_gaussian_batch_ckpt")
+        N.check(getattr(L, fn)(_cfg(*encoded.config), int(min_symbol), int(max_symbol), _ptr(encoded.words), None,
+                               encoded.words.shape[1], encoded.words.numel(), _ptr(encoded.n_words), jump.interval,
+                               _ptr(jump.pos), _ptr(jump.lower), _ptr(jump.range), _ptr(means), _ptr(stds), _ptr(out),
+                               n_streams, n_per, _ptr(scratch), _ptr(part_status), _stream_ptr()), fn)
         return out, _status_per_stream(part_status)
     return _decode_gaussian("cst_range_decode_gaussian_batch", False, encoded, min_symbol, max_symbol, means, stds, layout, offsets, out, config)
 
@@ -1452,7 +1466,7 @@ def range_decode_gaussian(encoded, min_symbol, max_symbol, means, stds, layout="
 # latent with its own (mean, std) -- the ragged calls' indexing (flat arrays + sym_offsets) on the Gaussian calls' models
 # ---------------------------------------------------------------------------------------------------------------------
 
-def _gaussian_ragged_args(sym_offsets, n_elements, means, stds):
+def _gaussian_ragged_args(sym_offsets, n_elements, means, stds, f32=False):
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
     n_streams = sym_offsets.numel() - 1
     if sym_offsets.dim() != 1 or n_streams < 0:
@@ -1461,7 +1475,7 @@ def _gaussian_ragged_args(sym_offsets, n_elements, means, stds):
         raise ValueError("means and stds must be flat")
     if n_elements is None:
         n_elements = means.numel()
-    means, stds = _gaussian_args((n_elements,), means, stds)
+    means, stds = _gaussian_args((n_elements,), means, stds, f32)
     return sym_offsets, n_streams, means, stds
 
 
@@ -1506,15 +1520,17 @@ def _encode_persymbol_ragged(fn_name, coder, symbols, sym_offsets, lo, hi, a, b,
     symbols = _require_cuda(symbols, torch.int32, "symbols")
     if symbols.dim() != 1:
         raise ValueError("symbols must be flat")
-    sym_offsets, n_streams, a, b = _gaussian_ragged_args(sym_offsets, symbols.numel(), a, b)
+    sym_offsets, n_streams, a, b = _gaussian_ragged_args(sym_offsets, symbols.numel(), a, b, f32=True)
     model = (*family, int(lo), int(hi), _ptr(_never_null(symbols)), _ptr(_never_null(a)), _ptr(_never_null(b)))
-    return _encode_ragged_slabs(fn_name, coder, symbols, sym_offsets, n_streams, config, order, jump_every, model)
+    return _encode_ragged_slabs(fn_name, coder, symbols, sym_offsets, n_streams, config, order, jump_every, model,
+                                "_f32" if a.dtype == torch.float32 else "")
 
 
-def _encode_ragged_slabs(fn_name, coder, symbols, sym_offsets, n_streams, config, order, jump_every, model) -> RaggedBatch:
+def _encode_ragged_slabs(fn_name, coder, symbols, sym_offsets, n_streams, config, order, jump_every, model, suffix="") -> RaggedBatch:
     """the slabs, the schedule, the jump table and the call of every ragged per-symbol encoder, once its arguments are judged: `model` is
     what the entry point takes between cfg and d_sym_offsets (the family's (lo, hi, symbols, a, b), or the Categorical's (symbols,
-    probabilities, prob_bytes, K, n_total)); `jump_every` has been through _persymbol_jump_every"""
+    probabilities, prob_bytes, K, n_total)); `jump_every` has been through _persymbol_jump_every; `suffix`: "_f32" for the twins over
+    float32 parameters (behind "_jump" where the jump form is taken)"""
     W, S, P = config
     dev = symbols.device
     lengths = sym_offsets[1:] - sym_offsets[:-1]
@@ -1546,13 +1562,15 @@ def _encode_ragged_slabs(fn_name, coder, symbols, sym_offsets, n_streams, config
             jump = RangeRaggedJump(jump_every, chunk_offsets, pos, torch.empty(n_chunks, dtype=torch.int64, device=dev),
                                    torch.empty(n_chunks, dtype=torch.int64, device=dev))
             table = (_ptr(jump.pos), _ptr(jump.lower), _ptr(jump.range))
-        N.check(getattr(N.lib(), fn_name + "_jump")(_cfg(*config), *model, _ptr(sym_offsets), n_streams, _ptr(order) if order is not None else None,
-                                                    _ptr(out.words), _ptr(word_offsets), 0, _ptr(out.n_words), jump_every, _ptr(chunk_offsets),
-                                                    *table, _ptr(out.status), _stream_ptr()), fn_name + "_jump")
+        N.check(getattr(N.lib(), fn_name + "_jump" + suffix)(_cfg(*config), *model, _ptr(sym_offsets), n_streams,
+                                                             _ptr(order) if order is not None else None, _ptr(out.words), _ptr(word_offsets), 0,
+                                                             _ptr(out.n_words), jump_every, _ptr(chunk_offsets), *table, _ptr(out.status),
+                                                             _stream_ptr()), fn_name + "_jump" + suffix)
         out.jump = jump
         return out
-    N.check(getattr(N.lib(), fn_name)(_cfg(*config), *model, _ptr(sym_offsets), n_streams, _ptr(order) if order is not None else None,
-                                      _ptr(out.words), _ptr(word_offsets), 0, _ptr(out.n_words), _ptr(out.status), _stream_ptr()), fn_name)
+    N.check(getattr(N.lib(), fn_name + suffix)(_cfg(*config), *model, _ptr(sym_offsets), n_streams, _ptr(order) if order is not None else None,
+                                               _ptr(out.words), _ptr(word_offsets), 0, _ptr(out.n_words), _ptr(out.status), _stream_ptr()),
+            fn_name + suffix)
     return out
 
 
@@ -1569,17 +1587,19 @@ def _decode_persymbol_ragged(fn_name, coder, encoded: RaggedBatch, sym_offsets, 
     """the body of every {ans,range}_decode_{gaussian,family}_ragged.  A batch with jump points (`jump_every` of the encoders) decodes
     its chunks side by side when `order` is None or "auto"; a schedule handed in is honoured on the whole streams."""
     jump = _ragged_jump_of(encoded, coder)
-    sym_offsets, n_streams, a, b = _gaussian_ragged_args(sym_offsets, None, a, b)
+    sym_offsets, n_streams, a, b = _gaussian_ragged_args(sym_offsets, None, a, b, f32=True)
     return _decode_ragged_slabs(fn_name, coder, encoded, jump, sym_offsets, n_streams, a.numel(), out, order, (*family, int(lo), int(hi)),
-                                (_ptr(_never_null(a)), _ptr(_never_null(b))))
+                                (_ptr(_never_null(a)), _ptr(_never_null(b))), suffix="_f32" if a.dtype == torch.float32 else "")
 
 
-def _decode_ragged_slabs(fn_name, coder, encoded: RaggedBatch, jump, sym_offsets, n_streams, total, out, order, head, model, plain_extra=None):
+def _decode_ragged_slabs(fn_name, coder, encoded: RaggedBatch, jump, sym_offsets, n_streams, total, out, order, head, model, plain_extra=None,
+                         suffix=""):
     """the schedule, the output, the route (whole streams, or the chunks of a jump table side by side) and the call of every ragged
     per-symbol decoder, once its arguments are judged: `head` is what the entry point takes between cfg and d_words (the family's
     (lo, hi)), `model` what it takes between d_n_words and d_symbols (the family's (a, b), or the Categorical's (probabilities,
     prob_bytes, K, n_total)); `total`: the symbols of all streams.  `plain_extra`: a callable, asked only on the whole-stream route, for
-    what the plain entry point takes behind `model` and the jump form does not (Categorical(perfect=True): max_len)"""
+    what the plain entry point takes behind `model` and the jump form does not (Categorical(perfect=True): max_len); `suffix`: as in
+    _encode_ragged_slabs"""
     if encoded.n_words.numel() != n_streams:
         raise ValueError("sym_offsets does not match the number of streams of the batch")
     take_jump = jump is not None and (order is None or (isinstance(order, str) and order == "auto"))
@@ -1604,16 +1624,16 @@ def _decode_ragged_slabs(fn_name, coder, encoded: RaggedBatch, jump, sym_offsets
         arrays = (jump.pos, jump.state) if coder == "ans" else (jump.pos, jump.lower, jump.range)
         n_chunks = min(int(t.numel()) for t in arrays)
         scratch = _ckpt_scratch("persymbol_ragged_jump", dev, L.cst_persymbol_ragged_jump_scratch_bytes(n_chunks))
-        N.check(getattr(L, fn_name + "_jump")(_cfg(*encoded.config), *head, _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
+        N.check(getattr(L, fn_name + "_jump" + suffix)(_cfg(*encoded.config), *head, _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
                                               encoded.words.numel(), _ptr(encoded.n_words), *model,
                                               _ptr(target), _ptr(sym_offsets), n_streams, jump.interval, _ptr(jump.chunk_offsets), n_chunks,
-                                              *(_ptr(t) for t in arrays), _ptr(scratch), _ptr(status), _stream_ptr()), fn_name + "_jump")
+                                              *(_ptr(t) for t in arrays), _ptr(scratch), _ptr(status), _stream_ptr()), fn_name + "_jump" + suffix)
         return out, status
     extra = plain_extra() if plain_extra is not None else ()
-    N.check(getattr(N.lib(), fn_name)(_cfg(*encoded.config), *head, _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
-                                      encoded.words.numel(), _ptr(encoded.n_words), *model, *extra, _ptr(target),
-                                      _ptr(sym_offsets), n_streams, _ptr(order) if order is not None else None, _ptr(status), _stream_ptr()),
-            fn_name)
+    N.check(getattr(N.lib(), fn_name + suffix)(_cfg(*encoded.config), *head, _ptr(encoded.words), _ptr(encoded.word_offsets), 0,
+                                               encoded.words.numel(), _ptr(encoded.n_words), *model, *extra, _ptr(target),
+                                               _ptr(sym_offsets), n_streams, _ptr(order) if order is not None else None, _ptr(status), _stream_ptr()),
+            fn_name + suffix)
     return out, status
 
 
@@ -1622,7 +1642,7 @@ def ans_encode_gaussian_ragged(symbols, sym_offsets, min_symbol, max_symbol, mea
                                jump_every=0) -> RaggedBatch:
     """One AnsCoder per stream, streams of different lengths: encode_reverse(symbols[lo:hi], QuantizedGaussian(min, max), means[lo:hi],
     stds[lo:hi]) + get_compressed with (lo, hi) = sym_offsets[s], sym_offsets[s + 1], for all streams in ONE launch.  `symbols` flat
-    int32; `means` / `stds` flat float64 of the same numel (float32 is widened); `sym_offsets` int64 [n + 1] as `ragged` returns it.
+    int32; `means` / `stds` flat float64 or float32 of the same numel (a float32 pair is read as it is, see _gaussian_args); `sym_offsets` int64 [n + 1] as `ragged` returns it.
     Every stream's words are those of ans_encode_gaussian for that stream alone.  The slabs are sized as in ans_encode_ragged; the
     batch carries the schedule it ran with in `.order` (see _ragged_order).
     jump_every: 0 (default) -- no jump points, `.jump` is None.  A positive multiple of 16: the encoder also notes AnsCoder.pos() in
@@ -1667,7 +1687,8 @@ def range_decode_gaussian_ragged(encoded: RaggedBatch, sym_offsets, min_symbol, 
 # per-symbol QuantizedLaplace / QuantizedCauchy: the same call with another family,
 #     coder.encode_reverse(symbols, QuantizedLaplace(lo, hi), means, scales) / coder.decode(QuantizedCauchy(lo, hi), locs, scales)
 # (src/pybindings/stream/model.rs:736-900), over the Gaussian's kernels and routes: the exact CDF is evaluated inside the coder
-# kernels, nothing is tabulated.  `a` / `b`: location and scale, float64 tensors of the symbols' shape (float32 is widened).
+# kernels, nothing is tabulated.  `a` / `b`: location and scale, float64 or float32 tensors of the symbols' shape (a float32 pair is read
+# by the kernels as it is and widened in registers; a float32 tensor next to a float64 one is widened: _gaussian_args).
 # ---------------------------------------------------------------------------------------------------------------------
 
 FAMILIES = {"laplace": N.FAMILY_LAPLACE, "cauchy": N.FAMILY_CAUCHY}
@@ -1761,9 +1782,9 @@ def _decode_persymbol_ragged_select(fn_name, coder, encoded: RaggedBatch, sym_of
     """the body of every {ans,range}_decode_{gaussian,family}_ragged_select: the queries of _select_queries on the arguments of
     _decode_persymbol_ragged"""
     jump = _ragged_jump_of(encoded, coder)
-    sym_offsets, _, a, b = _gaussian_ragged_args(sym_offsets, None, a, b)
+    sym_offsets, _, a, b = _gaussian_ragged_args(sym_offsets, None, a, b, f32=True)
     r = _select_queries(encoded, jump, sym_offsets, streams, first, count, out)
-    return _persymbol_select_call(fn_name, coder, encoded, jump, r, (*family, int(lo), int(hi)), (_ptr(_never_null(a)), _ptr(_never_null(b))))
+    return _persymbol_select_call(_f32_name(fn_name, a), coder, encoded, jump, r, (*family, int(lo), int(hi)), (_ptr(_never_null(a)), _ptr(_never_null(b))))
 
 
 def _persymbol_select_call(fn_name, coder, encoded: RaggedBatch, jump, r: _SelectQueries, front, model):
@@ -2388,7 +2409,8 @@ def ans_encode_gaussian_checkpointed(symbols, min_symbol, max_symbol, means, std
     batches of at least 16 384 streams, stream-major).  Returns (EncodedBatch, Checkpoints); the words are ans_encode_gaussian's."""
     symbols = _require_cuda(symbols, torch.int32, "symbols")
     n_streams, n_per, lay = _layout_shape(symbols, "stream_major")
-    means, stds = _gaussian_args(symbols.shape, means, stds)
+    means, stds = _gaussian_args(symbols.shape, means, stds, f32=True)
+    fn = _f32_name("cst_ans_encode_gaussian_batch_ckpt", means)
     dev = symbols.device
     n_chunks = (n_per + interval - 1) // interval
     if out is not None:
@@ -2400,10 +2422,9 @@ def ans_encode_gaussian_checkpointed(symbols, min_symbol, max_symbol, means, std
                            torch.empty(n_streams, dtype=torch.int32, device=dev), tuple(config))
         ck = Checkpoints(int(interval), torch.zeros((n_streams, n_chunks), dtype=torch.int32, device=dev),
                          torch.zeros((n_streams, n_chunks), dtype=torch.int64, device=dev))
-    N.check(N.lib().cst_ans_encode_gaussian_batch_ckpt(_cfg(*config), int(min_symbol), int(max_symbol), _ptr(symbols), _ptr(means), _ptr(stds),
-                                                       n_streams, n_per, lay, _ptr(out.words), out.words.shape[1], _ptr(out.n_words),
-                                                       int(interval), _ptr(ck.pos), _ptr(ck.state), _ptr(out.status), _stream_ptr()),
-            "cst_ans_encode_gaussian_batch_ckpt")
+    N.check(getattr(N.lib(), fn)(_cfg(*config), int(min_symbol), int(max_symbol), _ptr(symbols), _ptr(means), _ptr(stds),
+                                 n_streams, n_per, lay, _ptr(out.words), out.words.shape[1], _ptr(out.n_words),
+                                 int(interval), _ptr(ck.pos), _ptr(ck.state), _ptr(out.status), _stream_ptr()), fn)
     return out, ck
 
 
@@ -2413,7 +2434,8 @@ def ans_decode_gaussian_checkpointed(encoded: EncodedBatch, checkpoints: Checkpo
     if means.dim() != 2:
         raise ValueError("means must be 2-d")
     n_streams, n_per = means.shape
-    means, stds = _gaussian_args(means.shape, means, stds)
+    means, stds = _gaussian_args(means.shape, means, stds, f32=True)
+    fn = _f32_name("cst_ans_decode_gaussian_batch_ckpt", means)
     dev = encoded.words.device
     n_chunks = checkpoints.pos.shape[1]
     _check_jump_shape(checkpoints, n_per)
@@ -2425,10 +2447,10 @@ def ans_decode_gaussian_checkpointed(encoded: EncodedBatch, checkpoints: Checkpo
         status = torch.empty((n_streams, n_chunks), dtype=torch.int32, device=dev)
     L = N.lib()
     scratch = _ckpt_scratch("ans_ckpt", dev, L.cst_ckpt_scratch_bytes(n_streams, n_per, checkpoints.interval))
-    N.check(L.cst_ans_decode_gaussian_batch_ckpt(_cfg(*encoded.config), int(min_symbol), int(max_symbol), _ptr(encoded.words), None,
-                                                 encoded.words.shape[1], encoded.words.numel(), checkpoints.interval, _ptr(checkpoints.pos),
-                                                 _ptr(checkpoints.state), _ptr(means), _ptr(stds), _ptr(out), n_streams, n_per, _ptr(scratch),
-                                                 _ptr(status), _stream_ptr()), "cst_ans_decode_gaussian_batch_ckpt")
+    N.check(getattr(L, fn)(_cfg(*encoded.config), int(min_symbol), int(max_symbol), _ptr(encoded.words), None,
+                           encoded.words.shape[1], encoded.words.numel(), checkpoints.interval, _ptr(checkpoints.pos),
+                           _ptr(checkpoints.state), _ptr(means), _ptr(stds), _ptr(out), n_streams, n_per, _ptr(scratch),
+                           _ptr(status), _stream_ptr()), fn)
     return out, status
 
 

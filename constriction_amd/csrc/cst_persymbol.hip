@@ -218,14 +218,15 @@ __global__ __launch_bounds__(kBlock) void encode_entries_kernel(const EntriesEnc
 // One WAVE per stream.  Every lane carries the same coder state; the search for quantile_function (semantics of
 // quantize.rs:580-779 / lookup_contiguous.rs:564-605: the unique symbol with left(sym) <= q < left(sym+1)) evaluates up
 // to 64 candidate left cumulatives per round: two rounds for a 201-symbol support.  MODEL supplies left(element, i).
-struct GaussianLeft {
+template <class PT = double>
+struct GaussianLeftOf {
     static constexpr int32_t kBadModel = CST_STREAM_IMPOSSIBLE_SYMBOL;   // degenerate distribution (quantize.rs:562-565)
     static constexpr bool kErfTab = true;
     const PerSymbolDecodeArgs& a;
     const double2* erf_tab;
     double mu, sd;
     __device__ __forceinline__ bool load(size_t e) {
-        mu = a.means[e]; sd = a.stds[e];
+        mu = load_param(params_as<PT>(a.means) + e); sd = load_param(params_as<PT>(a.stds) + e);
         // the reference panics on an invalid model (pybindings/stream/model.rs:654-657)
         return sd > 0.0 && sd <= 1.7976931348623157e308 && mu == mu && mu <= 1.7976931348623157e308 && mu >= -1.7976931348623157e308;
     }
@@ -233,15 +234,16 @@ struct GaussianLeft {
         return leaky_gaussian_left_quick((int32_t)i, a.min_symbol, a.n_symbols, a.precision, 32, mu, sd, erf_tab);
     }
 };
+using GaussianLeft = GaussianLeftOf<double>;
 // QuantizedLaplace / QuantizedCauchy (a = mean / loc in `means`, b = scale in `stds`): 64 exact CDFs per round
-template <class FAM>
+template <class FAM, class PT = double>
 struct FamilyLeft {
     static constexpr int32_t kBadModel = CST_STREAM_IMPOSSIBLE_SYMBOL;
     static constexpr bool kErfTab = false;
     const PerSymbolDecodeArgs& a;
     const double2* unused;
     double pa, pb;
-    __device__ __forceinline__ bool load(size_t e) { pa = a.means[e]; pb = a.stds[e]; return FAM::valid(pa, pb); }
+    __device__ __forceinline__ bool load(size_t e) { pa = load_param(params_as<PT>(a.means) + e); pb = load_param(params_as<PT>(a.stds) + e); return FAM::valid(pa, pb); }
     __device__ __forceinline__ uint32_t left(uint32_t i) const {
         return FAM::template left<false>((int32_t)i, a.min_symbol, a.n_symbols, a.precision, pa, pb, nullptr);
     }
@@ -343,7 +345,14 @@ __device__ __noinline__ void store_symbol_tile16(int32_t* sym, size_t n_streams,
     }
 }
 
-template <int W, int S, int KIND, bool SMALL = false, class FAM = GaussianFamily>
+// The row length as a request at the matrix's edges sees it.  Float kernels: an opaque copy, so that the rows' starts are formed THERE and
+// not kept in registers through every tile -- the small geometry has none to spare (they cost it 16 bytes of scratch per lane).
+template <class PT> __device__ __forceinline__ size_t edge_row_length(size_t n) {
+    if constexpr (kParamF32<PT>) asm volatile("" : "+s"(n));
+    return n;
+}
+
+template <int W, int S, int KIND, bool SMALL = false, class FAM = GaussianFamily, class PT = double>
 __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane_kernel(const PerSymbolDecodeArgs a) {
     using G = LaneGeo<SMALL>;
     constexpr int kParTile = G::kParTile, kWordWindow = G::kWordWindow, kOutSyms = G::kOutSyms, kOutStride = G::kOutStride;
@@ -389,9 +398,22 @@ __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane
     // line of means and stds came in twice, ~16 000 cycles apart (round 5's counters: 10.24 GB per launch against 5.49 GB
     // algorithmic).  So a request there covers a PAIR of tiles -- whole lines, the big geometry's item mapping -- and the second
     // tile's half waits in the registers it arrived in: landed when its tile begins (mode 1 -> 2 -> 0 below).
-    constexpr int kReqTile = 16;                              // symbols a request can cover (= kParTile of the big geometry)
-    double mu_r[kReqTile], sd_r[kReqTile];
-    int mode = 0;                                             // (wave-uniform) 0: the registers hold ONE tile (or nothing); 1 / 2: a pair, its first / second half lands next
+    // PT = float: a line is 32 symbols -- two tiles of the big geometry, four of the small one.  The same scheme with kReqTile = 32: a
+    // request covers kReqParts tiles, in as many registers as the doubles took (32 floats for 16 doubles), and mode counts 1 .. kReqParts.
+    // A lane takes kVec consecutive floats of a line in one load -- kReqTile / kVec lanes to a line and as many loads per matrix: 64
+    // single loads next to the word window's are more than a wave may have in flight (the load counter holds 63), and the request then
+    // waits for its own first answers.  The small geometry loads PAIRS -- the loads, lanes and register pairs of its
+    // double kernel exactly.  The big geometry loads quadruples, but for its RANGE decoders, which keep single loads (their registers
+    // are the tightest: quadruples measured slower there).  Vector loads need rows that start on their size; others take the
+    // single-tile requests below.
+    constexpr int kVec = !kParamF32<PT> ? 1 : SMALL ? 2 : KIND != kRange ? 4 : 1;
+    constexpr int kReqTile = kParamsPerLine<PT>;              // symbols a request can cover: one line (doubles: kParTile of the big geometry)
+    constexpr int kReqParts = kReqTile / kParTile;            // tiles to a request: 1 (doubles, big), 2 (doubles, small; floats, big), 4 (floats, small)
+    constexpr bool kMulti = kReqParts > 1;
+    PT mu_r[kReqTile], sd_r[kReqTile];
+    const PT* const means = params_as<PT>(a.means);
+    const PT* const stds = params_as<PT>(a.stds);
+    int mode = 0;                                             // (wave-uniform) 0: the registers hold ONE tile (or nothing); m >= 1: a line, its m-th part lands next
     // item `it` of a tile that lies wholly inside the matrix: element base_e + t0 * t_stride + it * item_stride (stream-major:
     // stream s0 + lane / 16 + 4 it, symbol t0 + lane % 16; symbol-major: symbol t0 + it, stream s0 + lane), LDS slot
     // base_l + it * l_stride -- pointer increments; tiles that stick out (last streams, last symbols) take the general form
@@ -399,12 +421,29 @@ __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane
     const size_t t_stride = symbol_major ? a.n_streams : 1, item_stride = symbol_major ? a.n_streams : (size_t)(kWave / kParTile) * N;
     const int base_l = symbol_major ? lane : (lane % kParTile) * kParStride + lane / kParTile;
     const int l_stride = symbol_major ? kParStride : kWave / kParTile;
-    const bool pairs = SMALL && !symbol_major && s0 + kWave <= a.n_streams;
+    const bool vec_ok = kVec == 1 || (N % kVec == 0 && ((reinterpret_cast<uintptr_t>(means) | reinterpret_cast<uintptr_t>(stds)) & (4 * kVec - 1)) == 0);
+    const bool pairs = kMulti && !symbol_major && s0 + kWave <= a.n_streams && vec_ok;
+    constexpr int kLanesPerRow = kReqTile / kVec;             // (vector loads) lanes to a stream's kReqTile symbols = loads per matrix
+    typedef float vec_t __attribute__((ext_vector_type(kVec > 1 ? kVec : 2)));
     auto par_request = [&](size_t t0) {
-        if (SMALL && pairs && t0 % kReqTile == 0 && t0 + kReqTile <= N) {
+        if (kMulti && pairs && t0 % kReqTile == 0 && t0 + kReqTile <= N) {
+            if constexpr (kVec > 1) {
+                // item `it`: stream s0 + lane / kLanesPerRow + (64 / kLanesPerRow) it, symbols t0 + kVec (lane % kLanesPerRow) .. + kVec - 1,
+                // in registers [kVec it, kVec it + kVec)
+                const size_t ev = (s0 + (size_t)(lane / kLanesPerRow)) * N + (size_t)(kVec * (lane % kLanesPerRow)) + t0;
+#pragma unroll
+                for (int it = 0; it < kLanesPerRow; ++it) {
+                    const vec_t mv = __builtin_nontemporal_load(reinterpret_cast<const vec_t*>(means + ev + (size_t)it * (kWave / kLanesPerRow) * N));
+                    const vec_t sv = __builtin_nontemporal_load(reinterpret_cast<const vec_t*>(stds + ev + (size_t)it * (kWave / kLanesPerRow) * N));
+#pragma unroll
+                    for (int c = 0; c < kVec; ++c) { mu_r[kVec * it + c] = mv[c]; sd_r[kVec * it + c] = sv[c]; }
+                }
+                mode = 1;
+                return;
+            }
             const size_t e = (s0 + (size_t)(lane / kReqTile)) * N + (size_t)(lane % kReqTile) + t0;
-            const double* pm = a.means + e;
-            const double* ps = a.stds + e;
+            const PT* pm = means + e;
+            const PT* ps = stds + e;
 #pragma unroll
             for (int it = 0; it < kReqTile; ++it) {
                 mu_r[it] = __builtin_nontemporal_load(pm + (size_t)it * (size_t)(kWave / kReqTile) * N);
@@ -415,8 +454,8 @@ __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane
         }
         mode = 0;
         if (s0 + kWave <= a.n_streams && t0 + kParTile <= N) {
-            const double* pm = a.means + base_e + t0 * t_stride;
-            const double* ps = a.stds + base_e + t0 * t_stride;
+            const PT* pm = means + base_e + t0 * t_stride;
+            const PT* ps = stds + base_e + t0 * t_stride;
 #pragma unroll
             for (int it = 0; it < kParTile; ++it) {
                 mu_r[it] = __builtin_nontemporal_load(pm + (size_t)it * item_stride);
@@ -431,29 +470,45 @@ __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane
             // (idle lanes of a partial wave repeat its last stream -- with that stream's parameters: the chain coder's lanes
             // write their remainders as they go)
             const size_t sj = s0 + j < a.n_streams ? s0 + j : a.n_streams - 1;
-            const size_t e = t0 + tl < N ? (symbol_major ? (t0 + tl) * a.n_streams + sj : sj * N + t0 + tl) : 0;
-            mu_r[it] = __builtin_nontemporal_load(a.means + e);
-            sd_r[it] = __builtin_nontemporal_load(a.stds + e);
+            const size_t e = t0 + tl < N ? (symbol_major ? (t0 + tl) * a.n_streams + sj : sj * edge_row_length<PT>(N) + t0 + tl) : 0;
+            mu_r[it] = __builtin_nontemporal_load(means + e);
+            sd_r[it] = __builtin_nontemporal_load(stds + e);
         }
     };
     auto par_land = [&]() {
-        if (SMALL && mode != 0) {
-            // half (mode - 1) of the pair: the lanes that hold symbols 8 (mode - 1) .. + 7 of the sixteen write theirs
+        if (kMulti && mode != 0) {
+            if constexpr (kVec > 1) {
+                // part (mode - 1) of the request: the lanes whose kVec symbols lie in it write theirs, rows sub .. sub + kVec - 1 of the tile
+                const int sub = kVec * (lane % kLanesPerRow) - kParTile * (mode - 1);
+                if (sub >= 0 && sub < kParTile) {
+#pragma unroll
+                    for (int it = 0; it < kLanesPerRow; ++it) {
+#pragma unroll
+                        for (int c = 0; c < kVec; ++c) {
+                            par_mu[(sub + c) * kParStride + lane / kLanesPerRow + (kWave / kLanesPerRow) * it] = (double)mu_r[kVec * it + c];
+                            par_sd[(sub + c) * kParStride + lane / kLanesPerRow + (kWave / kLanesPerRow) * it] = (double)sd_r[kVec * it + c];
+                        }
+                    }
+                }
+                mode = mode < kReqParts ? mode + 1 : 0;
+                return;
+            }
+            // part (mode - 1) of the line: the lanes that hold symbols kParTile (mode - 1) .. + kParTile - 1 of it write theirs
             const int sub = (lane % kReqTile) - kParTile * (mode - 1);
             if (sub >= 0 && sub < kParTile) {
 #pragma unroll
                 for (int it = 0; it < kReqTile; ++it) {
-                    par_mu[sub * kParStride + lane / kReqTile + (kWave / kReqTile) * it] = mu_r[it];
-                    par_sd[sub * kParStride + lane / kReqTile + (kWave / kReqTile) * it] = sd_r[it];
+                    par_mu[sub * kParStride + lane / kReqTile + (kWave / kReqTile) * it] = (double)mu_r[it];
+                    par_sd[sub * kParStride + lane / kReqTile + (kWave / kReqTile) * it] = (double)sd_r[it];
                 }
             }
-            mode = mode == 1 ? 2 : 0;
+            mode = mode < kReqParts ? mode + 1 : 0;
             return;
         }
 #pragma unroll
         for (int it = 0; it < kParTile; ++it) {
-            par_mu[base_l + it * l_stride] = mu_r[it];
-            par_sd[base_l + it * l_stride] = sd_r[it];
+            par_mu[base_l + it * l_stride] = (double)mu_r[it];
+            par_sd[base_l + it * l_stride] = (double)sd_r[it];
         }
     };
     // ---- word window: a tile of 16 symbols takes at most 16 words, so with the 16 words behind the read position in
@@ -491,7 +546,7 @@ __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane
         wave_lds_fence();                                     // (the previous tile's parameters have been read)
         par_land();
         win_land();
-        if (t0 + kParTile < N && mode != 2) par_request(t0 + kParTile);      // (mode 2: the next tile's parameters are here already)
+        if (t0 + kParTile < N && mode == 0) par_request(t0 + kParTile);      // (mode >= 2: the next tile's parameters are here already)
         win_request(window_of(1));                            // (the words one tile further: used from the next tile on)
         wave_lds_fence();
         const int n_here = (int)(N - t0 < (size_t)kParTile ? N - t0 : (size_t)kParTile);
@@ -591,9 +646,9 @@ __global__ __launch_bounds__(LaneGeo<SMALL>::kThreads) void decode_gaussian_lane
 // earlier.  One ballot finds the lane, three compares the entry: ~45 instructions per symbol instead of ~600.
 constexpr int kRowsAhead = 16;
 
-template <class FAM = GaussianFamily>
-__global__ __launch_bounds__(kRowEntries) void gaussian_rows_kernel(int P, int32_t lo, int32_t n, const double* __restrict__ means,
-                                                                   const double* __restrict__ stds, int32_t layout, size_t n_streams,
+template <class FAM = GaussianFamily, class PT = double>
+__global__ __launch_bounds__(kRowEntries) void gaussian_rows_kernel(int P, int32_t lo, int32_t n, const PT* __restrict__ means,
+                                                                   const PT* __restrict__ stds, int32_t layout, size_t n_streams,
                                                                    size_t N, size_t t0, size_t count, uint32_t* __restrict__ rows) {
     const double2* erf_tab = nullptr;
     if constexpr (FAM::kErfTab) {
@@ -605,7 +660,7 @@ __global__ __launch_bounds__(kRowEntries) void gaussian_rows_kernel(int P, int32
     const size_t row = blockIdx.x;                     // = stream * count + (t - t0)
     const size_t s = row / count, t = t0 + row % count;
     const size_t e = layout == CST_LAYOUT_SYMBOL_MAJOR ? t * n_streams + s : s * N + t;
-    const double mu = means[e], sd = stds[e];
+    const double mu = load_param(means + e), sd = load_param(stds + e);
     const int32_t i = (int32_t)threadIdx.x;
     const uint32_t total = 1u << P;
     uint32_t v;
@@ -812,7 +867,7 @@ __global__ __launch_bounds__(kBlock) void chain_lookup_kernel(const PerSymbolDec
     uint32_t lo_i = 0, hi_i = n, lo_v = 0, hi_v = P >= 32 ? 0u : (1u << P);     // left(lo_i) = lo_v <= q < hi_v = left(hi_i)
     bool ok = true;
     if constexpr (GAUSSIAN) {
-        const double mu = a.means[e], sd = a.stds[e];
+        const double mu = params_as<double>(a.means)[e], sd = params_as<double>(a.stds)[e];     // (the chain coder takes doubles only)
         ok = sd > 0.0 && sd <= 1.7976931348623157e308 && fabs(mu) <= 1.7976931348623157e308;
         if (ok) {
             // the guess and the bracketing of decode_gaussian_lane_kernel
@@ -953,7 +1008,7 @@ hipError_t scratch_alloc(void** ptr, size_t bytes, hipStream_t hs) {
 }
 
 // few streams: cdf rows at full occupancy, then a lookup per symbol; in pieces of at most 64 MiB of rows
-template <int KIND, class FAM>
+template <int KIND, class FAM, class PT>
 static cst_status decode_gaussian_by_rows(cst_coder_config cfg, const PerSymbolDecodeArgs& a, hipStream_t hs) {
     const size_t N = a.n_per_stream;
     // 65 536 rows = 64 MiB of rows per piece (the piece size makes no measurable difference from 4096 rows up: the
@@ -961,8 +1016,8 @@ static cst_status decode_gaussian_by_rows(cst_coder_config cfg, const PerSymbolD
     size_t piece = ((size_t)65536 / a.n_streams) & ~(size_t)63;        // (n_streams < 64: at least 1024 symbols)
     if (piece > N) piece = N;
     return decode_in_pieces<KIND>(cfg, a, true, kRowEntries, piece, [&](size_t t0, size_t count, uint32_t* rows) -> cst_status {
-        hipLaunchKernelGGL(gaussian_rows_kernel<FAM>, dim3((unsigned)(a.n_streams * count)), dim3(kRowEntries), 0, hs, a.precision, a.min_symbol,
-                           a.n_symbols, a.means, a.stds, a.layout, a.n_streams, N, t0, count, rows);
+        hipLaunchKernelGGL((gaussian_rows_kernel<FAM, PT>), dim3((unsigned)(a.n_streams * count)), dim3(kRowEntries), 0, hs, a.precision, a.min_symbol,
+                           a.n_symbols, static_cast<const PT*>(a.means), static_cast<const PT*>(a.stds), a.layout, a.n_streams, N, t0, count, rows);
         return CST_OK;                  // (its launch error is read behind the decoder's launch)
     }, hs);
 }
@@ -987,11 +1042,12 @@ static cst_status decode_chains_in_three(cst_coder_config cfg, const PerSymbolDe
     return CST_OK;
 }
 
-// `gaussian`: per-symbol parameters of family FAM in a.means / a.stds (else explicit cdf rows)
-template <int KIND, class FAM = GaussianFamily>
+// `gaussian`: per-symbol parameters of family FAM in a.means / a.stds, matrices of PT (else explicit cdf rows)
+template <int KIND, class FAM = GaussianFamily, class PT = double>
 static cst_status decode_per_symbol(cst_coder_config cfg, const PerSymbolDecodeArgs& a, bool gaussian, hipStream_t hs) {
-    using WaveModel = std::conditional_t<FAM::kGaussian, GaussianLeft, FamilyLeft<FAM>>;
-    using Names = FamilyNames<FAM>;
+    static_assert(KIND != kChain || !kParamF32<PT>, "the chain coder takes doubles");
+    using WaveModel = std::conditional_t<FAM::kGaussian, GaussianLeftOf<PT>, FamilyLeft<FAM, PT>>;
+    using Names = FamilyNames<FAM, PT>;
     constexpr size_t kLdsBig = FAM::kErfTab ? LaneGeo<false>::kLdsBytes : LaneGeo<false>::kLdsBytesNoTab;
     constexpr size_t kLdsSmall = FAM::kErfTab ? LaneGeo<true>::kLdsBytes : LaneGeo<true>::kLdsBytesNoTab;
     if (a.n_streams == 0) return CST_OK;
@@ -1013,7 +1069,7 @@ static cst_status decode_per_symbol(cst_coder_config cfg, const PerSymbolDecodeA
         };
         auto lane = [&](auto small_geo) {                         // (std::bool_constant: the geometry)
             constexpr bool kSmall = decltype(small_geo)::value;
-            return dispatch_word_size(cfg, [&](auto W, auto S) { return go(decode_gaussian_lane_kernel<W, S, KIND, kSmall, FAM>, LaneGeo<kSmall>::kThreads, kSmall ? kLdsSmall : kLdsBig); });
+            return dispatch_word_size(cfg, [&](auto W, auto S) { return go(decode_gaussian_lane_kernel<W, S, KIND, kSmall, FAM, PT>, LaneGeo<kSmall>::kThreads, kSmall ? kLdsSmall : kLdsBig); });
         };
         cst_status rc;
         if constexpr (KIND != kChain) rc = small ? lane(std::true_type{}) : lane(std::false_type{});
@@ -1022,10 +1078,10 @@ static cst_status decode_per_symbol(cst_coder_config cfg, const PerSymbolDecodeA
         note_kernel(KIND == kChain || !small ? Names::lane[KIND] : Names::lane_small[KIND == kRange], CST_OK);
     } else if (KIND != kChain && gaussian && a.n_symbols < kRowEntries && a.n_per_stream >= 32) {
         note_kernel(Names::by_rows, CST_OK);
-        if constexpr (KIND != kChain) return decode_gaussian_by_rows<KIND, FAM>(cfg, a, hs);
+        if constexpr (KIND != kChain) return decode_gaussian_by_rows<KIND, FAM, PT>(cfg, a, hs);
     } else if (gaussian) {
         dispatch_word_size(cfg, [&](auto W, auto S) { hipLaunchKernelGGL((decode_wave_kernel<W, S, KIND, WaveModel>), dim3((unsigned)blocks), dim3(kBlock), 0, hs, a); });
-        if (!FAM::kGaussian) note_kernel(Names::wave[KIND == kRange], CST_OK);
+        if (!FAM::kGaussian || kParamF32<PT>) note_kernel(Names::wave[KIND == kRange], CST_OK);     // (the f64 Gaussian call has never recorded this route)
     } else {
         dispatch_word_size(cfg, [&](auto W, auto S) { hipLaunchKernelGGL((decode_wave_kernel<W, S, KIND, RowLeft>), dim3((unsigned)blocks), dim3(kBlock), 0, hs, a); });
     }
@@ -1059,6 +1115,22 @@ static cst_status chain_decode_common(PerSymbolDecodeArgs& a, cst_coder_config c
     // ahead of knowing whether they will need it)
     if (!d_heads || !d_n_push || !d_pop_words || (n_per_stream > 0 && !d_push_words)) return CST_ERR_INVALID_ARGUMENT;
     a.push_words = d_push_words; a.push_stride = push_stride; a.n_push = d_n_push; a.heads = d_heads; a.n_words_out = d_n_pop;
+    return CST_OK;
+}
+
+// What cst_{ans,range}_decode_gaussian_batch[_f32] say of their arguments, in their order, without the device -- and `a` filled for the
+// launch.  `raw_state`: the coder's raw state (d_state / d_rstate).  The jump-point decoders ask it too, BEFORE their first kernel, with
+// the arguments they will hand to the batch call: a refused call launches nothing and is refused with the status it always had.
+static cst_status gaussian_decode_args(PerSymbolDecodeArgs& a, cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                       const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                       const void* d_means, const void* d_stds, int32_t* d_symbols, size_t n_streams, size_t n_per_stream,
+                                       cst_layout layout, const void* raw_state, int32_t* d_status, uint32_t flags) {
+    if (max_symbol <= min_symbol) return CST_ERR_MODEL;
+    if (cst_status st = fill_decode_args(a, cfg, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_symbols, n_streams, n_per_stream, layout,
+                                         min_symbol, (int64_t)max_symbol - min_symbol + 1, d_status, flags)) return st;
+    if (n_per_stream > 0 && (!d_means || !d_stds)) return CST_ERR_INVALID_ARGUMENT;
+    if ((flags & CST_FLAG_RAW_STATE) && !raw_state) return CST_ERR_INVALID_ARGUMENT;
+    a.means = d_means; a.stds = d_stds;
     return CST_OK;
 }
 
@@ -1107,23 +1179,54 @@ __global__ void gaussian_ckpt_offsets_kernel(const uint64_t* __restrict__ offset
     v_state[v] = state_in[v];                  // (the raw decode updates its state array)
 }
 
-cst_status cst_ans_decode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
-                                              const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, size_t ckpt_interval,
-                                              const uint32_t* d_ckpt_pos, const uint64_t* d_ckpt_state, const double* d_means, const double* d_stds,
-                                              int32_t* d_symbols, size_t n_streams, size_t n_per_stream, void* d_scratch, int32_t* d_status, void* stream) {
+} // extern "C"
+
+// (defined below, with their entry points)
+template <class PT>
+static cst_status ans_decode_gaussian_batch_impl(cst_coder_config, int32_t, int32_t, const uint32_t*, const uint64_t*, size_t, size_t, const uint32_t*, const PT*,
+                                                 const PT*, int32_t*, size_t, size_t, cst_layout, uint64_t*, uint32_t*, int32_t*, uint32_t, void*);
+template <class PT>
+static cst_status range_decode_gaussian_batch_impl(cst_coder_config, int32_t, int32_t, const uint32_t*, const uint64_t*, size_t, size_t, const uint32_t*, const PT*,
+                                                   const PT*, int32_t*, size_t, size_t, cst_layout, cst_range_state*, int32_t*, uint32_t, void*);
+
+template <class PT>
+static cst_status ans_decode_gaussian_batch_ckpt_impl(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                      const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, size_t ckpt_interval,
+                                                      const uint32_t* d_ckpt_pos, const uint64_t* d_ckpt_state, const PT* d_means, const PT* d_stds,
+                                                      int32_t* d_symbols, size_t n_streams, size_t n_per_stream, void* d_scratch, int32_t* d_status, void* stream) {
     if (!d_ckpt_pos || !d_ckpt_state || !d_scratch || !d_status || ckpt_interval == 0 || n_per_stream % ckpt_interval != 0) return CST_ERR_INVALID_ARGUMENT;
     if (n_streams == 0 || n_per_stream == 0) return CST_OK;
     const size_t n_chunks = n_per_stream / ckpt_interval, n_virtual = n_streams * n_chunks;
     uint64_t* v_offsets = reinterpret_cast<uint64_t*>(d_scratch);
     uint64_t* v_state = v_offsets + n_virtual;
+    const size_t capacity = words_capacity ? words_capacity : (d_offsets ? 0 : n_streams * stride_words);
+    PerSymbolDecodeArgs judged{};           // (what the decode call below will say of its arguments: before anything is launched)
+    if (cst_status st = gaussian_decode_args(judged, cfg, min_symbol, max_symbol, d_words, v_offsets, 0, capacity, d_ckpt_pos, d_means, d_stds, d_symbols,
+                                             n_virtual, ckpt_interval, CST_LAYOUT_STREAM_MAJOR, v_state, d_status, CST_FLAG_RAW_STATE)) return st;
     hipLaunchKernelGGL(gaussian_ckpt_offsets_kernel, dim3((unsigned)((n_virtual + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_offsets, stride_words,
                        n_streams, n_chunks, d_ckpt_state, v_offsets, v_state);
     CST_HIP_TRY(hipGetLastError());
-    const size_t capacity = words_capacity ? words_capacity : (d_offsets ? 0 : n_streams * stride_words);
-    const cst_status rc = cst_ans_decode_gaussian_batch(cfg, min_symbol, max_symbol, d_words, v_offsets, 0, capacity, d_ckpt_pos, d_means, d_stds, d_symbols,
+    const cst_status rc = ans_decode_gaussian_batch_impl(cfg, min_symbol, max_symbol, d_words, v_offsets, 0, capacity, d_ckpt_pos, d_means, d_stds, d_symbols,
                                                         n_virtual, ckpt_interval, CST_LAYOUT_STREAM_MAJOR, v_state, nullptr, d_status, CST_FLAG_RAW_STATE, stream);
     if (rc != CST_OK) return rc;
     return flag_bad_jump_points(d_ckpt_pos, n_streams, n_chunks, d_offsets ? 0 : stride_words, d_status, (hipStream_t)stream);
+}
+
+extern "C" {
+
+cst_status cst_ans_decode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                              const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, size_t ckpt_interval,
+                                              const uint32_t* d_ckpt_pos, const uint64_t* d_ckpt_state, const double* d_means, const double* d_stds,
+                                              int32_t* d_symbols, size_t n_streams, size_t n_per_stream, void* d_scratch, int32_t* d_status, void* stream) {
+    return ans_decode_gaussian_batch_ckpt_impl(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, ckpt_interval,
+           d_ckpt_pos, d_ckpt_state, d_means, d_stds, d_symbols, n_streams, n_per_stream, d_scratch, d_status, stream);
+}
+cst_status cst_ans_decode_gaussian_batch_ckpt_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                  const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, size_t ckpt_interval,
+                                                  const uint32_t* d_ckpt_pos, const uint64_t* d_ckpt_state, const void* d_means, const void* d_stds,
+                                                  int32_t* d_symbols, size_t n_streams, size_t n_per_stream, void* d_scratch, int32_t* d_status, void* stream) {
+    return ans_decode_gaussian_batch_ckpt_impl(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, ckpt_interval,
+           d_ckpt_pos, d_ckpt_state, f32(d_means), f32(d_stds), d_symbols, n_streams, n_per_stream, d_scratch, d_status, stream);
 }
 
 size_t cst_range_gaussian_ckpt_scratch_bytes(size_t n_streams, size_t n_per_stream, size_t ckpt_interval) {
@@ -1168,13 +1271,12 @@ __global__ void gaussian_range_flag_kernel(const uint32_t* __restrict__ n_words,
     if (ckpt_pos[v] > n_words[v / n_chunks]) status[v] = CST_STREAM_INVALID_DATA;      // a jump point beyond its stream's words
 }
 
-extern "C" {
-
-cst_status cst_range_decode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
-                                                const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
-                                                size_t ckpt_interval, const uint32_t* d_ckpt_pos, const uint64_t* d_ckpt_lower,
-                                                const uint64_t* d_ckpt_range, const double* d_means, const double* d_stds, int32_t* d_symbols,
-                                                size_t n_streams, size_t n_per_stream, void* d_scratch, int32_t* d_status, void* stream) {
+template <class PT>
+static cst_status range_decode_gaussian_batch_ckpt_impl(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                        const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                        size_t ckpt_interval, const uint32_t* d_ckpt_pos, const uint64_t* d_ckpt_lower,
+                                                        const uint64_t* d_ckpt_range, const PT* d_means, const PT* d_stds, int32_t* d_symbols,
+                                                        size_t n_streams, size_t n_per_stream, void* d_scratch, int32_t* d_status, void* stream) {
     if (!d_n_words || !d_ckpt_pos || !d_ckpt_lower || !d_ckpt_range || !d_scratch || !d_status || ckpt_interval == 0 || n_per_stream % ckpt_interval != 0)
         return CST_ERR_INVALID_ARGUMENT;
     if (cfg.word_bits != 32 && cfg.word_bits != 16) return CST_ERR_INVALID_ARGUMENT;
@@ -1187,6 +1289,9 @@ cst_status cst_range_decode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t mi
     cst_range_state* v_state = reinterpret_cast<cst_range_state*>((reinterpret_cast<uintptr_t>(d_scratch) + 15) & ~(uintptr_t)15);
     uint64_t* v_offsets = reinterpret_cast<uint64_t*>(v_state + n_virtual);
     uint32_t* v_n = reinterpret_cast<uint32_t*>(v_offsets + n_virtual);
+    PerSymbolDecodeArgs judged{};           // (what the decode call below will say of its arguments: before anything is launched)
+    if (cst_status st = gaussian_decode_args(judged, cfg, min_symbol, max_symbol, d_words, v_offsets, 0, capacity, v_n, d_means, d_stds, d_symbols,
+                                             n_virtual, ckpt_interval, CST_LAYOUT_STREAM_MAJOR, v_state, d_status, CST_FLAG_RAW_STATE)) return st;
     const dim3 grid((unsigned)((n_virtual + 255) / 256));
     if (cfg.word_bits == 32)
         hipLaunchKernelGGL((gaussian_range_virtual_kernel<32, 64>), grid, dim3(256), 0, hs, d_words, d_offsets, stride_words, capacity, d_n_words, d_ckpt_pos,
@@ -1195,7 +1300,7 @@ cst_status cst_range_decode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t mi
         hipLaunchKernelGGL((gaussian_range_virtual_kernel<16, 32>), grid, dim3(256), 0, hs, d_words, d_offsets, stride_words, capacity, d_n_words, d_ckpt_pos,
                            d_ckpt_lower, d_ckpt_range, n_streams, n_chunks, v_offsets, v_n, v_state);
     CST_HIP_TRY(hipGetLastError());
-    const cst_status rc = cst_range_decode_gaussian_batch(cfg, min_symbol, max_symbol, d_words, v_offsets, 0, capacity, v_n, d_means, d_stds, d_symbols,
+    const cst_status rc = range_decode_gaussian_batch_impl(cfg, min_symbol, max_symbol, d_words, v_offsets, 0, capacity, v_n, d_means, d_stds, d_symbols,
                                                           n_virtual, ckpt_interval, CST_LAYOUT_STREAM_MAJOR, v_state, d_status, CST_FLAG_RAW_STATE, stream);
     if (rc != CST_OK) return rc;
     hipLaunchKernelGGL(gaussian_range_flag_kernel, grid, dim3(256), 0, hs, d_n_words, d_ckpt_pos, n_streams, n_chunks, d_status);
@@ -1203,34 +1308,92 @@ cst_status cst_range_decode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t mi
     return CST_OK;
 }
 
+extern "C" {
+
+cst_status cst_range_decode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                size_t ckpt_interval, const uint32_t* d_ckpt_pos, const uint64_t* d_ckpt_lower,
+                                                const uint64_t* d_ckpt_range, const double* d_means, const double* d_stds, int32_t* d_symbols,
+                                                size_t n_streams, size_t n_per_stream, void* d_scratch, int32_t* d_status, void* stream) {
+    return range_decode_gaussian_batch_ckpt_impl(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words,
+           ckpt_interval, d_ckpt_pos, d_ckpt_lower, d_ckpt_range, d_means, d_stds, d_symbols, n_streams, n_per_stream, d_scratch, d_status, stream);
+}
+cst_status cst_range_decode_gaussian_batch_ckpt_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                    const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                    size_t ckpt_interval, const uint32_t* d_ckpt_pos, const uint64_t* d_ckpt_lower,
+                                                    const uint64_t* d_ckpt_range, const void* d_means, const void* d_stds, int32_t* d_symbols,
+                                                    size_t n_streams, size_t n_per_stream, void* d_scratch, int32_t* d_status, void* stream) {
+    return range_decode_gaussian_batch_ckpt_impl(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words,
+           ckpt_interval, d_ckpt_pos, d_ckpt_lower, d_ckpt_range, f32(d_means), f32(d_stds), d_symbols, n_streams, n_per_stream, d_scratch, d_status,
+           stream);
+}
+
+} // extern "C"
+
+template <class PT>
+static cst_status ans_decode_gaussian_batch_impl(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                 const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                 const PT* d_means, const PT* d_stds, int32_t* d_symbols, size_t n_streams,
+                                                 size_t n_per_stream, cst_layout layout, uint64_t* d_state, uint32_t* d_n_words_out,
+                                                 int32_t* d_status, uint32_t flags, void* stream) {
+    PerSymbolDecodeArgs a{};
+    if (cst_status st = gaussian_decode_args(a, cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_means, d_stds,
+                                             d_symbols, n_streams, n_per_stream, layout, d_state, d_status, flags)) return st;
+    a.state = d_state; a.n_words_out = d_n_words_out;
+    return decode_per_symbol<kAns, GaussianFamily, PT>(cfg, a, true, (hipStream_t)stream);
+}
+
+extern "C" {
+
 cst_status cst_ans_decode_gaussian_batch(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
                                          const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
                                          const double* d_means, const double* d_stds, int32_t* d_symbols, size_t n_streams,
                                          size_t n_per_stream, cst_layout layout, uint64_t* d_state, uint32_t* d_n_words_out,
                                          int32_t* d_status, uint32_t flags, void* stream) {
-    PerSymbolDecodeArgs a{};
-    if (max_symbol <= min_symbol) return CST_ERR_MODEL;
-    if (cst_status st = fill_decode_args(a, cfg, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_symbols, n_streams, n_per_stream, layout,
-                                         min_symbol, (int64_t)max_symbol - min_symbol + 1, d_status, flags)) return st;
-    if (n_per_stream > 0 && (!d_means || !d_stds)) return CST_ERR_INVALID_ARGUMENT;
-    if ((flags & CST_FLAG_RAW_STATE) && !d_state) return CST_ERR_INVALID_ARGUMENT;
-    a.means = d_means; a.stds = d_stds; a.state = d_state; a.n_words_out = d_n_words_out;
-    return decode_per_symbol<kAns>(cfg, a, true, (hipStream_t)stream);
+    return ans_decode_gaussian_batch_impl(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_means, d_stds,
+           d_symbols, n_streams, n_per_stream, layout, d_state, d_n_words_out, d_status, flags, stream);
 }
+cst_status cst_ans_decode_gaussian_batch_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                             const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                             const void* d_means, const void* d_stds, int32_t* d_symbols, size_t n_streams,
+                                             size_t n_per_stream, cst_layout layout, uint64_t* d_state, uint32_t* d_n_words_out,
+                                             int32_t* d_status, uint32_t flags, void* stream) {
+    return ans_decode_gaussian_batch_impl(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words, f32(d_means),
+           f32(d_stds), d_symbols, n_streams, n_per_stream, layout, d_state, d_n_words_out, d_status, flags, stream);
+}
+
+} // extern "C"
+
+template <class PT>
+static cst_status range_decode_gaussian_batch_impl(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                   const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                   const PT* d_means, const PT* d_stds, int32_t* d_symbols, size_t n_streams,
+                                                   size_t n_per_stream, cst_layout layout, cst_range_state* d_rstate, int32_t* d_status,
+                                                   uint32_t flags, void* stream) {
+    PerSymbolDecodeArgs a{};
+    if (cst_status st = gaussian_decode_args(a, cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_means, d_stds,
+                                             d_symbols, n_streams, n_per_stream, layout, d_rstate, d_status, flags)) return st;
+    a.rstate = d_rstate;
+    return decode_per_symbol<kRange, GaussianFamily, PT>(cfg, a, true, (hipStream_t)stream);
+}
+
+extern "C" {
 
 cst_status cst_range_decode_gaussian_batch(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
                                            const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
                                            const double* d_means, const double* d_stds, int32_t* d_symbols, size_t n_streams,
                                            size_t n_per_stream, cst_layout layout, cst_range_state* d_rstate, int32_t* d_status,
                                            uint32_t flags, void* stream) {
-    PerSymbolDecodeArgs a{};
-    if (max_symbol <= min_symbol) return CST_ERR_MODEL;
-    if (cst_status st = fill_decode_args(a, cfg, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_symbols, n_streams, n_per_stream, layout,
-                                         min_symbol, (int64_t)max_symbol - min_symbol + 1, d_status, flags)) return st;
-    if (n_per_stream > 0 && (!d_means || !d_stds)) return CST_ERR_INVALID_ARGUMENT;
-    if ((flags & CST_FLAG_RAW_STATE) && !d_rstate) return CST_ERR_INVALID_ARGUMENT;
-    a.means = d_means; a.stds = d_stds; a.rstate = d_rstate;
-    return decode_per_symbol<kRange>(cfg, a, true, (hipStream_t)stream);
+    return range_decode_gaussian_batch_impl(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_means, d_stds,
+           d_symbols, n_streams, n_per_stream, layout, d_rstate, d_status, flags, stream);
+}
+cst_status cst_range_decode_gaussian_batch_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                               const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                               const void* d_means, const void* d_stds, int32_t* d_symbols, size_t n_streams,
+                                               size_t n_per_stream, cst_layout layout, cst_range_state* d_rstate, int32_t* d_status,
+                                               uint32_t flags, void* stream) {
+    return range_decode_gaussian_batch_impl(cfg, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words, f32(d_means),
+           f32(d_stds), d_symbols, n_streams, n_per_stream, layout, d_rstate, d_status, flags, stream);
 }
 
 cst_status cst_ans_decode_rows_batch(cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_offsets, size_t stride_words, size_t words_capacity,
@@ -1318,10 +1481,16 @@ cst_status check_family_args(cst_coder_config cfg, int32_t family, int32_t min_s
     return CST_OK;
 }
 
-template <int KIND>
+// (PT in front of FAM: CST_FAMILY_CALL names the coder and the family)
+template <int KIND, class FAM, class PT>
+static cst_status decode_per_symbol_of(const PT*, cst_coder_config cfg, const PerSymbolDecodeArgs& a, hipStream_t hs) {
+    return decode_per_symbol<KIND, FAM, PT>(cfg, a, true, hs);
+}
+
+template <int KIND, class PT>
 static cst_status decode_family(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
-                                const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const double* d_a,
-                                const double* d_b, int32_t* d_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout, uint64_t* d_state,
+                                const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, const PT* d_a,
+                                const PT* d_b, int32_t* d_symbols, size_t n_streams, size_t n_per_stream, cst_layout layout, uint64_t* d_state,
                                 uint32_t* d_n_words_out, cst_range_state* d_rstate, int32_t* d_status, uint32_t flags, hipStream_t hs) {
     if (cst_status st = check_family_args(cfg, family, min_symbol, max_symbol, layout, d_symbols, d_a, d_b, d_words, d_n_words, d_status,
                                           KIND == kAns ? (const void*)d_state : (const void*)d_rstate, flags)) return st;
@@ -1329,7 +1498,7 @@ static cst_status decode_family(cst_coder_config cfg, int32_t family, int32_t mi
     if (cst_status st = fill_decode_args(a, cfg, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_symbols, n_streams, n_per_stream, layout,
                                          min_symbol, (int64_t)max_symbol - min_symbol + 1, d_status, flags)) return st;
     a.means = d_a; a.stds = d_b; a.state = d_state; a.n_words_out = d_n_words_out; a.rstate = d_rstate;
-    return CST_FAMILY_CALL(decode_per_symbol, KIND, cfg, a, true, hs);
+    return CST_FAMILY_CALL(decode_per_symbol_of, KIND, d_a, cfg, a, hs);
 }
 
 } // namespace cst
@@ -1349,6 +1518,24 @@ cst_status cst_range_decode_family_batch(cst_coder_config cfg, int32_t family, i
                                          const double* d_a, const double* d_b, int32_t* d_symbols, size_t n_streams, size_t n_per_stream,
                                          cst_layout layout, cst_range_state* d_rstate, int32_t* d_status, uint32_t flags, void* stream) {
     return decode_family<kRange>(cfg, family, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_a, d_b, d_symbols,
+                                 n_streams, n_per_stream, layout, nullptr, nullptr, d_rstate, d_status, flags, (hipStream_t)stream);
+}
+
+// ---- the float32 twins (the header's "float32 parameters"): the originals' arguments with the arrays untyped, the same host templates ----
+
+cst_status cst_ans_decode_family_batch_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                           const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                           const void* d_a, const void* d_b, int32_t* d_symbols, size_t n_streams, size_t n_per_stream,
+                                           cst_layout layout, uint64_t* d_state, uint32_t* d_n_words_out, int32_t* d_status, uint32_t flags, void* stream) {
+    return decode_family<kAns>(cfg, family, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words, f32(d_a), f32(d_b), d_symbols,
+                               n_streams, n_per_stream, layout, d_state, d_n_words_out, nullptr, d_status, flags, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_family_batch_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                             const uint64_t* d_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                             const void* d_a, const void* d_b, int32_t* d_symbols, size_t n_streams, size_t n_per_stream,
+                                             cst_layout layout, cst_range_state* d_rstate, int32_t* d_status, uint32_t flags, void* stream) {
+    return decode_family<kRange>(cfg, family, min_symbol, max_symbol, d_words, d_offsets, stride_words, words_capacity, d_n_words, f32(d_a), f32(d_b), d_symbols,
                                  n_streams, n_per_stream, layout, nullptr, nullptr, d_rstate, d_status, flags, (hipStream_t)stream);
 }
 

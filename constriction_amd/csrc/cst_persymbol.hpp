@@ -23,6 +23,25 @@ namespace cst {
 
 enum CoderKind : int { kAns = 0, kRange = 1, kChain = 2 };
 
+// ------------------------------------------------------------------------------------------------
+// The element type PT of the per-symbol parameter matrices (means / stds, a / b): double, or float.  A kernel built for
+// float reads float32 and widens in registers right behind the load; the family policies, the erf path and the LDS tiles see doubles
+// either way.  Widening is exact for every float32 -- subnormals and signed zeros included: v_cvt_f64_f32 honours the f32 denormal mode,
+// and these kernels run with f32 denormals ON (the compiler's default for this target, .amdhsa_float_denorm_mode_32 = 3; nothing here is
+// built with -fgpu-flush-denormals-to-zero) -- so the models are those of the f64 call on the widened matrices, bit for bit.
+// The argument structs carry the matrices untyped; the kernel's PT says what they hold.
+// ------------------------------------------------------------------------------------------------
+template <class PT> __device__ __forceinline__ const PT* params_as(const void* p) { return static_cast<const PT*>(p); }
+template <class PT> __device__ __forceinline__ double load_param(const PT* p) { return (double)*p; }
+template <class PT> inline constexpr bool kParamF32 = std::is_same_v<PT, float>;
+// parameters to one 128-byte line
+template <class PT> inline constexpr int kParamsPerLine = 128 / (int)sizeof(PT);
+
+// Every entry point that takes parameter matrices exists twice: NAME over f64 matrices and NAME_f32 over f32 ones, which the header
+// declares untyped (`const void *`, as the Categorical calls take their matrices).  Both are one call of the same host template, which
+// deduces PT from the pointers: the twin makes it on the arrays as floats.
+inline const float* f32(const void* p) { return static_cast<const float*>(p); }
+
 __device__ __forceinline__ EncEntry make_entry(uint32_t c, uint32_t p) {
     uint64_t m = 0;
     if (p == 1) m = ~0ull;
@@ -124,8 +143,8 @@ struct PerSymbolDecodeArgs {
     size_t n_streams, n_per_stream;
     int32_t layout, precision;
     int32_t min_symbol, n_symbols;
-    const double* means;        // Gaussian
-    const double* stds;
+    const void* means;          // Gaussian (a family's a / b): PT matrices, PT the kernel's parameter type (params_as)
+    const void* stds;
     const uint32_t* cdf_rows;   // explicit rows
     uint64_t* state;            // ANS raw
     uint32_t* n_words_out;
@@ -325,26 +344,28 @@ template <typename F> auto dispatch_word_size(cst_coder_config cfg, F&& f) {
                                : f(std::integral_constant<int, 16>{}, std::integral_constant<int, 32>{});
 }
 
-// what note_kernel() reports for a family's routes
-template <class FAM> struct FamilyNames;
-#define CST_FAMILY_NAMES(FAM, word)                                                                                                       \
-    template <> struct FamilyNames<FAM> {                                                                                                 \
-        static constexpr const char* fused[2] = {"ans_encode_" word "_fused_kernel", "range_encode_" word "_fused_kernel"};               \
-        static constexpr const char* fused_ckpt[2] = {"ans_encode_" word "_fused_kernel<ckpt>", "range_encode_" word "_fused_kernel<ckpt>"}; \
-        static constexpr const char* two_pass[2] = {"ans_encode_" word "_two_pass", "range_encode_" word "_two_pass"};                    \
-        static constexpr const char* lane[3] = {"ans_decode_" word "_lane_kernel", "range_decode_" word "_lane_kernel", "chain_decode_" word "_lane_kernel"}; \
-        static constexpr const char* lane_small[2] = {"ans_decode_" word "_lane_kernel<small>", "range_decode_" word "_lane_kernel<small>"}; \
-        static constexpr const char* wave[2] = {"ans_decode_" word "_wave_kernel", "range_decode_" word "_wave_kernel"};                  \
-        static constexpr const char* by_rows = "decode_" word "_by_rows";                                                                 \
-        static constexpr const char* ragged[2][2] = {{"ans_encode_" word "_ragged_kernel", "ans_decode_" word "_ragged_kernel"},          \
-                                                     {"range_encode_" word "_ragged_kernel", "range_decode_" word "_ragged_kernel"}};     \
-        static constexpr const char* ragged_jump[2][2] = {{"ans_encode_" word "_ragged_kernel<jump>", "ans_decode_" word "_ragged_kernel<jump>"},      \
-                                                          {"range_encode_" word "_ragged_kernel<jump>", "range_decode_" word "_ragged_kernel<jump>"}}; \
-        static constexpr const char* ragged_select[2] = {"ans_decode_" word "_ragged_kernel<select>", "range_decode_" word "_ragged_kernel<select>"}; \
+// what note_kernel() reports for a family's routes; float parameter matrices (PT = float) add `f32` to a name's tag list
+template <class FAM, class PT = double> struct FamilyNames;
+#define CST_FAMILY_NAMES(FAM, PT, word, ALONE, MORE)                                                                                      \
+    template <> struct FamilyNames<FAM, PT> {                                                                                             \
+        static constexpr const char* fused[2] = {"ans_encode_" word "_fused_kernel" ALONE, "range_encode_" word "_fused_kernel" ALONE};   \
+        static constexpr const char* fused_ckpt[2] = {"ans_encode_" word "_fused_kernel<ckpt" MORE ">", "range_encode_" word "_fused_kernel<ckpt" MORE ">"}; \
+        static constexpr const char* two_pass[2] = {"ans_encode_" word "_two_pass" ALONE, "range_encode_" word "_two_pass" ALONE};        \
+        static constexpr const char* lane[3] = {"ans_decode_" word "_lane_kernel" ALONE, "range_decode_" word "_lane_kernel" ALONE, "chain_decode_" word "_lane_kernel" ALONE}; \
+        static constexpr const char* lane_small[2] = {"ans_decode_" word "_lane_kernel<small" MORE ">", "range_decode_" word "_lane_kernel<small" MORE ">"}; \
+        static constexpr const char* wave[2] = {"ans_decode_" word "_wave_kernel" ALONE, "range_decode_" word "_wave_kernel" ALONE};      \
+        static constexpr const char* by_rows = "decode_" word "_by_rows" ALONE;                                                           \
+        static constexpr const char* ragged[2][2] = {{"ans_encode_" word "_ragged_kernel" ALONE, "ans_decode_" word "_ragged_kernel" ALONE}, \
+                                                     {"range_encode_" word "_ragged_kernel" ALONE, "range_decode_" word "_ragged_kernel" ALONE}}; \
+        static constexpr const char* ragged_jump[2][2] = {{"ans_encode_" word "_ragged_kernel<jump" MORE ">", "ans_decode_" word "_ragged_kernel<jump" MORE ">"},      \
+                                                          {"range_encode_" word "_ragged_kernel<jump" MORE ">", "range_decode_" word "_ragged_kernel<jump" MORE ">"}}; \
+        static constexpr const char* ragged_select[2] = {"ans_decode_" word "_ragged_kernel<select" MORE ">", "range_decode_" word "_ragged_kernel<select" MORE ">"}; \
     }
-CST_FAMILY_NAMES(GaussianFamily, "gaussian");
-CST_FAMILY_NAMES(LaplaceFamily, "laplace");
-CST_FAMILY_NAMES(CauchyFamily, "cauchy");
+#define CST_FAMILY_NAMES_BOTH(FAM, word) CST_FAMILY_NAMES(FAM, double, word, "", ""); CST_FAMILY_NAMES(FAM, float, word, "<f32>", ", f32")
+CST_FAMILY_NAMES_BOTH(GaussianFamily, "gaussian");
+CST_FAMILY_NAMES_BOTH(LaplaceFamily, "laplace");
+CST_FAMILY_NAMES_BOTH(CauchyFamily, "cauchy");
+#undef CST_FAMILY_NAMES_BOTH
 #undef CST_FAMILY_NAMES
 
 // raises the kernel's dynamic LDS limit to `lds` bytes, launches it and reads the launch error

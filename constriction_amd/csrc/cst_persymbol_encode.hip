@@ -7,9 +7,9 @@ namespace cst {
 
 // (the kernels below are named after the family they were written for; FAM is a policy of cst_family_policy.hpp, and only the
 // Gaussian stages the erf tables)
-template <class FAM = GaussianFamily>
+template <class FAM = GaussianFamily, class PT = double>
 __global__ void gaussian_entries_kernel(int P, int32_t lo, int32_t hi, const int32_t* __restrict__ sym,
-                                        const double* __restrict__ mu, const double* __restrict__ sd, size_t n,
+                                        const PT* __restrict__ mu, const PT* __restrict__ sd, size_t n,
                                         EncEntry* __restrict__ out) {
     const double2* erf_tab = nullptr;
     if constexpr (FAM::kErfTab) {
@@ -21,7 +21,7 @@ __global__ void gaussian_entries_kernel(int P, int32_t lo, int32_t hi, const int
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t c = 0, p = 0;
-    const double m = mu[i], s = sd[i];
+    const double m = load_param(mu + i), s = load_param(sd + i);
     // `assert!(std > 0.0)` and finite parameters (pybindings/stream/model.rs:654-657); out-of-support symbols
     // (quantize.rs:537-539) and degenerate distributions (quantize.rs:562-565) all end up with p = 0 = impossible
     if (FAM::valid(m, s)) {
@@ -45,8 +45,8 @@ __global__ void gaussian_entries_kernel(int P, int32_t lo, int32_t hi, const int
 // ------------------------------------------------------------------------------------------------
 struct GaussianFusedArgs {
     const int32_t* symbols;
-    const double* means;
-    const double* stds;
+    const void* means;          // PT matrices, PT the kernel's parameter type (cst_persymbol.hpp)
+    const void* stds;
     size_t n_streams, n_per_stream;
     int32_t layout, precision, lo, hi;
     uint32_t* words;
@@ -71,7 +71,10 @@ struct GaussianFusedArgs {
 // (6.60 GB counted against 5.57 GB algorithmic, profiles/r04_pmc_summary.md).  So the symbols of both tiles of a line are
 // requested together, a pair of tiles ahead, and parked lane by lane in the ring columns of lanes 32..63 (a wave codes
 // kFuStreams = 32 streams: no coder ever writes there), where the items pick them up one item ahead of their use.
-template <int W, int S, int KIND, bool PAIR = false, class FAM = GaussianFamily>
+// PT = float, stream-major: a tile's sixteen parameters of a stream are HALF a line too, and they are requested tile by tile -- the
+// stash holds the symbols and has no room for 2 x 2 x 8 more values per lane, and registers that a rolled item loop indexes would go
+// to scratch.  The f32 encoder fetches its parameter lines as the f64 one does, twice as many symbols to a line.
+template <int W, int S, int KIND, bool PAIR = false, class FAM = GaussianFamily, class PT = double>
 __global__ __launch_bounds__(kFuBlock) void encode_gaussian_fused_kernel(const GaussianFusedArgs a) {
     constexpr size_t kTabBytes = FAM::kErfTab ? kFuTabBytes : 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -107,8 +110,10 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_fused_kernel(const G
     // a queue of kFuAhead requested items (HBM latency is two to three items' worth of arithmetic); the item loop below is
     // unrolled by kFuAhead so that every queue slot is a fixed set of registers
     int32_t sy_q[kFuAhead];
-    double mu_q[kFuAhead], sd_q[kFuAhead];
+    PT mu_q[kFuAhead], sd_q[kFuAhead];              // (widened where an item takes them up: a float in flight is one register)
     bool ok_q[kFuAhead];
+    const PT* const means = params_as<PT>(a.means);
+    const PT* const stds = params_as<PT>(a.stds);
     // Full waves over rows of whole tiles walk the matrices by ADDING: item `it` of tile k lies at
     //   base(lane) + it * item_stride + k * tile_stride      (both strides wave-uniform, in either layout)
     // and the items are requested in exactly that order, so one running index per lane replaces the per-item index arithmetic
@@ -123,8 +128,8 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_fused_kernel(const G
         if (walk) {
             ok_q[slot] = true;
             if constexpr (!PAIR) sy_q[slot] = __builtin_nontemporal_load(a.symbols + e_req);
-            mu_q[slot] = __builtin_nontemporal_load(a.means + e_req);
-            sd_q[slot] = __builtin_nontemporal_load(a.stds + e_req);
+            mu_q[slot] = __builtin_nontemporal_load(means + e_req);
+            sd_q[slot] = __builtin_nontemporal_load(stds + e_req);
             e_req += it == kFuIters - 1 ? wrap_delta : item_stride;
             return;
         }
@@ -133,8 +138,8 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_fused_kernel(const G
         // (unconditional loads from an address that is always valid: a conditional load is waited for at once)
         const size_t e = ok_q[slot] ? (symbol_major ? t * a.n_streams + sj : sj * N + t) : 0;
         sy_q[slot] = __builtin_nontemporal_load(a.symbols + e);
-        mu_q[slot] = __builtin_nontemporal_load(a.means + e);
-        sd_q[slot] = __builtin_nontemporal_load(a.stds + e);
+        mu_q[slot] = __builtin_nontemporal_load(means + e);
+        sd_q[slot] = __builtin_nontemporal_load(stds + e);
     };
 
     uint32_t* slab = a.words + (active ? s : 0) * a.stride_words;
@@ -210,7 +215,7 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_fused_kernel(const G
                 } else {
                     sy = ok_q[q] ? sy_q[q] : a.lo;                  // (items past the matrix: never coded)
                 }
-                const double m = ok_q[q] ? mu_q[q] : 0.0, sg = ok_q[q] ? sd_q[q] : 1.0;
+                const double m = ok_q[q] ? (double)mu_q[q] : 0.0, sg = ok_q[q] ? (double)sd_q[q] : 1.0;
                 if (it + kFuAhead < kFuIters) request(q, k, it + kFuAhead);
                 else if (step + 1 < n_tiles) request(q, tile_of(step + 1), it + kFuAhead - kFuIters);
                 uint32_t c = 0, p = 0;
@@ -327,9 +332,9 @@ static bool fused_encode_usable(size_t n_streams, size_t n_per_stream) {
     return n_streams >= knobs().fused_min_streams && n_per_stream >= 1;
 }
 
-template <int KIND, class FAM = GaussianFamily>
+template <int KIND, class FAM = GaussianFamily, class PT = double>
 static cst_status encode_gaussian_fused(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
-                                        const double* d_means, const double* d_stds, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                        const PT* d_means, const PT* d_stds, size_t n_streams, size_t n_per_stream, cst_layout layout,
                                         uint32_t* d_words, size_t stride_words, uint32_t* d_n_words, uint64_t* d_state,
                                         cst_range_state* d_rstate, int32_t* d_status, uint32_t flags, hipStream_t hs,
                                         size_t ckpt_interval = 0, uint32_t* d_ckpt_pos = nullptr, uint64_t* d_ckpt_state = nullptr,
@@ -353,24 +358,25 @@ static cst_status encode_gaussian_fused(cst_coder_config cfg, int32_t min_symbol
     // are arithmetic, not traffic, and the pair's sixteen parked symbols do not survive their calls without scratch.)
     const bool pair = FAM::kGaussian && layout == CST_LAYOUT_STREAM_MAJOR && n_streams % kFuStreams == 0 && n_per_stream % kFuTile == 0 && n_per_stream > 0;
     if constexpr (FAM::kGaussian)
-        if (cfg.word_bits == 32 && pair) return launch_with_lds(encode_gaussian_fused_kernel<32, 64, KIND, true, FAM>, blocks, kFuBlock, lds, a, hs);
-    return dispatch_word_size(cfg, [&](auto W, auto S) { return launch_with_lds(encode_gaussian_fused_kernel<W, S, KIND, false, FAM>, blocks, kFuBlock, lds, a, hs); });
+        if (cfg.word_bits == 32 && pair) return launch_with_lds(encode_gaussian_fused_kernel<32, 64, KIND, true, FAM, PT>, blocks, kFuBlock, lds, a, hs);
+    return dispatch_word_size(cfg, [&](auto W, auto S) { return launch_with_lds(encode_gaussian_fused_kernel<W, S, KIND, false, FAM, PT>, blocks, kFuBlock, lds, a, hs); });
 }
 
 // the routes of a rectangular encode call of family FAM; d_a / d_b are the family's two parameters; `note`: record the route
-template <int KIND, class FAM>
-static cst_status encode_family(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols, const double* d_a,
-                                const double* d_b, size_t n_streams, size_t n_per_stream, cst_layout layout, uint32_t* d_words,
+template <int KIND, class FAM, class PT>
+static cst_status encode_family(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols, const PT* d_a,
+                                const PT* d_b, size_t n_streams, size_t n_per_stream, cst_layout layout, uint32_t* d_words,
                                 size_t stride_words, uint32_t* d_n_words, uint64_t* d_state, cst_range_state* d_rstate, int32_t* d_status,
                                 uint32_t flags, hipStream_t hs, bool note = true) {
     const bool fused = fused_encode_usable(n_streams, n_per_stream);
-    if (note) note_kernel(fused ? FamilyNames<FAM>::fused[KIND == kRange] : FamilyNames<FAM>::two_pass[KIND == kRange], CST_OK);
+    // (`note` is false for one f64 call that has never recorded its route; the float calls all do)
+    if (note || kParamF32<PT>) note_kernel(fused ? FamilyNames<FAM, PT>::fused[KIND == kRange] : FamilyNames<FAM, PT>::two_pass[KIND == kRange], CST_OK);
     if (fused)
-        return encode_gaussian_fused<KIND, FAM>(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, n_streams, n_per_stream, layout, d_words,
+        return encode_gaussian_fused<KIND, FAM, PT>(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, n_streams, n_per_stream, layout, d_words,
                                                 stride_words, d_n_words, d_state, d_rstate, d_status, flags, hs);
     return encode_two_pass<KIND>(cfg, n_streams, n_per_stream, layout, d_words, stride_words, d_n_words, d_state, d_rstate, d_status, flags, hs,
                                  [&](EncEntry* out, size_t n) {
-        hipLaunchKernelGGL(gaussian_entries_kernel<FAM>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hs, cfg.precision, min_symbol, max_symbol,
+        hipLaunchKernelGGL((gaussian_entries_kernel<FAM, PT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hs, cfg.precision, min_symbol, max_symbol,
                            d_symbols, d_a, d_b, n, out);
     });
 }
@@ -379,27 +385,63 @@ static cst_status encode_family(cst_coder_config cfg, int32_t min_symbol, int32_
 
 using namespace cst;
 
-extern "C" {
-
-cst_status cst_ans_encode_gaussian_batch(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
-                                         const double* d_means, const double* d_stds, size_t n_streams, size_t n_per_stream,
-                                         cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
-                                         uint64_t* d_state, int32_t* d_status, uint32_t flags, void* stream) {
+template <class PT>
+static cst_status ans_encode_gaussian_batch_impl(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                                 const PT* d_means, const PT* d_stds, size_t n_streams, size_t n_per_stream,
+                                                 cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                                 uint64_t* d_state, int32_t* d_status, uint32_t flags, void* stream) {
     if (n_per_stream > 0 && (!d_symbols || !d_means || !d_stds)) return CST_ERR_INVALID_ARGUMENT;
     if (max_symbol <= min_symbol || support_too_large(cfg, min_symbol, max_symbol)) return CST_ERR_MODEL;
     return encode_family<kAns, GaussianFamily>(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, n_streams, n_per_stream, layout, d_words,
                                                stride_words, d_n_words, d_state, nullptr, d_status, flags, (hipStream_t)stream);
 }
 
-cst_status cst_range_encode_gaussian_batch(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
-                                           const double* d_means, const double* d_stds, size_t n_streams, size_t n_per_stream,
-                                           cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
-                                           cst_range_state* d_rstate, int32_t* d_status, uint32_t flags, void* stream) {
+extern "C" {
+
+cst_status cst_ans_encode_gaussian_batch(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                         const double* d_means, const double* d_stds, size_t n_streams, size_t n_per_stream,
+                                         cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                         uint64_t* d_state, int32_t* d_status, uint32_t flags, void* stream) {
+    return ans_encode_gaussian_batch_impl(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, n_streams, n_per_stream, layout, d_words,
+           stride_words, d_n_words, d_state, d_status, flags, stream);
+}
+cst_status cst_ans_encode_gaussian_batch_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                             const void* d_means, const void* d_stds, size_t n_streams, size_t n_per_stream,
+                                             cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                             uint64_t* d_state, int32_t* d_status, uint32_t flags, void* stream) {
+    return ans_encode_gaussian_batch_impl(cfg, min_symbol, max_symbol, d_symbols, f32(d_means), f32(d_stds), n_streams, n_per_stream, layout, d_words,
+           stride_words, d_n_words, d_state, d_status, flags, stream);
+}
+
+} // extern "C"
+
+template <class PT>
+static cst_status range_encode_gaussian_batch_impl(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                                   const PT* d_means, const PT* d_stds, size_t n_streams, size_t n_per_stream,
+                                                   cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                                   cst_range_state* d_rstate, int32_t* d_status, uint32_t flags, void* stream) {
     if (n_per_stream > 0 && (!d_symbols || !d_means || !d_stds)) return CST_ERR_INVALID_ARGUMENT;
     if (max_symbol <= min_symbol || support_too_large(cfg, min_symbol, max_symbol)) return CST_ERR_MODEL;
     // (this call has never recorded its route with note_kernel())
     return encode_family<kRange, GaussianFamily>(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, n_streams, n_per_stream, layout, d_words,
                                                  stride_words, d_n_words, nullptr, d_rstate, d_status, flags, (hipStream_t)stream, false);
+}
+
+extern "C" {
+
+cst_status cst_range_encode_gaussian_batch(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                           const double* d_means, const double* d_stds, size_t n_streams, size_t n_per_stream,
+                                           cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                           cst_range_state* d_rstate, int32_t* d_status, uint32_t flags, void* stream) {
+    return range_encode_gaussian_batch_impl(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, n_streams, n_per_stream, layout, d_words,
+           stride_words, d_n_words, d_rstate, d_status, flags, stream);
+}
+cst_status cst_range_encode_gaussian_batch_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                               const void* d_means, const void* d_stds, size_t n_streams, size_t n_per_stream,
+                                               cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                               cst_range_state* d_rstate, int32_t* d_status, uint32_t flags, void* stream) {
+    return range_encode_gaussian_batch_impl(cfg, min_symbol, max_symbol, d_symbols, f32(d_means), f32(d_stds), n_streams, n_per_stream, layout,
+           d_words, stride_words, d_n_words, d_rstate, d_status, flags, stream);
 }
 
 // Jump points for the reference's flagship call (every symbol its own (mean, std)): the fused encoder notes AnsCoder::pos() in
@@ -408,35 +450,77 @@ cst_status cst_range_encode_gaussian_batch(cst_coder_config cfg, int32_t min_sym
 // s is row s * n_chunks + j of all three matrices viewed as [n_streams * n_chunks][interval].  What that buys: the lane decoder of
 // 65 536 streams is ONE wave per SIMD and spends a third of its cycles waiting; with two jump points per stream the small-geometry
 // kernel (LaneGeo<true>) runs two.
-cst_status cst_ans_encode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
-                                              const double* d_means, const double* d_stds, size_t n_streams, size_t n_per_stream,
-                                              cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
-                                              size_t ckpt_interval, uint32_t* d_ckpt_pos, uint64_t* d_ckpt_state, int32_t* d_status, void* stream) {
+} // extern "C"
+
+template <class PT>
+static cst_status ans_encode_gaussian_batch_ckpt_impl(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                                      const PT* d_means, const PT* d_stds, size_t n_streams, size_t n_per_stream,
+                                                      cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                                      size_t ckpt_interval, uint32_t* d_ckpt_pos, uint64_t* d_ckpt_state, int32_t* d_status, void* stream) {
     if (n_per_stream > 0 && (!d_symbols || !d_means || !d_stds)) return CST_ERR_INVALID_ARGUMENT;
     if (!d_ckpt_pos || !d_ckpt_state || ckpt_interval == 0 || ckpt_interval % kFuTile != 0 || n_per_stream % ckpt_interval != 0) return CST_ERR_INVALID_ARGUMENT;
     if (max_symbol <= min_symbol || support_too_large(cfg, min_symbol, max_symbol)) return CST_ERR_MODEL;
     if (n_streams == 0) return CST_OK;
-    return note_kernel(FamilyNames<GaussianFamily>::fused_ckpt[0], encode_gaussian_fused<kAns>(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, n_streams, n_per_stream, layout, d_words, stride_words,
+    return note_kernel(FamilyNames<GaussianFamily, PT>::fused_ckpt[0], encode_gaussian_fused<kAns, GaussianFamily, PT>(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, n_streams, n_per_stream, layout, d_words, stride_words,
                                        d_n_words, nullptr, nullptr, d_status, CST_FLAG_NONE, (hipStream_t)stream, ckpt_interval, d_ckpt_pos, d_ckpt_state));
+}
+
+extern "C" {
+
+cst_status cst_ans_encode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                              const double* d_means, const double* d_stds, size_t n_streams, size_t n_per_stream,
+                                              cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                              size_t ckpt_interval, uint32_t* d_ckpt_pos, uint64_t* d_ckpt_state, int32_t* d_status, void* stream) {
+    return ans_encode_gaussian_batch_ckpt_impl(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, n_streams, n_per_stream, layout, d_words,
+           stride_words, d_n_words, ckpt_interval, d_ckpt_pos, d_ckpt_state, d_status, stream);
+}
+cst_status cst_ans_encode_gaussian_batch_ckpt_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                                  const void* d_means, const void* d_stds, size_t n_streams, size_t n_per_stream,
+                                                  cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                                  size_t ckpt_interval, uint32_t* d_ckpt_pos, uint64_t* d_ckpt_state, int32_t* d_status, void* stream) {
+    return ans_encode_gaussian_batch_ckpt_impl(cfg, min_symbol, max_symbol, d_symbols, f32(d_means), f32(d_stds), n_streams, n_per_stream, layout,
+           d_words, stride_words, d_n_words, ckpt_interval, d_ckpt_pos, d_ckpt_state, d_status, stream);
 }
 
 // ... and for the range coder (round 6): the fused encoder notes RangeEncoder::pos() in front of every chunk, the decoder builds the
 // RangeDecoder::seek states of the (stream, chunk) pairs (point re-read at the jump point: range_ckpt_virtual_state) and runs them as
 // streams of their own -- the small-geometry lane decoder, two waves per SIMD, where the plain decoder of 65 536 streams has one
-cst_status cst_range_encode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
-                                                const double* d_means, const double* d_stds, size_t n_streams, size_t n_per_stream,
-                                                cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
-                                                size_t ckpt_interval, uint32_t* d_ckpt_pos, uint64_t* d_ckpt_lower, uint64_t* d_ckpt_range,
-                                                int32_t* d_status, void* stream) {
+} // extern "C"
+
+template <class PT>
+static cst_status range_encode_gaussian_batch_ckpt_impl(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                                        const PT* d_means, const PT* d_stds, size_t n_streams, size_t n_per_stream,
+                                                        cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                                        size_t ckpt_interval, uint32_t* d_ckpt_pos, uint64_t* d_ckpt_lower, uint64_t* d_ckpt_range,
+                                                        int32_t* d_status, void* stream) {
     if (n_per_stream > 0 && (!d_symbols || !d_means || !d_stds)) return CST_ERR_INVALID_ARGUMENT;
     if (!d_ckpt_pos || !d_ckpt_lower || !d_ckpt_range || ckpt_interval == 0 || ckpt_interval % kFuTile != 0 || n_per_stream % ckpt_interval != 0)
         return CST_ERR_INVALID_ARGUMENT;
     if (max_symbol <= min_symbol || support_too_large(cfg, min_symbol, max_symbol)) return CST_ERR_MODEL;
     if (n_streams == 0) return CST_OK;
-    return note_kernel(FamilyNames<GaussianFamily>::fused_ckpt[1],
-                       encode_gaussian_fused<kRange>(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, n_streams, n_per_stream, layout, d_words,
+    return note_kernel(FamilyNames<GaussianFamily, PT>::fused_ckpt[1],
+                       encode_gaussian_fused<kRange, GaussianFamily, PT>(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, n_streams, n_per_stream, layout, d_words,
                                                      stride_words, d_n_words, nullptr, nullptr, d_status, CST_FLAG_NONE, (hipStream_t)stream, ckpt_interval,
                                                      d_ckpt_pos, nullptr, d_ckpt_lower, d_ckpt_range));
+}
+
+extern "C" {
+
+cst_status cst_range_encode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                                const double* d_means, const double* d_stds, size_t n_streams, size_t n_per_stream,
+                                                cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                                size_t ckpt_interval, uint32_t* d_ckpt_pos, uint64_t* d_ckpt_lower, uint64_t* d_ckpt_range,
+                                                int32_t* d_status, void* stream) {
+    return range_encode_gaussian_batch_ckpt_impl(cfg, min_symbol, max_symbol, d_symbols, d_means, d_stds, n_streams, n_per_stream, layout, d_words,
+           stride_words, d_n_words, ckpt_interval, d_ckpt_pos, d_ckpt_lower, d_ckpt_range, d_status, stream);
+}
+cst_status cst_range_encode_gaussian_batch_ckpt_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                                    const void* d_means, const void* d_stds, size_t n_streams, size_t n_per_stream,
+                                                    cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words,
+                                                    size_t ckpt_interval, uint32_t* d_ckpt_pos, uint64_t* d_ckpt_lower, uint64_t* d_ckpt_range,
+                                                    int32_t* d_status, void* stream) {
+    return range_encode_gaussian_batch_ckpt_impl(cfg, min_symbol, max_symbol, d_symbols, f32(d_means), f32(d_stds), n_streams, n_per_stream, layout,
+           d_words, stride_words, d_n_words, ckpt_interval, d_ckpt_pos, d_ckpt_lower, d_ckpt_range, d_status, stream);
 }
 
 cst_status cst_chain_encode_gaussian_batch(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
@@ -471,6 +555,28 @@ cst_status cst_range_encode_family_batch(cst_coder_config cfg, int32_t family, i
     if (cst_status st = check_family_args(cfg, family, min_symbol, max_symbol, layout, d_symbols, d_a, d_b, d_words, d_n_words, d_status, d_rstate, flags))
         return st;
     return CST_FAMILY_CALL(encode_family, kRange, cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, n_streams, n_per_stream, layout, d_words, stride_words,
+                           d_n_words, nullptr, d_rstate, d_status, flags, (hipStream_t)stream);
+}
+
+// ---- the float32 twins (the header's "float32 parameters"): the originals' arguments with the arrays untyped, the same host templates ----
+
+cst_status cst_ans_encode_family_batch_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                           const void* d_a, const void* d_b, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                           uint32_t* d_words, size_t stride_words, uint32_t* d_n_words, uint64_t* d_state, int32_t* d_status,
+                                           uint32_t flags, void* stream) {
+    if (cst_status st = check_family_args(cfg, family, min_symbol, max_symbol, layout, d_symbols, f32(d_a), f32(d_b), d_words, d_n_words, d_status, d_state, flags))
+        return st;
+    return CST_FAMILY_CALL(encode_family, kAns, cfg, min_symbol, max_symbol, d_symbols, f32(d_a), f32(d_b), n_streams, n_per_stream, layout, d_words, stride_words,
+                           d_n_words, d_state, nullptr, d_status, flags, (hipStream_t)stream);
+}
+
+cst_status cst_range_encode_family_batch_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                             const void* d_a, const void* d_b, size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                             uint32_t* d_words, size_t stride_words, uint32_t* d_n_words, cst_range_state* d_rstate, int32_t* d_status,
+                                             uint32_t flags, void* stream) {
+    if (cst_status st = check_family_args(cfg, family, min_symbol, max_symbol, layout, d_symbols, f32(d_a), f32(d_b), d_words, d_n_words, d_status, d_rstate, flags))
+        return st;
+    return CST_FAMILY_CALL(encode_family, kRange, cfg, min_symbol, max_symbol, d_symbols, f32(d_a), f32(d_b), n_streams, n_per_stream, layout, d_words, stride_words,
                            d_n_words, nullptr, d_rstate, d_status, flags, (hipStream_t)stream);
 }
 

@@ -37,8 +37,8 @@ __device__ __forceinline__ uint32_t persymbol_wave_max(uint32_t v) {
 
 struct GaussianRaggedEncodeArgs {
     const int32_t* symbols;
-    const double* means;
-    const double* stds;
+    const void* means;               // PT arrays, PT the kernel's parameter type (cst_persymbol.hpp)
+    const void* stds;
     const uint64_t* sym_offsets;     // [n_streams + 1]
     size_t n_streams;
     const uint32_t* order;           // null, or [n_streams]
@@ -74,7 +74,7 @@ constexpr size_t kRgEncWaveBytes = kFuWaveBytes + kRgMetaBytes;
 // chunk j, whichever path through phase B codes it: a stack notes AFTER that tile (AnsCoder::pos() once the symbols from t0 on are
 // encoded), a queue BEFORE it (RangeEncoder::pos()), as encode_gaussian_fused_kernel notes its checkpoints.  Only where t0 < len: no
 // chunk starts at the end of a stream.
-template <int W, int S, int KIND, class FAM = GaussianFamily, bool JUMP = false>
+template <int W, int S, int KIND, class FAM = GaussianFamily, bool JUMP = false, class PT = double>
 __global__ __launch_bounds__(kFuBlock) void encode_gaussian_ragged_kernel(const std::conditional_t<JUMP, GaussianRaggedEncodeJumpArgs, GaussianRaggedEncodeArgs> a) {
     static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
     constexpr size_t kTabBytes = FAM::kErfTab ? kFuTabBytes : 0;
@@ -110,8 +110,10 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_ragged_kernel(const 
     // phase A's work items: item w = it * 64 + lane of a tile is (stream j = w / 16, symbol tl = w % 16): sixteen consecutive
     // lanes on consecutive elements of one stream's row.  Requested kFuAhead items ahead of their use, as in the fused kernel.
     int32_t sy_q[kFuAhead];
-    double mu_q[kFuAhead], sd_q[kFuAhead];
+    PT mu_q[kFuAhead], sd_q[kFuAhead];              // (widened where an item takes them up)
     bool ok_q[kFuAhead];
+    const PT* const means = params_as<PT>(a.means);
+    const PT* const stds = params_as<PT>(a.stds);
     const int item_t = lane & (kFuTile - 1), item_j0 = lane >> 4;
     auto request = [&](int slot, uint32_t k, int it) {
         const uint4 m = meta[it * (kWave / kFuTile) + item_j0];
@@ -121,8 +123,8 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_ragged_kernel(const 
         //  exists: a conditional load is waited for at once)
         const uint64_t e = ok_q[slot] ? ((((uint64_t)m.y) << 32) | (uint64_t)m.x) + t : 0;
         sy_q[slot] = __builtin_nontemporal_load(a.symbols + e);
-        mu_q[slot] = __builtin_nontemporal_load(a.means + e);
-        sd_q[slot] = __builtin_nontemporal_load(a.stds + e);
+        mu_q[slot] = __builtin_nontemporal_load(means + e);
+        sd_q[slot] = __builtin_nontemporal_load(stds + e);
     };
 
     const uint64_t slab_lo = !active ? 0 : (a.word_offsets ? a.word_offsets[s] : (uint64_t)s * a.stride_words);
@@ -156,7 +158,7 @@ __global__ __launch_bounds__(kFuBlock) void encode_gaussian_ragged_kernel(const 
             for (int q = 0; q < kFuAhead; ++q) {
                 const int it = it0 + q;
                 const int32_t sy = ok_q[q] ? sy_q[q] : a.lo;       // (items past their stream's end: never coded)
-                const double m = ok_q[q] ? mu_q[q] : 0.0, sg = ok_q[q] ? sd_q[q] : 1.0;
+                const double m = ok_q[q] ? (double)mu_q[q] : 0.0, sg = ok_q[q] ? (double)sd_q[q] : 1.0;
                 if (it + kFuAhead < kFuIters) request(q, k, it + kFuAhead);
                 else if (step + 1 < n_tiles) request(q, KIND == kAns ? k - 1u : k + 1u, it + kFuAhead - kFuIters);
                 uint32_t c = 0, p = 0;
@@ -373,7 +375,7 @@ static __device__ __noinline__ void store_symbol_tile_select(int32_t* sym, uint3
 // wave-wide loads and fences.
 // MODE: kRgPlain, kRgJump (a lane per table entry) or kRgSelect (a lane per piece of a query: `len` below is skip + len of the piece,
 // `sym_lo` where its PARAMETERS begin; the symbols in front of `skip` run through the same loop and only their stores are left out).
-template <int W, int S, int KIND, class FAM = GaussianFamily, int MODE = kRgPlain>
+template <int W, int S, int KIND, class FAM = GaussianFamily, int MODE = kRgPlain, class PT = double>
 __global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(const GaussianRaggedDecodeArgsOf<MODE> ra) {
     static_assert(KIND == kAns || KIND == kRange, "a stack or a queue");
     using G = LaneGeo<true>;
@@ -422,7 +424,9 @@ __global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(c
     // ---- parameter tiles: item w = it * 64 + lane of a tile is (stream j = w / 8, symbol tl = w % 8): eight consecutive lanes
     // on consecutive doubles of one stream's row, element sym_offsets[sj] + t0 + tl, predicated on len_sj (lane j's values, by
     // cross-lane read) ----
-    double mu_r[kParTile], sd_r[kParTile];
+    PT mu_r[kParTile], sd_r[kParTile];              // (widened where they land in the f64 tiles)
+    const PT* const means = params_as<PT>(a.means);
+    const PT* const stds = params_as<PT>(a.stds);
     const int item_t = lane & (kParTile - 1), item_j0 = lane / kParTile;
     auto par_request = [&](uint64_t t0) {
 #pragma unroll
@@ -432,15 +436,15 @@ __global__ __launch_bounds__(kRgDecThreads) void decode_gaussian_ragged_kernel(c
             const uint64_t t = t0 + (uint64_t)item_t;
             // (an element that does not exist: element 0, which does -- the wave has a symbol to decode)
             const uint64_t e = t < (uint64_t)(uint32_t)__shfl((int)len, j) ? off + t : 0;
-            mu_r[it] = __builtin_nontemporal_load(a.means + e);
-            sd_r[it] = __builtin_nontemporal_load(a.stds + e);
+            mu_r[it] = __builtin_nontemporal_load(means + e);
+            sd_r[it] = __builtin_nontemporal_load(stds + e);
         }
     };
     auto par_land = [&]() {
 #pragma unroll
         for (int it = 0; it < kParTile; ++it) {
-            par_mu[item_t * kParStride + it * (kWave / kParTile) + item_j0] = mu_r[it];
-            par_sd[item_t * kParStride + it * (kWave / kParTile) + item_j0] = sd_r[it];
+            par_mu[item_t * kParStride + it * (kWave / kParTile) + item_j0] = (double)mu_r[it];
+            par_sd[item_t * kParStride + it * (kWave / kParTile) + item_j0] = (double)sd_r[it];
         }
     };
     // ---- word window: as in the lane kernel (a tile of 8 symbols takes at most 8 words; the range coder's first S / W words

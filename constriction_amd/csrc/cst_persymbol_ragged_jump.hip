@@ -6,9 +6,9 @@
 
 namespace cst {
 
-template <int KIND, class FAM>
-static cst_status encode_ragged_jump(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols, const double* d_a,
-                                     const double* d_b, const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order, uint32_t* d_words,
+template <int KIND, class FAM, class PT>
+static cst_status encode_ragged_jump(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols, const PT* d_a,
+                                     const PT* d_b, const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order, uint32_t* d_words,
                                      const uint64_t* d_word_offsets, size_t stride_words, uint32_t* d_n_words, size_t jump_interval,
                                      const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos, uint64_t* d_jump_a, uint64_t* d_jump_b,
                                      int32_t* d_status, hipStream_t hs) {
@@ -26,23 +26,23 @@ static cst_status encode_ragged_jump(cst_coder_config cfg, int32_t min_symbol, i
     const size_t blocks = (n_streams + per_block - 1) / per_block;
     if (blocks > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
     const size_t lds = (FAM::kErfTab ? kFuTabBytes : 0) + (size_t)(kFuBlock / kWave) * kRgEncWaveBytes;
-    return note_kernel(FamilyNames<FAM>::ragged_jump[KIND == kRange][0], dispatch_word_size(cfg, [&](auto W, auto S) {
-        return launch_with_lds(encode_gaussian_ragged_kernel<W, S, KIND, FAM, true>, blocks, kFuBlock, lds, a, hs);
+    return note_kernel(FamilyNames<FAM, PT>::ragged_jump[KIND == kRange][0], dispatch_word_size(cfg, [&](auto W, auto S) {
+        return launch_with_lds(encode_gaussian_ragged_kernel<W, S, KIND, FAM, true, PT>, blocks, kFuBlock, lds, a, hs);
     }));
 }
 
 // (the table kernels around decode_gaussian_ragged_kernel<JUMP>: decode_jump_chunks, cst_persymbol_ragged.hpp)
-template <int KIND, class FAM>
+template <int KIND, class FAM, class PT>
 static cst_status decode_ragged_jump(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
                                      const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
-                                     const double* d_a, const double* d_b, int32_t* d_symbols, const uint64_t* d_sym_offsets, size_t n_streams,
+                                     const PT* d_a, const PT* d_b, int32_t* d_symbols, const uint64_t* d_sym_offsets, size_t n_streams,
                                      size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint32_t* d_jump_pos,
                                      const uint64_t* d_jump_a, const uint64_t* d_jump_b, void* d_scratch, int32_t* d_status, hipStream_t hs) {
     const cst_status plain = check_ragged_gaussian_args(cfg, min_symbol, max_symbol, d_symbols, d_a, d_b, d_sym_offsets, d_words, d_word_offsets,
                                                         stride_words, d_n_words, d_status, nullptr, n_streams);
     return decode_jump_chunks<KIND>(cfg, plain, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_symbols, d_sym_offsets, n_streams,
                                     jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_a, d_jump_b, d_scratch, d_status,
-                                    FamilyNames<FAM>::ragged_jump[KIND == kRange][1], hs,
+                                    FamilyNames<FAM, PT>::ragged_jump[KIND == kRange][1], hs,
                                     [&](const PerSymbolDecodeArgs& p, const PerSymbolJumpScratch& v) {
         GaussianRaggedChunkArgs a{};
         a.p = p; a.p.min_symbol = min_symbol; a.p.n_symbols = (int32_t)((int64_t)max_symbol - min_symbol + 1); a.p.means = d_a; a.p.stds = d_b;
@@ -50,7 +50,7 @@ static cst_status decode_ragged_jump(cst_coder_config cfg, int32_t min_symbol, i
         const size_t blocks = (p.n_streams + kRgDecThreads - 1) / kRgDecThreads;
         const size_t lds = FAM::kErfTab ? kRgDecLdsBytes : kRgDecLdsBytesNoTab;
         return dispatch_word_size(cfg, [&](auto W, auto S) {
-            return launch_with_lds(decode_gaussian_ragged_kernel<W, S, KIND, FAM, kRgJump>, blocks, kRgDecThreads, lds, a, hs);
+            return launch_with_lds(decode_gaussian_ragged_kernel<W, S, KIND, FAM, kRgJump, PT>, blocks, kRgDecThreads, lds, a, hs);
         });
     });
 }
@@ -146,6 +146,92 @@ cst_status cst_range_decode_family_ragged_jump(cst_coder_config cfg, int32_t fam
                                                void* d_scratch, int32_t* d_status, void* stream) {
     return CST_FAMILY_CALL(decode_ragged_jump, kRange, cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_a,
                              d_b, d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_lower,
+                             d_jump_range, d_scratch, d_status, (hipStream_t)stream);
+}
+
+// ---- the float32 twins (the header's "float32 parameters"): the originals' arguments with the arrays untyped, the same host templates ----
+
+cst_status cst_ans_encode_gaussian_ragged_jump_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                                   const void* d_means, const void* d_stds, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                   const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                   uint32_t* d_n_words, size_t jump_interval, const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos,
+                                                   uint64_t* d_jump_state, int32_t* d_status, void* stream) {
+    return encode_ragged_jump<kAns, GaussianFamily>(cfg, min_symbol, max_symbol, d_symbols, f32(d_means), f32(d_stds), d_sym_offsets, n_streams, d_order, d_words,
+                                                    d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos, d_jump_state,
+                                                    nullptr, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_ans_encode_family_ragged_jump_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                                 const void* d_a, const void* d_b, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                 const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                 uint32_t* d_n_words, size_t jump_interval, const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos,
+                                                 uint64_t* d_jump_state, int32_t* d_status, void* stream) {
+    return CST_FAMILY_CALL(encode_ragged_jump, kAns, cfg, min_symbol, max_symbol, d_symbols, f32(d_a), f32(d_b), d_sym_offsets, n_streams, d_order, d_words,
+                             d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos, d_jump_state, nullptr, d_status,
+                             (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_gaussian_ragged_jump_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                   const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                   const void* d_means, const void* d_stds, int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                                   size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                   const uint32_t* d_jump_pos, const uint64_t* d_jump_state, void* d_scratch, int32_t* d_status,
+                                                   void* stream) {
+    return decode_ragged_jump<kAns, GaussianFamily>(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, f32(d_means),
+                                                    f32(d_stds), d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+                                                    d_jump_pos, d_jump_state, nullptr, d_scratch, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_family_ragged_jump_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                 const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                 const void* d_a, const void* d_b, int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                                 size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                 const uint32_t* d_jump_pos, const uint64_t* d_jump_state, void* d_scratch, int32_t* d_status,
+                                                 void* stream) {
+    return CST_FAMILY_CALL(decode_ragged_jump, kAns, cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, f32(d_a),
+                             f32(d_b), d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_state,
+                             nullptr, d_scratch, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_encode_gaussian_ragged_jump_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                                     const void* d_means, const void* d_stds, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                     const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                     uint32_t* d_n_words, size_t jump_interval, const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos,
+                                                     uint64_t* d_jump_lower, uint64_t* d_jump_range, int32_t* d_status, void* stream) {
+    return encode_ragged_jump<kRange, GaussianFamily>(cfg, min_symbol, max_symbol, d_symbols, f32(d_means), f32(d_stds), d_sym_offsets, n_streams, d_order, d_words,
+                                                      d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos, d_jump_lower,
+                                                      d_jump_range, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_encode_family_ragged_jump_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const int32_t* d_symbols,
+                                                   const void* d_a, const void* d_b, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                   const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words,
+                                                   uint32_t* d_n_words, size_t jump_interval, const uint64_t* d_chunk_offsets, uint32_t* d_jump_pos,
+                                                   uint64_t* d_jump_lower, uint64_t* d_jump_range, int32_t* d_status, void* stream) {
+    return CST_FAMILY_CALL(encode_ragged_jump, kRange, cfg, min_symbol, max_symbol, d_symbols, f32(d_a), f32(d_b), d_sym_offsets, n_streams, d_order, d_words,
+                             d_word_offsets, stride_words, d_n_words, jump_interval, d_chunk_offsets, d_jump_pos, d_jump_lower, d_jump_range, d_status,
+                             (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_gaussian_ragged_jump_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                     const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                     const void* d_means, const void* d_stds, int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                                     size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                     const uint32_t* d_jump_pos, const uint64_t* d_jump_lower, const uint64_t* d_jump_range,
+                                                     void* d_scratch, int32_t* d_status, void* stream) {
+    return decode_ragged_jump<kRange, GaussianFamily>(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                                                      f32(d_means), f32(d_stds), d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+                                                      d_jump_pos, d_jump_lower, d_jump_range, d_scratch, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_family_ragged_jump_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                   const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                   const void* d_a, const void* d_b, int32_t* d_symbols, const uint64_t* d_sym_offsets,
+                                                   size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                   const uint32_t* d_jump_pos, const uint64_t* d_jump_lower, const uint64_t* d_jump_range,
+                                                   void* d_scratch, int32_t* d_status, void* stream) {
+    return CST_FAMILY_CALL(decode_ragged_jump, kRange, cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, f32(d_a),
+                             f32(d_b), d_symbols, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_lower,
                              d_jump_range, d_scratch, d_status, (hipStream_t)stream);
 }
 

@@ -7,10 +7,10 @@
 
 namespace cst {
 
-template <int KIND, class FAM>
+template <int KIND, class FAM, class PT>
 static cst_status decode_ragged_select(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
                                        const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
-                                       const double* d_a, const double* d_b, const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                       const PT* d_a, const PT* d_b, const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval,
                                        const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint32_t* d_jump_pos, const uint64_t* d_jump_a,
                                        const uint64_t* d_jump_b, const uint32_t* d_query_stream, const uint64_t* d_query_first,
                                        const uint64_t* d_query_count, size_t n_queries, const uint64_t* d_piece_offsets, size_t n_pieces_total,
@@ -53,13 +53,13 @@ static cst_status decode_ragged_select(cst_coder_config cfg, int32_t min_symbol,
         const size_t blocks = (n_pieces_total + kRgDecThreads - 1) / kRgDecThreads;
         const size_t lds = FAM::kErfTab ? kRgDecLdsBytes : kRgDecLdsBytesNoTab;
         const cst_status rc = dispatch_word_size(cfg, [&](auto W, auto S) {
-            return launch_with_lds(decode_gaussian_ragged_kernel<W, S, KIND, FAM, kRgSelect>, blocks, kRgDecThreads, lds, a, hs);
+            return launch_with_lds(decode_gaussian_ragged_kernel<W, S, KIND, FAM, kRgSelect, PT>, blocks, kRgDecThreads, lds, a, hs);
         });
         if (rc != CST_OK) return rc;
     }
     hipLaunchKernelGGL(ragged_select_status_kernel<0>, dim3(q_grid), dim3(256), 0, hs, b, v.folded(), d_status);
     CST_HIP_TRY(hipGetLastError());
-    return note_kernel(FamilyNames<FAM>::ragged_select[KIND == kRange], CST_OK);
+    return note_kernel(FamilyNames<FAM, PT>::ragged_select[KIND == kRange], CST_OK);
 }
 
 } // namespace cst
@@ -125,6 +125,67 @@ cst_status cst_range_decode_family_ragged_select(cst_coder_config cfg, int32_t f
                                                  const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
     return CST_FAMILY_CALL(decode_ragged_select, kRange, cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
                              d_a, d_b, d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_lower,
+                             d_jump_range, d_query_stream, d_query_first, d_query_count, n_queries, d_piece_offsets, n_pieces_total, d_symbols_out,
+                             d_out_offsets, d_scratch, d_status, (hipStream_t)stream);
+}
+
+// ---- the float32 twins (the header's "float32 parameters"): the originals' arguments with the arrays untyped, the same host templates ----
+
+cst_status cst_ans_decode_gaussian_ragged_select_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                     const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                     const void* d_means, const void* d_stds, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                     size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                     const uint32_t* d_jump_pos, const uint64_t* d_jump_state, const uint32_t* d_query_stream,
+                                                     const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                                     const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                                     const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    return decode_ragged_select<kAns, GaussianFamily>(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                                                      f32(d_means), f32(d_stds), d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+                                                      d_jump_pos, d_jump_state, nullptr, d_query_stream, d_query_first, d_query_count, n_queries,
+                                                      d_piece_offsets, n_pieces_total, d_symbols_out, d_out_offsets, d_scratch, d_status,
+                                                      (hipStream_t)stream);
+}
+
+cst_status cst_ans_decode_family_ragged_select_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                   const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity, const uint32_t* d_n_words,
+                                                   const void* d_a, const void* d_b, const uint64_t* d_sym_offsets, size_t n_streams,
+                                                   size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                   const uint32_t* d_jump_pos, const uint64_t* d_jump_state, const uint32_t* d_query_stream,
+                                                   const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                                   const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                                   const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    return CST_FAMILY_CALL(decode_ragged_select, kAns, cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                             f32(d_a), f32(d_b), d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_state, nullptr,
+                             d_query_stream, d_query_first, d_query_count, n_queries, d_piece_offsets, n_pieces_total, d_symbols_out, d_out_offsets,
+                             d_scratch, d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_gaussian_ragged_select_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol, const uint32_t* d_words,
+                                                       const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity,
+                                                       const uint32_t* d_n_words, const void* d_means, const void* d_stds,
+                                                       const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                       const uint64_t* d_chunk_offsets, size_t n_chunks_total, const uint32_t* d_jump_pos,
+                                                       const uint64_t* d_jump_lower, const uint64_t* d_jump_range, const uint32_t* d_query_stream,
+                                                       const uint64_t* d_query_first, const uint64_t* d_query_count, size_t n_queries,
+                                                       const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                                       const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    return decode_ragged_select<kRange, GaussianFamily>(cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                                                        f32(d_means), f32(d_stds), d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total,
+                                                        d_jump_pos, d_jump_lower, d_jump_range, d_query_stream, d_query_first, d_query_count,
+                                                        n_queries, d_piece_offsets, n_pieces_total, d_symbols_out, d_out_offsets, d_scratch,
+                                                        d_status, (hipStream_t)stream);
+}
+
+cst_status cst_range_decode_family_ragged_select_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                                     const uint32_t* d_words, const uint64_t* d_word_offsets, size_t stride_words, size_t words_capacity,
+                                                     const uint32_t* d_n_words, const void* d_a, const void* d_b, const uint64_t* d_sym_offsets,
+                                                     size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets, size_t n_chunks_total,
+                                                     const uint32_t* d_jump_pos, const uint64_t* d_jump_lower, const uint64_t* d_jump_range,
+                                                     const uint32_t* d_query_stream, const uint64_t* d_query_first, const uint64_t* d_query_count,
+                                                     size_t n_queries, const uint64_t* d_piece_offsets, size_t n_pieces_total, int32_t* d_symbols_out,
+                                                     const uint64_t* d_out_offsets, void* d_scratch, int32_t* d_status, void* stream) {
+    return CST_FAMILY_CALL(decode_ragged_select, kRange, cfg, min_symbol, max_symbol, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                             f32(d_a), f32(d_b), d_sym_offsets, n_streams, jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_lower,
                              d_jump_range, d_query_stream, d_query_first, d_query_count, n_queries, d_piece_offsets, n_pieces_total, d_symbols_out,
                              d_out_offsets, d_scratch, d_status, (hipStream_t)stream);
 }

@@ -389,11 +389,21 @@ cst_status cst_ans_encode_gaussian_ragged(cst_coder_config cfg, int32_t min_symb
                                           const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
                                           uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                           uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_ans_encode_gaussian_ragged_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                              const int32_t *d_symbols, const void *d_means, const void *d_stds,
+                                              const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                              uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                              uint32_t *d_n_words, int32_t *d_status, void *stream);
 cst_status cst_ans_decode_gaussian_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                           const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                           size_t words_capacity, const uint32_t *d_n_words, const double *d_means,
                                           const double *d_stds, int32_t *d_symbols, const uint64_t *d_sym_offsets,
                                           size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_gaussian_ragged_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                              const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                              size_t words_capacity, const uint32_t *d_n_words, const void *d_means,
+                                              const void *d_stds, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                              size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
 
 /* ... the same pair for the range coder (a queue: the decoder reads the symbols in the order they were written), and both coders
  * over QuantizedLaplace / QuantizedCauchy.  Arguments, checks, statuses and the order / word_offsets conventions are those of
@@ -409,31 +419,61 @@ cst_status cst_range_encode_gaussian_ragged(cst_coder_config cfg, int32_t min_sy
                                             const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
                                             uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                             uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_range_encode_gaussian_ragged_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                const int32_t *d_symbols, const void *d_means, const void *d_stds,
+                                                const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                                uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                uint32_t *d_n_words, int32_t *d_status, void *stream);
 cst_status cst_range_decode_gaussian_ragged(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                             const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                             size_t words_capacity, const uint32_t *d_n_words, const double *d_means,
                                             const double *d_stds, int32_t *d_symbols, const uint64_t *d_sym_offsets,
                                             size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
+cst_status cst_range_decode_gaussian_ragged_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                size_t words_capacity, const uint32_t *d_n_words, const void *d_means,
+                                                const void *d_stds, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                                size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
 cst_status cst_ans_encode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                         const int32_t *d_symbols, const double *d_a, const double *d_b,
                                         const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
                                         uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                         uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_ans_encode_family_ragged_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                            const int32_t *d_symbols, const void *d_a, const void *d_b,
+                                            const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                            uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                            uint32_t *d_n_words, int32_t *d_status, void *stream);
 cst_status cst_ans_decode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                         const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                         size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
                                         const double *d_b, int32_t *d_symbols, const uint64_t *d_sym_offsets,
                                         size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_family_ragged_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                            const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                            size_t words_capacity, const uint32_t *d_n_words, const void *d_a,
+                                            const void *d_b, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                            size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
 cst_status cst_range_encode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                           const int32_t *d_symbols, const double *d_a, const double *d_b,
                                           const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
                                           uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                           uint32_t *d_n_words, int32_t *d_status, void *stream);
+cst_status cst_range_encode_family_ragged_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                              const int32_t *d_symbols, const void *d_a, const void *d_b,
+                                              const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                              uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                              uint32_t *d_n_words, int32_t *d_status, void *stream);
 cst_status cst_range_decode_family_ragged(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                           const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                           size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
                                           const double *d_b, int32_t *d_symbols, const uint64_t *d_sym_offsets,
                                           size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
+cst_status cst_range_decode_family_ragged_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                              const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                              size_t words_capacity, const uint32_t *d_n_words, const void *d_a,
+                                              const void *d_b, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                              size_t n_streams, const uint32_t *d_order, int32_t *d_status, void *stream);
 
 /* Jump points (the reference's Pos / Seek: src/stream/stack.rs:1107-1139, src/stream/queue.rs:172-196, 900-926) for the eight calls above.
  * Their decoders are chains -- one lane walks one stream, a launch lasts as long as its longest stream -- so the encoder notes the
@@ -470,6 +510,13 @@ cst_status cst_ans_encode_gaussian_ragged_jump(cst_coder_config cfg, int32_t min
                                                uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
                                                uint32_t *d_jump_pos, uint64_t *d_jump_state, int32_t *d_status,
                                                void *stream);
+cst_status cst_ans_encode_gaussian_ragged_jump_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                   const int32_t *d_symbols, const void *d_means, const void *d_stds,
+                                                   const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                                   uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                   uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                   uint32_t *d_jump_pos, uint64_t *d_jump_state, int32_t *d_status,
+                                                   void *stream);
 cst_status cst_ans_decode_gaussian_ragged_jump(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                                const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                                size_t words_capacity, const uint32_t *d_n_words, const double *d_means,
@@ -478,6 +525,14 @@ cst_status cst_ans_decode_gaussian_ragged_jump(cst_coder_config cfg, int32_t min
                                                size_t n_chunks_total, const uint32_t *d_jump_pos,
                                                const uint64_t *d_jump_state, void *d_scratch, int32_t *d_status,
                                                void *stream);
+cst_status cst_ans_decode_gaussian_ragged_jump_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                   const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                   size_t words_capacity, const uint32_t *d_n_words, const void *d_means,
+                                                   const void *d_stds, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                                   size_t n_streams, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                   size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                                   const uint64_t *d_jump_state, void *d_scratch, int32_t *d_status,
+                                                   void *stream);
 cst_status cst_range_encode_gaussian_ragged_jump(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                                  const int32_t *d_symbols, const double *d_means, const double *d_stds,
                                                  const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
@@ -485,6 +540,13 @@ cst_status cst_range_encode_gaussian_ragged_jump(cst_coder_config cfg, int32_t m
                                                  uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
                                                  uint32_t *d_jump_pos, uint64_t *d_jump_lower, uint64_t *d_jump_range,
                                                  int32_t *d_status, void *stream);
+cst_status cst_range_encode_gaussian_ragged_jump_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                     const int32_t *d_symbols, const void *d_means, const void *d_stds,
+                                                     const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                                     uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                     uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                     uint32_t *d_jump_pos, uint64_t *d_jump_lower, uint64_t *d_jump_range,
+                                                     int32_t *d_status, void *stream);
 cst_status cst_range_decode_gaussian_ragged_jump(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                                  const uint32_t *d_words, const uint64_t *d_word_offsets,
                                                  size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
@@ -494,12 +556,27 @@ cst_status cst_range_decode_gaussian_ragged_jump(cst_coder_config cfg, int32_t m
                                                  const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
                                                  const uint64_t *d_jump_range, void *d_scratch, int32_t *d_status,
                                                  void *stream);
+cst_status cst_range_decode_gaussian_ragged_jump_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                     const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                     size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                     const void *d_means, const void *d_stds, int32_t *d_symbols,
+                                                     const uint64_t *d_sym_offsets, size_t n_streams, size_t jump_interval,
+                                                     const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                     const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
+                                                     const uint64_t *d_jump_range, void *d_scratch, int32_t *d_status,
+                                                     void *stream);
 cst_status cst_ans_encode_family_ragged_jump(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                              const int32_t *d_symbols, const double *d_a, const double *d_b,
                                              const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
                                              uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                              uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
                                              uint32_t *d_jump_pos, uint64_t *d_jump_state, int32_t *d_status, void *stream);
+cst_status cst_ans_encode_family_ragged_jump_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                                 const int32_t *d_symbols, const void *d_a, const void *d_b,
+                                                 const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                                 uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                 uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                 uint32_t *d_jump_pos, uint64_t *d_jump_state, int32_t *d_status, void *stream);
 cst_status cst_ans_decode_family_ragged_jump(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                              const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                              size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
@@ -508,6 +585,14 @@ cst_status cst_ans_decode_family_ragged_jump(cst_coder_config cfg, int32_t famil
                                              size_t n_chunks_total, const uint32_t *d_jump_pos,
                                              const uint64_t *d_jump_state, void *d_scratch, int32_t *d_status,
                                              void *stream);
+cst_status cst_ans_decode_family_ragged_jump_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                                 const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                 size_t words_capacity, const uint32_t *d_n_words, const void *d_a,
+                                                 const void *d_b, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                                 size_t n_streams, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                 size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                                 const uint64_t *d_jump_state, void *d_scratch, int32_t *d_status,
+                                                 void *stream);
 cst_status cst_range_encode_family_ragged_jump(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                                const int32_t *d_symbols, const double *d_a, const double *d_b,
                                                const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
@@ -515,6 +600,13 @@ cst_status cst_range_encode_family_ragged_jump(cst_coder_config cfg, int32_t fam
                                                uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
                                                uint32_t *d_jump_pos, uint64_t *d_jump_lower, uint64_t *d_jump_range,
                                                int32_t *d_status, void *stream);
+cst_status cst_range_encode_family_ragged_jump_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                                   const int32_t *d_symbols, const void *d_a, const void *d_b,
+                                                   const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
+                                                   uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                   uint32_t *d_n_words, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                   uint32_t *d_jump_pos, uint64_t *d_jump_lower, uint64_t *d_jump_range,
+                                                   int32_t *d_status, void *stream);
 cst_status cst_range_decode_family_ragged_jump(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                                const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                                size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
@@ -523,6 +615,14 @@ cst_status cst_range_decode_family_ragged_jump(cst_coder_config cfg, int32_t fam
                                                size_t n_chunks_total, const uint32_t *d_jump_pos,
                                                const uint64_t *d_jump_lower, const uint64_t *d_jump_range, void *d_scratch,
                                                int32_t *d_status, void *stream);
+cst_status cst_range_decode_family_ragged_jump_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                                   const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                   size_t words_capacity, const uint32_t *d_n_words, const void *d_a,
+                                                   const void *d_b, int32_t *d_symbols, const uint64_t *d_sym_offsets,
+                                                   size_t n_streams, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                   size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                                   const uint64_t *d_jump_lower, const uint64_t *d_jump_range, void *d_scratch,
+                                                   int32_t *d_status, void *stream);
 
 /* Random access into a ragged per-symbol batch: cst_{ans,range}_decode_ragged_select (below, where queries, pieces, d_out_offsets,
  * d_piece_offsets and the per-query statuses are described) for the eight decoders above.  The arguments are the model's (cfg, the
@@ -559,6 +659,17 @@ cst_status cst_ans_decode_gaussian_ragged_select(cst_coder_config cfg, int32_t m
                                                  const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
                                                  const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status,
                                                  void *stream);
+cst_status cst_ans_decode_gaussian_ragged_select_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                     const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                     size_t words_capacity, const uint32_t *d_n_words, const void *d_means,
+                                                     const void *d_stds, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                     size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                     const uint32_t *d_jump_pos, const uint64_t *d_jump_state,
+                                                     const uint32_t *d_query_stream, const uint64_t *d_query_first,
+                                                     const uint64_t *d_query_count, size_t n_queries,
+                                                     const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
+                                                     const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status,
+                                                     void *stream);
 cst_status cst_range_decode_gaussian_ragged_select(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                                    const uint32_t *d_words, const uint64_t *d_word_offsets,
                                                    size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
@@ -571,6 +682,18 @@ cst_status cst_range_decode_gaussian_ragged_select(cst_coder_config cfg, int32_t
                                                    const uint64_t *d_piece_offsets, size_t n_pieces_total,
                                                    int32_t *d_symbols_out, const uint64_t *d_out_offsets, void *d_scratch,
                                                    int32_t *d_status, void *stream);
+cst_status cst_range_decode_gaussian_ragged_select_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                       const uint32_t *d_words, const uint64_t *d_word_offsets,
+                                                       size_t stride_words, size_t words_capacity, const uint32_t *d_n_words,
+                                                       const void *d_means, const void *d_stds, const uint64_t *d_sym_offsets,
+                                                       size_t n_streams, size_t jump_interval, const uint64_t *d_chunk_offsets,
+                                                       size_t n_chunks_total, const uint32_t *d_jump_pos,
+                                                       const uint64_t *d_jump_lower, const uint64_t *d_jump_range,
+                                                       const uint32_t *d_query_stream, const uint64_t *d_query_first,
+                                                       const uint64_t *d_query_count, size_t n_queries,
+                                                       const uint64_t *d_piece_offsets, size_t n_pieces_total,
+                                                       int32_t *d_symbols_out, const uint64_t *d_out_offsets, void *d_scratch,
+                                                       int32_t *d_status, void *stream);
 cst_status cst_ans_decode_family_ragged_select(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                                const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                                size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
@@ -581,6 +704,16 @@ cst_status cst_ans_decode_family_ragged_select(cst_coder_config cfg, int32_t fam
                                                const uint64_t *d_query_count, size_t n_queries,
                                                const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
                                                const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status, void *stream);
+cst_status cst_ans_decode_family_ragged_select_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                                   const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                   size_t words_capacity, const uint32_t *d_n_words, const void *d_a,
+                                                   const void *d_b, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                   size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                   const uint32_t *d_jump_pos, const uint64_t *d_jump_state,
+                                                   const uint32_t *d_query_stream, const uint64_t *d_query_first,
+                                                   const uint64_t *d_query_count, size_t n_queries,
+                                                   const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
+                                                   const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status, void *stream);
 cst_status cst_range_decode_family_ragged_select(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                                  const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
                                                  size_t words_capacity, const uint32_t *d_n_words, const double *d_a,
@@ -592,6 +725,17 @@ cst_status cst_range_decode_family_ragged_select(cst_coder_config cfg, int32_t f
                                                  const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
                                                  const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status,
                                                  void *stream);
+cst_status cst_range_decode_family_ragged_select_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                                     const uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
+                                                     size_t words_capacity, const uint32_t *d_n_words, const void *d_a,
+                                                     const void *d_b, const uint64_t *d_sym_offsets, size_t n_streams,
+                                                     size_t jump_interval, const uint64_t *d_chunk_offsets, size_t n_chunks_total,
+                                                     const uint32_t *d_jump_pos, const uint64_t *d_jump_lower,
+                                                     const uint64_t *d_jump_range, const uint32_t *d_query_stream,
+                                                     const uint64_t *d_query_first, const uint64_t *d_query_count, size_t n_queries,
+                                                     const uint64_t *d_piece_offsets, size_t n_pieces_total, int32_t *d_symbols_out,
+                                                     const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status,
+                                                     void *stream);
 
 /* The range coder with ONE SHARED TABLE for streams of different lengths: cst_ans_{encode,decode}_ragged / cst_ans_count_until for the
  * reference's queue -- one RangeEncoder / RangeDecoder per document (src/stream/queue.rs), the symbols decoded in the order they were
@@ -780,12 +924,23 @@ cst_status cst_ans_encode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t min_
                                               size_t n_streams, size_t n_per_stream, cst_layout layout, uint32_t *d_words,
                                               size_t stride_words, uint32_t *d_n_words, size_t ckpt_interval,
                                               uint32_t *d_ckpt_pos, uint64_t *d_ckpt_state, int32_t *d_status, void *stream);
+cst_status cst_ans_encode_gaussian_batch_ckpt_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                  const int32_t *d_symbols, const void *d_means, const void *d_stds,
+                                                  size_t n_streams, size_t n_per_stream, cst_layout layout, uint32_t *d_words,
+                                                  size_t stride_words, uint32_t *d_n_words, size_t ckpt_interval,
+                                                  uint32_t *d_ckpt_pos, uint64_t *d_ckpt_state, int32_t *d_status, void *stream);
 cst_status cst_ans_decode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                               const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words,
                                               size_t words_capacity, size_t ckpt_interval, const uint32_t *d_ckpt_pos,
                                               const uint64_t *d_ckpt_state, const double *d_means, const double *d_stds,
                                               int32_t *d_symbols, size_t n_streams, size_t n_per_stream, void *d_scratch,
                                               int32_t *d_status, void *stream);
+cst_status cst_ans_decode_gaussian_batch_ckpt_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                  const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words,
+                                                  size_t words_capacity, size_t ckpt_interval, const uint32_t *d_ckpt_pos,
+                                                  const uint64_t *d_ckpt_state, const void *d_means, const void *d_stds,
+                                                  int32_t *d_symbols, size_t n_streams, size_t n_per_stream, void *d_scratch,
+                                                  int32_t *d_status, void *stream);
 
 /* The same for the range coder: RangeEncoder::pos() / RangeDecoder::seek (src/stream/queue.rs:172-196, 900-926; test
  * :1333-1396).  A jump point is (d_ckpt_pos[s][j] = words emitted so far INCLUDING held-back ones, (d_ckpt_lower[s][j],
@@ -927,6 +1082,20 @@ cst_status cst_scatter_rccl(void *comm, int32_t n_ranks, int32_t rank, int32_t r
                             uint64_t *d_offsets, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * float32 parameters.  Every call below that takes per-symbol parameter arrays as `const double *d_means, *d_stds`
+ * (`d_a`, `d_b`) has a twin NAME_f32 whose arrays hold float32 -- what a hyperprior or context model emits.  The twins take
+ * them as `const void *` (the Categorical calls' convention for matrices whose element type the call names) and differ
+ * from their originals in nothing else: same arguments, same refusals, same scratch-size helpers; each is declared right
+ * behind its original.  A C compiler cannot check the element type behind a `const void *`: pass arrays of `float`, never of
+ * `double`, to a NAME_f32.  The kernels read the
+ * floats themselves and widen them in registers (exactly: subnormals and signed zeros included), so every word, count,
+ * status and jump-table entry is bit-identical to NAME on the arrays widened to double -- which is what the reference
+ * computes for float32 callers (src/pybindings/mod.rs:187-214) -- without the widened copy.  cst_last_kernel_name()
+ * reports the original's name with `f32` added to its tag list ("ans_encode_gaussian_fused_kernel<f32>",
+ * "range_decode_gaussian_ragged_kernel<jump, f32>").  The chain coder's calls take doubles only.
+ * ---------------------------------------------------------------------------------------- */
+
+/* ------------------------------------------------------------------------------------------
  * per-symbol quantized Gaussians: the reference's flagship Python call
  *     coder.encode_reverse(symbols, QuantizedGaussian(min, max), means, stds)
  *     coder.decode(QuantizedGaussian(min, max), means, stds)
@@ -940,6 +1109,11 @@ cst_status cst_ans_encode_gaussian_batch(cst_coder_config cfg, int32_t min_symbo
                                          size_t n_streams, size_t n_per_stream, cst_layout layout,
                                          uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
                                          uint64_t *d_state, int32_t *d_status, uint32_t flags, void *stream);
+cst_status cst_ans_encode_gaussian_batch_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                             const int32_t *d_symbols, const void *d_means, const void *d_stds,
+                                             size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                             uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                             uint64_t *d_state, int32_t *d_status, uint32_t flags, void *stream);
 
 cst_status cst_ans_decode_gaussian_batch(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                          const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
@@ -947,6 +1121,12 @@ cst_status cst_ans_decode_gaussian_batch(cst_coder_config cfg, int32_t min_symbo
                                          int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
                                          cst_layout layout, uint64_t *d_state, uint32_t *d_n_words_out,
                                          int32_t *d_status, uint32_t flags, void *stream);
+cst_status cst_ans_decode_gaussian_batch_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                             const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
+                                             const uint32_t *d_n_words, const void *d_means, const void *d_stds,
+                                             int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
+                                             cst_layout layout, uint64_t *d_state, uint32_t *d_n_words_out,
+                                             int32_t *d_status, uint32_t flags, void *stream);
 
 /* QuantizedLaplace / QuantizedCauchy with per-symbol parameters (src/pybindings/stream/model.rs:736-900): the Gaussian calls
  * above over another CDF -- the same kernels, routes, slabs, offsets, words_capacity, CST_FLAG_RAW_STATE and layouts; no jump
@@ -961,6 +1141,11 @@ cst_status cst_ans_encode_family_batch(cst_coder_config cfg, int32_t family, int
                                        size_t n_streams, size_t n_per_stream, cst_layout layout,
                                        uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
                                        uint64_t *d_state, int32_t *d_status, uint32_t flags, void *stream);
+cst_status cst_ans_encode_family_batch_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                           const int32_t *d_symbols, const void *d_a, const void *d_b,
+                                           size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                           uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                           uint64_t *d_state, int32_t *d_status, uint32_t flags, void *stream);
 
 cst_status cst_ans_decode_family_batch(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                        const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
@@ -968,6 +1153,12 @@ cst_status cst_ans_decode_family_batch(cst_coder_config cfg, int32_t family, int
                                        int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
                                        cst_layout layout, uint64_t *d_state, uint32_t *d_n_words_out,
                                        int32_t *d_status, uint32_t flags, void *stream);
+cst_status cst_ans_decode_family_batch_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                           const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
+                                           const uint32_t *d_n_words, const void *d_a, const void *d_b,
+                                           int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
+                                           cst_layout layout, uint64_t *d_state, uint32_t *d_n_words_out,
+                                           int32_t *d_status, uint32_t flags, void *stream);
 
 /* Categorical models with per-symbol probability vectors (Categorical(perfect=False) / Categorical(lazy=True) with a rank-2 array of
  * probabilities, src/pybindings/stream/model/internals.rs:399-514): symbol (s, t) is coded with the "fast" quantisation
@@ -1125,6 +1316,11 @@ cst_status cst_range_encode_gaussian_batch(cst_coder_config cfg, int32_t min_sym
                                            size_t n_streams, size_t n_per_stream, cst_layout layout,
                                            uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
                                            cst_range_state *d_rstate, int32_t *d_status, uint32_t flags, void *stream);
+cst_status cst_range_encode_gaussian_batch_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                               const int32_t *d_symbols, const void *d_means, const void *d_stds,
+                                               size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                               uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                               cst_range_state *d_rstate, int32_t *d_status, uint32_t flags, void *stream);
 
 cst_status cst_range_decode_gaussian_batch(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                            const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
@@ -1132,6 +1328,12 @@ cst_status cst_range_decode_gaussian_batch(cst_coder_config cfg, int32_t min_sym
                                            int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
                                            cst_layout layout, cst_range_state *d_rstate, int32_t *d_status,
                                            uint32_t flags, void *stream);
+cst_status cst_range_decode_gaussian_batch_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                               const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
+                                               const uint32_t *d_n_words, const void *d_means, const void *d_stds,
+                                               int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
+                                               cst_layout layout, cst_range_state *d_rstate, int32_t *d_status,
+                                               uint32_t flags, void *stream);
 
 /* ... and over QuantizedLaplace / QuantizedCauchy (see cst_ans_encode_family_batch) */
 cst_status cst_range_encode_family_batch(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
@@ -1139,6 +1341,11 @@ cst_status cst_range_encode_family_batch(cst_coder_config cfg, int32_t family, i
                                          size_t n_streams, size_t n_per_stream, cst_layout layout,
                                          uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
                                          cst_range_state *d_rstate, int32_t *d_status, uint32_t flags, void *stream);
+cst_status cst_range_encode_family_batch_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                             const int32_t *d_symbols, const void *d_a, const void *d_b,
+                                             size_t n_streams, size_t n_per_stream, cst_layout layout,
+                                             uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
+                                             cst_range_state *d_rstate, int32_t *d_status, uint32_t flags, void *stream);
 
 cst_status cst_range_decode_family_batch(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
                                          const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
@@ -1146,6 +1353,12 @@ cst_status cst_range_decode_family_batch(cst_coder_config cfg, int32_t family, i
                                          int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
                                          cst_layout layout, cst_range_state *d_rstate, int32_t *d_status,
                                          uint32_t flags, void *stream);
+cst_status cst_range_decode_family_batch_f32(cst_coder_config cfg, int32_t family, int32_t min_symbol, int32_t max_symbol,
+                                             const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words, size_t words_capacity,
+                                             const uint32_t *d_n_words, const void *d_a, const void *d_b,
+                                             int32_t *d_symbols, size_t n_streams, size_t n_per_stream,
+                                             cst_layout layout, cst_range_state *d_rstate, int32_t *d_status,
+                                             uint32_t flags, void *stream);
 
 /* ... and over Categorical probability matrices (see cst_ans_encode_categorical_batch) */
 cst_status cst_range_encode_categorical_batch(cst_coder_config cfg, const int32_t *d_symbols, const void *d_probs, int32_t prob_bytes,
@@ -1384,6 +1597,12 @@ cst_status cst_range_encode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t mi
                                                 size_t stride_words, uint32_t *d_n_words, size_t ckpt_interval,
                                                 uint32_t *d_ckpt_pos, uint64_t *d_ckpt_lower, uint64_t *d_ckpt_range,
                                                 int32_t *d_status, void *stream);
+cst_status cst_range_encode_gaussian_batch_ckpt_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                    const int32_t *d_symbols, const void *d_means, const void *d_stds,
+                                                    size_t n_streams, size_t n_per_stream, cst_layout layout, uint32_t *d_words,
+                                                    size_t stride_words, uint32_t *d_n_words, size_t ckpt_interval,
+                                                    uint32_t *d_ckpt_pos, uint64_t *d_ckpt_lower, uint64_t *d_ckpt_range,
+                                                    int32_t *d_status, void *stream);
 size_t cst_range_gaussian_ckpt_scratch_bytes(size_t n_streams, size_t n_per_stream, size_t ckpt_interval);
 cst_status cst_range_decode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
                                                 const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words,
@@ -1392,6 +1611,13 @@ cst_status cst_range_decode_gaussian_batch_ckpt(cst_coder_config cfg, int32_t mi
                                                 const uint64_t *d_ckpt_range, const double *d_means, const double *d_stds,
                                                 int32_t *d_symbols, size_t n_streams, size_t n_per_stream, void *d_scratch,
                                                 int32_t *d_status, void *stream);
+cst_status cst_range_decode_gaussian_batch_ckpt_f32(cst_coder_config cfg, int32_t min_symbol, int32_t max_symbol,
+                                                    const uint32_t *d_words, const uint64_t *d_offsets, size_t stride_words,
+                                                    size_t words_capacity, const uint32_t *d_n_words, size_t ckpt_interval,
+                                                    const uint32_t *d_ckpt_pos, const uint64_t *d_ckpt_lower,
+                                                    const uint64_t *d_ckpt_range, const void *d_means, const void *d_stds,
+                                                    int32_t *d_symbols, size_t n_streams, size_t n_per_stream, void *d_scratch,
+                                                    int32_t *d_status, void *stream);
 
 cst_status cst_range_decode_rows_batch(cst_coder_config cfg, const uint32_t *d_words, const uint64_t *d_offsets,
                                        size_t stride_words, size_t words_capacity, const uint32_t *d_n_words, const uint32_t *d_cdf_rows,

@@ -3,12 +3,18 @@
 n_streams x n_per symbols, every symbol with its own two f64 parameters; both coders; round trip checked.
 
     bench_per_symbol.py [n_streams [n_per]] [--family gaussian laplace cauchy] [--support LO HI] [--rows] [--reps N] [--rounds K]
+                        [--params f64|f32|both]
     bench_per_symbol.py [n_streams [n_per]] --categorical K [--f64] [--reps N] [--rounds K]
     bench_per_symbol.py [n_streams [n_per]] --categorical K --perfect [--f64] [--reps N] [--rounds K]
 
 --family: one or more of gaussian (mean, std), laplace (mean, scale), cauchy (loc, scale); several families are timed in the
           same process on the same parameter matrices, alternating, `--rounds` times over: compare medians, look at the spread.
           Next to another family the Gaussian is also timed without jump points, which the other families do not have.
+--params: the element type of the parameter matrices.  f64 (default): float64 tensors.  f32: float32 tensors, read by the kernels
+          themselves (the _f32 entry points).  both: the SAME values (rounded to float32 first) through (a) the float64 call on tensors
+          widened beforehand, (b) the float32 call, and (c) what a float32 caller paid before the _f32 entry points: `.double()` of both
+          matrices inside the timed region plus the float64 call -- alternating like the families; the words of (a) and (b) and the
+          symbols they decode to are compared at the timed size.
 --rows:   also times what a caller of Laplace / Cauchy had before the family calls: one tabulated cdf row per symbol
           (family_cdf_rows) + cst_ans_encode_cp_batch / cst_ans_decode_rows_batch.  n_symbols + 1 words of row per symbol: keep
           the batch small (4096 x 256 at a 201-symbol support is 850 MB of rows).
@@ -39,6 +45,7 @@ ap.add_argument("--perfect", action="store_true")
 ap.add_argument("--family", nargs="+", choices=["gaussian", "laplace", "cauchy"], default=["gaussian"])
 ap.add_argument("--support", nargs=2, type=int, default=[-127, 127], metavar=("LO", "HI"))
 ap.add_argument("--rows", action="store_true")
+ap.add_argument("--params", choices=["f64", "f32", "both"], default="f64")
 ap.add_argument("--reps", type=int, default=3, help="calls per timed window")
 ap.add_argument("--rounds", type=int, default=1, help="timed windows per entry (the median and the range are printed)")
 args = ap.parse_args()
@@ -181,15 +188,31 @@ if args.categorical:
 g = torch.Generator(device="cuda").manual_seed(1)
 means = (torch.rand((n_streams, n_per), generator=g, device="cuda", dtype=torch.float64) * 20 - 10)
 stds = torch.exp(torch.rand((n_streams, n_per), generator=g, device="cuda", dtype=torch.float64) * 3.4 - 0.7)
+means32 = stds32 = None
+if args.params != "f64":                     # float32-representable values: every form below codes the same models
+    means32, stds32 = means.float(), stds.float()
+    means, stds = means32.double(), stds32.double()
 sym = torch.clamp(torch.round(torch.randn((n_streams, n_per), generator=g, device="cuda", dtype=torch.float64) * stds + means), lo, hi).to(torch.int32)
+# (label, parameter matrices as the call gets them): "widen" = float32 matrices that the timed call itself widens first
+PARAM_FORMS = {"f64": [("", "f64")], "f32": [(" f32", "f32")],
+               "both": [(" (a) f64, widened beforehand", "f64"), (" (b) f32", "f32"), (" (c) f32 + .double() inside", "widen")]}[args.params]
 
 
-def family_calls(family, coder, jump_points="auto"):
+def params_of(form):
+    if form == "f64":
+        return lambda: (means, stds)
+    if form == "f32":
+        return lambda: (means32, stds32)
+    return lambda: (means32.double(), stds32.double())
+
+
+def family_calls(family, coder, jump_points="auto", form="f64"):
+    par = params_of(form)
     if family == "gaussian":
         enc_f, dec_f = getattr(B, f"{coder}_encode_gaussian"), getattr(B, f"{coder}_decode_gaussian")
-        return (lambda: enc_f(sym, lo, hi, means, stds, jump_points=jump_points)), (lambda enc: dec_f(enc, lo, hi, means, stds))
+        return (lambda: enc_f(sym, lo, hi, *par(), jump_points=jump_points)), (lambda enc: dec_f(enc, lo, hi, *par()))
     enc_f, dec_f = getattr(B, f"{coder}_encode_family"), getattr(B, f"{coder}_decode_family")
-    return (lambda: enc_f(family, sym, lo, hi, means, stds)), (lambda enc: dec_f(family, enc, lo, hi, means, stds))
+    return (lambda: enc_f(family, sym, lo, hi, *par())), (lambda enc: dec_f(family, enc, lo, hi, *par()))
 
 
 def rows_calls(family, coder):
@@ -232,9 +255,10 @@ def rows_calls(family, coder):
 entries = []
 for coder in ("ans", "range"):
     for family in args.family:
-        entries.append((coder, family, "", *family_calls(family, coder)))
-        if family == "gaussian" and len(args.family) > 1:      # the other families have no jump points: like for like
-            entries.append((coder, family, " without jump points", *family_calls(family, coder, 0)))
+        for label, form in PARAM_FORMS:
+            entries.append((coder, family, label, *family_calls(family, coder, form=form)))
+            if family == "gaussian" and len(args.family) > 1:      # the other families have no jump points: like for like
+                entries.append((coder, family, label + " without jump points", *family_calls(family, coder, 0, form)))
         if args.rows and family != "gaussian":
             entries.append((coder, family, " by rows", *rows_calls(family, coder)))
 results = {i: ([], []) for i in range(len(entries))}
@@ -244,6 +268,15 @@ for i, (coder, family, how, enc_f, dec_f) in enumerate(entries):          # warm
     dec, st = dec_f(encoded[i])
     torch.cuda.synchronize()
     checked[i] = bool(torch.equal(dec, sym)) and int(st.abs().sum()) == 0
+if args.params == "both":                                                   # (a) against (b): the same words, stream for stream
+    for i, (coder, family, how, _, _) in enumerate(entries):
+        if "(b)" not in how:
+            continue
+        j = next(k for k, e in enumerate(entries) if e[:2] == (coder, family) and e[2] == how.replace("(b) f32", "(a) f64, widened beforehand"))
+        x, y = encoded[i], encoded[j]
+        col = torch.arange(x.words.shape[1], device="cuda")[None, :] < x.n_words[:, None]
+        same = bool(torch.equal(x.n_words, y.n_words)) and bool(torch.equal(x.status, y.status)) and bool(torch.equal(x.words * col, y.words * col))
+        print(f"{coder:5s} per-symbol {family}{how}: words, counts and statuses equal to (a): {same}")
 for _ in range(args.rounds):                                                # alternating: every entry once per round
     for i, (coder, family, how, enc_f, dec_f) in enumerate(entries):
         e, enc = timed(enc_f, args.reps)

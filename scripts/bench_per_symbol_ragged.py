@@ -23,6 +23,12 @@ from the rows) in place of (mean, std) -- symbols x K x 4 bytes for the ragged b
 --perfect (with --family categorical): Categorical(perfect=True) -- the *_categorical_perfect_ragged calls beside *_categorical(...,
 perfect=True).  A wave quantises ONE row (millions of rows a second, not billions): take a batch of minutes, not hours, with --streams,
 --min-len and --max-len.
+--params f64|f32|both (gaussian, laplace, cauchy; default f64): the element type of the parameter arrays.  f32: float32 arrays
+everywhere, read by the kernels themselves (the _f32 entry points).  both: the values are rounded to float32 first, everything above
+runs on them widened beforehand, and (p) times the ragged pair -- with --jump-every's table and --select's ranges where those are given --
+through (a) the float64 call on the arrays widened beforehand, (b) the float32 call, and (c) what a float32 caller paid before:
+`.double()` of both arrays inside the timed region plus the float64 call; alternating, medians and ranges; the words, tables and
+decoded symbols of (a) and (b) are compared at the timed size.
 Device events on the launch stream, warmed up, in one process, the candidates alternating, medians of the alternations.  Every
 stream is checked by the decode round trip.  The one condition: (a) is faster than (b) in every alternation (exit status 1 otherwise);
 (c) is a recorded ratio."""
@@ -43,11 +49,13 @@ ap.add_argument("--k", type=int, default=16, help="--family categorical: entries
 ap.add_argument("--perfect", action="store_true", help="--family categorical: Categorical(perfect=True), quantised by the device quantiser")
 ap.add_argument("--jump-every", type=int, default=0, help="also time the pair with a jump point every N symbols (a multiple of 16)")
 ap.add_argument("--select", type=int, default=0, help="also time random access: N whole streams, and N ranges of 64 symbols")
+ap.add_argument("--params", choices=["f64", "f32", "both"], default="f64", help="element type of the parameter arrays (see above)")
 ap.add_argument("--skip-rectangular", action="store_true", help="leave (c), the rectangular matrix, out")
 ap.add_argument("--skip-grouped", action="store_true", help="leave (b), one rectangular call per distinct length, out")
 args = ap.parse_args()
 assert args.alternations >= 5 or args.streams < 16384, "the recorded figures are medians of at least five alternations"
 assert not args.perfect or args.family == "categorical", "--perfect goes with --family categorical"
+assert args.params == "f64" or args.family != "categorical", "--params is about (mean, std) / (a, b) arrays"
 
 CFG, LO, HI = (32, 64, 24), -100, 100
 torch.manual_seed(1)
@@ -57,8 +65,9 @@ enc_ragged, dec_ragged = getattr(B, f"{args.coder}_encode_{FORM}_ragged"), getat
 enc_rect, dec_rect = getattr(B, f"{args.coder}_encode_{args.family}"), getattr(B, f"{args.coder}_decode_{args.family}")
 if args.perfect:
     enc_rect, dec_rect = functools.partial(enc_rect, perfect=True), functools.partial(dec_rect, perfect=True)
-JUMP_KERNEL = f"{args.coder}_decode_categorical_perfect_ragged_by_rows<jump>" if args.perfect else f"{args.coder}_decode_{args.family}_ragged_kernel<jump>"
-SELECT_KERNEL = JUMP_KERNEL.replace("<jump>", "<select>")
+F32_TAG = ", f32" if args.params == "f32" else ""
+JUMP_KERNEL = f"{args.coder}_decode_categorical_perfect_ragged_by_rows<jump>" if args.perfect else f"{args.coder}_decode_{args.family}_ragged_kernel<jump{F32_TAG}>"
+SELECT_KERNEL = JUMP_KERNEL.replace("<jump", "<select")
 NO_JUMP = {"jump_points": 0} if args.family == "gaussian" else {}      # (the family calls have no jump points to switch off)
 CATEGORICAL = args.family == "categorical"
 HEAD = () if CATEGORICAL else (LO, HI)                                  # what the calls take in front of the model's tensors
@@ -77,13 +86,15 @@ def draw(*shape):
     mu = (torch.rand(*shape, dtype=torch.float64, device=dev) * 2 - 1) * (0.6 * HI)
     sd = torch.exp(torch.log(torch.tensor(0.3, dtype=torch.float64, device=dev))
                    + torch.rand(*shape, dtype=torch.float64, device=dev) * torch.log(torch.tensor(40.0 / 0.3, dtype=torch.float64, device=dev)))
+    if args.params != "f64":                   # float32-representable values: every form codes the same models
+        mu, sd = mu.float().double(), sd.float().double()
     if args.family == "gaussian":
         noise = torch.randn(*shape, dtype=torch.float64, device=dev)
     else:
         u = torch.rand(*shape, dtype=torch.float64, device=dev) - 0.5
         noise = -torch.sign(u) * torch.log1p(-2 * u.abs()) if args.family == "laplace" else torch.tan(torch.pi * u)
     sym = torch.clamp(torch.round(mu + sd * noise), LO, HI).to(torch.int32)
-    return sym, (mu, sd)
+    return sym, ((mu.float(), sd.float()) if args.params == "f32" else (mu, sd))
 
 
 def timed(fn):
@@ -237,6 +248,48 @@ if args.select:
     select_info = {"queries": args.select, "whole_symbols": int(idx_whole.numel()), "range_symbols": int(idx_range.numel()),
                    "table_every": args.jump_every}
     del out_all, idx_whole, idx_range, want_whole, want_range
+# ---- (p): float32 parameters, beside the float64 call and the conversion a float32 caller paid before ----
+ok_p, t_p, params_info = True, {}, None
+if args.params == "both":
+    m32 = tuple(m.float() for m in model)
+    widened = lambda: tuple(m.double() for m in m32)
+    je = {"jump_every": args.jump_every} if args.jump_every else {}
+    enc_a = enc_j if args.jump_every else enc
+    enc_b = enc_ragged(sym, offsets, *HEAD, *m32, CFG, **je)
+    name_b = B.last_kernel()
+    dec_b, st_b = dec_ragged(enc_b, offsets, *HEAD, *m32)
+    name_b = (name_b, B.last_kernel())
+    torch.cuda.synchronize()
+    same = bool(torch.equal(enc_b.n_words, enc_a.n_words)) and bool(torch.equal(enc_b.status, enc_a.status)) and \
+        bool(torch.equal(enc_b.word_offsets, enc_a.word_offsets))
+    if same:                                   # every stream's words (what lies behind them in a slab was never written)
+        pos = torch.arange(enc_a.words.numel(), dtype=torch.int64, device=dev)
+        owner = torch.searchsorted(enc_a.word_offsets[1:].contiguous(), pos, right=True).clamp(max=n - 1)
+        written = pos < enc_a.word_offsets[owner] + enc_a.n_words[owner]
+        same = bool(torch.equal(enc_b.words[written], enc_a.words[written]))
+        del pos, owner, written
+    if args.jump_every:
+        k = int(enc_a.jump.chunk_offsets[-1])
+        fields = ("pos", "state") if args.coder == "ans" else ("pos", "lower", "range")
+        same = same and all(bool(torch.equal(getattr(enc_b.jump, f)[:k], getattr(enc_a.jump, f)[:k])) for f in fields)
+    ok_p = same and all("f32" in x for x in name_b) and bool(torch.equal(dec_b, sym)) and int(st_b.abs().sum()) == 0
+    dec_p = torch.empty_like(sym)
+    cands = {"a_encode": lambda: enc_ragged(sym, offsets, *HEAD, *model, CFG, **je),
+             "b_encode": lambda: enc_ragged(sym, offsets, *HEAD, *m32, CFG, **je),
+             "c_encode": lambda: enc_ragged(sym, offsets, *HEAD, *widened(), CFG, **je),
+             "a_decode": lambda: dec_ragged(enc_a, offsets, *HEAD, *model, out=dec_p),
+             "b_decode": lambda: dec_ragged(enc_a, offsets, *HEAD, *m32, out=dec_p),
+             "c_decode": lambda: dec_ragged(enc_a, offsets, *HEAD, *widened(), out=dec_p),
+             "conversion_alone": widened}
+    if args.select:
+        got_b = sel_ragged(enc_a, offsets, *HEAD, *m32, q_streams, q_first, q_count)
+        ok_p = ok_p and "f32" in B.last_kernel() and bool(torch.equal(got_b[0], sym[gather_index(q_first, q_count)])) and int(got_b[2].abs().sum()) == 0
+        cands.update({"a_select_ranges": lambda: sel_ragged(enc_a, offsets, *HEAD, *model, q_streams, q_first, q_count),
+                      "b_select_ranges": lambda: sel_ragged(enc_a, offsets, *HEAD, *m32, q_streams, q_first, q_count),
+                      "c_select_ranges": lambda: sel_ragged(enc_a, offsets, *HEAD, *widened(), q_streams, q_first, q_count)})
+    t_p = alternate(cands, args.alternations)
+    params_info = {"kernels": list(name_b), "same_words_tables_symbols": ok_p, "jump_every": args.jump_every}
+    del m32, dec_p, enc_b, dec_b
 if args.jump_every:
     del enc_j, dec_j
 
@@ -295,6 +348,14 @@ if args.select:
     print(f"      all {n} streams in order through the select call: {m_s['select_all']:9.3f} ms"
           + (f" against {m_s['full_jump']:9.3f} ms of the jump decode ({m_s['select_all'] / m_s['full_jump']:.2f}x)" if args.jump_every else "")
           + f"  symbols ok={ok_s}")
+if args.params == "both":
+    spread_p = lambda k: f"{statistics.median(t_p[k]):9.3f} ms ({min(t_p[k]):.3f} - {max(t_p[k]):.3f})"
+    print(f"  (p) float32 parameters{f', a jump point every {args.jump_every} symbols' if args.jump_every else ''}: {params_info['kernels']}, "
+          f"words, tables and symbols equal to the float64 call's: {ok_p}")
+    for what in ["encode", "decode"] + (["select_ranges"] if args.select else []):
+        print(f"      {what:14s} (a) f64, widened beforehand {spread_p('a_' + what)}  (b) f32 {spread_p('b_' + what)}  "
+              f"(c) f32 + .double() inside {spread_p('c_' + what)}")
+    print(f"      the conversion alone (two .double()): {spread_p('conversion_alone')}")
 if args.skip_rectangular:
     print("  (c) rectangular matrix:        left out (--skip-rectangular)")
 else:
@@ -304,5 +365,6 @@ else:
 print(json.dumps({"coder": args.coder, "family": args.family, "perfect": args.perfect, "k": args.k if CATEGORICAL else None, "grouped": not args.skip_grouped, "streams": n, "symbols": total, "alternations": args.alternations, "ms": {**m_ab, **m_c}, "all_ms": {**t_ab, **t_c},
                   "jump": jump_info, "jump_ms": {k: med(v) for k, v in t_j.items()}, "jump_all_ms": t_j,
                   "select": select_info, "select_ms": {k: med(v) for k, v in t_s.items()}, "select_all_ms": t_s,
-                  "a_faster_than_b": faster, "round_trips_ok": ok_a and ok_b and ok_c and ok_j and ok_s}))
-sys.exit(0 if faster and ok_a and ok_b and ok_c and ok_j and ok_s else 1)
+                  "params": args.params, "params_info": params_info, "params_ms": {k: med(v) for k, v in t_p.items()}, "params_all_ms": t_p,
+                  "a_faster_than_b": faster, "round_trips_ok": ok_a and ok_b and ok_c and ok_j and ok_s and ok_p}))
+sys.exit(0 if faster and ok_a and ok_b and ok_c and ok_j and ok_s and ok_p else 1)
