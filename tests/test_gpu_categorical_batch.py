@@ -5,8 +5,10 @@ probability rows quantised inside the coder kernels.
 
 Every expected word and symbol comes from the CPU oracle: one tabulated model per symbol over oracle.categorical_fast_cdf (f32 rows
 in f32, f64 rows in f64), fed to one oracle coder per stream.  No GPU result is the reference for another.  The rows are
-Dirichlet(0.3) draws with exact zeros inside and a last entry of at least 1e-3 of the sum, so that the reference's table is never
-degenerate (an f32 row that ENDS in a zero can have an empty last interval: that case is tested on its own below)."""
+Dirichlet(0.3) draws with exact zeros inside and a last entry of at least 1e-3 of the sum: every table here is strictly increasing
+(an f32 row that ENDS in a zero can have an empty last interval: that case is tested on its own below).  The degenerate tables --
+tiny sums with an infinite scale, sums at the edges of the normal range -- and every other hard row go through these kernels in
+tests/test_gpu_categorical_extremes.py."""
 import ctypes as C
 
 import numpy as np

@@ -5,8 +5,9 @@ Every expected word, count and jump table comes from the CPU oracle alone: one t
 oracle.categorical_fast_cdf (f32 rows in f32, f64 rows in f64) fed to one oracle coder per stream, and the same coder coded chunk by chunk
 for the tables (tests/persymbol_jump_oracle.py).  No GPU result is the reference for another, except where a test says that two GPU
 calls must agree.  Rows and symbols are drawn by the recipe of tests/test_gpu_categorical_batch.py::workload: unnormalised Dirichlet(0.3)
-rows with exact zeros inside, a last entry of at least 2e-3 of the sum (the reference's table is never degenerate), and symbols 0 and
-K - 1 in front of every stream.  A batch and its oracle results are built once per key, shared, and never modified."""
+rows with exact zeros inside, a last entry of at least 2e-3 of the sum (every table here is strictly increasing; the degenerate ones
+are run through these kernels by tests/test_gpu_categorical_extremes.py), and symbols 0 and K - 1 in front of every stream.  A batch
+and its oracle results are built once per key, shared, and never modified."""
 import numpy as np
 import pytest
 

@@ -4,7 +4,8 @@ batched.{ans,range}_decode_categorical[_perfect]_ragged_select and the C entry p
 The expected symbols are always slices of the INPUT symbols (exact integers, no tolerance): the batches are encoded with
 batched.*_categorical[_perfect]_ragged(jump_every=...), whose words and tables tests/test_gpu_categorical_ragged.py and
 tests/test_gpu_categorical_perfect_ragged.py pin to the CPU oracle.  No GPU result is the reference for another, except where a test
-says that two GPU calls must agree.  The workloads are those two files' (only the symbols and the rows: no oracle model is built here);
+says that two GPU calls must agree.  The workloads are those two files' (only the symbols and the rows: no oracle model is built here;
+every table is strictly increasing -- queries on and next to degenerate and refused rows are in tests/test_gpu_categorical_extremes.py);
 a batch is encoded once per (coder, quantiser, preset, lengths, K, dtype, interval)."""
 import ctypes as C
 import dataclasses
