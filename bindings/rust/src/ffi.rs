@@ -143,6 +143,21 @@ extern "C" {
         out: *mut *mut CstModel,
     ) -> CstStatus;
 
+    /// One table PER STREAM from cdf rows that are in device memory already: d_cdfs [n_tables][n_symbols + 1], row s the table of
+    /// stream s -- the general form of cst_model_create_gaussian_per_stream (the same limits: precision <= 16, at most 1023 symbols
+    /// for the coding calls; the same kernels code with it) and the inverse of cst_model_copy_cdfs.  The rows are copied on `stream`;
+    /// every row is validated on the device as cst_model_create_table validates its one row (cdf[0] = 0 < cdf[1] < ... < cdf[n] = 2^P),
+    /// and one bad row makes the call return CST_ERR_MODEL.  Rows fitted to data come from cst_fit_cdf_rows.
+    pub fn cst_model_create_tables_per_stream(
+        precision: i32,
+        min_symbol: i32,
+        n_symbols: i32,
+        d_cdfs: *const u32,
+        n_tables: usize,
+        stream: *mut c_void,
+        out: *mut *mut CstModel,
+    ) -> CstStatus;
+
     /// A tabulated model over an ARBITRARY alphabet of distinct i32 symbols (NonContiguousCategoricalEncoderModel /
     /// NonContiguousLookupDecoderModel, src/stream/model/categorical/{non_contiguous,lookup_noncontiguous}.rs:429-470, 602-646):
     /// h_symbols[i] is the symbol with left cumulative h_cdf[i].  The model proper works on the indices 0..n-1; the two
@@ -2091,6 +2106,7 @@ extern "C" {
     ///   CST_AUTO_JUMP=0          cst_jump_points_auto* answer 0                  CST_RAGGED_GROUP=8|16|32   ragged encoder: symbols per memory point
     ///   CST_PERFECT_RAGGED_BUDGET=n   ragged Categorical(perfect=True) decoders: 32-bit words of tabulated rows per step (default 16777216 = 64 MiB)
     ///   CST_INDEXED_BUCKET_BITS=0..8  table sets built from now on: the most bits of bucket index (default 8; 0: the indexed decoders search whole rows)
+    ///   CST_FIT_REPLICAS=1|2|4|8  cst_count_symbols: the most LDS replicas of a bin (default 8)      CST_FIT_WAVE_UNIFORM=0   ... no single add for a wave of one bin
     /// (CST_RCCL_LIB=<path>, read at the first collective call, names the RCCL library to open.)
     /// cst_debug_reload_knobs re-reads them: for tests that drive several paths inside one process; not thread-safe against
     /// concurrent coder calls.
@@ -2520,6 +2536,72 @@ extern "C" {
         h_rows: *mut u32,
         h_bad: *mut i32,
         h_moves: *mut u32,
+    ) -> CstStatus;
+
+    /// Fitting table models to the data ON THE DEVICE (static two-pass coding: count, quantise, code).
+    ///
+    /// cst_count_symbols: histograms of n_total int32 symbols.  d_indices == NULL (n_tables must be 1): one histogram of the whole
+    /// array.  Otherwise symbol i counts into row d_indices[i] of d_counts [n_tables][n_symbols]; index_bytes is 1 (uint8) or 4
+    /// (int32) as in the indexed coders.  A symbol outside [min_symbol, min_symbol + n_symbols) or with an index outside [0, n_tables)
+    /// goes into no bin and adds one to *d_outside.  1 <= n_tables <= 256, 2 <= n_symbols <= 65536, n_total < 2^31.
+    ///
+    /// cst_count_symbols_per_stream: one histogram per stream, d_counts [n_streams][n_symbols], 2 <= n_symbols <= 1024.  The input is
+    /// stream-major with n_per_stream symbols per stream, or ragged with d_sym_offsets [n_streams + 1] (stream s is the flat range
+    /// [d_sym_offsets[s], d_sym_offsets[s + 1]), as in the ragged coders; n_per_stream is ignored then).  Fewer than 2^31 symbols in all.
+    ///
+    /// Both zero d_counts and *d_outside themselves on `stream`; n_total == 0 returns CST_OK with zeroed counts.  NULL pointers, a bad
+    /// index_bytes and sizes outside the limits return CST_ERR_INVALID_ARGUMENT before the device is touched.
+    ///
+    /// cst_fit_cdf_rows: row r of d_rows [n_rows][n_symbols + 1] is what Categorical(counts[r] as f64, perfect) tabulates: the counts
+    /// are widened to f64 (exact) and handed to cst_categorical_fast_cdf_rows, or with perfect != 0 to cst_categorical_perfect_cdf_rows
+    /// (n_symbols <= CST_CATEGORICAL_PERFECT_MAX_K), whose limits and error codes apply.  A row WITHOUT any count (an empty stream, an
+    /// index class nobody names) is quantised as if every count were 1, and d_empty[r] (optional) is 1 for it, else 0 -- the reference
+    /// refuses such a row; here one empty stream does not void a batch.  cst_fit_cdf_rows_host: the same over host buffers, no device.
+    /// The rows feed cst_model_create_tables_per_stream, or, read back, cst_model_create_table / cst_table_set_create.
+    pub fn cst_count_symbols(
+        d_symbols: *const i32,
+        n_total: usize,
+        min_symbol: i32,
+        n_symbols: i32,
+        d_indices: *const c_void,
+        index_bytes: i32,
+        n_tables: i32,
+        d_counts: *mut u32,
+        d_outside: *mut u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_count_symbols_per_stream(
+        d_symbols: *const i32,
+        d_sym_offsets: *const u64,
+        n_streams: usize,
+        n_per_stream: usize,
+        min_symbol: i32,
+        n_symbols: i32,
+        d_counts: *mut u32,
+        d_outside: *mut u32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_fit_cdf_rows(
+        precision: i32,
+        perfect: i32,
+        d_counts: *const u32,
+        n_rows: usize,
+        n_symbols: i32,
+        d_rows: *mut u32,
+        d_empty: *mut i32,
+        stream: *mut c_void,
+    ) -> CstStatus;
+
+    pub fn cst_fit_cdf_rows_host(
+        precision: i32,
+        perfect: i32,
+        h_counts: *const u32,
+        n_rows: usize,
+        n_symbols: i32,
+        h_rows: *mut u32,
+        h_empty: *mut i32,
     ) -> CstStatus;
 
     pub fn cst_ans_encode_categorical_perfect_batch(

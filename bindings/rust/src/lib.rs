@@ -318,6 +318,135 @@ pub fn categorical_perfect_cdf_host<F: Probability>(
     Ok((bad, moves))
 }
 
+/// Histograms of `symbols` over the support `min_symbol .. min_symbol + n_symbols`, counted on the device: one for the whole buffer,
+/// or with `indices` (uint8, one per symbol) one per index class, `n_tables` rows.  Returns the counts `[n_tables][n_symbols]` and the
+/// number of symbols that fell into no bin (outside the support, or an index outside `0 .. n_tables`).
+pub fn count_symbols(
+    symbols: &DeviceBuffer<i32>,
+    min_symbol: i32,
+    n_symbols: usize,
+    indices: Option<&DeviceBuffer<u8>>,
+    n_tables: usize,
+    stream: &Stream,
+) -> Result<(DeviceBuffer<u32>, DeviceBuffer<u32>)> {
+    if n_symbols > i32::MAX as usize || n_tables > i32::MAX as usize || indices.map_or(false, |i| i.len() < symbols.len()) {
+        return Err(Error::InvalidArgument);
+    }
+    let bins = n_tables.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+    let mut counts: DeviceBuffer<u32> = DeviceBuffer::new(bins)?;
+    let mut outside: DeviceBuffer<u32> = DeviceBuffer::new(1)?;
+    check(unsafe {
+        ffi::cst_count_symbols(
+            symbols.as_ptr(),
+            symbols.len(),
+            min_symbol,
+            n_symbols as i32,
+            indices.map_or(core::ptr::null(), |i| i.as_ptr() as *const c_void),
+            if indices.is_some() { 1 } else { 0 },
+            n_tables as i32,
+            counts.as_mut_ptr(),
+            outside.as_mut_ptr(),
+            stream.as_raw(),
+        )
+    })?;
+    Ok((counts, outside))
+}
+
+/// One histogram per stream: `symbols` is stream-major with `n_per_stream` symbols per stream, or with `sym_offsets` (`n_streams + 1`
+/// entries) ragged, stream `s` being `symbols[sym_offsets[s] .. sym_offsets[s + 1]]`.  Returns the counts `[n_streams][n_symbols]`
+/// (`n_symbols <= 1024`) and the number of symbols outside the support.
+pub fn count_symbols_per_stream(
+    symbols: &DeviceBuffer<i32>,
+    sym_offsets: Option<&DeviceBuffer<u64>>,
+    n_streams: usize,
+    n_per_stream: usize,
+    min_symbol: i32,
+    n_symbols: usize,
+    stream: &Stream,
+) -> Result<(DeviceBuffer<u32>, DeviceBuffer<u32>)> {
+    if n_symbols > i32::MAX as usize {
+        return Err(Error::InvalidArgument);
+    }
+    match sym_offsets {
+        Some(offsets) if offsets.len() < n_streams + 1 => return Err(Error::InvalidArgument),
+        None if symbols.len() < n_streams.checked_mul(n_per_stream).ok_or(Error::InvalidArgument)? => return Err(Error::InvalidArgument),
+        _ => {}
+    }
+    let bins = n_streams.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+    let mut counts: DeviceBuffer<u32> = DeviceBuffer::new(bins)?;
+    let mut outside: DeviceBuffer<u32> = DeviceBuffer::new(1)?;
+    check(unsafe {
+        ffi::cst_count_symbols_per_stream(
+            symbols.as_ptr(),
+            sym_offsets.map_or(core::ptr::null(), |o| o.as_ptr()),
+            n_streams,
+            n_per_stream,
+            min_symbol,
+            n_symbols as i32,
+            counts.as_mut_ptr(),
+            outside.as_mut_ptr(),
+            stream.as_raw(),
+        )
+    })?;
+    Ok((counts, outside))
+}
+
+/// The cdf rows of `n_rows` count rows of `n_symbols` entries, quantised on the device as `Categorical(counts as f64, perfect)` does.
+/// A row without any count is quantised as if every count were 1 and flagged in the second buffer.
+pub fn fit_cdf_rows(
+    precision: u32,
+    perfect: bool,
+    counts: &DeviceBuffer<u32>,
+    n_rows: usize,
+    n_symbols: usize,
+    stream: &Stream,
+) -> Result<(DeviceBuffer<u32>, DeviceBuffer<i32>)> {
+    let count = n_rows.checked_mul(n_symbols).ok_or(Error::InvalidArgument)?;
+    if counts.len() < count || n_symbols > i32::MAX as usize {
+        return Err(Error::InvalidArgument);
+    }
+    let mut rows: DeviceBuffer<u32> = DeviceBuffer::new(count + n_rows)?;
+    let mut empty: DeviceBuffer<i32> = DeviceBuffer::new(n_rows)?;
+    check(unsafe {
+        ffi::cst_fit_cdf_rows(
+            precision as i32,
+            perfect as i32,
+            counts.as_ptr(),
+            n_rows,
+            n_symbols as i32,
+            rows.as_mut_ptr(),
+            empty.as_mut_ptr(),
+            stream.as_raw(),
+        )
+    })?;
+    Ok((rows, empty))
+}
+
+/// The same on the CPU over host slices: `rows` takes `n_symbols + 1` cumulatives per count row.  Returns one flag per row, `true`
+/// where the row held no count.
+pub fn fit_cdf_rows_host(precision: u32, perfect: bool, counts: &[u32], n_symbols: usize, rows: &mut [u32]) -> Result<Vec<bool>> {
+    if n_symbols == 0 || counts.len() % n_symbols != 0 || n_symbols > i32::MAX as usize {
+        return Err(Error::InvalidArgument);
+    }
+    let n_rows = counts.len() / n_symbols;
+    if rows.len() < n_rows * (n_symbols + 1) {
+        return Err(Error::InvalidArgument);
+    }
+    let mut empty = vec![0i32; n_rows];
+    check(unsafe {
+        ffi::cst_fit_cdf_rows_host(
+            precision as i32,
+            perfect as i32,
+            counts.as_ptr(),
+            n_rows,
+            n_symbols as i32,
+            rows.as_mut_ptr(),
+            empty.as_mut_ptr(),
+        )
+    })?;
+    Ok(empty.into_iter().map(|e| e != 0).collect())
+}
+
 /// A device-resident entropy model over a contiguous `i32` support: the encoder side is
 /// `EncoderModel::left_cumulative_and_probability` as a table (ContiguousCategoricalEntropyModel,
 /// src/stream/model/categorical/contiguous.rs:673-700), the decoder side `ContiguousLookupDecoderModel`
@@ -370,6 +499,28 @@ impl DeviceModel {
                 stream.as_raw(),
                 &mut raw,
             )
+        })?;
+        Ok(DeviceModel { raw })
+    }
+
+    /// One table PER STREAM from `n_tables` cdf rows of `n_symbols + 1` cumulatives in device memory (the rows of [`fit_cdf_rows`],
+    /// or of another per-stream model): the general form of [`DeviceModel::quantized_gaussian_per_stream`].  Every row is validated
+    /// on the device; one bad row is `Error::Model`.
+    pub fn from_cdf_rows_per_stream(
+        precision: u32,
+        min_symbol: i32,
+        n_symbols: usize,
+        rows: &DeviceBuffer<u32>,
+        n_tables: usize,
+        stream: &Stream,
+    ) -> Result<Self> {
+        let count = n_tables.checked_mul(n_symbols + 1).ok_or(Error::InvalidArgument)?;
+        if rows.len() < count || n_symbols > i32::MAX as usize {
+            return Err(Error::InvalidArgument);
+        }
+        let mut raw = core::ptr::null_mut();
+        check(unsafe {
+            ffi::cst_model_create_tables_per_stream(precision as i32, min_symbol, n_symbols as i32, rows.as_ptr(), n_tables, stream.as_raw(), &mut raw)
         })?;
         Ok(DeviceModel { raw })
     }

@@ -229,6 +229,11 @@ SIGNATURES = {
     "cst_range_decode_categorical_perfect_batch": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _vp, _z, _z, _i32, _vp, _vp, _u32, _vp]),
     "cst_categorical_perfect_cdf_rows": (_i32, [_i32, _vp, _i32, _z, _i32, _vp, _vp, _vp, _vp]),
     "cst_categorical_perfect_cdf_host": (_i32, [_i32, _vp, _i32, _z, _i32, _vp, _vp, _vp]),
+    "cst_count_symbols": (_i32, [_vp, _z, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "cst_count_symbols_per_stream": (_i32, [_vp, _vp, _z, _z, _i32, _i32, _vp, _vp, _vp]),
+    "cst_fit_cdf_rows": (_i32, [_i32, _i32, _vp, _z, _i32, _vp, _vp, _vp]),
+    "cst_fit_cdf_rows_host": (_i32, [_i32, _i32, _vp, _z, _i32, _vp, _vp]),
+    "cst_model_create_tables_per_stream": (_i32, [_i32, _i32, _i32, _vp, _z, _vp, C.POINTER(_vp)]),
     "cst_range_encode_gaussian_batch": (_i32, [CoderConfig, _i32, _i32, _vp, _vp, _vp, _z, _z, _i32, _vp, _z, _vp, _vp, _vp, _u32, _vp]),
     "cst_range_decode_gaussian_batch": (_i32, [CoderConfig, _i32, _i32, _vp, _vp, _z, _z, _vp, _vp, _vp, _vp, _z, _z, _i32, _vp, _vp, _u32, _vp]),
     "cst_range_decode_rows_batch": (_i32, [CoderConfig, _vp, _vp, _z, _z, _vp, _vp, _i32, _i32, _vp, _z, _z, _i32, _vp, _vp, _u32, _vp]),

@@ -117,6 +117,48 @@ class Model:
                 "cst_model_create_gaussian_per_stream")
         return cls(h)
 
+    @classmethod
+    def from_cdf_rows_per_stream(cls, rows, min_symbol: int, precision: int) -> "Model":
+        """One table per stream from cdf rows [n_streams, n + 1] (a device tensor, int32-typed like cdfs_device() gives them, or a
+        numpy array): the inverse of cdfs_device() -- a decoder rebuilds the encoder's per-stream model from the rows alone.  Every
+        row is validated on the device (cdf[0] = 0 < ... < cdf[n] = 2^P); a bad row raises ValueError."""
+        if isinstance(rows, np.ndarray):
+            if rows.ndim != 2 or rows.dtype.kind not in "iu":
+                raise ValueError("rows must be a 2-d integer array [n_streams, n_symbols + 1]")
+            host = np.ascontiguousarray(rows, dtype=np.uint32).view(np.int32)
+            _fit_rows_shape(host.shape, precision)
+            rows = torch.from_numpy(host).to(torch.device("cuda", torch.cuda.current_device()))
+        elif not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype != torch.int32:
+            raise ValueError("rows must be a 2-d torch.int32 tensor (or numpy array) [n_streams, n_symbols + 1]")
+        _fit_rows_shape(tuple(rows.shape), precision)
+        if not rows.is_cuda:
+            raise ValueError("rows must live in device memory (HBM)")
+        rows = rows.contiguous()
+        h = C.c_void_p()
+        N.check(N.lib().cst_model_create_tables_per_stream(int(precision), int(min_symbol), rows.shape[1] - 1, _ptr(rows), rows.shape[0],
+                                                           _stream_ptr(), C.byref(h)), "cst_model_create_tables_per_stream")
+        return cls(h)
+
+    @classmethod
+    def fit(cls, symbols, min_symbol: int, max_symbol: int, precision: int, perfect: bool = False) -> "Model":
+        """One shared table fitted to `symbols` (any shape) on the device: count, quantise like Categorical(counts, perfect=...),
+        build.  ValueError if a symbol lies outside [min_symbol, max_symbol]: such a model could not encode its own data."""
+        _fit_precision(precision, 24)
+        counts, outside = count_symbols(symbols.reshape(-1) if isinstance(symbols, torch.Tensor) else symbols, min_symbol, max_symbol)
+        _fit_refuse_outside(outside)
+        rows = fit_cdf_rows(counts, precision, perfect)
+        return cls.from_cdf(rows[0].cpu().numpy().view(np.uint32), min_symbol, precision)
+
+    @classmethod
+    def fit_per_stream(cls, symbols, min_symbol: int, max_symbol: int, precision: int, perfect: bool = False,
+                       sym_offsets: Optional[torch.Tensor] = None) -> "Model":
+        """One table per stream, each fitted to its own stream on the device: `symbols` [n_streams, n_per_stream], or flat with
+        `sym_offsets` [n_streams + 1] (ragged).  An empty stream gets the uniform table.  ValueError as for fit()."""
+        _fit_precision(precision, 16)
+        counts, outside = count_symbols(symbols, min_symbol, max_symbol, per_stream=True, sym_offsets=sym_offsets)
+        _fit_refuse_outside(outside)
+        return cls.from_cdf_rows_per_stream(fit_cdf_rows(counts, precision, perfect), min_symbol, precision)
+
     @property
     def precision(self):
         return N.load_library().cst_model_precision(self._h)
@@ -145,6 +187,123 @@ class Model:
         out = np.zeros(self.n_symbols + 1, dtype=np.uint32)
         N.check(N.lib().cst_model_get_cdf(self._h, index, out.ctypes.data, _stream_ptr()), "cst_model_get_cdf")
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Fitting table models on the device (csrc/cst_fit.hip): count -> quantise -> model, nothing leaves HBM but
+# the one row of a shared model and the K rows of a table set
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _fit_precision(precision, most):
+    if not 1 <= int(precision) <= most:
+        raise ValueError(f"precision must be 1 .. {most}")
+
+
+def _fit_rows_shape(shape, precision):
+    _fit_precision(precision, 16)
+    if len(shape) != 2 or shape[0] < 1 or shape[1] < 3:
+        raise ValueError("rows must be 2-d: one row of n_symbols + 1 >= 3 cumulatives per stream")
+
+
+def _fit_refuse_outside(outside):
+    n = int(outside.item())
+    if n:
+        raise ValueError(f"{n} symbols lie outside the support (or name no table): a model fitted to the rest could not encode them")
+
+
+def count_symbols(symbols, min_symbol: int, max_symbol: int, *, indices=None, n_tables=None, per_stream: bool = False, sym_offsets=None):
+    """Histograms of int32 `symbols` over the support [min_symbol, max_symbol], counted on the device.  Returns (counts, outside):
+    `counts` a torch.int32 tensor in HBM, `outside` a 1-element tensor with the number of symbols that fell into no bin.
+      default                  one histogram of the whole tensor (any shape): counts [1, n]
+      indices=, n_tables=K     symbol i counts into row indices[i] (torch.uint8 or torch.int32, the symbols' shape): counts [K, n];
+                               an index outside [0, K) counts as outside.  K <= 256, n <= 65536
+      per_stream=True          one histogram per row of `symbols` [n_streams, n_per_stream], or with sym_offsets= [n_streams + 1]
+                               (torch.int64) per stream of the flat `symbols`: counts [n_streams, n].  n <= 1024"""
+    if not isinstance(symbols, torch.Tensor) or symbols.dtype != torch.int32:
+        raise ValueError("symbols must be a torch.int32 tensor")
+    n = int(max_symbol) - int(min_symbol) + 1
+    if not -2**31 <= int(min_symbol) <= int(max_symbol) < 2**31:
+        raise ValueError("the support [min_symbol, max_symbol] must lie inside int32")
+    if not 2 <= n <= (1024 if per_stream else 65536):
+        raise ValueError(f"the support must hold 2 .. {1024 if per_stream else 65536} symbols")
+    if symbols.numel() >= 2**31:
+        raise ValueError("fewer than 2^31 symbols per call")
+    if per_stream:
+        if indices is not None or n_tables is not None:
+            raise ValueError("per_stream counts take no indices")
+        if sym_offsets is None:
+            if symbols.dim() != 2 or symbols.shape[0] < 1:
+                raise ValueError("per_stream counts need symbols [n_streams, n_per_stream] or flat symbols with sym_offsets")
+            rows = symbols.shape[0]
+        else:
+            if not isinstance(sym_offsets, torch.Tensor) or sym_offsets.dtype != torch.int64 or sym_offsets.dim() != 1 or sym_offsets.numel() < 2:
+                raise ValueError("sym_offsets must be a 1-d torch.int64 tensor of n_streams + 1 entries")
+            if symbols.dim() != 1:
+                raise ValueError("with sym_offsets the symbols are flat")
+            rows = sym_offsets.numel() - 1
+    else:
+        if sym_offsets is not None:
+            raise ValueError("sym_offsets go with per_stream=True")
+        if (indices is None) != (n_tables is None):
+            raise ValueError("indices and n_tables come together")
+        rows = 1 if n_tables is None else int(n_tables)
+        if not 1 <= rows <= 256:
+            raise ValueError("n_tables must be 1 .. 256")
+        if indices is not None:
+            if not isinstance(indices, torch.Tensor) or indices.dtype not in (torch.uint8, torch.int32):
+                raise ValueError("indices must be a torch.uint8 or torch.int32 tensor")
+            if tuple(indices.shape) != tuple(symbols.shape):
+                raise ValueError("indices must have the shape of the symbols")
+    if not symbols.is_cuda:
+        raise ValueError("symbols must live in device memory (HBM)")
+    for name, t in (("indices", indices), ("sym_offsets", sym_offsets)):
+        if t is not None and (not t.is_cuda or t.device != symbols.device):
+            raise ValueError(f"{name} must live in device memory (HBM), on the device of the symbols")
+    symbols = symbols.contiguous()
+    counts = torch.empty((rows, n), dtype=torch.int32, device=symbols.device)
+    outside = torch.empty(1, dtype=torch.int32, device=symbols.device)
+    if per_stream:
+        if sym_offsets is not None:
+            sym_offsets = sym_offsets.contiguous()
+            first, last = int(sym_offsets[0].item()), int(sym_offsets[-1].item())
+            if not 0 <= first <= last <= symbols.numel():
+                raise ValueError("sym_offsets must ascend within the symbols")
+        n_per = 0 if sym_offsets is not None else symbols.shape[1]
+        N.check(N.lib().cst_count_symbols_per_stream(_ptr(symbols), _ptr(sym_offsets), rows, n_per, int(min_symbol), n, _ptr(counts),
+                                                     _ptr(outside), _stream_ptr()), "cst_count_symbols_per_stream")
+    else:
+        index_bytes = 0
+        if indices is not None:
+            indices, index_bytes = indices.contiguous(), (1 if indices.dtype == torch.uint8 else 4)
+        N.check(N.lib().cst_count_symbols(_ptr(symbols), symbols.numel(), int(min_symbol), n, _ptr(indices), index_bytes, rows, _ptr(counts),
+                                          _ptr(outside), _stream_ptr()), "cst_count_symbols")
+    return counts, outside
+
+
+def fit_cdf_rows(counts, precision: int, perfect: bool = False, return_empty: bool = False):
+    """The cdf rows of count rows [n_rows, n] (count_symbols), quantised on the device as Categorical(counts[r], perfect=...) does:
+    an int32-typed tensor [n_rows, n + 1] in HBM in the format of categorical_cdf_rows.  A row without any count is quantised as if
+    every count were 1 (the reference refuses it; here an empty stream does not void a batch); return_empty=True returns
+    (rows, empty) with empty[r] = 1 for such rows."""
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.dim() != 2:
+        raise ValueError("counts must be a 2-d torch.int32 tensor [n_rows, n_symbols]")
+    n_rows, n = counts.shape
+    if not 1 <= int(precision) <= 31:
+        raise ValueError("precision must be 1 .. 31")
+    if perfect:
+        if n < 2 or n > min(N.CATEGORICAL_PERFECT_MAX_K, 1 << int(precision)):
+            raise ValueError(f"perfect=True needs 2 <= n_symbols <= min({N.CATEGORICAL_PERFECT_MAX_K}, 2**precision)")
+    elif n < 2 or n >= (1 << int(precision)) - 1:
+        raise ValueError("the fast quantisation needs 2 <= n_symbols < 2**precision - 1")
+    if not counts.is_cuda:
+        raise ValueError("counts must live in device memory (HBM)")
+    counts = counts.contiguous()
+    rows = torch.empty((n_rows, n + 1), dtype=torch.int32, device=counts.device)
+    empty = torch.zeros(max(n_rows, 1), dtype=torch.int32, device=counts.device)
+    if n_rows:
+        N.check(N.lib().cst_fit_cdf_rows(int(precision), int(bool(perfect)), _ptr(counts), n_rows, n, _ptr(rows), _ptr(empty), _stream_ptr()),
+                "cst_fit_cdf_rows")
+    return (rows, empty[:n_rows]) if return_empty else rows
 
 
 def family_cdf_rows(family: int, min_symbol: int, max_symbol: int, a, b=None, n_per_row=None, precision: int = 24,
@@ -2519,6 +2678,19 @@ class TableSet:
             cdfs = np.stack([Model.quantized_gaussian(min_symbol, max_symbol, float(m), float(s), precision).cdf()
                              for m, s in zip(means.tolist(), stds.tolist())])
         return cls.from_cdfs(cdfs, min_symbol, precision)
+
+    @classmethod
+    def fit(cls, symbols, indices, n_tables: int, min_symbol: int, max_symbol: int, precision: int, perfect: bool = False) -> "TableSet":
+        """K tables, table k fitted on the device to the symbols whose index is k (count_symbols + fit_cdf_rows): the factorised
+        prior of static two-pass coding.  A class nobody names gets the uniform table.  ValueError if a symbol lies outside
+        [min_symbol, max_symbol] or an index outside [0, n_tables)."""
+        _fit_precision(precision, 24)
+        if indices is None or n_tables is None:
+            raise ValueError("TableSet.fit needs indices and n_tables")
+        counts, outside = count_symbols(symbols, min_symbol, max_symbol, indices=indices, n_tables=n_tables)
+        _fit_refuse_outside(outside)
+        rows = fit_cdf_rows(counts, precision, perfect)
+        return cls.from_cdfs(rows.cpu().numpy().view(np.uint32), min_symbol, precision)
 
     @property
     def precision(self):

@@ -40,6 +40,8 @@ static Knobs read_knobs() {
     if (const char* e = env("CST_RAGGED_GROUP")) k.ragged_group = e[0] == '8' ? 8 : e[0] == '3' ? 32 : 16;
     if (const char* e = env("CST_CATEGORICAL_ROUTE")) k.categorical_route = e[0] == 'f' ? 1 : e[0] == 'r' ? 2 : 0;
     if (const char* e = env("CST_INDEXED_BUCKET_BITS")) k.indexed_bucket_bits = (int)strtol(e, nullptr, 10);
+    if (const char* e = env("CST_FIT_REPLICAS")) k.fit_replicas = (int)strtol(e, nullptr, 10);
+    if (const char* e = env("CST_FIT_WAVE_UNIFORM")) k.fit_wave_uniform = e[0] != '0';
     if (const char* e = env("CST_PERFECT_RAGGED_BUDGET")) {
         const unsigned long long words = strtoull(e, nullptr, 10);          // (a launch has at most 2^31 - 1 blocks, one per row)
         if (words >= 1) k.perfect_ragged_budget = (size_t)(words < 0x7fffffffull ? words : 0x7fffffffull);

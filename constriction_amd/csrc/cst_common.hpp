@@ -158,6 +158,8 @@ struct Knobs {
     int ragged_group = 16;            // CST_RAGGED_GROUP=8|16|32: symbols per memory point of the ragged encoder (cst_ans_ragged.hip)
     int categorical_route = 0;        // CST_CATEGORICAL_ROUTE=fused|rows: 1 / 2 forces a route of the per-symbol Categorical decoders (0: by shape)
     int indexed_bucket_bits = 8;      // CST_INDEXED_BUCKET_BITS=0..8: the most bucket bits a table set built from now on takes (0: its decoders search whole rows)
+    int fit_replicas = 8;             // CST_FIT_REPLICAS=1|2|4|8: the most LDS replicas of a bin the shared / indexed count takes (cst_fit.hip)
+    bool fit_wave_uniform = true;     // CST_FIT_WAVE_UNIFORM=0: no single add for a wave whose 256 symbols fall into one bin
     size_t perfect_ragged_budget = (size_t)16 << 20;   // CST_PERFECT_RAGGED_BUDGET=words: the tabulated rows of one step of the ragged
                                                        // Categorical(perfect=True) decoders (64 MiB; 1 .. 2^31 - 1)
 };

@@ -29,8 +29,10 @@ __global__ void gaussian_cdf_kernel(int P, int32_t lo, int32_t n, const double* 
 }
 
 // 16-bit per-stream cdf rows for the LDS-resident per-stream models (values modulo 2^16).  Also validates
-// every table: status[tbl] = 1 if some probability is zero (quantize.rs:562-565 panics) or a parameter is invalid.
-__global__ void cdf_to_u16_kernel(const uint32_t* __restrict__ cdf, size_t n_tables, int32_t n, int32_t stride16,
+// every table: status[tbl] = 1 if some probability is zero (quantize.rs:562-565 panics) or a parameter is invalid.  Rows that
+// come from a caller and not from a Gaussian (means == nullptr) have their two ends checked in the parameters' place:
+// cdf[0] = 0 and cdf[n] = 2^P, the rules of cdf_valid.
+__global__ void cdf_to_u16_kernel(const uint32_t* __restrict__ cdf, size_t n_tables, int32_t n, int32_t stride16, int32_t P,
                                   uint16_t* __restrict__ out, const double* __restrict__ means,
                                   const double* __restrict__ stds, int32_t* __restrict__ bad) {
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -41,9 +43,13 @@ __global__ void cdf_to_u16_kernel(const uint32_t* __restrict__ cdf, size_t n_tab
     out[gid] = (i <= n) ? (uint16_t)row[i] : (uint16_t)0xffff;
     if (i < n && row[i + 1] <= row[i]) atomicOr(&bad[tbl], 1);
     if (i == 0) {
-        const double m = means[tbl], s = stds[tbl];
-        if (!(s > 0.0 && s <= 1.7976931348623157e308 && m == m && m <= 1.7976931348623157e308 && m >= -1.7976931348623157e308))
+        if (means) {
+            const double m = means[tbl], s = stds[tbl];
+            if (!(s > 0.0 && s <= 1.7976931348623157e308 && m == m && m <= 1.7976931348623157e308 && m >= -1.7976931348623157e308))
+                atomicOr(&bad[tbl], 1);
+        } else if (row[0] != 0u || row[n] != (1u << P)) {
             atomicOr(&bad[tbl], 1);
+        }
     }
 }
 
@@ -390,13 +396,11 @@ cst_status cst_model_create_gaussian(int32_t precision, int32_t min_symbol, int3
     return CST_OK;
 }
 
-cst_status cst_model_create_gaussian_per_stream(int32_t precision, int32_t min_symbol, int32_t max_symbol,
-                                                const double* d_means, const double* d_stds, size_t n_streams,
-                                                void* stream, cst_model** out) {
-    if (!out || !d_means || !d_stds || n_streams == 0) return CST_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (max_symbol <= min_symbol) return CST_ERR_MODEL;
-    const int64_t n64 = (int64_t)max_symbol - min_symbol + 1;
+// One table per stream, the body of both constructors: the rows are tabulated from (d_means, d_stds) or copied from d_cdfs
+// (device rows [n_streams][n + 1], d_means == nullptr); every row is validated on the device, then the 16-bit rows, the
+// reciprocals and the compact image are built.
+static cst_status create_per_stream(int32_t precision, int32_t min_symbol, int64_t n64, const double* d_means, const double* d_stds,
+                                    const uint32_t* d_cdfs, size_t n_streams, void* stream, cst_model** out) {
     if (cst_status st = check_model_args(precision, n64)) return st;
     if (precision > 16) return CST_ERR_INVALID_ARGUMENT; // per-stream tables are kept as 16-bit rows
     int ndev = 0;
@@ -415,15 +419,18 @@ cst_status cst_model_create_gaussian_per_stream(int32_t precision, int32_t min_s
     if (e == hipSuccess) {
         const int threads = 256;
         const size_t blocks = (total + threads - 1) / threads;
-        hipLaunchKernelGGL(gaussian_cdf_kernel, dim3((unsigned)blocks), dim3(threads), 0, hs, precision, min_symbol, n,
-                           d_means, d_stds, 0.0, 1.0, n_streams, m->d_cdf);
+        if (d_means)
+            hipLaunchKernelGGL(gaussian_cdf_kernel, dim3((unsigned)blocks), dim3(threads), 0, hs, precision, min_symbol, n,
+                               d_means, d_stds, 0.0, 1.0, n_streams, m->d_cdf);
+        else
+            e = hipMemcpyAsync(m->d_cdf, d_cdfs, 4 * total, hipMemcpyDeviceToDevice, hs);
         const size_t total16 = n_streams * (size_t)m->cdf16_stride;
         int32_t* d_bad = nullptr;
-        e = hipMallocAsync((void**)&d_bad, 4 * n_streams, hs);
+        if (e == hipSuccess) e = hipMallocAsync((void**)&d_bad, 4 * n_streams, hs);
         if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 4 * n_streams, hs);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(cdf_to_u16_kernel, dim3((unsigned)((total16 + threads - 1) / threads)), dim3(threads), 0, hs,
-                               (const uint32_t*)m->d_cdf, n_streams, n, m->cdf16_stride, m->d_cdf16, d_means, d_stds, d_bad);
+                               (const uint32_t*)m->d_cdf, n_streams, n, m->cdf16_stride, precision, m->d_cdf16, d_means, d_stds, d_bad);
             e = hipGetLastError();
         }
         // any invalid table makes the whole model invalid (the reference panics when such a model is constructed)
@@ -443,10 +450,28 @@ cst_status cst_model_create_gaussian_per_stream(int32_t precision, int32_t min_s
         e = hipMalloc(&m->d_recip, 8 * np);
         if (e == hipSuccess) e = hipMemcpy(m->d_recip, rec.data(), 8 * np, hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) { set_hip_error(e, "per-stream gaussian tables"); cst_model_destroy(m); return CST_ERR_HIP; }
+    if (e != hipSuccess) { set_hip_error(e, "per-stream tables"); cst_model_destroy(m); return CST_ERR_HIP; }
     build_pt_image(m, hs);
     *out = m;
     return CST_OK;
+}
+
+cst_status cst_model_create_gaussian_per_stream(int32_t precision, int32_t min_symbol, int32_t max_symbol,
+                                                const double* d_means, const double* d_stds, size_t n_streams,
+                                                void* stream, cst_model** out) {
+    if (!out || !d_means || !d_stds || n_streams == 0) return CST_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (max_symbol <= min_symbol) return CST_ERR_MODEL;
+    return create_per_stream(precision, min_symbol, (int64_t)max_symbol - min_symbol + 1, d_means, d_stds, nullptr, n_streams, stream, out);
+}
+
+cst_status cst_model_create_tables_per_stream(int32_t precision, int32_t min_symbol, int32_t n_symbols, const uint32_t* d_cdfs,
+                                              size_t n_tables, void* stream, cst_model** out) {
+    if (!out || !d_cdfs || n_tables == 0) return CST_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (n_symbols < 2) return CST_ERR_MODEL;
+    if ((int64_t)min_symbol + n_symbols - 1 > INT32_MAX) return CST_ERR_INVALID_ARGUMENT;
+    return create_per_stream(precision, min_symbol, n_symbols, nullptr, nullptr, d_cdfs, n_tables, stream, out);
 }
 
 cst_status cst_model_create_table_noncontiguous(int32_t precision, int32_t n_symbols, const int32_t* h_symbols, const uint32_t* h_cdf,
