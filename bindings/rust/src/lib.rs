@@ -3435,6 +3435,8 @@ impl BatchedRangeEncoder {
 
     /// Per stream: `RangeEncoder::new()`, `encode_iid_symbols(symbols[s], &model)?`, `into_compressed()`
     /// (src/stream/queue.rs:612-705, 458-523).
+    /// `model`: one shared table, or one table per stream ([`DeviceModel::quantized_gaussian_per_stream`],
+    /// [`DeviceModel::from_cdf_rows_per_stream`]: as many tables as streams, precision <= 16).
     pub fn encode_iid_symbols(
         &self,
         symbols: &DeviceBuffer<i32>,
@@ -3469,7 +3471,8 @@ impl BatchedRangeEncoder {
 
     /// Encoding with jump tables: what `RangeEncoder::pos()` returns in front of every chunk of `interval` symbols
     /// (`Pos`, src/stream/queue.rs:172-196: words emitted so far including held-back ones, and `RangeCoderState`); the words are
-    /// those of `encode_iid_symbols`.
+    /// those of `encode_iid_symbols`.  A model with one table per stream is taken too (stream-major, any `interval >= 1`);
+    /// [`BatchedRangeEncoder::auto_jump_interval`] answers 0 for it.
     pub fn encode_iid_symbols_with_checkpoints(
         &self,
         symbols: &DeviceBuffer<i32>,

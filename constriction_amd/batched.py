@@ -1309,13 +1309,30 @@ def range_max_words(n_per_stream: int, config=(32, 64, 12)) -> int:
     return N.load_library().cst_range_max_words(n_per_stream, _cfg(*config))
 
 
+def _check_range_per_stream(model: Model, n_streams: int, layout: str, jump) -> None:
+    """What the range coder asks of a model with one table per stream, said before any launch (a shared table passes)."""
+    if model.n_tables == 1:
+        return
+    if model.noncontiguous:
+        raise ValueError("tables per stream: contiguous alphabets only")
+    if model.n_tables != n_streams:
+        raise ValueError(f"the model has {model.n_tables} tables, the batch {n_streams} streams: one table per stream")
+    if jump and layout != "stream_major":
+        raise ValueError("tables per stream with jump points: stream-major batches only")
+
+
 def range_encode(symbols: torch.Tensor, model: Model, config=(32, 64, 12), layout="stream_major",
                  stride=None, out: Optional[EncodedBatch] = None, jump_points="auto") -> EncodedBatch:
     """One RangeEncoder per stream: encode_iid_symbols + get_compressed (queue.rs:612-705, 458-523).
     stride: words per slab (default range_max_words), or "tuned" (tuned_stride(..., coder="range")).
     jump_points: as for ans_encode -- `RangeEncoder.pos()` (queue.rs:172-196) in front of every k-th part of a stream, carried as
     `.jump` for range_decode; "auto" (default) = cst_jump_points_auto (the range decoder's division chain is latency-bound at one
-    wave per SIMD: two lanes per stream at 65 536 streams), an integer k, or 0."""
+    wave per SIMD: two lanes per stream at 65 536 streams), an integer k, or 0.
+    model: one shared table, or one table per stream (quantized_gaussian_per_stream, from_cdf_rows_per_stream, fit_per_stream: as
+    many tables as streams, presets (32, 64) and (16, 32), P <= 16, either layout, int8 / int16 matrices widened on the device).
+    With tables per stream "auto" notes no jump points (nothing has measured whether they pay there); an integer k is honoured
+    for stream-major matrices."""
+    _check_range_per_stream(model, _layout_shape(symbols, layout)[0], layout, 0 if isinstance(jump_points, str) else jump_points)
     if isinstance(stride, str):
         if stride != "tuned":
             raise ValueError("stride must be a number of words or 'tuned'")
@@ -1334,7 +1351,7 @@ def range_encode(symbols: torch.Tensor, model: Model, config=(32, 64, 12), layou
     if out is None:
         out = _new_batch(n_streams, stride or range_max_words(n_per, config), symbols.device, config)
     L = N.lib()
-    interval = 0 if model.n_tables != 1 else _jump_interval(jump_points, n_per, lambda: L.cst_jump_points_auto(
+    interval = _jump_interval(jump_points, n_per, lambda: L.cst_jump_points_auto(
         model._h, _cfg(*config), N.CODER_RANGE, narrow, _ptr(symbols), n_streams, n_per, lay, _ptr(out.words), out.words.shape[1]))
     if interval:
         ck = _jump_table(out, RangeCheckpoints, interval, n_streams, n_per, symbols.device)
@@ -1357,7 +1374,9 @@ def range_encode(symbols: torch.Tensor, model: Model, config=(32, 64, 12), layou
 def range_decode(encoded, model: Model, n_per_stream: int, layout="stream_major", offsets: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None, config=None, dtype=torch.int32):
     """One RangeDecoder per stream: from_compressed + decode_iid_symbols (queue.rs:847-868, 968-1033).
-    dtype (or the dtype of `out`): int32, or int16 / int8 -- narrowed on the device behind the decoder (cst_symbols_narrow)."""
+    dtype (or the dtype of `out`): int32, or int16 / int8 -- narrowed on the device behind the decoder (cst_symbols_narrow).
+    model: as for range_encode -- one shared table, or one table per stream.  A batch that carries jump points for exactly this
+    shape (range_encode, jump_points=k) decodes every part of a stream on a lane of its own."""
     if isinstance(encoded, EncodedBatch):
         words, n_words, config = encoded.words, encoded.n_words, config or encoded.config
         stride = words.shape[1]
@@ -1367,6 +1386,7 @@ def range_decode(encoded, model: Model, n_per_stream: int, layout="stream_major"
         config = config or (32, 64, 12)
     n_streams = n_words.numel()
     dev = words.device
+    _check_range_per_stream(model, n_streams, layout, 0)
     dtype = out.dtype if out is not None else dtype
     if dtype not in _SYMBOL_BYTES:
         raise TypeError("decoded symbols are int32, int16 or int8")
@@ -2482,7 +2502,8 @@ class RangeCheckpoints:
 def range_encode_checkpointed(symbols: torch.Tensor, model: Model, interval: int, config=(32, 64, 12), layout="stream_major",
                               stride: Optional[int] = None, out=None):
     """range_encode + a jump point in front of every `interval` symbols.  Returns (EncodedBatch, RangeCheckpoints); the words
-    are those of range_encode."""
+    are those of range_encode.  One table per stream (as for range_encode): stream-major only, any interval >= 1."""
+    _check_range_per_stream(model, _layout_shape(symbols, layout)[0], layout, interval)
     narrow = _SYMBOL_BYTES.get(symbols.dtype, 4) if symbols.dtype in _SYMBOL_BYTES else 4
     if narrow != 4:        # int8 / int16 matrices (round 6: cst_range_encode_batch_ckpt_sym; int8 tiles are read by the encoder loop itself)
         if model.noncontiguous:
@@ -2522,7 +2543,8 @@ def range_decode_checkpointed(encoded, checkpoints: RangeCheckpoints, model: Mod
                               offsets: Optional[torch.Tensor] = None, config=None, dtype=torch.int32):
     """Every chunk on its own lane: RangeDecoder.seek(pos, (lower, range)) + `interval` symbols per chunk.
     Returns (symbols [n_streams, n_per_stream], status [n_streams, n_chunks]).  `encoded`: an EncodedBatch, or (packed words, n_words)
-    with `offsets` (int64 [n_streams + 1]) and `config` for the words of compact() / container.load() / a gather."""
+    with `offsets` (int64 [n_streams + 1]) and `config` for the words of compact() / container.load() / a gather.
+    model: one shared table, or one table per stream (every chunk lane then holds its own copy of its stream's row)."""
     stride_arg = None
     if not isinstance(encoded, EncodedBatch):
         if offsets is None:
@@ -2534,6 +2556,7 @@ def range_decode_checkpointed(encoded, checkpoints: RangeCheckpoints, model: Mod
     dev = encoded.words.device
     n_chunks = checkpoints.pos.shape[1]
     _check_jump_shape(checkpoints, n_per_stream)
+    _check_range_per_stream(model, n_streams, "stream_major", checkpoints.interval)
     if checkpoints.pos.shape[0] != n_streams:
         raise ValueError("jump points of another batch: one row per stream")
     if out is None:

@@ -1,17 +1,14 @@
 // cst_ans_ps.hip -- batched ANS with ONE MODEL PER STREAM (BASELINE config C3): every lane codes its stream with
 // its own quantized-Gaussian table (learned-image-compression latents: one (mean, std) per channel / tile).
 //
-// Each lane's cumulative table (n+1 entries of 16 bits, row length L = 2^k) is held in LDS for the whole
-// kernel, TRANSPOSED per wave: entry e of lane l lives at [e][l] (like the word rings).  The bank of an access then
-// depends on the lane only, whatever index the lane probes: two lanes per bank instead of the ~6-way conflicts random
-// per-lane indices cause in a row-per-lane layout (PMC: 200 of 1100 cycles per decoded symbol were bank conflicts).  Encoding needs (c, p) =
+// Each lane's cumulative table is held in LDS for the whole kernel, transposed per wave (cst_per_stream_rows.hpp: the
+// rows, their staging and the decoder's search, shared with the per-stream range coder).  Encoding needs (c, p) =
 // (row[i], row[i+1]-row[i]) and the reciprocal floor(2^64/p), which comes from a small table indexed by p
-// (shared by all streams, L1/L2 resident).  Decoding finds the largest i with row[i] <= q by a 4-ary search
-// (3 probes per round, ceil(log4 n) rounds, branch free).
+// (shared by all streams, L1/L2 resident).
 // The encoder reads stream-major symbols through wave-private LDS tiles like the shared-table kernels (128-byte row
 // segments per access); the decoder writes 16 B per lane per 4 steps (see there); compressed words go through the
 // same per-lane LDS rings.
-#include "cst_ans_kernels.hpp"
+#include "cst_per_stream_rows.hpp"
 
 namespace cst {
 
@@ -35,31 +32,6 @@ struct PsArgs {
     uint32_t flags;
     uint64_t words_capacity;   // decode: uint32 slots behind `words_in` (0 = unknown): see word_slice
 };
-
-// this lane's column of its wave's transposed table: entry i at base[i * kWave]
-struct LaneRow {
-    const uint16_t* base;  // &table_of_wave[0][lane]
-    __device__ __forceinline__ uint32_t at(uint32_t i) const { return base[i * kWave]; }
-};
-
-// `pad`: entries behind cdf[n] become 0xFFFF, a sentinel above every quantile when P <= 15 (the decoder's search
-// then needs no bounds checks)
-__device__ __forceinline__ void stage_rows(uint16_t* lds_rows, const PsArgs& a, size_t block_s0, bool pad = false) {
-    const uint32_t L = (uint32_t)a.L, mask = L - 1;
-    const uint32_t total = blockDim.x * L;
-    const int shift = __builtin_ctz(L);
-    for (uint32_t idx = threadIdx.x; idx < total; idx += blockDim.x) {
-        const uint32_t j = idx >> shift, e = idx & mask;
-        const size_t s = block_s0 + j;
-        uint16_t v = s < a.n_streams ? a.cdf16[s * L + e] : (uint16_t)0;
-        if (pad && e > (uint32_t)a.n_symbols) v = 0xFFFFu;
-        lds_rows[((size_t)(j >> 6) * L + e) * kWave + (j & 63u)] = v;      // [wave][entry][lane]
-    }
-}
-
-// Bucket index of the per-stream decoder: kPsBuckets + 1 entries per stream, start[b] = the symbol index whose bin
-// holds quantile b * 2^(P - log2 kPsBuckets); kPsIdxStride entries per lane, stored [bucket][lane] like the tables.
-constexpr int kPsBucketBits = 6, kPsBuckets = 1 << kPsBucketBits, kPsIdxStride = 66;
 
 template <int W, int S>
 __global__ void ans_encode_ps_kernel(const PsArgs a) {
@@ -155,7 +127,7 @@ __global__ void ans_decode_ps_kernel(const PsArgs a) {
     const size_t block_s0 = (size_t)blockIdx.x * blockDim.x;
     uint16_t* rows = reinterpret_cast<uint16_t*>(smem);
     uint32_t* ring = reinterpret_cast<uint32_t*>(smem + (size_t)blockDim.x * a.L * 2) + (threadIdx.x >> 6) * kRingWords;
-    stage_rows(rows, a, block_s0, a.precision >= kPsBucketBits && a.precision <= 15);
+    stage_rows(rows, a, block_s0, ps_indexed(a.precision));
     __syncthreads();
 
     const size_t s = block_s0 + threadIdx.x;
@@ -177,52 +149,15 @@ __global__ void ans_decode_ps_kernel(const PsArgs a) {
     wave_lds_fence();
 
     // P in [6, 15]: bucket index + sentinel-padded rows (see stage_rows); otherwise the plain bounded 4-ary search
-    const bool indexed = P >= kPsBucketBits && P <= 15;
+    const bool indexed = ps_indexed(P);
     uint16_t* bidx = reinterpret_cast<uint16_t*>(smem + (size_t)blockDim.x * a.L * 2 + (size_t)(blockDim.x / kWave) * kRingWords * 4) +
                      (size_t)(threadIdx.x >> 6) * kPsIdxStride * kWave + lane;     // [wave][bucket][lane]
-    if (indexed) {
-        // this lane's own row -> its bucket index (one pass over the row)
-        uint32_t i = 0;
-        const uint32_t w = 1u << (P - kPsBucketBits);
-        for (uint32_t b = 0; b < (uint32_t)kPsBuckets; ++b) {
-            const uint32_t q0 = b * w;
-            while (i + 1 < n && R.at(i + 1) <= q0) ++i;
-            bidx[b * kWave] = (uint16_t)i;
-        }
-        bidx[kPsBuckets * kWave] = (uint16_t)(n - 1);
-        wave_lds_fence();
-    }
+    if (indexed) ps_build_bucket_index(R, bidx, P, n);
 
     auto decode_one = [&]() -> int32_t {
         const uint32_t q = (uint32_t)L.state & qmask;
         const uint32_t next_word = *L.in.slot(L.in.rd - 1u + L.in.shift);
-        uint32_t lo;
-        if (indexed) {
-            // the answer lies in [start[b], start[b+1]]; everything behind start[b+1] (including the padding) is > q,
-            // so the 4-ary refinement needs no bounds checks and a lane that is done is not disturbed by extra rounds
-            const uint32_t b = q >> (P - kPsBucketBits);
-            lo = bidx[b * kWave];
-            uint32_t size = (uint32_t)bidx[(b + 1) * kWave] - lo + 1u;
-            while (__any(size > 1)) {
-                const uint32_t step = (size + 3) >> 2;
-                // (probes clamped to index n, whose entry 2^P is itself above every quantile: the row may be exactly
-                // n + 1 entries long, and an index behind it would wrap around to the row's small first entries)
-                const uint32_t v1 = R.at(min(lo + step, n)), v2 = R.at(min(lo + 2 * step, n)), v3 = R.at(min(lo + 3 * step, n));
-                lo += ((v1 <= q ? 1u : 0u) + (v2 <= q ? 1u : 0u) + (v3 <= q ? 1u : 0u)) * step;
-                size = step;
-            }
-        } else {
-            // largest i in [0, n) with row[i] <= q: 4-ary search, wave-uniform trip count
-            lo = 0;
-            uint32_t size = n;
-            while (size > 1) {
-                const uint32_t step = (size + 3) >> 2;
-                const uint32_t p1 = lo + step, p2 = p1 + step, p3 = p2 + step;
-                const uint32_t v1 = p1 < n ? R.at(p1) : 0x10000u, v2 = p2 < n ? R.at(p2) : 0x10000u, v3 = p3 < n ? R.at(p3) : 0x10000u;
-                lo += ((v1 <= q ? 1u : 0u) + (v2 <= q ? 1u : 0u) + (v3 <= q ? 1u : 0u)) * step;
-                size = step;
-            }
-        }
+        const uint32_t lo = ps_search(R, bidx, indexed, q, P, n);
         const uint32_t c = R.at(lo);
         const uint32_t p = (R.at(lo + 1) - c) & 0xffffu;
         st_t st = (st_t)((st_t)(L.state >> P) * (st_t)p + (st_t)(q - c));          // stack.rs:1086-1088
@@ -260,30 +195,6 @@ __global__ void ans_decode_ps_kernel(const PsArgs a) {
         a.state[s] = (uint64_t)L.state;
         if (a.n_words_left) a.n_words_left[s] = L.in.rd;
     }
-}
-
-// threads per block such that rows + rings + symbol tiles fit in the 160 KiB of LDS of one CU
-static int pick_block(int L, bool with_tiles, size_t& lds) {
-    for (int threads = 256; threads >= 64; threads -= 64) {
-        lds = (size_t)threads * L * 2 + (size_t)(threads / kWave) * (kRingWords + (with_tiles ? kWave * kTileStride : 0)) * sizeof(uint32_t) +
-              (with_tiles ? 0 : (size_t)threads * kPsIdxStride * 2);   // encoder: symbol tiles; decoder: bucket index
-        if (lds <= 160 * 1024) return threads;
-    }
-    return 0;
-}
-
-template <typename K>
-static cst_status launch_ps(K kernel, const PsArgs& a, bool with_tiles, hipStream_t hs) {
-    size_t lds = 0;
-    const int threads = pick_block(a.L, with_tiles, lds);
-    if (threads == 0) return CST_ERR_INVALID_ARGUMENT;   // support too large for LDS-resident per-stream tables
-    const size_t blocks = (a.n_streams + threads - 1) / threads;
-    if (blocks > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
-    if (lds > 64 * 1024)
-        CST_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), lds, hs, a);
-    CST_HIP_TRY(hipGetLastError());
-    return CST_OK;
 }
 
 cst_status ans_encode_per_stream(const cst_model* model, cst_coder_config cfg, const int32_t* d_symbols, size_t n_streams,

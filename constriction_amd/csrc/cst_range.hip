@@ -384,7 +384,11 @@ cst_status cst_range_encode_batch(const cst_model* model, cst_coder_config cfg, 
     if (n_per_stream > 0 && !d_symbols) return CST_ERR_INVALID_ARGUMENT;
     if (!config_supported(cfg) || cfg.precision != model->precision) return CST_ERR_INVALID_ARGUMENT;
     if (layout != CST_LAYOUT_STREAM_MAJOR && layout != CST_LAYOUT_SYMBOL_MAJOR) return CST_ERR_INVALID_ARGUMENT;
-    if (model->per_stream) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream) {       // one table per stream (cst_range_ps.hip); no raw state: a caller continues streams with shared tables only
+        if ((flags & CST_FLAG_RAW_STATE) || model->n_tables != n_streams || !model->d_cdf16) return CST_ERR_INVALID_ARGUMENT;
+        return note_kernel("range_encode_ps_kernel", range_encode_per_stream(model, cfg, d_symbols, n_streams, n_per_stream, layout, d_words, stride_words,
+                                                                             d_n_words, d_status, nullptr, (hipStream_t)stream));
+    }
     if (n_streams == 0) return CST_OK;
     RangeEncodeArgs a{};
     a.symbols = d_symbols; a.n_streams = n_streams; a.n_per_stream = n_per_stream; a.enc = model->d_enc;
@@ -406,7 +410,12 @@ cst_status cst_range_decode_batch(const cst_model* model, cst_coder_config cfg, 
     if (n_per_stream > 0 && !d_symbols) return CST_ERR_INVALID_ARGUMENT;
     if (!config_supported(cfg) || cfg.precision != model->precision) return CST_ERR_INVALID_ARGUMENT;
     if (layout != CST_LAYOUT_STREAM_MAJOR && layout != CST_LAYOUT_SYMBOL_MAJOR) return CST_ERR_INVALID_ARGUMENT;
-    if (model->per_stream) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream) {       // one table per stream (cst_range_ps.hip)
+        if ((flags & CST_FLAG_RAW_STATE) || model->n_tables != n_streams || !model->d_cdf16) return CST_ERR_INVALID_ARGUMENT;
+        return note_kernel("range_decode_ps_kernel", range_decode_per_stream(model, cfg, d_words, d_offsets, stride_words, words_capacity, d_n_words, d_symbols,
+                                                                             n_streams, n_per_stream, layout, d_status, 0, nullptr, nullptr, nullptr,
+                                                                             (hipStream_t)stream));
+    }
     if (n_streams == 0) return CST_OK;
     RangeDecodeArgs a{};
     a.words = d_words; a.offsets = d_offsets; a.stride_words = stride_words; a.n_words = d_n_words; a.symbols = d_symbols;
@@ -426,8 +435,16 @@ cst_status cst_range_encode_batch_ckpt(const cst_model* model, cst_coder_config 
                                        int32_t* d_status, void* stream) {
     if (!model || !d_words || !d_n_words || !d_status || !d_ckpt_pos || !d_ckpt_lower || !d_ckpt_range || ckpt_interval == 0) return CST_ERR_INVALID_ARGUMENT;
     if (n_per_stream > 0 && !d_symbols) return CST_ERR_INVALID_ARGUMENT;
-    if (!config_supported(cfg) || cfg.precision != model->precision || model->per_stream) return CST_ERR_INVALID_ARGUMENT;
+    if (!config_supported(cfg) || cfg.precision != model->precision) return CST_ERR_INVALID_ARGUMENT;
     if (layout != CST_LAYOUT_STREAM_MAJOR && layout != CST_LAYOUT_SYMBOL_MAJOR) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream) {       // one table per stream (cst_range_ps.hip): stream-major, any interval >= 1
+        if (layout != CST_LAYOUT_STREAM_MAJOR || model->n_tables != n_streams || !model->d_cdf16) return CST_ERR_INVALID_ARGUMENT;
+        int dev = -1;
+        if (hipGetDevice(&dev) != hipSuccess || dev != model->device) return CST_ERR_INVALID_ARGUMENT;
+        const RangeCkptOut ck{d_ckpt_pos, d_ckpt_lower, d_ckpt_range, ckpt_interval, (n_per_stream + ckpt_interval - 1) / ckpt_interval};
+        return note_kernel("range_encode_ps_kernel<ckpt>", range_encode_per_stream(model, cfg, d_symbols, n_streams, n_per_stream, layout, d_words, stride_words,
+                                                                                   d_n_words, d_status, &ck, (hipStream_t)stream));
+    }
     if (n_streams == 0) return CST_OK;
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != model->device) return CST_ERR_INVALID_ARGUMENT;
@@ -459,7 +476,8 @@ cst_status cst_range_decode_batch_ckpt(const cst_model* model, cst_coder_config 
                                        void* stream) {
     if (!model || !d_n_words || !d_ckpt_pos || !d_ckpt_lower || !d_ckpt_range || !d_scratch || !d_status || ckpt_interval == 0) return CST_ERR_INVALID_ARGUMENT;
     if (n_per_stream % ckpt_interval != 0) return CST_ERR_INVALID_ARGUMENT;      // whole chunks only: rows of the virtual matrix
-    if (!config_supported(cfg) || cfg.precision != model->precision || model->per_stream) return CST_ERR_INVALID_ARGUMENT;
+    if (!config_supported(cfg) || cfg.precision != model->precision) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream && (model->n_tables != n_streams || !model->d_cdf16)) return CST_ERR_INVALID_ARGUMENT;
     if (n_streams == 0 || n_per_stream == 0) return CST_OK;
     if (!d_symbols || !d_words) return CST_ERR_INVALID_ARGUMENT;
     int dev = -1;
@@ -468,6 +486,10 @@ cst_status cst_range_decode_batch_ckpt(const cst_model* model, cst_coder_config 
     if (n_virtual > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
     hipStream_t hs = (hipStream_t)stream;
     const size_t capacity = words_capacity ? words_capacity : (d_offsets ? 0 : n_streams * stride_words);
+    if (model->per_stream)         // one table per stream (cst_range_ps.hip): every chunk on a lane of its own, continued at its jump point
+        return note_kernel("range_decode_ps_kernel<chunks>", range_decode_per_stream(model, cfg, d_words, d_offsets, stride_words, capacity, d_n_words, d_symbols,
+                                                                                     n_streams, n_per_stream, CST_LAYOUT_STREAM_MAJOR, d_status, ckpt_interval,
+                                                                                     d_ckpt_pos, d_ckpt_lower, d_ckpt_range, hs));
     RangeDecodeArgs a{};
     a.words = d_words; a.offsets = d_offsets; a.stride_words = stride_words; a.n_words = d_n_words; a.symbols = d_symbols;
     a.n_streams = n_streams; a.n_per_stream = n_per_stream; a.dec_cp = model->d_dec_cp; a.dec_idx = model->d_dec_idx;

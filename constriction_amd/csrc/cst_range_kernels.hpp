@@ -70,6 +70,16 @@ cst_status range_encode_ckpt_n8(const RangeEncodeArgs& a, const RangeCkptOut& ck
 bool range_decode_sub_n8_usable(const RangeDecodeArgs& a);
 cst_status range_decode_sub_n8(const RangeDecodeArgs& a, hipStream_t hs);
 
+// cst_range_ps.hip: one table per stream (model->per_stream; presets (32,64) and (16,32), P <= 16).  `ck` non-null: the encoder notes
+// jump points (stream-major only).  `interval` != 0: the decoder runs one lane per chunk, d_status [n_streams][n_per_stream / interval].
+cst_status range_encode_per_stream(const cst_model* model, cst_coder_config cfg, const int32_t* d_symbols, size_t n_streams, size_t n_per_stream,
+                                   cst_layout layout, uint32_t* d_words, size_t stride_words, uint32_t* d_n_words, int32_t* d_status,
+                                   const RangeCkptOut* ck, hipStream_t hs);
+cst_status range_decode_per_stream(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_offsets, size_t stride_words,
+                                   size_t words_capacity, const uint32_t* d_n_words, int32_t* d_symbols, size_t n_streams, size_t n_per_stream,
+                                   cst_layout layout, int32_t* d_status, size_t interval, const uint32_t* d_ckpt_pos, const uint64_t* d_ckpt_lower,
+                                   const uint64_t* d_ckpt_range, hipStream_t hs);
+
 // Forward-reading counterpart of RingReader (queue semantics).
 template <int SLOTS = kRingSlots, int AHEAD = kAhead>
 struct RingReaderFwd {

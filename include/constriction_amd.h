@@ -957,7 +957,10 @@ cst_status cst_ans_decode_gaussian_batch_ckpt_f32(cst_coder_config cfg, int32_t 
  * layout on the encoder side (the hand-scheduled (32,64) kernel for stream-major batches notes the jump points on its way);
  * the decoder wants stream-major symbols and n_per_stream a multiple of the interval, takes the whole streams' counts
  * (d_n_words: a lane reads past its chunk, never past its stream) and writes n_streams * n_chunks status entries; a jump point
- * beyond its stream's words reports CST_STREAM_INVALID_DATA for that chunk.  d_scratch: cst_range_ckpt_scratch_bytes(...). */
+ * beyond its stream's words reports CST_STREAM_INVALID_DATA for that chunk.  d_scratch: cst_range_ckpt_scratch_bytes(...).
+ * One table per stream (cst_model_create_gaussian_per_stream / cst_model_create_tables_per_stream with as many tables as
+ * streams): taken by both calls, stream-major only, any ckpt_interval >= 1 on the encoder side ("range_encode_ps_kernel<ckpt>");
+ * the decoder runs one lane per chunk, each with its own copy of its stream's row ("range_decode_ps_kernel<chunks>"). */
 cst_status cst_range_encode_batch_ckpt(const cst_model *model, cst_coder_config cfg, const int32_t *d_symbols,
                                        size_t n_streams, size_t n_per_stream, cst_layout layout, uint32_t *d_words,
                                        size_t stride_words, uint32_t *d_n_words, size_t ckpt_interval,
@@ -1301,7 +1304,12 @@ typedef struct cst_range_state {
 } cst_range_state;
 
 /* d_rstate (may be NULL unless CST_FLAG_RAW_STATE) is in/out with CST_FLAG_RAW_STATE: the encoder then starts
- * from it and appends no seal words, the decoder does not re-read `point` and continues at ->position. */
+ * from it and appends no seal words, the decoder does not re-read `point` and continues at ->position.
+ * The model has one shared table, or one table per stream (cst_model_create_gaussian_per_stream /
+ * cst_model_create_tables_per_stream: table s codes stream s; n_tables must equal n_streams, presets (32,64) and (16,32),
+ * precision <= 16, either layout; "range_encode_ps_kernel" / "range_decode_ps_kernel": the stream's 16-bit cdf row sits in
+ * LDS, a support too large for that is CST_ERR_INVALID_ARGUMENT).  With such a model CST_FLAG_RAW_STATE is refused
+ * (CST_ERR_INVALID_ARGUMENT).  cst_jump_points_auto answers 0 for it. */
 cst_status cst_range_encode_batch(const cst_model *model, cst_coder_config cfg, const int32_t *d_symbols,
                                   size_t n_streams, size_t n_per_stream, cst_layout layout,
                                   uint32_t *d_words, size_t stride_words, uint32_t *d_n_words,
@@ -1319,7 +1327,7 @@ cst_status cst_range_decode_batch(const cst_model *model, cst_coder_config cfg, 
  * 8 <= P <= 24, is read by the hand-scheduled encoder itself ("range_encode_n8_kernel" / "range_encode_ckpt_n8_kernel": a quarter of the
  * symbol bytes, one more instruction per symbol) and written by the sub-lane decoder itself ("range_decode_n8_kernel" /
  * "range_decode_sub_n8_kernel": its byte tiles hold the symbols); every other shape converts next to the int32 call
- * (cst_symbols_widen / cst_symbols_narrow).  The decoders want a support that fits the type.
+ * (cst_symbols_widen / cst_symbols_narrow), models with one table per stream among them.  The decoders want a support that fits the type.
  * d_scratch: cst_range_sym_scratch_bytes(n_streams, n_per_stream, ckpt_interval or 0, symbol_bytes) bytes, contents irrelevant. */
 size_t cst_range_sym_scratch_bytes(size_t n_streams, size_t n_per_stream, size_t ckpt_interval, int32_t symbol_bytes);
 cst_status cst_range_encode_batch_sym(const cst_model *model, cst_coder_config cfg, const void *d_symbols, int32_t symbol_bytes,
