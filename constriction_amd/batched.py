@@ -95,6 +95,7 @@ class Model:
         return out
 
     noncontiguous = False
+    per_stream = False            # True: table s belongs to stream s (the *_per_stream constructors), whatever the number of tables
 
     @classmethod
     def quantized_gaussian(cls, min_symbol: int, max_symbol: int, mean: float, std: float, precision: int) -> "Model":
@@ -115,7 +116,9 @@ class Model:
         N.check(N.lib().cst_model_create_gaussian_per_stream(precision, int(min_symbol), int(max_symbol), _ptr(means),
                                                              _ptr(stds), means.numel(), _stream_ptr(), C.byref(h)),
                 "cst_model_create_gaussian_per_stream")
-        return cls(h)
+        m = cls(h)
+        m.per_stream = True
+        return m
 
     @classmethod
     def from_cdf_rows_per_stream(cls, rows, min_symbol: int, precision: int) -> "Model":
@@ -137,7 +140,9 @@ class Model:
         h = C.c_void_p()
         N.check(N.lib().cst_model_create_tables_per_stream(int(precision), int(min_symbol), rows.shape[1] - 1, _ptr(rows), rows.shape[0],
                                                            _stream_ptr(), C.byref(h)), "cst_model_create_tables_per_stream")
-        return cls(h)
+        m = cls(h)
+        m.per_stream = True
+        return m
 
     @classmethod
     def fit(cls, symbols, min_symbol: int, max_symbol: int, precision: int, perfect: bool = False) -> "Model":
@@ -801,6 +806,29 @@ def _ragged_order(order, n_streams, keys):
     return order
 
 
+def _ragged_per_stream(model: Model, n_streams: int, config) -> bool:
+    """What the ragged calls ask of a model with one table per stream (quantized_gaussian_per_stream, from_cdf_rows_per_stream,
+    fit_per_stream with sym_offsets), said before any launch.  False: a shared table, of which nothing is asked here."""
+    if not (model.per_stream or model.n_tables != 1):
+        return False
+    if model.noncontiguous:
+        raise ValueError("tables per stream: contiguous alphabets only")
+    if model.n_tables != n_streams:
+        raise ValueError(f"the model has {model.n_tables} tables, the batch {n_streams} streams: one table per stream")
+    W, S, P = (int(x) for x in config)
+    if P != model.precision:
+        raise ValueError(f"the config's precision is {P}, the model's {model.precision}")
+    if (W, S) not in ((32, 64), (16, 32)):
+        raise ValueError("tables per stream: presets (32, 64) and (16, 32) only")
+    return True
+
+
+def _refuse_per_stream(model: Model, what: str) -> None:
+    if model.per_stream or model.n_tables != 1:
+        raise ValueError(f"{what}: shared tables only (a model with one table per stream decodes whole batches: ans_decode_ragged / "
+                         f"range_decode_ragged)")
+
+
 def _require_coder(encoded: RaggedBatch, coder: str) -> None:
     if encoded.coder != coder:
         raise ValueError(f"the batch holds the words of the {encoded.coder!r} coder: a {coder!r} decoder cannot read them")
@@ -815,12 +843,18 @@ def ans_encode_ragged(symbols: torch.Tensor, sym_offsets: torch.Tensor, model: M
     jump_every: the encoder also notes AnsCoder.pos() in front of every jump_every symbols of every stream (a multiple of 8; the words
     are unchanged) and the batch carries the table as `.jump`: ans_decode_ragged then decodes all chunks side by side -- a launch
     lasts as long as its longest CHAIN, and a 2000-symbol document among short ones is 2000 dependent steps without jump points.
-    "auto" (default): every RAGGED_JUMP_EVERY symbols if the streams average more than a quarter of that; 0: none."""
+    "auto" (default): every RAGGED_JUMP_EVERY symbols if the streams average more than a quarter of that; 0: none.
+    model: one shared table, or ONE TABLE PER STREAM (Model.fit_per_stream(..., sym_offsets=), from_cdf_rows_per_stream,
+    quantized_gaussian_per_stream): as many tables as streams, contiguous alphabets, presets (32, 64) and (16, 32), the config's precision
+    the model's (<= 16) -- anything else raises ValueError before a launch.  Stream s is coded with table s; its words are those of
+    ans_encode for that stream alone.  With tables per stream "auto" notes NO jump points (every chunk lane of the decoder stages its own
+    copy of its stream's row, and nothing has measured where that pays); an explicit jump_every is honoured."""
     symbols = _to_indices(model, _require_cuda(symbols, torch.int32, "symbols"))
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
     n_streams = sym_offsets.numel() - 1
     if symbols.dim() != 1 or n_streams < 0:
         raise ValueError("symbols must be flat and sym_offsets hold n_streams + 1 entries")
+    per_stream = _ragged_per_stream(model, n_streams, config)
     W, S, P = config
     lengths = sym_offsets[1:] - sym_offsets[:-1]
     # a stream of n symbols fills at most min(n, ceil(n P / W)) + S / W words (cst_ans_max_words without its rounding to 64 bytes:
@@ -838,7 +872,7 @@ def ans_encode_ragged(symbols: torch.Tensor, sym_offsets: torch.Tensor, model: M
     if isinstance(jump_every, str):
         if jump_every != "auto":
             raise ValueError("jump_every: 'auto', 0 or a multiple of 8")
-        jump_every = RAGGED_JUMP_EVERY if n_streams > 0 and symbols.numel() * 4 > n_streams * RAGGED_JUMP_EVERY else 0
+        jump_every = RAGGED_JUMP_EVERY if n_streams > 0 and symbols.numel() * 4 > n_streams * RAGGED_JUMP_EVERY and not per_stream else 0
     jump_every = int(jump_every or 0)
     if jump_every < 0 or jump_every % 8 != 0:
         raise ValueError("jump_every: 'auto', 0 or a multiple of 8")
@@ -865,10 +899,13 @@ def ans_decode_ragged(encoded: RaggedBatch, model: Model, sym_offsets: torch.Ten
     """from_compressed + decode_iid_symbols per stream (stack.rs:299-318, 1070-1100): stream s yields
     sym_offsets[s + 1] - sym_offsets[s] symbols at out[sym_offsets[s]:].  Returns (symbols flat, status per stream).
     `order`: the schedule (see _ragged_order); "auto" reuses the encoder's, or sorts by word count from RAGGED_BALANCE_FROM
-    streams on."""
+    streams on.
+    model: the shared table, or the per-stream model the batch was encoded with (as many tables as streams; ValueError otherwise, or if
+    the batch's precision is not the model's); a table of jump points is followed for either."""
     _require_coder(encoded, "ans")
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
     n_streams = sym_offsets.numel() - 1
+    _ragged_per_stream(model, n_streams, encoded.config)
     # a batch with jump points decodes its chunks side by side (they are all at most `interval` symbols long: no schedule needed) --
     # unless the caller hands in a schedule of their own, which is then honoured on the whole streams
     take_jump = encoded.jump is not None and (order is None or (isinstance(order, str) and order == "auto"))
@@ -904,7 +941,9 @@ def ans_decode_until(encoded: RaggedBatch, model: Model, eof_symbol: int, max_sy
     -- count, prefix sum, decode.  Returns (symbols flat, sym_offsets [n + 1], status); the terminator is the last symbol of
     every stream; status CAPACITY (2): no terminator among the first max_symbols symbols -- such a stream (corrupt data, a wrong
     eof_symbol) decodes to NO symbols: its length is 0 in sym_offsets, so that a batch of bad documents cannot ask for
-    n_streams x max_symbols symbols of output.  max_symbols defaults to 2^20."""
+    n_streams x max_symbols symbols of output.  max_symbols defaults to 2^20.  Shared tables only: a model with one table per stream
+    raises ValueError."""
+    _refuse_per_stream(model, "ans_decode_until")
     max_symbols = (1 << 20) if max_symbols is None else int(max_symbols)
     if model.noncontiguous:
         raise ValueError("ans_decode_until: contiguous alphabets only")
@@ -943,7 +982,10 @@ def range_encode_ragged(symbols: torch.Tensor, sym_offsets: torch.Tensor, model:
     """One RangeEncoder per stream, streams of different lengths (`symbols` flat, stream s = symbols[sym_offsets[s]:sym_offsets[s+1]]):
     encode_iid_symbols + get_compressed per stream (queue.rs:612-705, 458-523) in ONE launch.  Every stream's words are those of
     range_encode for that stream alone; a slab holds min(n, ceil(n P / W)) + 2 words, rounded up to 4.  The batch says
-    `.coder == "range"`, carries no jump points (`.jump` is None) and the schedule it ran with in `.order` (see _ragged_order)."""
+    `.coder == "range"`, carries no jump points (`.jump` is None) and the schedule it ran with in `.order` (see _ragged_order).
+    model: one shared table, or one table per stream (as many tables as streams, contiguous alphabets, presets (32, 64) and (16, 32), the
+    config's precision the model's: ValueError otherwise, before a launch); stream s is then coded with table s, its words those of
+    range_encode for that stream alone."""
     return _range_encode_ragged(symbols, sym_offsets, model, config, order, 0)
 
 
@@ -956,7 +998,9 @@ def range_encode_ragged_jump(symbols: torch.Tensor, sym_offsets: torch.Tensor, m
     chunk each (not the ANS rule of a quarter of that: 100 000 documents of 200 symbols, one chunk each, encode in 0.133 instead of
     0.104 ms and decode in 0.142 instead of 0.126 ms with a table that buys them nothing, while documents of 20 .. 2000 symbols, 430 on
     average, decode in 0.30 instead of 0.94 ms for 0.55 instead of 0.51 ms of encoding); 0: none -- the result is
-    exactly range_encode_ragged's."""
+    exactly range_encode_ragged's.  A model with one table per stream (see range_encode_ragged): "auto" is 0 -- every chunk lane of the
+    decoder stages its own copy of its stream's row, nothing has measured where that pays, and on rectangular per-stream batches the
+    points were a loss --, an explicit jump_every is honoured."""
     return _range_encode_ragged(symbols, sym_offsets, model, config, order, _range_jump_every(jump_every))
 
 
@@ -967,6 +1011,7 @@ def _range_encode_ragged(symbols, sym_offsets, model, config, order, jump_every)
     n_streams = sym_offsets.numel() - 1
     if symbols.dim() != 1 or sym_offsets.dim() != 1 or n_streams < 0:
         raise ValueError("symbols must be flat and sym_offsets hold n_streams + 1 entries")
+    per_stream = _ragged_per_stream(model, n_streams, config)
     W, S, P = config
     dev = symbols.device
     lengths = sym_offsets[1:] - sym_offsets[:-1]
@@ -984,7 +1029,7 @@ def _range_encode_ragged(symbols, sym_offsets, model, config, order, jump_every)
     if n_streams == 0:
         return out
     if jump_every == "auto":
-        jump_every = RAGGED_JUMP_EVERY if symbols.numel() > n_streams * RAGGED_JUMP_EVERY else 0
+        jump_every = RAGGED_JUMP_EVERY if symbols.numel() > n_streams * RAGGED_JUMP_EVERY and not per_stream else 0
     if jump_every:
         chunk_offsets = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
         torch.cumsum((lengths + (jump_every - 1)) // jump_every, 0, out=chunk_offsets[1:])
@@ -1009,10 +1054,13 @@ def range_decode_ragged(encoded: RaggedBatch, model: Model, sym_offsets: torch.T
     sym_offsets[s + 1] - sym_offsets[s] symbols at out[sym_offsets[s]:], in the order they were encoded.  Returns (symbols flat,
     status per stream).  `order`: the schedule (see _ragged_order); "auto" reuses the encoder's, or sorts by word count from
     RAGGED_BALANCE_FROM streams on.  A batch with jump points (range_encode_ragged_jump) decodes its chunks side by side when `order` is
-    None or "auto"; a schedule handed in is honoured on the whole streams."""
+    None or "auto"; a schedule handed in is honoured on the whole streams.
+    model: the shared table, or the per-stream model the batch was encoded with (as many tables as streams; ValueError otherwise, or if
+    the batch's precision is not the model's); a table of jump points is followed for either."""
     _require_coder(encoded, "range")
     sym_offsets = _require_cuda(sym_offsets, torch.int64, "sym_offsets")
     n_streams = sym_offsets.numel() - 1
+    _ragged_per_stream(model, n_streams, encoded.config)
     if sym_offsets.dim() != 1 or encoded.n_words.numel() != n_streams:
         raise ValueError("sym_offsets does not match the number of streams of the batch")
     jump = encoded.jump
@@ -1171,6 +1219,7 @@ def _decode_ragged_select(coder, jump_type, encoded, model, sym_offsets, streams
     jump = encoded.jump
     if jump is not None and not isinstance(jump, jump_type):
         raise ValueError("the batch carries the jump points of another coder")
+    _refuse_per_stream(model, f"{coder}_decode_ragged_select")
     r = _select_queries(encoded, jump, sym_offsets, streams, first, count, out)
     sym_offsets, n_streams, interval, n_pieces, out, out_offsets, status, total = (r.sym_offsets, r.n_streams, r.interval, r.n_pieces, r.out,
                                                                                    r.out_offsets, r.status, r.total)
@@ -1206,7 +1255,7 @@ def ans_decode_ragged_select(encoded: RaggedBatch, model: Model, sym_offsets: to
     WITHOUT them a query starts where its document starts and discards `first` symbols -- correct, and as slow as `first` is deep: that
     is what jump points are for.  A query the device refuses (no such document, a range beyond its document, a table or counts that do
     not fit) reports INVALID_DATA (3) and writes nothing; the others decode.  (Sized on the device: the output total is the only
-    read-back.)"""
+    read-back.)  Shared tables only: a model with one table per stream raises ValueError."""
     return _decode_ragged_select("ans", RaggedJump, encoded, model, sym_offsets, streams, first, count, out)
 
 
@@ -1214,7 +1263,7 @@ def range_decode_ragged_select(encoded: RaggedBatch, model: Model, sym_offsets: 
                                out: Optional[torch.Tensor] = None):
     """ans_decode_ragged_select for a range batch (range_encode_ragged / range_encode_ragged_jump): the same queries, the same three
     results.  A piece seeks to its (pos, lower, range) entry and reads forward; without jump points it starts at word 0 of its document
-    and discards `first` symbols."""
+    and discards `first` symbols.  Shared tables only: a model with one table per stream raises ValueError."""
     return _decode_ragged_select("range", RangeRaggedJump, encoded, model, sym_offsets, streams, first, count, out)
 
 
@@ -1223,8 +1272,9 @@ def range_decode_until(encoded: RaggedBatch, model: Model, eof_symbol: int, max_
     count, prefix sum, decode -- as ans_decode_until.  Returns (symbols flat, sym_offsets [n + 1], status); the terminator is the last
     symbol of every stream.  A range decoder never runs out of words (the reference shifts in zeros), so `max_symbols` (default 2^20)
     is the only stop for a stream without a terminator: status CAPACITY (2), and such a stream decodes to NO symbols (its length is 0
-    in sym_offsets).  Contiguous alphabets only."""
+    in sym_offsets).  Contiguous alphabets and shared tables only: a model with one table per stream raises ValueError."""
     _require_coder(encoded, "range")
+    _refuse_per_stream(model, "range_decode_until")
     max_symbols = (1 << 20) if max_symbols is None else int(max_symbols)
     if model.noncontiguous:
         raise ValueError("range_decode_until: contiguous alphabets only")

@@ -24,6 +24,7 @@
 // Every stream's words are those of cst_ans_encode_batch for that stream alone (stack.rs:835-849, 891-895; 1070-1100).
 #include "cst_ans_kernels.hpp"
 #include "cst_ragged_select.hpp"
+#include "cst_ragged_ps.hpp"
 
 namespace cst {
 
@@ -582,6 +583,20 @@ cst_status ans_decode_ragged_jump(const cst_model* model, cst_coder_config cfg, 
     uint64_t* v_word = v_sym + n_chunks_total + 2;
     int32_t* v_status = reinterpret_cast<int32_t*>(v_word + n_chunks_total + 1);
     const unsigned grid = (unsigned)((n_streams + 255) / 256);
+    if (model->per_stream) {
+        // one table per stream (cst_ragged_ps.hip): every chunk lane finds the stream that owns it -- whose row it stages -- and its
+        // symbols itself, so no virtual offsets are written; the statuses are folded as below
+        if (n_chunks_total > 0) {
+            const cst_status rc = ans_decode_ragged_ps_chunks(model, cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_symbols,
+                                                              d_sym_offsets, n_streams, interval, d_chunk_offsets, n_chunks_total, d_jump_pos, d_jump_state,
+                                                              v_status, hs);
+            if (rc != CST_OK) return rc;
+        }
+        hipLaunchKernelGGL(ragged_jump_status_kernel, dim3(grid), dim3(256), 0, hs, v_status, d_sym_offsets, d_chunk_offsets, d_jump_pos, d_n_words,
+                           n_streams, n_chunks_total, interval, d_status);
+        CST_HIP_TRY(hipGetLastError());
+        return CST_OK;
+    }
     const size_t v_threads = n_streams > n_chunks_total + 1 ? n_streams : n_chunks_total + 1;
     hipLaunchKernelGGL(ragged_jump_virtual_kernel, dim3((unsigned)((v_threads + 255) / 256)), dim3(256), 0, hs, d_sym_offsets, d_word_offsets, stride_words, d_chunk_offsets, n_streams,
                        n_chunks_total, interval, v_sym, v_word);

@@ -5,6 +5,7 @@
 #include <string>
 
 #include "cst_ans_kernels.hpp"
+#include "cst_ragged_ps.hpp"
 
 namespace cst {
 
@@ -362,10 +363,15 @@ cst_status cst_ans_encode_ragged_ordered(const cst_model* model, cst_coder_confi
                                          size_t n_streams, const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets,
                                          size_t stride_words, uint32_t* d_n_words, int32_t* d_status, void* stream) {
     if (!model || !config_supported(cfg) || cfg.precision != model->precision) return CST_ERR_INVALID_ARGUMENT;
-    if (model->per_stream) return CST_ERR_INVALID_ARGUMENT;      // one shared table (the pattern of tests/issue52.rs)
+    // one shared table (the pattern of tests/issue52.rs), or one table per stream: table s codes stream s (cst_ragged_ps.hip)
+    if (model->per_stream && !ragged_ps_model_ok(model, cfg, n_streams, true)) return CST_ERR_INVALID_ARGUMENT;
     if (n_streams == 0) return CST_OK;
     if (!d_sym_offsets || !d_words || !d_n_words || !d_status || !ragged_order_ok(d_order, n_streams)) return CST_ERR_INVALID_ARGUMENT;
     if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream)
+        return note_kernel("ans_encode_ragged_ps_kernel", ans_encode_ragged_ps(model, cfg, d_symbols, d_sym_offsets, n_streams, d_words, d_word_offsets,
+                                                                            stride_words, d_n_words, d_status, d_order, 0, nullptr, nullptr, nullptr,
+                                                                            (hipStream_t)stream));
     return note_kernel("ans_encode_ragged_kernel", ans_encode_ragged(model, cfg, d_symbols, d_sym_offsets, n_streams, d_words, d_word_offsets, stride_words,
                                                                      d_n_words, d_status, d_order, (hipStream_t)stream));
 }
@@ -382,10 +388,13 @@ cst_status cst_ans_decode_ragged_ordered(const cst_model* model, cst_coder_confi
                                          const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order, int32_t* d_status,
                                          void* stream) {
     if (!model || !config_supported(cfg) || cfg.precision != model->precision) return CST_ERR_INVALID_ARGUMENT;
-    if (model->per_stream) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream && !ragged_ps_model_ok(model, cfg, n_streams, false)) return CST_ERR_INVALID_ARGUMENT;
     if (n_streams == 0) return CST_OK;
     if (!d_sym_offsets || !d_n_words || !d_status || !ragged_order_ok(d_order, n_streams)) return CST_ERR_INVALID_ARGUMENT;
     if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream)
+        return note_kernel("ans_decode_ragged_ps_kernel", ans_decode_ragged_ps(model, cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+                                                                            d_symbols, d_sym_offsets, n_streams, d_status, d_order, (hipStream_t)stream));
     return note_kernel("ans_decode_ragged_kernel", ans_decode_ragged(model, cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words, d_symbols,
                                                                      d_sym_offsets, n_streams, d_status, d_order, (hipStream_t)stream));
 }
@@ -404,12 +413,17 @@ cst_status cst_ans_encode_ragged_jump(const cst_model* model, cst_coder_config c
                                       size_t n_streams, const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets,
                                       size_t stride_words, uint32_t* d_n_words, size_t jump_interval, const uint64_t* d_chunk_offsets,
                                       uint32_t* d_jump_pos, uint64_t* d_jump_state, int32_t* d_status, void* stream) {
-    if (!model || !config_supported(cfg) || cfg.precision != model->precision || model->per_stream) return CST_ERR_INVALID_ARGUMENT;
+    if (!model || !config_supported(cfg) || cfg.precision != model->precision) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream && !ragged_ps_model_ok(model, cfg, n_streams, true)) return CST_ERR_INVALID_ARGUMENT;
     if (jump_interval == 0 || jump_interval % 8 != 0 || jump_interval > 0x7fffffffull) return CST_ERR_INVALID_ARGUMENT;
     if (n_streams == 0) return CST_OK;
     if (!d_sym_offsets || !d_words || !d_n_words || !d_status || !d_chunk_offsets || !d_jump_pos || !d_jump_state || !ragged_order_ok(d_order, n_streams))
         return CST_ERR_INVALID_ARGUMENT;
     if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream)
+        return note_kernel("ans_encode_ragged_ps_kernel<jump>", ans_encode_ragged_ps(model, cfg, d_symbols, d_sym_offsets, n_streams, d_words, d_word_offsets,
+                                                                                  stride_words, d_n_words, d_status, d_order, (uint32_t)jump_interval,
+                                                                                  d_chunk_offsets, d_jump_pos, d_jump_state, (hipStream_t)stream));
     return note_kernel("ans_encode_ragged_kernel<jump>", ans_encode_ragged_jump(model, cfg, d_symbols, d_sym_offsets, n_streams, d_words, d_word_offsets,
                                                                                  stride_words, d_n_words, d_status, d_order, (uint32_t)jump_interval,
                                                                                  d_chunk_offsets, d_jump_pos, d_jump_state, (hipStream_t)stream));
@@ -420,12 +434,14 @@ cst_status cst_ans_decode_ragged_jump(const cst_model* model, cst_coder_config c
                                       const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets,
                                       size_t n_chunks_total, const uint32_t* d_jump_pos, const uint64_t* d_jump_state, void* d_scratch,
                                       int32_t* d_status, void* stream) {
-    if (!model || !config_supported(cfg) || cfg.precision != model->precision || model->per_stream) return CST_ERR_INVALID_ARGUMENT;
+    if (!model || !config_supported(cfg) || cfg.precision != model->precision) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream && !ragged_ps_model_ok(model, cfg, n_streams, false)) return CST_ERR_INVALID_ARGUMENT;
     if (jump_interval == 0 || jump_interval % 8 != 0 || jump_interval > 0x7fffffffull || n_chunks_total > 0xffffffffull) return CST_ERR_INVALID_ARGUMENT;
     if (n_streams == 0) return CST_OK;
     if (!d_sym_offsets || !d_n_words || !d_status || !d_chunk_offsets || !d_jump_pos || !d_jump_state || !d_scratch) return CST_ERR_INVALID_ARGUMENT;
     if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
-    return note_kernel("ans_decode_ragged_kernel<jump>", ans_decode_ragged_jump(model, cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
+    // (a per-stream model: the same host path, its chunk lanes on ans_decode_ragged_ps_kernel -- cst_ans_ragged.hip decides)
+    return note_kernel(model->per_stream ? "ans_decode_ragged_ps_kernel<jump>" : "ans_decode_ragged_kernel<jump>", ans_decode_ragged_jump(model, cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
                                                                                  d_symbols, d_sym_offsets, n_streams, (uint32_t)jump_interval, d_chunk_offsets,
                                                                                  n_chunks_total, d_jump_pos, d_jump_state, d_scratch, d_status,
                                                                                  (hipStream_t)stream));
@@ -453,9 +469,11 @@ cst_status cst_ans_count_until(const cst_model* model, cst_coder_config cfg, con
 
 // ---- the range coder with a shared table over streams of different lengths (cst_range_ragged.hip) ----
 // every refusal comes before the device is touched, whatever the number of streams (as the per-symbol ragged calls do it)
+// `per_stream_too`: the call also takes a model with one table per stream, table s for stream s (cst_ragged_ps.hip)
 static bool range_ragged_args_ok(const cst_model* model, cst_coder_config cfg, const uint64_t* d_word_offsets, size_t stride_words,
-                                 const uint32_t* d_order, size_t n_streams) {
-    if (!model || !config_supported(cfg) || cfg.precision != model->precision || model->per_stream) return false;
+                                 const uint32_t* d_order, size_t n_streams, bool per_stream_too = false) {
+    if (!model || !config_supported(cfg) || cfg.precision != model->precision) return false;
+    if (model->per_stream && (!per_stream_too || !ragged_ps_model_ok(model, cfg, n_streams, false))) return false;
     if (!d_word_offsets && stride_words == 0) return false;
     return ragged_order_ok(d_order, n_streams);
 }
@@ -463,10 +481,14 @@ static bool range_ragged_args_ok(const cst_model* model, cst_coder_config cfg, c
 cst_status cst_range_encode_ragged(const cst_model* model, cst_coder_config cfg, const int32_t* d_symbols, const uint64_t* d_sym_offsets,
                                    size_t n_streams, const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets,
                                    size_t stride_words, uint32_t* d_n_words, int32_t* d_status, void* stream) {
-    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, d_order, n_streams)) return CST_ERR_INVALID_ARGUMENT;
+    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, d_order, n_streams, true)) return CST_ERR_INVALID_ARGUMENT;
     if (!d_sym_offsets || !d_words || !d_n_words || !d_status) return CST_ERR_INVALID_ARGUMENT;
     if (n_streams == 0) return CST_OK;
     if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream)
+        return note_kernel("range_encode_ragged_ps_kernel", range_encode_ragged_ps(model, cfg, d_symbols, d_sym_offsets, n_streams, d_words, d_word_offsets,
+                                                                                stride_words, d_n_words, d_status, d_order, 0, nullptr, nullptr, nullptr,
+                                                                                nullptr, (hipStream_t)stream));
     return note_kernel("range_encode_ragged_kernel", range_encode_ragged(model, cfg, d_symbols, d_sym_offsets, n_streams, d_words, d_word_offsets,
                                                                          stride_words, d_n_words, d_status, d_order, (hipStream_t)stream));
 }
@@ -474,10 +496,14 @@ cst_status cst_range_encode_ragged(const cst_model* model, cst_coder_config cfg,
 cst_status cst_range_decode_ragged(const cst_model* model, cst_coder_config cfg, const uint32_t* d_words, const uint64_t* d_word_offsets,
                                    size_t stride_words, size_t words_capacity, const uint32_t* d_n_words, int32_t* d_symbols,
                                    const uint64_t* d_sym_offsets, size_t n_streams, const uint32_t* d_order, int32_t* d_status, void* stream) {
-    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, d_order, n_streams)) return CST_ERR_INVALID_ARGUMENT;
+    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, d_order, n_streams, true)) return CST_ERR_INVALID_ARGUMENT;
     if (!d_sym_offsets || !d_n_words || !d_status) return CST_ERR_INVALID_ARGUMENT;
     if (n_streams == 0) return CST_OK;
     if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream)
+        return note_kernel("range_decode_ragged_ps_kernel", range_decode_ragged_ps(model, cfg, d_words, d_word_offsets, stride_words, words_capacity,
+                                                                                d_n_words, d_symbols, d_sym_offsets, n_streams, d_status, d_order,
+                                                                                (hipStream_t)stream));
     return note_kernel("range_decode_ragged_kernel", range_decode_ragged(model, cfg, d_words, d_word_offsets, stride_words, words_capacity, d_n_words,
                                                                          d_symbols, d_sym_offsets, n_streams, d_status, d_order, (hipStream_t)stream));
 }
@@ -504,12 +530,17 @@ cst_status cst_range_encode_ragged_jump(const cst_model* model, cst_coder_config
                                         size_t n_streams, const uint32_t* d_order, uint32_t* d_words, const uint64_t* d_word_offsets,
                                         size_t stride_words, uint32_t* d_n_words, size_t jump_interval, const uint64_t* d_chunk_offsets,
                                         uint32_t* d_jump_pos, uint64_t* d_jump_lower, uint64_t* d_jump_range, int32_t* d_status, void* stream) {
-    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, d_order, n_streams) || !ragged_jump_interval_ok(jump_interval))
+    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, d_order, n_streams, true) || !ragged_jump_interval_ok(jump_interval))
         return CST_ERR_INVALID_ARGUMENT;
     if (!d_sym_offsets || !d_words || !d_n_words || !d_status || !d_chunk_offsets || !d_jump_pos || !d_jump_lower || !d_jump_range)
         return CST_ERR_INVALID_ARGUMENT;
     if (n_streams == 0) return CST_OK;
     if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
+    if (model->per_stream)
+        return note_kernel("range_encode_ragged_ps_kernel<jump>", range_encode_ragged_ps(model, cfg, d_symbols, d_sym_offsets, n_streams, d_words,
+                                                                                      d_word_offsets, stride_words, d_n_words, d_status, d_order,
+                                                                                      (uint32_t)jump_interval, d_chunk_offsets, d_jump_pos, d_jump_lower,
+                                                                                      d_jump_range, (hipStream_t)stream));
     return note_kernel("range_encode_ragged_kernel<jump>", range_encode_ragged_jump(model, cfg, d_symbols, d_sym_offsets, n_streams, d_words, d_word_offsets,
                                                                                      stride_words, d_n_words, d_status, d_order, (uint32_t)jump_interval,
                                                                                      d_chunk_offsets, d_jump_pos, d_jump_lower, d_jump_range,
@@ -521,14 +552,15 @@ cst_status cst_range_decode_ragged_jump(const cst_model* model, cst_coder_config
                                         const uint64_t* d_sym_offsets, size_t n_streams, size_t jump_interval, const uint64_t* d_chunk_offsets,
                                         size_t n_chunks_total, const uint32_t* d_jump_pos, const uint64_t* d_jump_lower,
                                         const uint64_t* d_jump_range, void* d_scratch, int32_t* d_status, void* stream) {
-    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, nullptr, n_streams) || !ragged_jump_interval_ok(jump_interval) ||
+    if (!range_ragged_args_ok(model, cfg, d_word_offsets, stride_words, nullptr, n_streams, true) || !ragged_jump_interval_ok(jump_interval) ||
         n_chunks_total > 0xffffffffull)
         return CST_ERR_INVALID_ARGUMENT;
     if (!d_sym_offsets || !d_n_words || !d_status || !d_chunk_offsets || !d_jump_pos || !d_jump_lower || !d_jump_range || !d_scratch)
         return CST_ERR_INVALID_ARGUMENT;
     if (n_streams == 0) return CST_OK;
     if (!on_model_device(model)) return CST_ERR_INVALID_ARGUMENT;
-    return note_kernel("range_decode_ragged_kernel<jump>", range_decode_ragged_jump(model, cfg, d_words, d_word_offsets, stride_words, words_capacity,
+    // (a per-stream model: the same host path, its chunk lanes on range_decode_ragged_ps_kernel -- cst_range_ragged.hip decides)
+    return note_kernel(model->per_stream ? "range_decode_ragged_ps_kernel<jump>" : "range_decode_ragged_kernel<jump>", range_decode_ragged_jump(model, cfg, d_words, d_word_offsets, stride_words, words_capacity,
                                                                                      d_n_words, d_symbols, d_sym_offsets, n_streams,
                                                                                      (uint32_t)jump_interval, d_chunk_offsets, n_chunks_total, d_jump_pos,
                                                                                      d_jump_lower, d_jump_range, d_scratch, d_status, (hipStream_t)stream));

@@ -1,5 +1,5 @@
 // cst_per_stream_rows.hpp -- one cdf row per stream, held in LDS for a whole kernel: what the per-stream ANS coder
-// (cst_ans_ps.hip) and the per-stream range coder (cst_range_ps.hip) share.
+// (cst_ans_ps.hip), the per-stream range coder (cst_range_ps.hip) and their ragged forms (cst_ragged_ps.hip) share.
 //
 // Each lane's cumulative table (n+1 entries of 16 bits, row length L = 2^k) is TRANSPOSED per wave: entry e of lane l
 // lives at [e][l] (like the word rings).  The bank of an access then depends on the lane only, whatever index the lane
@@ -32,6 +32,24 @@ __device__ __forceinline__ void stage_rows(uint16_t* lds_rows, const Args& a, si
         const size_t s = block_s0 + j;
         const size_t row = lanes_per_table == 1 ? s : s / lanes_per_table;
         uint16_t v = s < a.n_streams ? a.cdf16[row * L + e] : (uint16_t)0;
+        if (pad && e > (uint32_t)a.n_symbols) v = 0xFFFFu;
+        lds_rows[((size_t)(j >> 6) * L + e) * kWave + (j & 63u)] = v;      // [wave][entry][lane]
+    }
+}
+
+// The same staging where a lane's row is not a function of its number (ragged batches, cst_ragged_ps.hip: the stream a
+// schedule gives the lane, or the stream that owns the lane's chunk): `lane_row` [blockDim.x] in LDS, written by the lanes
+// themselves (a barrier between that and this call); kPsNoRow = a lane without a stream, whose row is staged as zeros.
+constexpr uint32_t kPsNoRow = 0xffffffffu;
+template <class Args>
+__device__ __forceinline__ void stage_rows_by_index(uint16_t* lds_rows, const Args& a, const uint32_t* lane_row, bool pad = false) {
+    const uint32_t L = (uint32_t)a.L, mask = L - 1;
+    const uint32_t total = blockDim.x * L;
+    const int shift = __builtin_ctz(L);
+    for (uint32_t idx = threadIdx.x; idx < total; idx += blockDim.x) {
+        const uint32_t j = idx >> shift, e = idx & mask;
+        const uint32_t row = lane_row[j];
+        uint16_t v = row != kPsNoRow ? a.cdf16[(size_t)row * L + e] : (uint16_t)0;
         if (pad && e > (uint32_t)a.n_symbols) v = 0xFFFFu;
         lds_rows[((size_t)(j >> 6) * L + e) * kWave + (j & 63u)] = v;      // [wave][entry][lane]
     }

@@ -23,6 +23,7 @@
 // decoder's body (its MODE: kRrPlain, kRrJump, kRrSelect), around it the kernels of cst_ragged_select.hpp.
 #include "cst_range_kernels.hpp"
 #include "cst_ragged_select.hpp"
+#include "cst_ragged_ps.hpp"
 
 namespace cst {
 
@@ -592,7 +593,11 @@ cst_status range_decode_ragged_jump(const cst_model* model, cst_coder_config cfg
         RangeRaggedArgs a = rr_decode_args(model, d_words, nullptr, 0, words_capacity, nullptr, n_chunks_total, v.status, nullptr);
         a.symbols_out = d_symbols;
         const RangeRaggedChunks ch{v.sym_lo, v.len, v.word_off, v.n_words, d_jump_pos, d_jump_lower, d_jump_range};
-        const cst_status rc = rr_decode_chunks(model, cfg, a, ch, hs);
+        // (one table per stream: the chunk lanes of cst_ragged_ps.hip, each with a copy of its owner's row)
+        const cst_status rc = model->per_stream ? range_decode_ragged_ps_chunks(model, cfg, d_words, words_capacity, d_symbols, n_chunks_total, v.sym_lo,
+                                                                                v.len, v.word_off, v.n_words, v.owner, d_jump_pos, d_jump_lower,
+                                                                                d_jump_range, v.status, hs)
+                                                : rr_decode_chunks(model, cfg, a, ch, hs);
         if (rc != CST_OK) return rc;
     }
     hipLaunchKernelGGL(rr_chunk_status_kernel, dim3((unsigned)((n_streams + 255) / 256)), dim3(256), 0, hs, v, d_sym_offsets, d_word_offsets, stride_words,

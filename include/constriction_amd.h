@@ -312,8 +312,14 @@ cst_status cst_ans_decode_batch_sym(const cst_model *model, cst_coder_config cfg
  *                           d_words[s * stride_words .. + stride_words)
  * Every stream's words, count and status are those of cst_ans_encode_batch / the reference coder for that stream alone; the
  * decoder takes the same offsets (only d_word_offsets[s] and d_n_words[s] are read) or a packed layout, with the bounds
- * check of cst_ans_decode_batch.  Shared-table models, stream-major symbols, any preset.  A wave of 64 consecutive streams
- * runs as long as its longest one. */
+ * check of cst_ans_decode_batch.  Stream-major symbols.  A wave of 64 consecutive streams runs as long as its longest one.
+ * The model has one shared table (any preset), or ONE TABLE PER STREAM (cst_model_create_gaussian_per_stream /
+ * cst_model_create_tables_per_stream, e.g. rows fitted per document from cst_count_symbols_per_stream with d_sym_offsets): table s
+ * codes stream s, and every stream's words are those of cst_ans_encode_batch with that per-stream model for that stream alone.
+ * With a per-stream model n_tables must equal n_streams, the presets are (32,64) and (16,32), P <= 16, and the tables of a
+ * workgroup live in LDS (a support too large for that is CST_ERR_INVALID_ARGUMENT, as in cst_ans_encode_batch); all of
+ * cst_ans_{encode,decode}_ragged[_ordered] and cst_ans_{encode,decode}_ragged_jump take such a model (cst_last_kernel_name:
+ * "ans_{encode,decode}_ragged_ps_kernel", with "<jump>" appended by the jump calls). */
 cst_status cst_ans_encode_ragged(const cst_model *model, cst_coder_config cfg, const int32_t *d_symbols,
                                  const uint64_t *d_sym_offsets, size_t n_streams, uint32_t *d_words,
                                  const uint64_t *d_word_offsets, size_t stride_words, uint32_t *d_n_words,
@@ -327,7 +333,7 @@ cst_status cst_ans_decode_ragged(const cst_model *model, cst_coder_config cfg, c
  * the first pass of that: every stream is decoded until `eof_symbol` appears, nothing is stored but the number of
  * symbols decoded, terminator included (d_lengths, uint64 [n_streams]); a stream without a terminator among its first
  * `max_symbols` symbols reports CST_STREAM_CAPACITY and max_symbols.  An exclusive prefix sum of d_lengths is the
- * d_sym_offsets of cst_ans_decode_ragged. */
+ * d_sym_offsets of cst_ans_decode_ragged.  Shared-table models only: a per-stream model is CST_ERR_INVALID_ARGUMENT. */
 cst_status cst_ans_count_until(const cst_model *model, cst_coder_config cfg, const uint32_t *d_words,
                                const uint64_t *d_word_offsets, size_t stride_words, size_t words_capacity,
                                const uint32_t *d_n_words, size_t n_streams, int32_t eof_symbol, size_t max_symbols,
@@ -341,7 +347,10 @@ cst_status cst_ans_count_until(const cst_model *model, cst_coder_config cfg, con
  * jump_interval steps.  Chunk j of stream s is entry d_chunk_offsets[s] + j of d_jump_pos / d_jump_state, with
  * d_chunk_offsets[n_streams + 1] the exclusive prefix sum of ceil(length / jump_interval) (n_chunks_total = its last entry).  The
  * decoder writes one status per STREAM (the worst of its chunks'; a table that does not describe its stream, or a jump point with more
- * words than the stream has, reports CST_STREAM_INVALID_DATA).  d_scratch: cst_ragged_jump_scratch_bytes(n_chunks_total) bytes. */
+ * words than the stream has, reports CST_STREAM_INVALID_DATA).  d_scratch: cst_ragged_jump_scratch_bytes(n_chunks_total) bytes.
+ * Both calls take a per-stream model as cst_ans_{encode,decode}_ragged do (n_tables == n_streams): the encoder's table is the one
+ * the reference's AnsCoder gives under that stream's table, and every chunk lane of the decoder holds its own copy of the row of the
+ * stream that owns its chunk (found on the device from d_chunk_offsets: a table entry no stream owns decodes nothing). */
 size_t cst_ragged_jump_scratch_bytes(size_t n_chunks_total);
 cst_status cst_ans_encode_ragged_jump(const cst_model *model, cst_coder_config cfg, const int32_t *d_symbols,
                                       const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order, uint32_t *d_words,
@@ -361,7 +370,8 @@ cst_status cst_ans_decode_ragged_jump(const cst_model *model, cst_coder_config c
  * d_order = the stream indices sorted by length (or, for the decoders, by d_n_words) in descending order.  Results (words,
  * counts, symbols, status, all indexed by STREAM as above) do not depend on the order; an entry that is not a stream index
  * leaves its slot idle, a stream that no entry names is not coded.  1 000 000 documents of 20 .. 2000 symbols: encode
- * 2.0 -> 1.3 ms, decode 4.9 -> 1.4 ms (scripts/bench_ragged_big.py). */
+ * 2.0 -> 1.3 ms, decode 4.9 -> 1.4 ms (scripts/bench_ragged_big.py).  The two coding calls take a per-stream model
+ * (n_tables == n_streams; a lane's table is that of the stream its slot names); cst_ans_count_until_ordered does not. */
 cst_status cst_ans_encode_ragged_ordered(const cst_model *model, cst_coder_config cfg, const int32_t *d_symbols,
                                          const uint64_t *d_sym_offsets, size_t n_streams, const uint32_t *d_order,
                                          uint32_t *d_words, const uint64_t *d_word_offsets, size_t stride_words,
@@ -745,7 +755,7 @@ cst_status cst_range_decode_family_ragged_select_f32(cst_coder_config cfg, int32
                                                      const uint64_t *d_out_offsets, void *d_scratch, int32_t *d_status,
                                                      void *stream);
 
-/* The range coder with ONE SHARED TABLE for streams of different lengths: cst_ans_{encode,decode}_ragged / cst_ans_count_until for the
+/* The range coder for streams of different lengths, with ONE SHARED TABLE or one table per stream: cst_ans_{encode,decode}_ragged / cst_ans_count_until for the
  * reference's queue -- one RangeEncoder / RangeDecoder per document (src/stream/queue.rs), the symbols decoded in the order they were
  * encoded, so that a terminator is simply written last.  Symbols, slabs, d_word_offsets / stride_words / words_capacity / d_n_words
  * and d_order (NULL = the identity; an entry that is no stream index idles its slot) are those of the ragged calls above.
@@ -764,8 +774,15 @@ cst_status cst_range_decode_family_ragged_select_f32(cst_coder_config cfg, int32
  *     d_sym_offsets of cst_range_decode_ragged.
  *   - CST_ERR_INVALID_ARGUMENT, before the device is touched: a NULL model or a NULL sym_offsets / words (encoder) / n_words /
  *     lengths / status pointer, an unsupported configuration, cfg.precision != the model's (as cst_range_encode_batch refuses it), a
- *     per-stream-table model, d_word_offsets == NULL with stride_words == 0, n_streams > 2^32 - 1 with an order.
+ *     per-stream model whose n_tables != n_streams (cst_range_count_until: any per-stream model), d_word_offsets == NULL with
+ *     stride_words == 0, n_streams > 2^32 - 1 with an order.
  *   - n_streams == 0: CST_OK, nothing is launched.
+ *   - One table per stream (cst_model_create_gaussian_per_stream / cst_model_create_tables_per_stream with as many tables as
+ *     streams): cst_range_{encode,decode}_ragged and cst_range_{encode,decode}_ragged_jump code stream s with table s -- the words of
+ *     the reference RangeEncoder over that stream's table, those of cst_range_encode_batch with the per-stream model.  P <= 16; the
+ *     tables of a workgroup live in LDS, a support too large for that is CST_ERR_INVALID_ARGUMENT.  cst_last_kernel_name:
+ *     "range_{encode,decode}_ragged_ps_kernel", with "<jump>" appended by the jump calls.  cst_range_count_until,
+ *     cst_range_decode_ragged_select and cst_ans_decode_ragged_select keep refusing such a model.
  * Presets (32,64) and (16,32), every precision cst_range_encode_batch takes.
  *
  * Jump points (RangeEncoder::pos / RangeDecoder::seek, src/stream/queue.rs:172-196, 900-926) -- cst_range_{encode,decode}_ragged_jump,
@@ -847,7 +864,8 @@ cst_status cst_range_decode_ragged_jump(const cst_model *model, cst_coder_config
  *     arrays, arrays without an interval); n_chunks_total or n_pieces_total > 2^32 - 1; exactly one of d_query_first / d_query_count
  *     NULL; with n_queries > 0 a NULL d_query_stream, d_piece_offsets, d_out_offsets, d_scratch or d_status.  n_queries == 0: CST_OK,
  *     nothing is launched.
- * cst_last_kernel_name: "ans_decode_ragged_kernel<select>" / "range_decode_ragged_kernel<select>".  Shared-table models; the
+ * cst_last_kernel_name: "ans_decode_ragged_kernel<select>" / "range_decode_ragged_kernel<select>".  Shared-table models only (a
+ * per-stream model, which the plain and jump decoders of ragged batches take, is CST_ERR_INVALID_ARGUMENT here); the
  * per-symbol ragged coders (Gaussian, Laplace, Cauchy) have cst_{ans,range}_decode_{gaussian,family}_ragged_select, where a piece also
  * carries the position its parameters start at. */
 size_t cst_ragged_select_scratch_bytes(size_t n_pieces_total);

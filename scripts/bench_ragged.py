@@ -8,8 +8,13 @@ model at P = 24 through `batched.ans_{encode,decode}_ragged` (one launch each), 
 plain pair on the same documents in the same run; every figure is measured twice (the second run shows the spread).
 `--select N [--coder range] --jump-every I`: random access on the first batch (20 .. 2000 symbols, shuffled) with a jump point every I
 symbols (default 256) -- N documents drawn at random through `batched.{ans,range}_decode_ragged_select` beside the full decode of the
-batch followed by a device gather of those documents, and N ranges of 64 symbols at random depths with the table and without."""
-import argparse, sys, time
+batch followed by a device gather of those documents, and N ranges of 64 symbols at random depths with the table and without.
+`--tables per-stream [--coder range] [--jump-every I]`: 16 384 streams of 256 .. 8192 symbols (support -127 .. 127, P = 12), ONE FITTED TABLE
+PER STREAM (`Model.fit_per_stream(..., sym_offsets=)`) through the ragged pair of the coder, beside (a) the shared-table ragged pair on the
+same symbols and (b), on the first `--loop-streams` streams, a loop of rectangular per-stream calls, one per distinct length -- the only
+route to the same words without the ragged per-stream kernels; the words of (b) are compared with the batched call's.  Writes
+profiles/ragged_per_stream.json (one entry per coder and interval, merged into the file)."""
+import argparse, json, sys, time
 from pathlib import Path
 import numpy as np, torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
@@ -21,9 +26,93 @@ args = argparse.ArgumentParser(description=__doc__)
 args.add_argument("--coder", choices=("ans", "range"), default="ans")
 args.add_argument("--jump-every", type=int, default=0, help="range coder: also time the pair with a jump point every N symbols")
 args.add_argument("--select", type=int, default=0, metavar="N", help="time random access to N documents / N ranges of 64 symbols, then stop")
+args.add_argument("--tables", choices=("shared", "per-stream"), default="shared", help="per-stream: one fitted table per stream, then stop")
+args.add_argument("--streams", type=int, default=16384, help="--tables per-stream: streams of the batch")
+args.add_argument("--loop-streams", type=int, default=512, help="--tables per-stream: streams of the subset that route (b) loops over")
 opts = args.parse_args()
 coder, jump_every = opts.coder, opts.jump_every
 best = lambda fn: min(bench.event_ms(fn, 5) for _ in range(3))      # best of three event timings of five calls
+
+
+def bench_per_stream(n_streams, n_loop, every):
+    lo, hi, P, cfg = -127, 127, 12, (32, 64, 12)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    lengths = torch.randint(256, 8193, (n_streams,), generator=gen, device="cuda")
+    off_d = torch.zeros(n_streams + 1, dtype=torch.int64, device="cuda"); torch.cumsum(lengths, 0, out=off_d[1:])
+    mean = torch.rand(n_streams, generator=gen, device="cuda") * 80 - 40
+    std = torch.exp(torch.rand(n_streams, generator=gen, device="cuda") * (np.log(16) - np.log(0.5)) + np.log(0.5))
+    total = int(off_d[-1])
+    noise = torch.randn(total, generator=gen, device="cuda")
+    flat = (noise * torch.repeat_interleave(std, lengths) + torch.repeat_interleave(mean, lengths)).round().clamp(lo, hi).to(torch.int32)
+    del noise
+    if coder == "range":
+        encode = lambda sym, off, m, I: B.range_encode_ragged_jump(sym, off, m, cfg, jump_every=I) if I else B.range_encode_ragged(sym, off, m, cfg)
+        decode, rect_encode, rect_decode = B.range_decode_ragged, B.range_encode, B.range_decode
+    else:
+        encode = lambda sym, off, m, I: B.ans_encode_ragged(sym, off, m, cfg, jump_every=I)
+        decode, rect_encode, rect_decode = B.ans_decode_ragged, B.ans_encode, B.ans_decode
+    t0 = time.perf_counter()
+    model = B.Model.fit_per_stream(flat, lo, hi, P, sym_offsets=off_d)
+    torch.cuda.synchronize()
+    fit_ms = (time.perf_counter() - t0) * 1e3
+    shared = B.Model.fit(flat, lo, hi, P)
+
+    def pair(m, sym, off):
+        enc = encode(sym, off, m, every)
+        enc_name = B.last_kernel()
+        dec, st = decode(enc, m, off)
+        dec_name = B.last_kernel()
+        ok = bool(torch.equal(dec, sym)) and int(enc.status.abs().sum()) == 0 and int(st.abs().sum()) == 0
+        e = best(lambda: encode(sym, off, m, every))
+        d = best(lambda: decode(enc, m, off, out=dec))
+        return enc, e, d, ok, int(enc.n_words.sum()), (enc_name, dec_name)
+
+    enc, e, d, ok, words, names = pair(model, flat, off_d)
+    _, se, sd, sok, swords, snames = pair(shared, flat, off_d)
+    # route (b) on a subset: one rectangular per-stream call per distinct length, the models and matrices made outside the timed region
+    n_loop = min(n_loop, n_streams)
+    sub_off = off_d[: n_loop + 1].clone()
+    sub_flat = flat[: int(sub_off[-1])]
+    rows = model.cdfs_device(0, n_loop)
+    sub_model = B.Model.from_cdf_rows_per_stream(rows, lo, P)
+    sub_enc, be, bd, bok, _, _ = pair(sub_model, sub_flat, sub_off)
+    len_h, off_h = lengths[:n_loop].cpu().numpy(), sub_off.cpu().numpy()
+    groups = []
+    for n in np.unique(len_h):
+        idx = np.flatnonzero(len_h == n)
+        sym = torch.stack([sub_flat[off_h[s]: off_h[s] + n] for s in idx]).contiguous()
+        groups.append((int(n), idx, sym, B.Model.from_cdf_rows_per_stream(rows[torch.from_numpy(idx).cuda()].contiguous(), lo, P)))
+    loop_encode = lambda: [rect_encode(sym, m, cfg, jump_points=0) for _, _, sym, m in groups]
+    encs = loop_encode()
+    loop_decode = lambda: [rect_decode(x, m, n) for x, (n, _, _, m) in zip(encs, groups)]
+    same = True
+    w, wo, nw = sub_enc.words.cpu().numpy(), sub_enc.word_offsets.cpu().numpy(), sub_enc.n_words.cpu().numpy()
+    for x, (n, idx, sym, m), (back, st) in zip(encs, groups, loop_decode()):
+        rw, rn = x.words.cpu().numpy(), x.n_words.cpu().numpy()
+        same = same and bool(torch.equal(back, sym)) and int(st.abs().sum()) == 0
+        for k, s in enumerate(idx):
+            same = same and rn[k] == nw[s] and np.array_equal(rw[k, : rn[k]], w[wo[s]: wo[s] + nw[s]])
+    le, ld = best(loop_encode), best(loop_decode)
+    result = {"coder": coder, "jump_every": every, "n_streams": n_streams, "symbols": total, "config": list(cfg), "kernels": list(names),
+              "fit_per_stream_ms": round(fit_ms, 3),
+              "per_stream": {"encode_ms": round(e, 4), "decode_ms": round(d, 4), "words": words, "ok": ok},
+              "shared_table": {"encode_ms": round(se, 4), "decode_ms": round(sd, 4), "words": swords, "ok": sok, "kernels": list(snames)},
+              "per_stream_over_shared": {"encode": round(e / se, 3), "decode": round(d / sd, 3), "words": round(words / swords, 4)},
+              "subset": {"n_streams": n_loop, "symbols": int(sub_off[-1]), "rectangular_calls": len(groups),
+                         "batched": {"encode_ms": round(be, 4), "decode_ms": round(bd, 4), "ok": bok},
+                         "rectangular_loop": {"encode_ms": round(le, 4), "decode_ms": round(ld, 4)},
+                         "loop_over_batched": {"encode": round(le / be, 2), "decode": round(ld / bd, 2)}, "same_words": bool(same)}}
+    print(json.dumps(result), flush=True)
+    path = Path(__file__).resolve().parent.parent / "profiles" / "ragged_per_stream.json"
+    runs = json.loads(path.read_text()) if path.exists() else {}
+    runs[f"{coder}, jump_every={every}"] = result
+    path.parent.mkdir(exist_ok=True)
+    path.write_text(json.dumps(runs, indent=1) + "\n")
+
+
+if opts.tables == "per-stream":
+    bench_per_stream(opts.streams, opts.loop_streams, jump_every)
+    sys.exit(0)
 rng = np.random.default_rng(1)
 n_docs, n_sym, P = 100_000, 64, 24
 probs = rng.dirichlet(np.ones(n_sym) * 0.5)
